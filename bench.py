@@ -2,7 +2,7 @@
 """Headline benchmark: decode tokens/s (+ p50 TTFT) of Llama-3-8B W4A16 (AWQ g128) + int8 KV, batch 64,
 1k-token synthetic prompts, on N MI355X GPUs of one node (TP=N, one process per GPU, RCCL).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -297,6 +297,27 @@ def claim_stdout():
         os.dup2(2, 1)
 
 
+DUMP_BYTES = 64 << 20       # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: what the timed decode path hands its caller after its last step -- the greedy token of every sequence
+    (tm_engine_fetch) and the logits it was drawn from (tm_engine_fetch_logits: rank 0's vocabulary shard when tp > 1) -- as
+    float32 .npy files, so that two builds can be compared output for output on the same seeded inputs.  Logits larger than the
+    byte budget are replaced by a fixed seeded sample of their entries (flat order).  Returns {file name: shape} for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    tokens = eng.fetch()[:, -1].astype(np.float32)          # token ids < 2**24: exact in float32
+    logits = eng.fetch_logits().astype(np.float32)
+    keep = (DUMP_BYTES - tokens.nbytes) // 4 - 1024          # room for the two .npy headers
+    if logits.size > keep:
+        idx = np.sort(np.random.default_rng(0).choice(logits.size, keep, replace=False))
+        logits = logits.reshape(-1)[idx]
+    files = {'tokens.npy': tokens, 'logits.npy': logits}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name), arr)
+    return {name: list(arr.shape) for name, arr in files.items()}
+
+
 def emit_json(obj):
     data = (json.dumps(obj) + '\n').encode()
     if _JSON_FD is None:
@@ -341,7 +362,13 @@ def main():
     ap.add_argument('--cpu-config0', action='store_true',
                     help='BASELINE.json configs[0] only: InternLM2-1.8B fp16 greedy decode on the host cores (oracle/cpu_baseline.py::run_config0, the '
                          'torch-CPU port of the reference\'s default-backend ops); prints its own JSON line; no GPU is touched')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps, write the tokens and logits of the last timed step as DIR/<name>.npy (float32, '
+                         f'at most {DUMP_BYTES >> 20} MB in all; rank 0).  The inputs are seeded; --tune 0 also fixes the GEMM tilings, which the '
+                         'start-up measurement may pick differently from run to run (same math, other summation order)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.cpu_config0:
         from oracle import cpu_baseline
         b = 1 if args.batch == 64 else args.batch
@@ -550,6 +577,7 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dumped = dump_outputs(args.dump_outputs, eng) if args.dump_outputs and rank == 0 else None
 
     ctx_first = S + 1 + W               # context length (incl. the new token) of the first timed step
     ctx_mean = ctx_first + (K - 1) / 2.0
@@ -760,6 +788,8 @@ def main():
             from oracle import cpu_baseline
             out['cpu_baseline'] = cpu_baseline.run(model, B, S, sample_layers=2)
         out['sample_tokens'] = toks[0, :4].tolist()
+        if dumped:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'files': dumped}
         import ctypes
         ctypes.CDLL(None).fflush(None)     # whatever C stdio still buffers goes to stderr (claim_stdout), the JSON line alone to stdout
         emit_json(out)
