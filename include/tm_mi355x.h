@@ -117,6 +117,11 @@ int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, 
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st);
 /* greedy top-1 on fp32-cast logits (generation/sampling.cc:92-183); out_val (fp16 [batch]) may be NULL */
 int tm_argmax(int* out_ids, void* out_val, const void* logits, int batch, int vocab, int ld, tm_stream_t st);
+/* Per-row cross-entropy (kernels/cross_entropy_kernels.cu:31-73): nll fp32 [rows] = logf(sum_v exp(x_v - max) + 1e-9f) + max
+ * - x[targets[r]] over fp16 logits [rows][ld] of `vocab` columns, in fp32 from the raw logits (max starts at -FLT_MAX: a row of
+ * -inf gives +inf).  targets (device int32 [rows]) < 0: nll = 0 and the row is not read; >= vocab: NaN.  One pass, fixed
+ * reduction order, no atomics: bitwise reproducible.  rows == 0 is a no-op. */
+int tm_cross_entropy(float* nll, const void* logits, const int* targets, int rows, int vocab, int ld, tm_stream_t st);
 /* Stochastic sampling (generation/sampling.cc:92-183, logits_processor.cc:105-112, kernels/sampling_*.cu): per row
  * logits / temperature -> keep the top_k most probable (top_k <= 0: all) -> softmax -> keep the shortest prefix whose
  * cumulative probability exceeds top_p (>= 1: all) -> drop p < min_p * p_max -> renormalise -> first candidate whose
@@ -409,6 +414,15 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
 /* run `steps` decode iterations for the admitted batch (every sequence generates one token per step,
  * ignore_eos semantics).  Asynchronous on the engine stream; tm_engine_sync() waits. */
 int tm_engine_decode(tm_engine* e, int steps);
+/* Prompt scoring (Pipeline.get_ppl; the reference's return_ppl path, models/output_processor.cc:236-300).  Synchronous.
+ * `batch` sequences (host ids concatenated, host lens) run through chunked prefill with the lm_head over EVERY prompt row and
+ * per-row cross-entropy against the next token, from the raw logits (no penalties, bans or sampling).  host_nll receives
+ * sum(len_b - 1) floats: sequence by sequence, position p scored against ids[b][p + 1].  Each sequence holds ceil(len / 64)
+ * blocks for the call only; on return every block is free again and the engine is idle (batch slots, next ids, logits and
+ * the decode graph untouched; the scoring scratch stays allocated until tm_engine_destroy).  Refusals:
+ * TM_CONFLICT (engine thread running), TM_INVALID (a batch admitted / scheduler session open, tp > 1, len < 2, an id
+ * outside [0, vocab)), TM_TOO_LONG (len >= session_len), TM_OOM (not enough free KV blocks). */
+int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int batch, float* host_nll);
 int tm_engine_sync(tm_engine* e);
 /* per-sequence time-to-first-token of the last tm_engine_prefill, milliseconds since the call started (host [batch]) */
 int tm_engine_prefill_times(tm_engine* e, float* host_ms);

@@ -90,6 +90,7 @@ _SIGNATURES = {
                                      c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'tm_embedding': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'tm_argmax': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tm_cross_entropy': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'tm_silu_mul': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'tm_sample_workspace': (c_size_t, [c_int]),
     'tm_moe_create': (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_float]),
@@ -166,6 +167,7 @@ _SIGNATURES = {
     'tm_engine_start': (c_int, [c_void_p]),
     'tm_engine_prefill': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
     'tm_engine_decode': (c_int, [c_void_p, c_int]),
+    'tm_engine_score': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'tm_engine_sync': (c_int, [c_void_p]),
     'tm_engine_prefill_times': (c_int, [c_void_p, c_void_p]),
     'tm_engine_profile_decode': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

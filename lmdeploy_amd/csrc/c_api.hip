@@ -238,6 +238,11 @@ int tm_argmax(int* out_ids, void* out_val, const void* logits, int batch, int vo
     return launch_argmax(out_ids, (half_t*)out_val, (const half_t*)logits, batch, vocab, ld, 0, (hipStream_t)st);
 }
 
+int tm_cross_entropy(float* nll, const void* logits, const int* targets, int rows, int vocab, int ld, tm_stream_t st)
+{
+    return launch_cross_entropy(nll, (const half_t*)logits, targets, rows, vocab, ld, (hipStream_t)st);
+}
+
 int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st)
 {
     TM_REQUIRE(out && gate_up, "null pointer");

@@ -696,7 +696,8 @@ int tm_engine_destroy(tm_engine* e)
                     (void*)e->d_u, (void*)e->d_topk, (void*)e->d_seed, e->d_sample_ws, (void*)e->d_logits_gather, (void*)e->d_logits_full,
                     (void*)e->d_seen, (void*)e->d_lp_rep,
                     (void*)e->d_lp_minlen, (void*)e->d_lp_ban, (void*)e->d_lp_end, (void*)e->d_lpr_vals, (void*)e->d_lpr_idx, (void*)e->d_lpr_num,
-                    (void*)e->d_lpr_sel, (void*)e->d_kept, (void*)e->d_cb_lp_vals, (void*)e->d_cb_lp_idx, (void*)e->d_cb_lp_num, (void*)e->d_cb_lp_sel}) {
+                    (void*)e->d_lpr_sel, (void*)e->d_kept, (void*)e->d_cb_lp_vals, (void*)e->d_cb_lp_idx, (void*)e->d_cb_lp_num, (void*)e->d_cb_lp_sel,
+                    (void*)e->d_score_logits, (void*)e->d_score_nll, (void*)e->d_score_tgt}) {
         if (q) {
             (void)hipFree(q);
         }

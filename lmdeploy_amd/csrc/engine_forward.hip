@@ -530,6 +530,19 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
         TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true)));
         TM_TRY(linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN));
     }
+    if (e->scoring) {
+        // tm_engine_score: every row's final-normed hidden state through the lm_head, then its NLL against the next token (the
+        // reference's ComputeAndOutputLogits + ComputeCeLoss, output_processor.cc:236-300); no arg-max, sampling or processors
+        TM_REQUIRE(!decode && !md && !e->use_comm, "internal: scoring forward");
+        for (int r0 = 0; r0 < M; r0 += e->score_rows) {
+            const int n = std::min(e->score_rows, M - r0);
+            TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, e->d_x + (size_t)r0 * e->hidden, e->hidden, e->d_score_logits, e->score_ld,
+                                                   n, false)));
+            TM_PROF(P_SAMPLE, TM_TRY(launch_cross_entropy(e->d_score_nll + e->score_base + r0, e->d_score_logits,
+                                                          e->d_score_tgt + e->score_base + r0, n, e->vocab_local, e->score_ld, st)));
+        }
+        return 0;
+    }
     // last-token hidden states -> logits -> next ids, for `n` sequences whose logits / next ids land in the batch slots
     // [slot, slot + n): hx = their hidden rows, ids / cu_q (nullptr: one token per sequence) / ntok = the tokens this forward
     // consumed for them, k_len = their context lengths
@@ -814,6 +827,7 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
     // logits / first tokens of the iteration land in d_logits / d_next_ids at slot b0 + i.
     int b0 = 0;
     int done_in_b0 = 0;  // tokens of sequence b0 already prefilled (chunked long prompt)
+    int consumed   = 0;  // tokens of the concatenated sequences prefilled by earlier iterations (the scoring rows' positions)
     while (b0 < batch) {
         std::vector<int> cu_q{0}, klen, koff{0}, rows, ids;
         int b1 = b0, tokens = 0, max_q = 0, max_k = 0;
@@ -880,6 +894,8 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
         e->d_block_ptrs += (size_t)(slot0 + b0) * e->max_blocks_per_seq;
         const MixedDecode md{nd, merge ? mix->k_len : nullptr, merge ? mix->block_ptrs : nullptr, merge ? mix->cu_q : nullptr,
                              merge ? mix->active : nullptr};
+        e->score_base   = consumed;
+        consumed       += tokens;
         const int rc    = forward(e, e->d_prefill_ids, nd + tokens, nseq, false, max_q, max_k, e->kflat_stride, slot0 + b0,
                                   merge ? &md : nullptr);
         e->d_block_ptrs = saved_ptrs;
@@ -1080,6 +1096,102 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
         // (with logprobs on the record pointers and the cap are captured kernel arguments: always re-capture)
         (void)hipGraphExecDestroy(e->graph);
         e->graph = nullptr;
+    }
+    return 0;
+}
+
+// Prompt scoring: chunked prefill of `batch` sequences whose forwards end in the scoring head (forward(), e->scoring) instead of
+// the last-token lm_head.  Each sequence holds ceil(len / 64) blocks for the call only (no room for generation); the batch slots,
+// d_next_ids, d_logits and the decode graph are not touched, so a later prefill / decode runs as on a fresh engine.
+int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int batch, float* host_nll)
+{
+    if (e && e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    TM_REQUIRE(e && host_ids && host_lens && host_nll, "null pointer");
+    TM_REQUIRE(e->started, "engine not started");
+    TM_REQUIRE(e->batch == 0 && !e->sched, "a batch is already admitted (release it first)");
+    TM_REQUIRE(e->cfg.tp == 1 && !e->use_comm, "scoring at tp > 1 is not supported (the vocabulary is sharded across the ranks)");
+    TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
+    TM_HIP_CHECK(hipSetDevice(e->cfg.device));
+    const tm_engine_config& c = e->cfg;
+    const int               V = c.model.vocab;
+
+    int64_t need = 0, total = 0;
+    for (int b = 0; b < batch; ++b) {
+        TM_REQUIRE(host_lens[b] >= 2, "scoring needs at least 2 tokens per sequence");
+        if (host_lens[b] >= c.session_len) {
+            set_last_error("input length >= session_len");
+            return TM_TOO_LONG;
+        }
+        need += (host_lens[b] + 63) / 64;
+        total += host_lens[b];
+    }
+    for (int64_t i = 0; i < total; ++i) {
+        TM_REQUIRE(host_ids[i] >= 0 && host_ids[i] < V, "token id outside [0, vocab)");
+    }
+    if (need > (int64_t)e->free_blocks.size()) {
+        set_last_error("out of KV cache blocks");
+        return TM_OOM;
+    }
+    if (!e->d_score_logits) {
+        e->score_rows        = std::min(1024, e->max_tokens);
+        e->score_ld          = (e->vocab_local + 7) / 8 * 8;
+        const size_t per_seq = (size_t)c.max_batch_size * c.session_len;
+        if (hipMalloc((void**)&e->d_score_logits, (size_t)e->score_rows * e->score_ld * sizeof(half_t)) != hipSuccess
+            || hipMalloc((void**)&e->d_score_nll, per_seq * sizeof(float)) != hipSuccess
+            || hipMalloc((void**)&e->d_score_tgt, per_seq * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(e->d_score_logits), (void)hipFree(e->d_score_nll), (void)hipFree(e->d_score_tgt);
+            e->d_score_logits = nullptr, e->d_score_nll = nullptr, e->d_score_tgt = nullptr;
+            set_last_error("scoring scratch allocation failed");
+            return TM_OOM;
+        }
+    }
+    // targets of every position of the concatenated sequences: the next token, -1 at a sequence's last position (no target)
+    std::vector<int>         tgt(total);
+    std::vector<const int*>  seq_ids(batch);
+    std::vector<int>         blocks;
+    std::vector<uint64_t>    ptrs((size_t)batch * e->max_blocks_per_seq, 0);
+    for (int b = 0, off = 0; b < batch; off += host_lens[b], ++b) {
+        seq_ids[b] = host_ids + off;
+        for (int p = 0; p < host_lens[b]; ++p) {
+            tgt[off + p] = p + 1 < host_lens[b] ? host_ids[off + p + 1] : -1;
+        }
+        for (int i = 0; i < (host_lens[b] + 63) / 64; ++i) {
+            const int blk = e->free_blocks.back();
+            e->free_blocks.pop_back();
+            blocks.push_back(blk);
+            ptrs[(size_t)b * e->max_blocks_per_seq + i] = (uint64_t)(e->pool + (int64_t)blk * e->block_bytes);
+        }
+    }
+    std::vector<float> nll(total);
+    auto run = [&]() -> int {
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_block_ptrs, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice, e->stream));
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_score_tgt, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, e->stream));
+        e->scoring  = true;
+        const int r = prefill_slots(e, seq_ids.data(), host_lens, batch, 0, nullptr);
+        e->scoring  = false;
+        TM_TRY(r);
+        TM_HIP_CHECK(hipMemcpyAsync(nll.data(), e->d_score_nll, nll.size() * 4, hipMemcpyDeviceToHost, e->stream));
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+        return 0;
+    };
+    const int rc = run();
+    if (rc) {
+        (void)hipStreamSynchronize(e->stream);  // the pageable vectors above must outlive every copy queued from them
+    }
+    // the blocks go back in reverse order of their removal: the free list is exactly what it was
+    for (auto it = blocks.rbegin(); it != blocks.rend(); ++it) {
+        e->free_blocks.push_back(*it);
+    }
+    if (rc) {
+        return rc;
+    }
+    for (int b = 0, off = 0, out = 0; b < batch; off += host_lens[b], ++b) {
+        memcpy(host_nll + out, nll.data() + off, (size_t)(host_lens[b] - 1) * sizeof(float));
+        out += host_lens[b] - 1;
     }
     return 0;
 }

@@ -250,6 +250,18 @@ struct tm_engine {
     std::vector<tm_logits_param>       h_logits;   // static batch: parameters of the next prefill
     std::map<int64_t, tm_logits_param> cb_logits;  // continuous batching: per request
 
+    // prompt scoring (tm_engine_score): while `scoring`, forward() REPLACES its head -- the lm_head runs over every row of the
+    // forward in chunks of score_rows into d_score_logits, the CE kernel writes one NLL per row into d_score_nll at the row's
+    // position in the call's concatenated tokens (score_base = position of the forward's first row), no arg-max / sampling.
+    // Scratch allocated by the first score call, outside any capture.
+    bool    scoring     = false;
+    int     score_base  = 0;
+    int     score_rows  = 0;        // kScoreRows = min(1024, max_prefill_token_num)
+    int     score_ld    = 0;        // round_up(vocab, 8)
+    half_t* d_score_logits = nullptr;  // [score_rows][score_ld]
+    float*  d_score_nll    = nullptr;  // [max_batch_size * session_len]
+    int*    d_score_tgt    = nullptr;  // [max_batch_size * session_len] next token of every position, -1 at a sequence's last
+
     // engine thread (tm_engine_serve_start): runs step_locked() while requests exist.  `mu` serialises the scheduler
     // and every device-side effect of submit / step / poll / cancel; API callers announce themselves in api_waiting so
     // that the loop (which re-locks immediately) lets them in between two steps.

@@ -344,6 +344,11 @@ int launch_fill_uniform_f16(half_t* out, size_t n, float amp, uint32_t seed, hip
 int launch_argmax(int* out_ids, half_t* out_val, const half_t* logits, int B, int V, int ld, int id_offset,
                   hipStream_t st);
 int launch_gather_rows(half_t* out, const half_t* in, const int* rows, int n, int H, hipStream_t st);
+
+// ---- cross_entropy.hip ------------------------------------------------------------------
+// nll[r] = logf(sum exp(x_r - max) + 1e-9f) + max - x_r[targets[r]] over fp16 logits rows [rows][ld] of vocab V (fp32, raw logits);
+// targets[r] < 0: 0 (row not read); targets[r] >= V: NaN.  rows == 0: no-op.
+int launch_cross_entropy(float* nll, const half_t* logits, const int* targets, int rows, int V, int ld, hipStream_t st);
 int launch_silu_mul(half_t* out, const half_t* gate_up, int M, int inter, hipStream_t st);
 int launch_quantize_groupwise_u4(int32_t* qweight, half_t* scales, half_t* zeros, half_t* dequant, const half_t* w,
                                  int K, int N, int group, hipStream_t st);

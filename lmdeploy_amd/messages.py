@@ -98,6 +98,9 @@ class GenerationConfig:
                        'repetition_ngram_size': 0, 'repetition_ngram_threshold': 0}
         if self.do_sample and self.temperature == 0:
             raise ValueError('temperature must be > 0 when do_sample=True')
+        if self.return_ppl:     # Response has no field for it (in the reference too): prompt scoring is its own call
+            raise NotImplementedError('GenerationConfig.return_ppl=True: use Pipeline.get_ppl(input_ids) for the mean cross-entropy of '
+                                      'prompts')
         for k, default in unsupported.items():
             if getattr(self, k) != default:
                 raise NotImplementedError(f'GenerationConfig.{k}={getattr(self, k)!r}: the MI355X hot path implements '

@@ -19,6 +19,8 @@ from .turbomind import checkpoint
 from .turbomind.engine import Engine
 from .turbomind.loader import export_weights
 
+STATUS_OOM = 11     # tm_status TM_OOM: not enough free KV blocks
+
 # synthetic model shapes (no checkpoints on disk in CI): "synthetic:<name>"
 SYNTHETIC = {
     'llama3_8b': dict(hidden=4096, layers=32, q_heads=32, kv_heads=8, head_dim=128, inter=14336, vocab=128256,
@@ -145,6 +147,37 @@ class Pipeline:
         request ends ('stop' | 'length'); the stop token itself is never part of the output.  stream_response=False: one
         final Response per request, in completion order."""
         yield from self.generate_continuous(list(prompts), gen_config or GenerationConfig(), stream=stream_response)
+
+    def get_ppl(self, input_ids: list[int] | list[list[int]]) -> list[float]:
+        """Mean cross-entropy of every input (lmdeploy/pipeline.py:291-317, serve/core/async_engine.py:899-945): position p is scored
+        against token p + 1 from the raw lm_head logits, the per-token NLLs are summed in position order (float64) and divided by
+        len - 1.  A flat list is one input; results come back in input order.  Not the exponential: the reference's value."""
+        assert isinstance(input_ids, list)
+        if isinstance(input_ids[0], (int, np.integer)):
+            input_ids = [input_ids]
+        assert all(len(_) > 1 for _ in input_ids)
+        if self.backend_config.tp > 1:
+            raise NotImplementedError('get_ppl at tp > 1: the vocabulary is sharded across the ranks')
+        for i, ids in enumerate(input_ids):
+            if len(ids) >= self.session_len:
+                raise ValueError(f'input {i}: length {len(ids)} >= session_len {self.session_len}')
+        nll = [None] * len(input_ids)
+        todo = [list(range(b0, min(b0 + self.max_batch_size, len(input_ids)))) for b0 in range(0, len(input_ids), self.max_batch_size)]
+        while todo:
+            group = todo.pop(0)
+            try:
+                res = self.engine.score([input_ids[i] for i in group])
+            except _ffi.TmError as e:
+                if e.status != STATUS_OOM:
+                    raise
+                if len(group) == 1:
+                    raise ValueError(f'input {group[0]} (length {len(input_ids[group[0]])}) does not fit the KV cache') from e
+                half = (len(group) + 1) // 2     # not enough KV blocks for the whole group: halve it and retry both parts
+                todo[:0] = [group[:half], group[half:]]
+                continue
+            for i, r in zip(group, res):
+                nll[i] = r
+        return [float(np.cumsum(r, dtype=np.float64)[-1] / len(r)) for r in nll]     # cumsum: sequential, in position order
 
     def close(self):
         self.engine.close()

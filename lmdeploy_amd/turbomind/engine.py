@@ -185,6 +185,15 @@ class Engine:
     def decode(self, steps: int = 1):
         _ffi.check(self._lib.tm_engine_decode(self._h, steps))
 
+    def score(self, seqs: Sequence[Sequence[int]]) -> list:
+        """Prompt scoring (tm_engine_score): per-token NLL in fp32 from the raw lm_head logits, one array of length len - 1 per
+        sequence -- entry p is position p scored against token p + 1.  Synchronous; the engine is idle again on return."""
+        lens = np.asarray([len(p) for p in seqs], np.int32)
+        ids = np.concatenate([np.asarray(p, np.int32) for p in seqs]).astype(np.int32)
+        out = np.zeros(int(np.sum(lens - 1)), np.float32)
+        _ffi.check(self._lib.tm_engine_score(self._h, ids.ctypes.data, lens.ctypes.data, len(seqs), out.ctypes.data))
+        return np.split(out, np.cumsum(lens - 1)[:-1])
+
     PROF_CATEGORIES = ('embed', 'gemm_qkv', 'kv_store', 'attention', 'gemm_o', 'residual_norm', 'gemm_gate_up',
                        'gemm_down', 'lm_head', 'sample', 'allreduce')
 
