@@ -334,6 +334,10 @@ int tm_debug_tiling_candidates(int K, int N, int M, int* shapes, int* splits, in
  * (cu_block_nums must say the same); 0 = ragged (default).  The engine's own table is rectangular and always takes this
  * path: the decode kernel then needs no dependent pointer loads (test hook for that path). */
 int tm_debug_set_block_stride(int stride);
+/* Grouped expert GEMMs launched by the CALLING thread (tm_moe_forward) use `rows`-row tiles: u4 / fp8 weight-only 16, 32 or
+ * 64 (decode-sized forwards, tokens <= 64), e4m3 on the fp8 matrix cores 32 or 64 (any size); 0 = off, the measured entry or
+ * the launcher's own rule (test hook: every row tile against the oracle, whatever the routing). */
+int tm_debug_set_grouped_rows(int rows);
 
 /* ----------------------------------------------------------------------------------------------
  * Engine level (static batcher around LanguageModel::Forward)

@@ -131,6 +131,7 @@ _SIGNATURES = {
     'tm_gemm_import': (c_int, [c_char_p]),
     'tm_gemm_export': (c_int, [c_char_p]),
     'tm_debug_set_block_stride': (c_int, [c_int]),
+    'tm_debug_set_grouped_rows': (c_int, [c_int]),
     'tm_debug_pick_tiling': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     'tm_debug_pick_general': (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tm_debug_grouped_tile': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),

@@ -925,6 +925,13 @@ int tm_debug_set_block_stride(int stride)
     return 0;
 }
 
+int tm_debug_set_grouped_rows(int rows)
+{
+    TM_REQUIRE(rows == 0 || rows == 16 || rows == 32 || rows == 64, "rows in {0, 16, 32, 64}");
+    gen_grouped_rows_override(rows);
+    return 0;
+}
+
 int tm_debug_set_gemm_trace(void* dev_buf)
 {
     tmk::g_gemm_dbg = (uint64_t*)dev_buf;

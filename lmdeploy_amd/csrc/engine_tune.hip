@@ -420,7 +420,8 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
             int   br = 0;
             TM_TRY(time_graph_us(e, chain, &t_heur));  // no entry: the launchers' own rule
             for (int i = 0; i < nc; ++i) {
-                gen_grouped_rows_override(rows[i]);  // this thread's launches only: nothing transient enters the shared table
+                // this thread's launches of this linear only (the other one stays on its own rule): nothing transient enters the shared table
+                gen_grouped_rows_override(rows[i], proto.K, proto.N);
                 float     us = 1e30f;
                 const int rc = time_graph_us(e, chain, &us);
                 gen_grouped_rows_override(0);

@@ -827,10 +827,18 @@ bool gen_table_get(int kind, int role, int K, int N, int M, int v[4])
 
 // the start-up tuner's candidate row tile of the grouped expert GEMMs: an override of THIS thread only (a transient entry
 // in the process-wide table was picked up by other engines / rank threads launching MoE forwards during the timing window)
-static thread_local int tl_grouped_rows = 0;
-void gen_grouped_rows_override(int rows)
+// K = N = 0: every grouped GEMM of the thread; else only the expert linear of that shape (the tuner times w1w3 and w2 separately)
+static thread_local int tl_grouped_rows = 0, tl_grouped_K = 0, tl_grouped_N = 0;
+void gen_grouped_rows_override(int rows, int K, int N)
 {
     tl_grouped_rows = rows;
+    tl_grouped_K    = K;
+    tl_grouped_N    = N;
+}
+
+int gen_grouped_rows_forced(int K, int N)
+{
+    return (tl_grouped_K == 0 || (tl_grouped_K == K && tl_grouped_N == N)) ? tl_grouped_rows : 0;
 }
 
 void gen_table_clear()
@@ -1367,8 +1375,8 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
         const int want = std::min(m_cap, std::max(1, 2 * m_hint));
         int       mt   = want <= 16 ? 1 : (want <= 32 ? 2 : 4);
         int       tv[4];
-        if (tl_grouped_rows > 0) {
-            mt = tl_grouped_rows / 16;  // the tuner's candidate on this thread
+        if (const int forced = gen_grouped_rows_forced(proto.K, proto.N)) {
+            mt = forced / 16;  // the tuner's candidate (or a test's) on this thread
         }
         else if (gen_table_get(kGenGrouped + proto.type, 0, proto.K, proto.N, dec32_m_bucket(m_cap), tv)) {
             mt = tv[0] / 16;  // measured (tm_engine_tune_gemm): 16 / 32 / 64-row tiles
