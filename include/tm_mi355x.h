@@ -330,6 +330,13 @@ int tm_debug_grouped_tile(int weight_type, int K, int N, int tokens, int* rows);
  * src/turbomind/kernels/gemm/gemm.cu:92-224) may pick for a K x N linear at M rows; *count = how many exist (<= 128), the first
  * min(cap, *count) are written.  The full-size parity tests sweep exactly this list. */
 int tm_debug_tiling_candidates(int K, int N, int M, int* shapes, int* splits, int cap, int* count);
+/* Host-only: every (tiles per wave, split-K) pair the start-up tuner times for a dense linear of the general kernel (gemm_w4a16.hip:
+ * the fp16 lm_head, TM_WEIGHT_F16, and e4m3 weight-only linears, TM_WEIGHT_FP8) of K x N at M rows with a split-K workspace of
+ * `workspace_bytes` -- exactly gen_dense_candidates (the tuner adds the heuristic's own pick when it is not in the list).  *count =
+ * how many exist (0 for other weight types and M > 256), the first min(cap, *count) are written.  The general-kernel parity tests
+ * sweep exactly this list. */
+int tm_debug_general_candidates(int weight_type, int K, int N, int M, int64_t workspace_bytes, int* nt, int* splits, int cap,
+                                int* count);
 /* Operator-level calls that follow treat tm_kv_cache::block_ptrs as a rectangular table: sequence b starts at b * stride
  * (cu_block_nums must say the same); 0 = ragged (default).  The engine's own table is rectangular and always takes this
  * path: the decode kernel then needs no dependent pointer loads (test hook for that path). */

@@ -254,6 +254,10 @@ int tm_linear_create(tm_linear** out, int in_features, int out_features, int wei
     TM_REQUIRE(out, "null pointer");
     TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_FP8, "weight_type");
     TM_REQUIRE(in_features > 0 && out_features > 0, "shape");
+    TM_REQUIRE(gemm_general_image_bytes(in_features, out_features, weight_type) < kGeneralImageLimit,
+               "linear " + std::to_string(in_features) + " x " + std::to_string(out_features) + ": its general-kernel image of "
+                   + std::to_string(gemm_general_image_bytes(in_features, out_features, weight_type))
+                   + " bytes reaches 2^31 (the kernel addresses it with 32-bit offsets)");
     auto* l     = new tm_linear();
     l->w.K      = in_features;
     l->w.N      = out_features;
@@ -913,6 +917,26 @@ int tm_debug_tiling_candidates(int K, int N, int M, int* shapes, int* splits, in
     for (int i = 0; i < n && i < cap; ++i) {
         shapes[i] = cand[i][0];
         splits[i] = cand[i][1];
+    }
+    *count = n;
+    return 0;
+}
+
+int tm_debug_general_candidates(int weight_type, int K, int N, int M, int64_t workspace_bytes, int* nt, int* splits, int cap,
+                                int* count)
+{
+    TM_REQUIRE(nt && splits && count && cap >= 0 && K > 0 && N > 0 && M > 0 && workspace_bytes >= 0, "arguments");
+    TM_REQUIRE(weight_type >= 0 && weight_type <= 2, "weight_type");
+    TM_REQUIRE(K % 128 == 0 && N % 16 == 0, "gemm_kernel takes K % 128 == 0, N % 16 == 0");
+    LinearWeight w{};
+    w.K    = K;
+    w.N    = N;
+    w.type = weight_type;
+    GemmConfig cand[16];
+    const int  n = gen_dense_candidates(w, M, (size_t)workspace_bytes, cand, 16);
+    for (int i = 0; i < n && i < cap; ++i) {
+        nt[i]     = cand[i].nt;
+        splits[i] = cand[i].splits;
     }
     *count = n;
     return 0;

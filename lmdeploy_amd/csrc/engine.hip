@@ -102,6 +102,26 @@ static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, 
     }
 }
 
+// every linear of this rank's shard against the general kernel's addressing limit (its packed image is addressed with 32-bit offsets,
+// gemm_w4a16.hip): add_linear cannot report an error, so engine creation refuses such a model up front
+static int check_linear_images(const tm_model_config& m, int tp)
+{
+    const int q = m.q_heads / tp, kv = std::max(1, m.kv_heads / tp), inter = m.inter / tp;
+    const struct {
+        const char* name;
+        int         K, N, type;
+    } lin[] = {{"w_qkv", m.hidden, (q + 2 * kv) * m.head_dim, m.weight_type}, {"wo", q * m.head_dim, m.hidden, m.weight_type},
+               {"w1w3", m.hidden, 2 * inter, m.weight_type}, {"w2", inter, m.hidden, m.weight_type},
+               {"lm_head", m.hidden, m.vocab / tp, TM_WEIGHT_F16}};
+    for (const auto& l : lin) {
+        const size_t bytes = gemm_general_image_bytes(l.K, l.N, l.type);
+        TM_REQUIRE(bytes < kGeneralImageLimit, std::string(l.name) + " " + std::to_string(l.K) + " x " + std::to_string(l.N)
+                                                   + ": its general-kernel image of " + std::to_string(bytes)
+                                                   + " bytes reaches 2^31 (the kernel addresses it with 32-bit offsets)");
+    }
+    return 0;
+}
+
 static int ensure_slot(tm_engine* e, const std::string& name, Slot** out)
 {
     auto it = e->slots.find(name);
@@ -189,6 +209,7 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8, "weight_type");
     TM_REQUIRE(c->max_batch_size >= 1 && c->max_batch_size <= 1024 && c->session_len >= 1,
                "1 <= max_batch_size <= 1024, session_len >= 1");
+    TM_TRY(check_linear_images(m, c->tp));
     TM_HIP_CHECK(hipSetDevice(c->device));
 
     auto* e        = new tm_engine();

@@ -738,6 +738,12 @@ size_t gemm_workspace_bytes(int M, int N, int splits)
     return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
 }
 
+size_t gemm_general_image_bytes(int K, int N, int type)
+{
+    const size_t wv = type == 0 ? 1 : (type == 2 ? 2 : 4);  // u32x4 per (tile, k-block) per lane: u4 / fp8 / f16 (gemm_kernel's WV)
+    return (size_t)((K + 127) / 128) * ((N + 15) / 16) * 1024 * wv;
+}
+
 uint64_t* g_gemm_dbg = nullptr;  // set through tm_debug_set_gemm_trace (timing experiments)
 
 // trace arena (tm_debug_trace_arena): see tm_kernels.h

@@ -166,6 +166,10 @@ void   linear_weight_free(LinearWeight& w);
 int    linear_weight_build_f16_image(LinearWeight& w, hipStream_t st);  // u4 linear with its P32 image -> w.image16 ([N][K] fp16)
 int    launch_dequant_p32_f16(half_t* out_nk /*[N][K]*/, const LinearWeight& w, hipStream_t st);  // gemm_decode.hip: the operand as an fp16 image
 size_t gemm_workspace_bytes(int M, int N, int splits);
+// bytes of the packed image gemm_kernel streams for a K x N linear of `type` (KB * N/16 * 1024 * WV): the kernel addresses it with
+// 32-bit offsets, so linears whose image reaches 2^31 bytes are refused where shapes are accepted (kGeneralImageLimit)
+size_t gemm_general_image_bytes(int K, int N, int type);
+constexpr size_t kGeneralImageLimit = (size_t)1 << 31;
 int    launch_splitk_reduce(half_t* y, int ldy, const float* partial, int splits, int M, int N, bool gated, hipStream_t st);
 GemmConfig gemm_pick_config(const LinearWeight& w, int M);  // a P32 kernel when it applies, else ...
 GemmConfig gemm_pick_config_general(const LinearWeight& w, int M);  // ... the tiling of gemm_kernel (gemm_w4a16.hip)

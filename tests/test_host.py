@@ -641,3 +641,94 @@ def test_bench_gemm_family_roofline_arithmetic():
     # one rank of TP = 8: every linear is an eighth (column- / row-parallel), the family with it
     per8, tot8 = bench.gemm_family_bytes(bench.LLAMA3_8B, 8)
     assert abs(tot8 * 8 - tot) < 1 and per8['w_qkv'] * 8 == per['w_qkv']
+
+
+def _engine_gemm_ws(m, tp=1):
+    """the engine's split-K workspace (engine.hip): 16 slabs of 64 rows of the widest of w_qkv / w1w3 / wo-w2 output, fp32"""
+    q, kv, inter = m['q_heads'] // tp, max(1, m['kv_heads'] // tp), m['inter'] // tp
+    return 16 * 64 * max((q + 2 * kv) * m['head_dim'], 2 * inter, m['hidden']) * 4
+
+
+def _general_candidates(lib, wt, K, N, M, ws):
+    nt, sp = np.zeros(16, np.int32), np.zeros(16, np.int32)
+    n = _ffi.C.c_int(-1)
+    _ffi.check(lib.tm_debug_general_candidates(wt, K, N, M, ws, nt.ctypes.data, sp.ctypes.data, 16, _ffi.C.byref(n)))
+    return sorted(zip(nt[:n.value].tolist(), sp[:n.value].tolist()))
+
+
+def test_general_kernel_tuner_candidates():
+    """tm_debug_general_candidates = gen_dense_candidates, the list tune_aux_gemms times for the fp16 lm_head and the e4m3 weight-only
+    linears: nt 1 / 2 x the split-K counts that divide the k-blocks, keep >= 8 of them per slice and whose fp32 slabs fit the engine's
+    workspace.  Pinned at the published shapes with each model's own engine workspace; tests/test_gpu_general_gemm.py runs the list."""
+    import bench
+    lib = _ffi.load()
+    grid = lambda splits: sorted((nt, sp) for nt in (1, 2) for sp in splits)
+    # Llama-3-8B head at batch 64: split 4 needs 4 x 64 x 128256 x 4 B = 131 MB > 117 MB of workspace; split 8 leaves 4 k-blocks
+    ws8b = _engine_gemm_ws(bench.LLAMA3_8B)
+    assert ws8b == 117440512 and 4 * 64 * 128256 * 4 > ws8b
+    assert _general_candidates(lib, 1, 4096, 128256, 64, ws8b) == grid((1, 2))
+    assert _general_candidates(lib, 1, 4096, 128256, 64, 1 << 40) == grid((1, 2, 4))      # the K rule alone: 32 k-blocks
+    for M in (257, 1000, 1024):                                                           # above 256 rows: the heuristic alone
+        assert _general_candidates(lib, 1, 4096, 128256, M, 1 << 40) == []
+    assert _general_candidates(lib, 1, 4096, 128256, 256, 1 << 40) == grid((1, 2, 4))
+    # Llama-3-70B head on one TP = 8 rank (N 16032): 64 k-blocks allow split 8 and 8 slabs of 64 x 16032 fit the rank's 33.5 MB
+    ws70 = _engine_gemm_ws(bench.LLAMA3_70B, 8)
+    assert ws70 == 33554432 and 8 * 64 * 16032 * 4 <= ws70
+    assert _general_candidates(lib, 1, 8192, 16032, 64, ws70) == grid((1, 2, 4, 8))
+    assert _general_candidates(lib, 1, 8192, 16032, 128, ws70) == grid((1, 2, 4))         # 128 rows: 8 slabs no longer fit
+    # InternLM2-20B head at batch 128: 48 k-blocks -> split 8 leaves 6; 2 slabs of 128 x 92544 (95 MB) fit its 134 MB, 4 do not
+    ws20 = _engine_gemm_ws(bench.INTERNLM2_20B)
+    assert ws20 == 134217728 and 2 * 128 * 92544 * 4 <= ws20 < 4 * 128 * 92544 * 4
+    assert _general_candidates(lib, 1, 6144, 92544, 128, ws20) == grid((1, 2))
+    assert _general_candidates(lib, 1, 6144, 92544, 128, 1 << 40) == grid((1, 2, 4))
+    # Mixtral fp8 weight-only w_qkv / wo at batch 64, TP = 1 and one TP = 2 rank (KB 16 for wo: split <= 2)
+    mx = bench.MIXTRAL_8X7B
+    ws1, ws2 = _engine_gemm_ws(mx), _engine_gemm_ws(mx, 2)
+    assert (ws1, ws2) == (117440512, 58720256)
+    assert _general_candidates(lib, 2, 4096, 6144, 64, ws1) == grid((1, 2, 4))
+    assert _general_candidates(lib, 2, 4096, 4096, 64, ws1) == grid((1, 2, 4))
+    assert _general_candidates(lib, 2, 4096, 3072, 64, ws2) == grid((1, 2, 4))
+    assert _general_candidates(lib, 2, 2048, 4096, 64, ws2) == grid((1, 2))
+    assert _general_candidates(lib, 2, 4096, 6144, 300, 1 << 40) == []
+    # u4 linears of the general kernel keep the heuristic; a workspace of 0 leaves the unsplit tilings
+    assert _general_candidates(lib, 0, 4096, 4096, 64, 1 << 40) == []
+    assert _general_candidates(lib, 1, 4096, 128256, 64, 0) == grid((1,))
+    # cap < count: the count is still reported
+    nt, sp, n = np.zeros(1, np.int32), np.zeros(1, np.int32), _ffi.C.c_int(-1)
+    _ffi.check(lib.tm_debug_general_candidates(1, 8192, 16032, 64, ws70, nt.ctypes.data, sp.ctypes.data, 1, _ffi.C.byref(n)))
+    assert n.value == 8 and (nt[0], sp[0]) == (1, 1)
+    assert lib.tm_debug_general_candidates(1, 4096, 100, 64, ws8b, nt.ctypes.data, sp.ctypes.data, 1, _ffi.C.byref(n)) == 1
+
+
+def test_linears_the_general_kernel_cannot_address_are_refused():
+    """gemm_kernel addresses a linear's packed image (KB x N/16 x 1024 x WV bytes = 2 K N for fp16) with 32-bit offsets: tm_linear_create
+    and engine creation refuse any linear whose image reaches 2^31 bytes.  The largest supported head, Llama-3-70B's 8192 x 128256 at
+    tp = 1 (2 101 346 304 B, 97.9 % of 2^31), is accepted; 8192 x 131072 (exactly 2^31) is not."""
+    lib = _ffi.load()
+    h = _ffi.C.c_void_p()
+    assert lib.tm_linear_create(_ffi.C.byref(h), 8192, 131072, 1, 128) == 1 and '2^31' in _ffi.last_error()
+    assert lib.tm_linear_create(_ffi.C.byref(h), 16384, 131072, 2, 128) == 1 and '2^31' in _ffi.last_error()   # e4m3: K N bytes
+    assert lib.tm_linear_create(_ffi.C.byref(h), 65536, 65536, 0, 128) == 1 and '2^31' in _ffi.last_error()    # u4: K N / 2 bytes
+    for K, N, wt in ((8192, 128256, 1), (16384, 131056, 2), (65536, 65520, 0)):
+        h = _ffi.C.c_void_p()
+        assert lib.tm_linear_create(_ffi.C.byref(h), K, N, wt, 128) == 0, _ffi.last_error()
+        assert lib.tm_linear_destroy(h) == 0
+
+    import bench
+
+    def create(vocab, tp=1, **over):
+        """engine creation up to the device: device -1 makes the first HIP call fail on any machine, after every shape check"""
+        m = dict(bench.LLAMA3_70B, vocab=vocab, **over)
+        mc = _ffi.ModelConfig(hidden=m['hidden'], layers=m['layers'], q_heads=m['q_heads'], kv_heads=m['kv_heads'],
+                              head_dim=m['head_dim'], inter=m['inter'], vocab=m['vocab'], rms_eps=1e-5, group_size=128,
+                              weight_type=m.get('weight_type', 0))
+        cfg = _ffi.EngineConfig(model=mc, tp=tp, rank=0, device=-1, max_batch_size=64, session_len=4096, quant_policy=8,
+                                cache_block_seq_len=64)
+        e = _ffi.C.c_void_p()
+        assert lib.tm_engine_create(_ffi.C.byref(e), _ffi.C.byref(cfg)) != 0 and not e.value     # never reaches a device
+        return _ffi.last_error()
+
+    assert 'lm_head 8192 x 131072' in create(131072) and '2^31' in create(131072)
+    assert '2^31' not in create(128256)
+    assert 'lm_head 8192 x 131072' in create(262144, tp=2) and '2^31' not in create(262144, tp=4)   # per rank's shard
+    assert 'w1w3 8192 x 262144' in create(128256, inter=131072, weight_type=2)                   # e4m3 w1w3: K x 2 inter bytes
