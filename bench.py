@@ -2,14 +2,19 @@
 """Headline benchmark: decode tokens/s (+ p50 TTFT) of Llama-3-8B W4A16 (AWQ g128) + int8 KV, batch 64,
 1k-token synthetic prompts, on N MI355X GPUs of one node (TP=N, one process per GPU, RCCL).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 A "step" = one decode iteration of the whole batch (64 tokens).  Rank 0 prints ONE JSON line.
 `value` = batch * K / t, where t brackets exactly K steps (graph replays) with barrier + device sync on both
 sides, max over ranks.  Inputs (weights, KV cache of the prefilled prompts) are resident in HBM.
-`roofline` is for the kernel family that takes the most TIME of a step -- at the driver command's context the four W4A16
+A plain run does only what `value` needs: set-up (engine, synthetic weights, start-up GEMM tuning, prefill), W warm-up
+steps, the K timed steps, --dump-outputs, the JSON line.  `--full` adds everything else the line can carry, all of it after
+the timed steps: the eager per-kernel profile (`kernel_ms_per_step`, `roofline`, `gemm_roofline`), the rocprofv3 child passes
+(in-graph durations for `roofline` / `attention_roofline` / `gemm_family_roofline`, traffic), the continuation to 1024 generated tokens
+(`value_1k_out`) and the CPU baseline; the --no-* switches and --profile-steps thin a --full run.
+`roofline` (--full) is for the kernel family that takes the most TIME of a step -- at the driver command's context the four W4A16
 decode GEMMs of a layer (algorithmic weight bytes of the layer / the sum of their mean launch durations), else the paged decode
 attention (algorithmic KV bytes per launch / mean launch duration); the other one follows as `attention_roofline` /
 `gemm_family_roofline`, the whole step as `step_roofline`.  Durations are IN-GRAPH: a rocprofv3 --kernel-trace child run of this
@@ -338,16 +343,16 @@ def main():
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--prompt-len', type=int, default=1024)
     ap.add_argument('--quant-policy', type=int, default=8)
-    ap.add_argument('--profile-steps', type=int, default=8)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--profile-steps', type=int, default=8, help='--full: eager HIP-event steps after the timed region (kernel_ms_per_step)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-graph', action='store_true', help='eager launches (rocprofv3 --pmc passes)')
     ap.add_argument('--layers', type=int, default=0, help='debug only: override the layer count (result is then INVALID)')
     ap.add_argument('--model', default='llama3_8b', choices=['llama3_8b', 'internlm2_20b', 'llama3_70b', 'mixtral_8x7b'],
                     help='shapes to time; the headline metric is llama3_8b (anything else changes metric/config in the output)')
     ap.add_argument('--tune', type=int, default=1, help='1 (default): TM_GEMM_TUNE=1 -- the engine measures its decode GEMM tilings at '
                     'start-up, outside the timed region (the reference\'s warm-up tuning); 0: heuristics only')
-    ap.add_argument('--no-traffic', action='store_true', help='skip the rocprofv3 --pmc FETCH_SIZE child run (roofline.traffic = null)')
-    ap.add_argument('--no-full-run', action='store_true', help='skip the continuation to 1024 generated tokens (value_full_run)')
+    ap.add_argument('--no-traffic', action='store_true', help='--full: skip the rocprofv3 child runs (in-graph durations, roofline.traffic = null)')
+    ap.add_argument('--no-full-run', action='store_true', help='--full: skip the continuation to 1024 generated tokens (value_full_run)')
     ap.add_argument('--traffic-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--allow-shared-devices', action='store_true',
                     help='let several ranks share one GPU when the box has fewer GPUs than --gpus (launcher / bring-up tests only: the '
@@ -366,6 +371,9 @@ def main():
                     help='after the timed steps, write the tokens and logits of the last timed step as DIR/<name>.npy (float32, '
                          f'at most {DUMP_BYTES >> 20} MB in all; rank 0).  The inputs are seeded; --tune 0 also fixes the GEMM tilings, which the '
                          'start-up measurement may pick differently from run to run (same math, other summation order)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything beyond `value`: eager per-kernel profile, rocprofv3 roofline / '
+                         'traffic child passes, continuation to 1024 generated tokens (value_1k_out), CPU baseline')
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
@@ -453,8 +461,11 @@ def main():
     K, W, B, S = args.steps, args.warmup, args.batch, args.prompt_len
     P = args.profile_steps
     child = args.traffic_child
-    full_run = (not args.no_full_run) and not child and 1 + W + K < 1024     # continue to 1024 generated tokens after the timed region
-    max_new = max(1 + W + K + P + 2, (1024 + P + 2) if full_run else 0)
+    # the engine is sized for the --full extras (profile steps, continuation to 1024 generated tokens) whether or not they run, so that a
+    # plain run times the same engine -- session length, block tables -- as a --full one
+    sized_for_full_run = (not args.no_full_run) and not child and 1 + W + K < 1024
+    full_run = args.full and sized_for_full_run      # continue to 1024 generated tokens after the timed region
+    max_new = max(1 + W + K + P + 2, (1024 + P + 2) if sized_for_full_run else 0)
     weight_type = int(model.pop('weight_type', 0))
     eng = Engine.from_model_config(_Cfg(model), weight_type=weight_type, tp=tp, rank=rank if tp > 1 else 0, device=local_dev, max_batch_size=B,
                                    session_len=S + max_new + 1, quant_policy=args.quant_policy,
@@ -536,7 +547,7 @@ def main():
                     eng.import_gemm_table(path)
         tuned = bool(table)
     table_text = None
-    if not child and rank == 0:
+    if args.full and not child and rank == 0:
         try:    # the dispatch this process runs (measured + imported entries): the trace child imports it instead of tuning again
             import tempfile
             with tempfile.TemporaryDirectory() as td:
@@ -585,7 +596,7 @@ def main():
     step_bytes, kv_tok = algorithmic_bytes(model, B, ctx_mean, kv_bits, tp)
 
     # ---- per-kernel durations: HIP events on the engine stream, eager steps right after the timed region ----
-    prof = eng.profile_decode(P) if P > 0 else {}
+    prof = eng.profile_decode(P) if args.full and P > 0 else {}
     ctx_prof = S + 1 + W + K + (P - 1) / 2.0
     # ---- the rest of the 1k-out window (64 x 1024 generated tokens, steady state without the first steps):
     # the timed K steps sit at the CHEAP end of the run (shortest contexts), so also report the rate over everything
@@ -784,7 +795,7 @@ def main():
             out['value_full_run']['step_roofline_frac'] = round(
                 algorithmic_bytes(model, B, (full['ctx_first'] + full['ctx_last']) / 2.0, kv_bits, tp)[0] / (full['ms_per_step'] / 1e3) / 1e9
                 / HBM_PEAK_GBPS, 4) if weight_type == 0 and not model.get('moe_experts') else None
-        if not args.no_cpu_baseline and world == 1 and not child:
+        if args.full and not args.no_cpu_baseline and world == 1 and not child:
             from oracle import cpu_baseline
             out['cpu_baseline'] = cpu_baseline.run(model, B, S, sample_layers=2)
         out['sample_tokens'] = toks[0, :4].tolist()

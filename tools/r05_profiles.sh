@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profile_r05
 mkdir -p $OUT
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 timeout 700 $B > $OUT/bench_line_default.json 2> $OUT/bench_line_default.err
 timeout 400 $B --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line_driver_command.json 2>/dev/null
 TM_FOLD_NORM=0 timeout 400 $B --steps 20 --warmup 5 --no-cpu-baseline --no-traffic > $OUT/bench_line_driver_command_unfolded_norm.json 2>/dev/null

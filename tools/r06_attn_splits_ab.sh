@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $R
 for rep in 1 2; do
 for s in 1 2 4; do
-  timeout 400 python bench.py --decode-splits $s --no-cpu-baseline --no-traffic --profile-steps 0 > $OUT/bench_splits${s}_$rep.json 2>/dev/null
+  timeout 400 python bench.py --full --decode-splits $s --no-cpu-baseline --no-traffic --profile-steps 0 > $OUT/bench_splits${s}_$rep.json 2>/dev/null
 done
 done
 python - <<PY

@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "split_k_merg
 tail -3 $OUT/pytest_merge.txt
 timeout 600 python -m pytest tests/test_gpu_fullsize.py -x -q -m gpu -k "every_tuner_candidate and 64" > $OUT/pytest_cands.txt 2>&1
 tail -3 $OUT/pytest_cands.txt
-B="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
+B="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
 TM_GEMM_TUNE_VERBOSE=1 timeout 400 $B > $OUT/bench_default.json 2> $OUT/tune_verbose.txt
 grep "tm tune" $OUT/tune_verbose.txt | grep -E "M=64" > $OUT/tune_m64.txt
 # forced arms: dispatch table lines K N M shape splits role

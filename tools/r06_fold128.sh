@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 timeout 900 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "folded_norm" > $OUT/pytest_fold.txt 2>&1; tail -3 $OUT/pytest_fold.txt
 timeout 900 python -m pytest tests/test_gpu_engine.py -x -q -m gpu -k "folded_norm_batch_128 or matches_oracle" > $OUT/pytest_engine.txt 2>&1; tail -3 $OUT/pytest_engine.txt
-B="python $R/bench.py --model internlm2_20b --batch 128 --steps 128 --no-cpu-baseline --no-full-run --no-traffic"
+B="python $R/bench.py --full --model internlm2_20b --batch 128 --steps 128 --no-cpu-baseline --no-full-run --no-traffic"
 TM_GEMM_TUNE_VERBOSE=1 timeout 900 $B > $OUT/bench_line_config2_internlm2_20b_b128.json 2> $OUT/tune_fold128.txt
 TM_FOLD_MAX_M=64 TM_GEMM_TUNE_VERBOSE=1 timeout 900 $B > $OUT/bench_line_config2_internlm2_20b_b128_fold_max_64.json 2> $OUT/tune_fold64.txt
 timeout 900 $B > $OUT/bench_line_config2_internlm2_20b_b128_again.json 2>/dev/null

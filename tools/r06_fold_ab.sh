@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r06_fold_ab
 mkdir -p $OUT
 cd $R
-B="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
+B="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
 for i in 1 2 3 4; do
   TM_FOLD_NORM=3 timeout 400 $B > $OUT/bench_fold3_$i.json 2>/dev/null
   TM_FOLD_NORM=0 timeout 400 $B > $OUT/bench_fold0_$i.json 2>/dev/null

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r06_merge_ab
 mkdir -p $OUT
 cd $R
-B="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 TM_GEMM_TUNE_VERBOSE=1 timeout 500 $B > $OUT/bench_line_driver_command_default.json 2> $OUT/tune_verbose.txt
 grep "tm tune" $OUT/tune_verbose.txt | grep -E "M=64" > $OUT/tuner_candidates_m64.txt
 for arm in "26 2" "16 2" "10 1"; do

@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $R
 TM_D32_L2PF=1 timeout 600 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "w4a16_linear or folded_norm or split_k_merged or gated_silu" > $OUT/pytest_l2pf1.txt 2>&1; tail -2 $OUT/pytest_l2pf1.txt
 TM_D32_L2PF=2 timeout 600 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "folded_norm" > $OUT/pytest_l2pf2.txt 2>&1; tail -2 $OUT/pytest_l2pf2.txt
-B="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
+B="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
 for v in 0 1 2 0 1; do
   TM_D32_L2PF=$v TM_GEMM_TUNE_VERBOSE=1 timeout 400 $B > $OUT/bench_l2pf${v}_$RANDOM.json 2> $OUT/tune_$v.txt
 done

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r06_power
 mkdir -p $OUT
 cd $R
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic"
 for i in 1 2; do for v in 1 0; do TM_SYNTH_WEIGHT_SCALE=$v timeout 400 $B > $OUT/bench_wscale${v}_$i.json 2>/dev/null; done; done
 python - <<PY
 import json,glob

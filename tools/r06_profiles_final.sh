@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profile_r06
 mkdir -p $OUT
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 timeout 700 $B > $OUT/bench_line_default.json 2> $OUT/bench_line_default.err
 timeout 400 $B --steps 20 --warmup 5 > $OUT/bench_line_driver_command.json 2>/dev/null
 timeout 400 $B --quant-policy 4 --steps 256 --no-cpu-baseline --no-full-run > $OUT/bench_line_llama3_8b_int4kv.json 2>/dev/null

@@ -8,11 +8,11 @@ mkdir -p $OUT
 cd $R
 timeout 900 python -m pytest tests/test_gpu_engine.py -x -q -m gpu -k "collective_path or side_stream" > $OUT/pytest_collective.txt 2>&1; tail -3 $OUT/pytest_collective.txt
 timeout 1200 python -m pytest tests/test_gpu_tp.py tests/test_gpu_p2p.py -x -q -m gpu > $OUT/pytest_tp.txt 2>&1; tail -3 $OUT/pytest_tp.txt
-B="python $R/bench.py --emulate-tp 8 --steps 128 --no-cpu-baseline --no-traffic --no-full-run"
+B="python $R/bench.py --full --emulate-tp 8 --steps 128 --no-cpu-baseline --no-traffic --no-full-run"
 timeout 600 $B > $OUT/bench_line_llama3_8b_tp8_rank_emulation.json 2>/dev/null
 TM_COMM=rccl timeout 600 $B > $OUT/bench_line_llama3_8b_tp8_rank_emulation_rccl_plus_norm_launch.json 2>/dev/null
 timeout 600 $B > $OUT/bench_line_llama3_8b_tp8_rank_emulation_again.json 2>/dev/null
-B2="python $R/bench.py --emulate-tp 2 --steps 128 --no-cpu-baseline --no-traffic --no-full-run"
+B2="python $R/bench.py --full --emulate-tp 2 --steps 128 --no-cpu-baseline --no-traffic --no-full-run"
 timeout 600 $B2 > $OUT/bench_line_llama3_8b_tp2_rank_emulation.json 2>/dev/null
 TM_COMM=rccl timeout 600 $B2 > $OUT/bench_line_llama3_8b_tp2_rank_emulation_rccl_plus_norm_launch.json 2>/dev/null
 python - <<PY
