@@ -85,6 +85,13 @@ int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rop
  * cos_sin may be NULL (no rotation). */
 int tm_kv_rope_store(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                      const void* cos_sin, int max_pos, const tm_kv_cache* cache, tm_stream_t st);
+/* The same with the Qwen attention prologue in front of RoPE, each part optional (NULL = off): q_norm / k_norm fp16 [128]
+ * (both or neither) -> per-head RMSNorm of every q / k head, y = h(h(f32(x) * inv) * w), inv = 1 / sqrt(sum f32(x)^2 / 128 + eps)
+ * (Qwen3); then qkv_bias fp16 [(q_heads + 2 kv_heads)*128] added to q, k and v in fp16 (Qwen2).  With all three NULL this is
+ * tm_kv_rope_store. */
+int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                        const void* cos_sin, int max_pos, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                        const tm_kv_cache* cache, tm_stream_t st);
 /* FlattenKV_v2: dequantise the whole context into linear fp16 scratch.  k_out [kv_heads][k_stride][128];
  * v_out the same, or transposed [kv_heads][128][k_stride] when transpose_v != 0.  Sequence b starts at
  * cu_k_off[b] (device; must be 64-aligned when transposing). */
@@ -109,6 +116,12 @@ int    tm_decode_attention(void* out, const void* q, int q_stride, const int* k_
 int tm_decode_attention_fused(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
                               const int* k_len, int batch, int q_heads, float softmax_scale, int splits,
                               void* workspace, const tm_kv_cache* cache, tm_stream_t st);
+/* The same with the Qwen prologue of tm_kv_rope_store_qk (norm -> bias -> RoPE) applied to the new token's q / k / v; cache
+ * bytes / params bit-identical to tm_kv_rope_store_qk with the same arguments. */
+int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
+                                 const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps, const int* k_len,
+                                 int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
+                                 tm_stream_t st);
 /* Causal prefill attention over flattened KV (dispatchAttention).  vt is the transposed V of tm_flatten_kv. */
 int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
                          const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
@@ -362,6 +375,10 @@ typedef struct tm_model_config {
      * `inter` (sharded over tp like the dense FFN), `moe_top_k` per token (Mixtral: 8 / 2, norm_topk = 1) */
     int   moe_experts, moe_top_k, moe_norm_topk;
     float moe_routed_scale;
+    /* Qwen attention prologue (0 = off): attn_bias -> slot "layers.{i}.attention.w_qkv.bias" fp16 [local qkv columns] added to
+     * q / k / v (Qwen2); qk_norm -> slots "layers.{i}.attention.{q,k}_norm.weight" fp16 [head_dim], per-head RMSNorm of q / k with
+     * rms_eps (Qwen3).  Order: norm -> bias -> RoPE. */
+    int   attn_bias, qk_norm;
 } tm_model_config;
 
 typedef struct tm_engine_config {

@@ -56,7 +56,7 @@ class ModelConfig(C.Structure):
                 ('rope_type', c_int), ('rope_factor', c_float), ('rope_low_freq_factor', c_float),
                 ('rope_high_freq_factor', c_float), ('rope_original_max_position', c_int), ('group_size', c_int),
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
-                ('moe_routed_scale', c_float)]
+                ('moe_routed_scale', c_float), ('attn_bias', c_int), ('qk_norm', c_int)]
 
 
 class EngineConfig(C.Structure):
@@ -79,6 +79,8 @@ _SIGNATURES = {
     'tm_rope_table': (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_float, c_int]),
     'tm_kv_rope_store': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                  POINTER(KvCache), c_void_p]),
+    'tm_kv_rope_store_qk': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_float, POINTER(KvCache), c_void_p]),
     'tm_flatten_kv': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(KvCache),
                               c_void_p]),
     'tm_decode_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
@@ -86,6 +88,9 @@ _SIGNATURES = {
                                     POINTER(KvCache), c_void_p]),
     'tm_decode_attention_fused': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_float, c_int, c_void_p, POINTER(KvCache), c_void_p]),
+    'tm_decode_attention_fused_qk': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_float, c_void_p, c_int, c_int, c_float, c_int, c_void_p, POINTER(KvCache),
+                                             c_void_p]),
     'tm_prefill_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'tm_embedding': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

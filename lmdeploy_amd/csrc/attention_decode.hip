@@ -408,6 +408,8 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     }
     const bool fused = p.qkv_slabs || p.qkv_f16;
     TM_REQUIRE(!fused || L.bits == 8 || L.bits == 4, "fused decode prologue: int8 / int4 KV only");
+    // the Qwen prologue (bias / q-k norm) exists only in the fused MFMA path; unfused kernels read q after launch_kv_rope_store applied it
+    TM_REQUIRE(fused || (!p.qkv_bias && !p.q_norm && !p.k_norm), "qkv bias / q-k norm need the fused decode prologue");
     switch (L.bits) {
         case 16:
             return launch_bits<16>(p, st);

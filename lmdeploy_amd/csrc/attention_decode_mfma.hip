@@ -148,7 +148,8 @@ __device__ __forceinline__ void expand_u4x32(u32x4 w, u32x4& a, u32x4& b)
 // BITS = 8: the cache bytes are the codes.  BITS = 4: the block is half as large in HBM; the nibbles are expanded to
 // one byte per code when the block is written to the wave's LDS image, everything after that is the int8 path
 // (scales / zeros are per token either way, quantization.h:316-366).
-template<bool FUSED, int BITS>
+// QKX (FUSED only): the Qwen prologue -- per-head RMSNorm of q / k, then the q / k / v bias, then RoPE (DecodeAttnParams).
+template<bool FUSED, int BITS, bool QKX = false>
 __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(DecodeAttnParams p, int head_chunks, int hpw)
 {
     static_assert(BITS == 8 || BITS == 4, "int8 / int4 KV");
@@ -307,10 +308,39 @@ __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(Decode
         const QkvRaw  rk    = qkv_issue(p, b, kvcol);
         const half8_t csq   = *(const GLOBAL_AS half8_t*)(cs + wave * 32 + g * 8);
         const half8_t csk   = *(const GLOBAL_AS half8_t*)(cs + l16 * 8);
+        // Qwen prologue operands, issued with the loads above (a pointer left nullptr reads the valid start of the qkv input instead)
+        half8_t qnw{}, qbias{}, knw{}, kbias{};
+        if constexpr (QKX) {
+            const half_t* any = p.qkv_f16 ? p.qkv_f16 : (const half_t*)p.qkv_slabs;
+            const half_t* bs  = p.qkv_bias ? p.qkv_bias : any;
+            qnw               = *(const GLOBAL_AS half8_t*)((p.q_norm ? p.q_norm : any) + wave * 32 + g * 8);
+            knw               = *(const GLOBAL_AS half8_t*)((p.k_norm ? p.k_norm : any) + l16 * 8);
+            qbias             = *(const GLOBAL_AS half8_t*)(bs + qcol);
+            kbias             = *(const GLOBAL_AS half8_t*)(bs + kvcol);
+        }
         asm volatile("" ::: "memory");  // the scheduler keeps this order
         load_tile(ptr_cur, tile, std::true_type{});
         asm volatile("" ::: "memory");
         half8_t t = qkv_finish(p, b, qcol, rq);
+        if constexpr (QKX) {
+            if (p.q_norm) {
+                // head i16's 128 channels sit in lanes (g = 0..3) x waves (0..3): chunk 4 * wave + g.  In-wave over g, then the four waves'
+                // partials through LDS (one extra barrier): the same tree as group_sum<16> over a 16-lane row (tm_common.h)
+                float ss = sumsq8(t);
+                ss += __shfl_xor(ss, 16);
+                ss += __shfl_xor(ss, 32);
+                float* red = (float*)(smem + 4 * kWaveLds + 4096);  // [4 waves][16 heads]
+                if (g == 0) {
+                    red[wave * 16 + i16] = ss;
+                }
+                __syncthreads();
+                ss = (red[i16] + red[16 + i16]) + (red[32 + i16] + red[48 + i16]);
+                t  = head_norm8(t, ss, qnw, p.qk_eps);
+            }
+            if (p.qkv_bias) {
+                t = t + qbias;
+            }
+        }
         if (p.cos_sin) {
             t = rope8(t, csq);
         }
@@ -320,6 +350,17 @@ __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(Decode
         *(half8_t*)(smem + 4 * kWaveLds + (wave * 64 + lane) * 16) = t;
         if (owns_newest) {
             half8_t x = qkv_finish(p, b, kvcol, rk);
+            if constexpr (QKX) {
+                if (p.q_norm) {  // lanes 0-15 hold the K row: a row16 reduction (the V row reduces alongside and keeps x)
+                    const float ss = group_sum<16>(sumsq8(x));
+                    if (!isv) {
+                        x = head_norm8(x, ss, knw, p.qk_eps);
+                    }
+                }
+                if (p.qkv_bias) {
+                    x = x + kbias;
+                }
+            }
             if (!isv && p.cos_sin) {
                 x = rope8(x, csk);
             }
@@ -619,7 +660,29 @@ int launch_decode_attention_i8_mfma(const DecodeAttnParams& p_in, hipStream_t st
     // 4 wave-private images (+ 4 KB q exchange for the fused prologue); the merge buffers overlay the images
     static_assert(4 * kWaveLds + 4096 > 4 * 16 * 128 * 4 + 4 * 16 * 2 * 4, "merge buffers must fit");
     const int lds = 4 * kWaveLds + 4096;
-    const void* const k = (p.qkv_slabs || p.qkv_f16) ?
+    const bool fused = p.qkv_slabs || p.qkv_f16;
+    if (fused) {
+        TM_REQUIRE(p.qkv_n % 8 == 0 && (p.qkv_splits == 0) == (p.qkv_slabs == nullptr), "fused qkv input");
+    }
+    TM_REQUIRE((p.q_norm == nullptr) == (p.k_norm == nullptr), "q_norm and k_norm come together");
+    if (fused && (p.qkv_bias || p.q_norm)) {
+        // + the four waves' partial sums of squares of the q-norm ([4][16] fp32)
+        const int   lds_x = lds + 4 * 16 * 4;
+        const void* kx    = p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<true, 4, true> :
+                                                       (const void*)decode_attention_i8_mfma_kernel<true, 8, true>;
+        if (const int rc = ensure_dynamic_lds(kx, lds_x)) {
+            return rc;
+        }
+        if (p.cache.layout.bits == 4) {
+            decode_attention_i8_mfma_kernel<true, 4, true><<<grid, 256, lds_x, st>>>(p, chunks, hpw);
+        }
+        else {
+            decode_attention_i8_mfma_kernel<true, 8, true><<<grid, 256, lds_x, st>>>(p, chunks, hpw);
+        }
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    const void* const k = fused ?
                               (p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<true, 4> :
                                                           (const void*)decode_attention_i8_mfma_kernel<true, 8>) :
                               (p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<false, 4> :
@@ -627,8 +690,7 @@ int launch_decode_attention_i8_mfma(const DecodeAttnParams& p_in, hipStream_t st
     if (const int rc = ensure_dynamic_lds(k, lds)) {
         return rc;
     }
-    if (p.qkv_slabs || p.qkv_f16) {
-        TM_REQUIRE(p.qkv_n % 8 == 0 && (p.qkv_splits == 0) == (p.qkv_slabs == nullptr), "fused qkv input");
+    if (fused) {
         if (p.cache.layout.bits == 4) {
             decode_attention_i8_mfma_kernel<true, 4><<<grid, 256, lds, st>>>(p, chunks, hpw);
         }

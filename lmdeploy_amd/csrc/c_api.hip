@@ -137,9 +137,18 @@ int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rop
 int tm_kv_rope_store(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                      const void* cos_sin, int max_pos, const tm_kv_cache* cache, tm_stream_t st)
 {
+    return tm_kv_rope_store_qk(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, nullptr, nullptr, nullptr, 0.f,
+                               cache, st);
+}
+
+int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                        const void* cos_sin, int max_pos, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                        const tm_kv_cache* cache, tm_stream_t st)
+{
     TM_REQUIRE(qkv && cu_q_len && k_len && cache, "null pointer");
     return launch_kv_rope_store((half_t*)qkv, q_heads, cu_q_len, k_len, batch, total_tokens, (const half2_t*)cos_sin,
-                                max_pos, to_view(cache), (hipStream_t)st);
+                                max_pos, to_view(cache), (hipStream_t)st, (const half_t*)qkv_bias, (const half_t*)q_norm,
+                                (const half_t*)k_norm, qk_eps);
 }
 
 int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
@@ -179,6 +188,15 @@ int tm_decode_attention_fused(void* out, const void* qkv, int qkv_splits, int qk
                               const int* k_len, int batch, int q_heads, float softmax_scale, int splits,
                               void* workspace, const tm_kv_cache* cache, tm_stream_t st)
 {
+    return tm_decode_attention_fused_qk(out, qkv, qkv_splits, qkv_n, cos_sin, max_pos, nullptr, nullptr, nullptr, 0.f, k_len, batch,
+                                        q_heads, softmax_scale, splits, workspace, cache, st);
+}
+
+int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
+                                 const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps, const int* k_len,
+                                 int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
+                                 tm_stream_t st)
+{
     TM_REQUIRE(out && qkv && k_len && cache, "null pointer");
     TM_REQUIRE(cache->bits == 8 || cache->bits == 4, "fused decode prologue: int8 / int4 KV only");
     TM_REQUIRE(qkv_n == (q_heads + 2 * cache->kv_heads) * 128, "qkv_n != (q_heads + 2 kv_heads) * 128");
@@ -199,6 +217,10 @@ int tm_decode_attention_fused(void* out, const void* qkv, int qkv_splits, int qk
     p.qkv_n      = qkv_n;
     p.cos_sin    = (const half2_t*)cos_sin;
     p.max_pos    = cos_sin ? max_pos : 1 << 30;
+    p.qkv_bias   = (const half_t*)qkv_bias;
+    p.q_norm     = (const half_t*)q_norm;
+    p.k_norm     = (const half_t*)k_norm;
+    p.qk_eps     = qk_eps;
     return launch_decode_attention(p, (hipStream_t)st);
 }
 

@@ -258,6 +258,13 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
         }
         e->slots[p + ".attention_norm.weight"].bytes = (int64_t)m.hidden * 2;
         e->slots[p + ".ffn_norm.weight"].bytes       = (int64_t)m.hidden * 2;
+        if (m.attn_bias) {  // this rank's Q | K | V columns, q / k channel-permuted like the weights
+            e->slots[p + ".attention.w_qkv.bias"].bytes = (int64_t)e->qkv_n * 2;
+        }
+        if (m.qk_norm) {  // one head, permuted like one head of q / k; replicated over the ranks
+            e->slots[p + ".attention.q_norm.weight"].bytes = (int64_t)e->D * 2;
+            e->slots[p + ".attention.k_norm.weight"].bytes = (int64_t)e->D * 2;
+        }
     }
     e->slots["tok_embeddings.weight"].bytes = (int64_t)m.vocab * m.hidden * 2;  // replicated
     e->slots["norm.weight"].bytes           = (int64_t)m.hidden * 2;
@@ -373,6 +380,13 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
         }
         TM_TRY(vec(p + ".attention_norm.weight", m.hidden, 1.f, 0.02f));
         TM_TRY(vec(p + ".ffn_norm.weight", m.hidden, 1.f, 0.02f));
+        if (m.attn_bias) {
+            TM_TRY(vec(p + ".attention.w_qkv.bias", e->qkv_n, 0.f, 0.02f));
+        }
+        if (m.qk_norm) {
+            TM_TRY(vec(p + ".attention.q_norm.weight", e->D, 1.f, 0.05f));
+            TM_TRY(vec(p + ".attention.k_norm.weight", e->D, 1.f, 0.05f));
+        }
     }
     TM_TRY(vec("tok_embeddings.weight", (size_t)m.vocab * m.hidden, 0.f, 0.02f));
     TM_TRY(vec("norm.weight", m.hidden, 1.f, 0.02f));
@@ -441,6 +455,13 @@ int tm_engine_process_weights(tm_engine* e)
         }
         TM_TRY(norm(p + ".attention_norm.weight", &L.attn_norm));
         TM_TRY(norm(p + ".ffn_norm.weight", &L.ffn_norm));
+        if (m.attn_bias) {
+            TM_TRY(norm(p + ".attention.w_qkv.bias", &L.qkv_bias));
+        }
+        if (m.qk_norm) {
+            TM_TRY(norm(p + ".attention.q_norm.weight", &L.q_norm));
+            TM_TRY(norm(p + ".attention.k_norm.weight", &L.k_norm));
+        }
     }
     TM_TRY(norm("tok_embeddings.weight", &e->tok_embeddings));
     TM_TRY(norm("norm.weight", &e->final_norm));

@@ -227,7 +227,7 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             KvCacheView cv = cache_view(e, li);
             cv.block_ptrs += (size_t)P.s0 * e->max_blocks_per_seq;  // cu_block_nums[b] = b * max_blocks_per_seq: the part's sequence 0
             TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv, e->q_heads, P.cu_q, e->d_k_len + P.s0, P.nseq, P.rows, e->d_rope, e->rope_max_pos,
-                                                           cv, st)));
+                                                           cv, st, L.qkv_bias, L.q_norm, L.k_norm, eps)));
             TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + P.s0, e->d_k_len + P.s0, P.nseq, max_k_len,
                                                         kflat_stride, cv, st)));
             PrefillAttnParams p{};
@@ -388,7 +388,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             ss_tiles = 0;
             if (!fuse_qkv) {
                 TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                               e->rope_max_pos, cv, st)));
+                                                               e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
             }
         }
         else if (fuse_qkv) {
@@ -405,7 +405,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             }
             qkv_done = false;
             TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                           e->rope_max_pos, cv, st)));
+                                                           e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
         }
         if (md) {
             // decode rows: (fused prologue: RoPE + K/V quantise-store) + attention on the fp16 projection rows; they share
@@ -425,10 +425,14 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
                 p.qkv_n   = e->qkv_n;
                 p.cos_sin = e->d_rope;
                 p.max_pos = e->rope_max_pos;
+                p.qkv_bias = L.qkv_bias;
+                p.q_norm   = L.q_norm;
+                p.k_norm   = L.k_norm;
+                p.qk_eps   = m.rms_eps;
             }
             else {  // fp16 KV (no fused prologue): RoPE + store of the decode rows' K/V first
                 TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(e->d_qkv, e->q_heads, md->cu_q, md->k_len, nd, nd, e->d_rope,
-                                                               e->rope_max_pos, cvd, dst)));
+                                                               e->rope_max_pos, cvd, dst, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
             }
             p.q              = e->d_qkv;
             p.q_stride       = e->qkv_n;
@@ -455,6 +459,10 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
                 p.qkv_n      = e->qkv_n;
                 p.cos_sin    = e->d_rope;
                 p.max_pos    = e->rope_max_pos;
+                p.qkv_bias   = L.qkv_bias;
+                p.q_norm     = L.q_norm;
+                p.k_norm     = L.k_norm;
+                p.qk_eps     = m.rms_eps;
             }
             p.q          = e->d_qkv;
             p.q_stride   = e->qkv_n;

@@ -61,6 +61,10 @@ struct Layer {
     LinearSlots qkv, wo, w13, w2;
     half_t*     attn_norm = nullptr;
     half_t*     ffn_norm  = nullptr;
+    // Qwen attention prologue (tm_model_config.attn_bias / qk_norm; nullptr when off): [qkv_n] bias, [D] per-head norm weights
+    half_t*     qkv_bias  = nullptr;
+    half_t*     q_norm    = nullptr;
+    half_t*     k_norm    = nullptr;
     // mixture of experts: the dense w13 / w2 are unused; gate slot + per-expert slots feed `moe`
     bool                     is_moe = false;
     std::vector<LinearSlots> ex13, ex2;

@@ -41,7 +41,9 @@ __device__ __forceinline__ float row16_max(float v)
     return v;
 }
 
-template<int BITS>
+// QKX: the Qwen prologue (per-head RMSNorm of q / k, then the q / k / v bias; either may be nullptr) in front of RoPE.
+// One 16-lane row holds one head of one token, so the head's sum of squares is a row16 DPP reduction like row16_max.
+template<int BITS, bool QKX>
 __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__ qkv,
                                                             int q_heads,
                                                             const int* __restrict__ cu_q_len,
@@ -50,7 +52,11 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
                                                             int total_tokens,
                                                             const half2_t* __restrict__ cos_sin,
                                                             int         max_pos,
-                                                            KvCacheView cache)
+                                                            KvCacheView cache,
+                                                            const half_t* __restrict__ qkv_bias,
+                                                            const half_t* __restrict__ q_norm,
+                                                            const half_t* __restrict__ k_norm,
+                                                            float qk_eps)
 {
     constexpr int  D       = 128;
     const KvLayout L       = cache.layout;
@@ -72,6 +78,19 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
 
     const bool is_q = head < q_heads;
     const bool is_k = !is_q && head < q_heads + kv_heads;
+
+    if constexpr (QKX) {
+        if (q_norm != nullptr) {  // grid-uniform; V rows reduce too (whole rows stay in step) and keep x
+            const float   ss = group_sum<16>(sumsq8(x));
+            const half8_t w  = *(const half8_t*)((is_q ? q_norm : k_norm) + lane16 * 8);
+            if (is_q || is_k) {
+                x = head_norm8(x, ss, w, qk_eps);
+            }
+        }
+        if (qkv_bias != nullptr) {
+            x = x + *(const half8_t*)(qkv_bias + (size_t)head * D + lane16 * 8);
+        }
+    }
 
     if ((is_q || is_k) && cos_sin != nullptr) {
         // interleaved pairs (x[2i], x[2i+1]); c,s already cast to fp16; fp16 mul/sub/add, no fma
@@ -160,24 +179,37 @@ int launch_kv_rope_store(half_t*        qkv,
                          const half2_t* cos_sin,
                          int            max_pos,
                          KvCacheView    cache,
-                         hipStream_t    st)
+                         hipStream_t    st,
+                         const half_t*  qkv_bias,
+                         const half_t*  q_norm,
+                         const half_t*  k_norm,
+                         float          qk_eps)
 {
     TM_REQUIRE(cache.layout.head_dim == 128, "head_dim must be 128");
     TM_REQUIRE(cache.layout.bits == 16 || cache.layout.bits == 8 || cache.layout.bits == 4, "kv bits in {16,8,4}");
+    TM_REQUIRE((q_norm == nullptr) == (k_norm == nullptr), "q_norm and k_norm come together");
     if (total_tokens == 0) {
         return 0;
     }
     dim3 grid((total_tokens + 15) / 16, q_heads + 2 * cache.layout.kv_heads);
+    const bool qkx = qkv_bias != nullptr || q_norm != nullptr;
+#define TM_KV_STORE(B_, X_)                                                                                                 \
+    kv_rope_store_kernel<B_, X_><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, \
+                                                       cache, qkv_bias, q_norm, k_norm, qk_eps)
     switch (cache.layout.bits) {
         case 16:
-            kv_rope_store_kernel<16><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, cache);
+            if (qkx) TM_KV_STORE(16, true);
+            else TM_KV_STORE(16, false);
             break;
         case 8:
-            kv_rope_store_kernel<8><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, cache);
+            if (qkx) TM_KV_STORE(8, true);
+            else TM_KV_STORE(8, false);
             break;
         default:
-            kv_rope_store_kernel<4><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, cache);
+            if (qkx) TM_KV_STORE(4, true);
+            else TM_KV_STORE(4, false);
     }
+#undef TM_KV_STORE
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }

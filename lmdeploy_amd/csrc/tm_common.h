@@ -103,6 +103,32 @@ __device__ __forceinline__ float group_max(float v)
     return v;
 }
 
+// Qwen attention prologue on 8 channels of one 128-wide head (the reference's order: per-head RMSNorm,
+// unified_attention_layer.cc:720-748 / rms_norm.cu:141-207, then the fp16 bias add, attention_universal.h:110-165 and
+// kv_cache_utils_v2.cu:73-124, then RoPE).  The sum of squares is the fp32 sum of the 8 squares in channel order, the 16
+// partials of a head combined as ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)) + (the same over 8..15) -- the tree group_sum<16>
+// computes, so every kernel that normalises a head gets the same bits.
+__device__ __forceinline__ float sumsq8(half8_t x)
+{
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        s = __builtin_fmaf((float)x[e], (float)x[e], s);  // x^2 of an fp16 is exact in fp32: the fma rounds like mul + add
+    }
+    return s;
+}
+// y = h(h(f32(x) * inv) * w),  inv = 1 / sqrt(ss / 128 + eps)   (oracle.rmsnorm over the head)
+__device__ __forceinline__ half8_t head_norm8(half8_t x, float ss, half8_t w, float eps)
+{
+    const float inv = 1.0f / __builtin_sqrtf(ss * (1.0f / 128.0f) + eps);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const half_t t = (half_t)((float)x[e] * inv);
+        x[e]           = t * w[e];
+    }
+    return x;
+}
+
 // reduce across the lanes that differ in bits >= log2(LOW) (i.e. keep the low LOW lanes distinct)
 template<int LOW>
 __device__ __forceinline__ float upper_sum(float v)

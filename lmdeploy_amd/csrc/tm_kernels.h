@@ -48,8 +48,12 @@ int launch_residual_rmsnorm(half_t* y, half_t* resid, const half_t* hidden, cons
 // ---- kv_cache.hip -----------------------------------------------------------------------
 // RoPE(q,k) in fp16 from a (cos,sin) table, quantise K/V of the new tokens and scatter them into the
 // paged cache.  q is rotated in place inside the qkv buffer.
+// Qwen prologue (all nullptr: today's kernel): qkv_bias [q_heads + 2 kv_heads][D] is added to q, k and v (fp16); q_norm /
+// k_norm [D] run a per-head RMSNorm (eps qk_eps) on q / k first.  Order: norm -> bias -> RoPE.
 int launch_kv_rope_store(half_t* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
-                         const half2_t* cos_sin, int max_pos, KvCacheView cache, hipStream_t st);
+                         const half2_t* cos_sin, int max_pos, KvCacheView cache, hipStream_t st,
+                         const half_t* qkv_bias = nullptr, const half_t* q_norm = nullptr, const half_t* k_norm = nullptr,
+                         float qk_eps = 0.f);
 // Gather + dequantise (two-rounding "flatten" form) the whole context of every sequence into linear
 // scratch: K [kv_heads][k_stride][D]; V either [kv_heads][k_stride][D] or transposed [kv_heads][D][k_stride].
 int launch_flatten_kv(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
@@ -79,6 +83,12 @@ struct DecodeAttnParams {
     const half2_t* cos_sin    = nullptr;
     int            max_pos    = 0;
     uint64_t*      dbg        = nullptr;  // optional per-workgroup timing stamps (tm_debug_set_gemm_trace)
+    // Qwen prologue of the fused path (nullptr: none; see launch_kv_rope_store): bias [qkv_n] on q / k / v, per-head
+    // RMSNorm of q / k with the [D] weights q_norm / k_norm (both or neither), norm -> bias -> RoPE
+    const half_t*  qkv_bias = nullptr;
+    const half_t*  q_norm   = nullptr;
+    const half_t*  k_norm   = nullptr;
+    float          qk_eps   = 0.f;
 };
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip

@@ -1,8 +1,9 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
-Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral with AWQ (W4A16 g128), FP8 (e4m3, 128x128 block
-scales, `.weight_scale_inv`) or fp16 / bf16 weights:
-  * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106
+Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 with AWQ (W4A16 g128), FP8 (e4m3,
+128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights:
+  * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
+                                     qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head)
   * FP8 normalize / dequant          lmdeploy/turbomind/weight_format.py:349-384 (HF [out, in] -> [in, out], scales alike)
   * AWQ normalize (unpack order)     lmdeploy/turbomind/weight_format.py:200-234
   * RoPE q/k channel permutation     lmdeploy/turbomind/models/utils.py:306-373 (weight, scales and zeros alike)
@@ -54,6 +55,13 @@ class ModelConfig:
     moe_routed_scale: float = 1.0
     eos_token_id: int | list | None = None
     max_position_embeddings: int = 8192
+    attn_bias: int = 0                 # Qwen2 (and Qwen3 with attention_bias): q / k / v projections carry a bias
+    qk_norm: int = 0                   # Qwen3: per-head RMSNorm of q and k before RoPE
+    tie_word_embeddings: bool = False
+
+
+# dense Qwen decoders: the Llama layout plus the attention prologue (exact names: the MoE variants stay refused)
+QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM')
 
 
 def read_config(model_path: str) -> ModelConfig:
@@ -61,11 +69,22 @@ def read_config(model_path: str) -> ModelConfig:
         c = json.load(f)
     arch = (c.get('architectures') or ['LlamaForCausalLM'])[0]
     kind = 'internlm2' if 'InternLM2' in arch else 'llama'
-    if kind == 'llama' and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
-        raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / Mixtral decoders')
+    qwen = arch in QWEN_ARCHS
+    if kind == 'llama' and not qwen and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
+        raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 '
+                                  f'dense decoders')
     H = c['hidden_size']
     heads = c['num_attention_heads']
     D = c.get('head_dim') or H // heads
+    attn_bias = qk_norm = 0
+    if qwen:
+        kind = 'qwen3' if arch == 'Qwen3ForCausalLM' else 'qwen2'
+        if c.get('use_sliding_window'):
+            raise NotImplementedError(f'{arch} with use_sliding_window: sliding-window attention is not implemented')
+        if D != 128:
+            raise NotImplementedError(f'{arch} with head_dim {D}: the attention kernels need head_dim 128')
+        attn_bias = 1 if kind == 'qwen2' else int(bool(c.get('attention_bias', False)))
+        qk_norm = 1 if kind == 'qwen3' else 0
     q = c.get('quantization_config')
     wfmt = 'f16'
     if q is not None:
@@ -106,7 +125,8 @@ def read_config(model_path: str) -> ModelConfig:
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
                        max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt,
                        moe_experts=int(c.get('num_local_experts', 0) or 0) if 'Mixtral' in arch else 0,
-                       moe_top_k=int(c.get('num_experts_per_tok', 0) or 0) if 'Mixtral' in arch else 0)
+                       moe_top_k=int(c.get('num_experts_per_tok', 0) or 0) if 'Mixtral' in arch else 0,
+                       attn_bias=attn_bias, qk_norm=qk_norm, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
 class _Tensors:
@@ -174,8 +194,10 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
     t = _Tensors(model_path)
     D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
     layers = []
+    llama_names = cfg.arch != 'internlm2'        # Llama / Mixtral / Qwen2 / Qwen3
     for i in range(cfg.layers):
-        if cfg.arch == 'llama':
+        extra = {}
+        if llama_names:
             p = f'model.layers.{i}'
             q = _linear(t, p + '.self_attn.q_proj', cfg.quantized)
             k = _linear(t, p + '.self_attn.k_proj', cfg.quantized)
@@ -195,6 +217,15 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
                 w2 = _linear(t, p + '.mlp.down_proj', cfg.quantized)
             n1 = t.get(p + '.input_layernorm.weight')
             n2 = t.get(p + '.post_attention_layernorm.weight')
+            if getattr(cfg, 'attn_bias', 0):      # fp16 [Hq*D | Hkv*D | Hkv*D], q / k channel-permuted like the weights (qwen2.py)
+                a = p + '.self_attn.'
+                extra['qkv_bias'] = np.concatenate([
+                    permute_qk_for_interleaved_rope(t.get(a + 'q_proj.bias').astype(np.float16), Hq, D),
+                    permute_qk_for_interleaved_rope(t.get(a + 'k_proj.bias').astype(np.float16), Hkv, D),
+                    t.get(a + 'v_proj.bias').astype(np.float16)])
+            if getattr(cfg, 'qk_norm', 0):        # [D] each, reordered as one head (qwen3.py: self.norm(pfx + 'q_norm', reorder))
+                for n in ('q_norm', 'k_norm'):
+                    extra[n] = permute_qk_for_interleaved_rope(t.get(f'{p}.self_attn.{n}.weight').astype(np.float16), 1, D)
         else:   # internlm2: fused wqkv, per kv group [q_0..q_{g-1}, k, v] (models/internlm2.py:34-87)
             p = f'model.layers.{i}'
             moe = None
@@ -219,11 +250,13 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
         q = _map(q, lambda a: permute_qk_for_interleaved_rope(a, Hq, D))
         k = _map(k, lambda a: permute_qk_for_interleaved_rope(a, Hkv, D))
         ffn = moe if moe is not None else dict(w1w3=_fuse_w1w3(w1, w3), w2=w2)
-        layers.append(dict(attn_norm=n1.astype(np.float16), ffn_norm=n2.astype(np.float16), w_qkv=_cat([q, k, v]), wo=wo, **ffn))
-    if cfg.arch == 'llama':
+        layers.append(dict(attn_norm=n1.astype(np.float16), ffn_norm=n2.astype(np.float16), w_qkv=_cat([q, k, v]), wo=wo, **ffn,
+                           **extra))
+    if llama_names:
         emb = t.get('model.embed_tokens.weight')
         norm = t.get('model.norm.weight')
-        head = t.get('lm_head.weight') if 'lm_head.weight' in t else emb
+        tied = getattr(cfg, 'tie_word_embeddings', False) or 'lm_head.weight' not in t
+        head = emb if tied else t.get('lm_head.weight')
     else:
         emb = t.get('model.tok_embeddings.weight')
         norm = t.get('model.norm.weight')

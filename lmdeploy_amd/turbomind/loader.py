@@ -101,7 +101,8 @@ def _emit(slots: dict, prefix: str, lin: dict):
 def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     """weights (unsharded, TM layout): {'tok_embeddings' [V,H], 'norm' [H], 'output' [H,V],
     'layers': [{'attn_norm','ffn_norm', 'w_qkv','wo','w1w3','w2': linear dicts}]} with w_qkv = [Q|K|V] along N and
-    w1w3 already (gate_j, up_j)-interleaved.  Returns {slot name: contiguous numpy array} for this rank."""
+    w1w3 already (gate_j, up_j)-interleaved; Qwen layers add 'qkv_bias' [Hq*D + 2*Hkv*D] (q / k permuted like w_qkv) and /
+    or 'q_norm', 'k_norm' [D].  Returns {slot name: contiguous numpy array} for this rank."""
     D = cfg.head_dim
     Hq, Hkv, I, G = cfg.q_heads, cfg.kv_heads, cfg.inter, cfg.group
     assert Hq % tp == 0 and I % tp == 0 and cfg.vocab % tp == 0
@@ -132,6 +133,12 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
             _emit(slots, p + '.feed_forward.w1w3',
                   _shard_linear(L['w1w3'], 'col', tp, rank, G, [(2 * rank * i_l, 2 * (rank + 1) * i_l)]))
             _emit(slots, p + '.feed_forward.w2', _shard_linear(L['w2'], 'row', tp, rank, G))
+        if 'qkv_bias' in L:    # the same column slices as w_qkv (replicated kv heads included)
+            slots[p + '.attention.w_qkv.bias'] = np.ascontiguousarray(
+                np.concatenate([L['qkv_bias'][lo:hi] for lo, hi in qkv_slices]), dtype=np.float16)
+        if 'q_norm' in L:      # one head: replicated
+            slots[p + '.attention.q_norm.weight'] = np.ascontiguousarray(L['q_norm'], dtype=np.float16)
+            slots[p + '.attention.k_norm.weight'] = np.ascontiguousarray(L['k_norm'], dtype=np.float16)
         slots[p + '.attention_norm.weight'] = np.ascontiguousarray(L['attn_norm'], dtype=np.float16)
         slots[p + '.ffn_norm.weight'] = np.ascontiguousarray(L['ffn_norm'], dtype=np.float16)
     slots['tok_embeddings.weight'] = np.ascontiguousarray(weights['tok_embeddings'], dtype=np.float16)
