@@ -250,7 +250,16 @@ int    tm_linear_destroy(tm_linear* w);
  * boundary layouts of tm_linear_prepare; w13 = [hidden][2*inter] with (gate_j, up_j) column-interleaved, w2 =
  * [inter][hidden].  FP8 w13: w1 and w3 are block-quantised separately in a checkpoint, so the scale row of w13 is
  * [w1's inter/128 blocks | w3's inter/128 blocks] (inter % 128 == 0) -- also for the engine's *.w1w3.scales slots.  gate: fp16 [hidden][experts].  All pointers device.  topk_ids_out / topk_w_out (device
- * [tokens][top_k], may be NULL) expose the routing for tests. */
+ * [tokens][top_k], may be NULL) expose the routing for tests.
+ * Bounds: 1 <= top_k <= 8, top_k <= experts <= 256 (Mixtral 8 / 2, Qwen3-MoE 128 / 8).  Up to 64 experts the router is the serial
+ * one written for Mixtral; above, or for every count with TM_MOE_ROUTER=wide, the wide one (hidden % 128 == 0).  Both fill the
+ * same tables.  experts x ceil(tokens / 64) must stay within 65535 (the grouped GEMMs' grid.z).
+ * tm_moe_router runs the router alone (gate + top-k + routing tables): logits_out fp32 [tokens][experts] (may be NULL),
+ * offsets int32 [experts + 1], f2n int32 [tokens * top_k] (flat row -> token), en2f int32 [top_k][tokens] (choice j of token t ->
+ * flat row); the tokens of an expert are in ascending order.
+ * tm_moe_forward_stages enqueues a subset of tm_moe_forward's launches (bits: gate + top-k 1, routing tables 2, grouped w1w3 with its
+ * activation quantisation 4, grouped w2 8, combine 16; 31 = tm_moe_forward) on what an earlier forward of the same x and tokens
+ * left in `workspace`: the measurement tool times the launches one by one with it. */
 typedef struct tm_moe tm_moe;
 int    tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk,
                      float routed_scale);
@@ -260,6 +269,9 @@ int    tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const vo
 size_t tm_moe_workspace(const tm_moe* m, int tokens);
 int    tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* workspace, int* topk_ids_out, float* topk_w_out,
                       tm_stream_t st);
+int    tm_moe_forward_stages(tm_moe* m, void* out, const void* x, int tokens, void* workspace, unsigned stages, tm_stream_t st);
+int    tm_moe_router(tm_moe* m, const void* x, int tokens, int* topk_ids, float* topk_w, float* logits_out, int* offsets, int* f2n,
+                     int* en2f, tm_stream_t st);
 int    tm_moe_destroy(tm_moe* m);
 
 /* IntegralQuantizer<half,4> (kernels/quantization.cu:384-440): w fp16 [K][N] -> qweight int32 [K][N/8],
@@ -358,6 +370,9 @@ int tm_debug_set_block_stride(int stride);
  * 64 (decode-sized forwards, tokens <= 64), e4m3 on the fp8 matrix cores 32 or 64 (any size); 0 = off, the measured entry or
  * the launcher's own rule (test hook: every row tile against the oracle, whatever the routing). */
 int tm_debug_set_grouped_rows(int rows);
+/* Router of the MoE block for this process: -1 = what TM_MOE_ROUTER says (auto | wide), 0 = auto, 1 = wide.  Not thread-safe (a
+ * plain global that every launch reads): for tests and the benchmark tool only, set while no thread enqueues a forward. */
+int tm_debug_set_moe_router(int mode);
 
 /* ----------------------------------------------------------------------------------------------
  * Engine level (static batcher around LanguageModel::Forward)

@@ -103,6 +103,8 @@ _SIGNATURES = {
     'tm_moe_set_expert': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_moe_workspace': (c_size_t, [c_void_p, c_int]),
     'tm_moe_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_moe_forward_stages': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, C.c_uint, c_void_p]),
+    'tm_moe_router': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_moe_destroy': (c_int, [c_void_p]),
     'tm_sample': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p]),
@@ -137,6 +139,7 @@ _SIGNATURES = {
     'tm_gemm_export': (c_int, [c_char_p]),
     'tm_debug_set_block_stride': (c_int, [c_int]),
     'tm_debug_set_grouped_rows': (c_int, [c_int]),
+    'tm_debug_set_moe_router': (c_int, [c_int]),
     'tm_debug_pick_tiling': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     'tm_debug_pick_general': (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tm_debug_grouped_tile': (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),

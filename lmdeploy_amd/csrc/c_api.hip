@@ -581,7 +581,7 @@ int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, i
 {
     TM_REQUIRE(out, "null pointer");
     TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8, "moe experts: u4 or fp8 weights");
-    TM_REQUIRE(hidden % 128 == 0 && inter % 128 == 0 && experts >= 1 && experts <= 64 && top_k >= 1 && top_k <= 8 && top_k <= experts,
+    TM_REQUIRE(hidden % 128 == 0 && inter % 128 == 0 && experts >= 1 && experts <= 256 && top_k >= 1 && top_k <= 8 && top_k <= experts,
                "moe geometry");
     auto* o         = new tm_moe();
     o->m.hidden     = hidden;
@@ -644,6 +644,28 @@ int tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* worksp
     }
     return moe_forward(m->m, (half_t*)out, m->m.hidden, (const half_t*)x, m->m.hidden, tokens, workspace, topk_ids_out, topk_w_out,
                        (hipStream_t)st);
+}
+
+int tm_moe_forward_stages(tm_moe* m, void* out, const void* x, int tokens, void* workspace, unsigned stages, tm_stream_t st)
+{
+    TM_REQUIRE(m && out && x && workspace, "null pointer");
+    TM_REQUIRE(stages >= 1 && stages <= kMoeAll, "moe stages: a non-empty subset of gate 1, route 2, w1w3 4, w2 8, combine 16");
+    if (!m->prepared) {
+        TM_TRY_RC(moe_prepare(m->m, (hipStream_t)st));
+        m->prepared = true;
+    }
+    return moe_forward(m->m, (half_t*)out, m->m.hidden, (const half_t*)x, m->m.hidden, tokens, workspace, nullptr, nullptr,
+                       (hipStream_t)st, stages);
+}
+
+int tm_moe_router(tm_moe* m, const void* x, int tokens, int* topk_ids, float* topk_w, float* logits_out, int* offsets, int* f2n,
+                  int* en2f, tm_stream_t st)
+{
+    TM_REQUIRE(m && x && topk_ids && topk_w && offsets && f2n && en2f, "null pointer");
+    TM_REQUIRE(m->m.gate && tokens >= 1, "moe router: gate set, tokens >= 1");
+    TM_TRY_RC(launch_moe_gate(topk_ids, topk_w, logits_out, (const half_t*)x, m->m.hidden, m->m.gate, tokens, m->m.hidden, m->m.experts,
+                              m->m.top_k, m->m.norm_topk, m->m.routed_scale, (hipStream_t)st));
+    return launch_moe_route(offsets, f2n, en2f, topk_ids, tokens, m->m.experts, m->m.top_k, (hipStream_t)st);
 }
 
 int tm_moe_destroy(tm_moe* m)
@@ -975,6 +997,13 @@ int tm_debug_set_grouped_rows(int rows)
 {
     TM_REQUIRE(rows == 0 || rows == 16 || rows == 32 || rows == 64, "rows in {0, 16, 32, 64}");
     gen_grouped_rows_override(rows);
+    return 0;
+}
+
+int tm_debug_set_moe_router(int mode)
+{
+    TM_REQUIRE(mode >= -1 && mode <= 1, "mode in {-1 (environment), 0 (auto), 1 (wide)}");
+    moe_router_override(mode);
     return 0;
 }
 

@@ -519,6 +519,8 @@ int launch_linear_fp8_grouped(const LinearWeight& proto, const void* d_groups, i
     else if (gen_table_get(kGenGrouped + 2, 0, proto.K, proto.N, dec32_m_bucket(m_cap), tv)) {
         rows = tv[0] == 32 ? 32 : 64;  // measured (tm_engine_tune_gemm)
     }
+    TM_REQUIRE((int64_t)E * ((m_cap + rows - 1) / rows) <= 65535,
+               "grouped fp8 linear: experts x row blocks exceed grid.z (65535): split the forward into fewer tokens");
     if (rows == 32) {
         p.zper = (m_cap + 31) / 32;
         dim3 grid((p.ncg + 3) / 4, 1, E * p.zper);

@@ -1388,6 +1388,7 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
             mt = tv[0] / 16;  // measured (tm_engine_tune_gemm): 16 / 32 / 64-row tiles
         }
         p.zper         = (m_cap + 16 * mt - 1) / (16 * mt);
+        TM_REQUIRE((int64_t)E * p.zper <= 65535, "grouped linear: experts x row blocks exceed grid.z (65535): split the forward into fewer tokens");
         dim3 grid((ntiles + 7) / 8, 1, E * p.zper);
         if (proto.type == 0) {
             rc = mt == 1 ? launch_one<0, 1, 1, 8, 1, 1, 4, 0, true>(p, grid, st) : mt == 2 ? launch_one<0, 2, 1, 8, 1, 1, 4, 0, true>(p, grid, st) :
@@ -1400,6 +1401,7 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
     }
     else {  // prefill: 64-row blocks x 2 tiles per wave; blocks past an expert's segment exit at once
         p.zper = (m_cap + 63) / 64;
+        TM_REQUIRE((int64_t)E * p.zper <= 65535, "grouped linear: experts x row blocks exceed grid.z (65535): split the forward into fewer tokens");
         dim3 grid((ntiles + 15) / 16, 1, E * p.zper);
         rc = proto.type == 0 ? launch_one<0, 4, 2, 8, 1, 1, 4, 0, true>(p, grid, st) : launch_one<2, 4, 2, 8, 1, 1, 2, 0, true>(p, grid, st);
     }

@@ -10,6 +10,8 @@
 //   route:  for every expert the tokens that selected it, in ascending token order:
 //           offsets[e] .. offsets[e+1] index the flat pair list; f2n[f] = token; en2f[j][t] = f.
 //   combine: out[t] = fp16( sum_j w[t][j] * float(y[en2f[j][t]]) ).
+// Two routers fill the same tables: the serial kernels (8-expert Mixtral, the default for experts <= 64) and the wide ones
+// (moe_gate_wide_kernel / moe_route_wide_kernel, 1 <= experts <= 256: Qwen3-MoE), chosen by the expert count or TM_MOE_ROUTER.
 #include "tm_common.h"
 #include "tm_kernels.h"
 
@@ -25,6 +27,7 @@ namespace tmk {
 
 constexpr int kMaxExperts = 64;
 constexpr int kMaxTopK    = 8;
+constexpr int kMaxExpertsWide = 256;  // the wide router below
 
 // one 256-thread workgroup per token; Wg fp16 [H][E] (input-major like every other weight)
 __global__ __launch_bounds__(256) void moe_gate_kernel(int* __restrict__ topk_ids,      // [T][k]
@@ -163,6 +166,219 @@ __global__ __launch_bounds__(1024) void moe_route_kernel(int* __restrict__ offse
     }
 }
 
+// ---- wide router: 1 <= E <= 256 ------------------------------------------------------------------------------------------
+// (value, lower id) arg-max exchange with the lane CTRL pairs this one with; every pairing is an involution, so both lanes of a
+// pair end up with the same winner
+__device__ __forceinline__ void argmax_take(float& v, int& id, float ov, int oid)
+{
+    if (ov > v || (ov == v && oid < id)) {
+        v  = ov;
+        id = oid;
+    }
+}
+__device__ __forceinline__ void wave_argmax(float& v, int& id)
+{
+    argmax_take(v, id, dpp_f32<DPP_XOR1>(v), (int)dpp_u32<DPP_XOR1>((uint32_t)id));
+    argmax_take(v, id, dpp_f32<DPP_XOR2>(v), (int)dpp_u32<DPP_XOR2>((uint32_t)id));
+    argmax_take(v, id, dpp_f32<DPP_HMIRR>(v), (int)dpp_u32<DPP_HMIRR>((uint32_t)id));
+    argmax_take(v, id, dpp_f32<DPP_ROR8>(v), (int)dpp_u32<DPP_ROR8>((uint32_t)id));
+    argmax_take(v, id, __shfl_xor(v, 16), __shfl_xor(id, 16));
+    argmax_take(v, id, __shfl_xor(v, 32), __shfl_xor(id, 32));
+}
+__device__ __forceinline__ int wave_sum_i32(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        v += __shfl_xor(v, d);
+    }
+    return v;
+}
+
+constexpr int kGateTile = 16;   // tokens per workgroup: Wg comes from L2 once per 16 tokens
+constexpr int kLogitLd  = 260;  // fp32 row stride of the logit tile in LDS: rows 4g apart land 16 banks apart
+
+// Gate + top-k in one launch.  One 256-thread workgroup per 16 tokens: logits[16][E] = x[16][H] . Wg[H][E] on
+// v_mfma_f32_16x16x32_f16 (A = x: row = token, B = Wg: column = expert, 8 consecutive h per lane; fp32 accumulators), the 16-expert
+// column tiles dealt round-robin to the four waves (NT = ceil(tiles / 4) <= 4 each, a template argument so that the k loop is
+// branch-free and unrolls: four k-steps of loads are in flight per wave).  The tile goes to LDS once; then every wave selects for four tokens:
+// a lane holds the logits of experts lane, lane + 64, lane + 128, lane + 192 and the k winners come from k wave-wide arg-max rounds.
+// NaN logits (a NaN in x or Wg) are not ordered: no comparison replaces a NaN or takes one, so such a token may list an expert twice;
+// its ids stay in [0, E) and the tables stay consistent (every pair is placed once), its output is NaN through the weights anyway.
+template<int NT>
+__global__ __launch_bounds__(256) void moe_gate_wide_kernel(int* __restrict__ topk_ids,      // [T][k]
+                                                            float* __restrict__ topk_w,      // [T][k]
+                                                            float* __restrict__ logits_out,  // [T][E] or nullptr
+                                                            const half_t* __restrict__ x,
+                                                            int ldx,
+                                                            const half_t* __restrict__ wg,
+                                                            int T,
+                                                            int H,
+                                                            int E,
+                                                            int k,
+                                                            int norm_topk,
+                                                            float routed_scale)
+{
+    __shared__ float s_logit[kGateTile][kLogitLd];
+    const int        lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int        col = lane & 15, g = lane >> 4;
+    const int        t0     = blockIdx.x * kGateTile;
+    const int        ntiles = (E + 15) >> 4;
+    // rows past T repeat the last token (their logits are never read); columns past E read column 0 (never read either)
+    const half_t* xr = x + (size_t)min(t0 + col, T - 1) * ldx + g * 8;
+    const half_t* wr = wg + (size_t)(g * 8) * E;
+    int           ecol[NT];
+    floatx4       acc[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const int e = (wave + 4 * i) * 16 + col;
+        ecol[i]     = e < E ? e : 0;
+        acc[i]      = floatx4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int h0 = 0; h0 < H; h0 += 128) {  // H % 128 == 0: four 32-wide k-steps, their loads issued together
+        half8_t a[4], b[4][NT];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            a[u]            = *(const half8_t*)(xr + h0 + 32 * u);
+            const half_t* w = wr + (size_t)(h0 + 32 * u) * E;
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    b[u][i][j] = w[(size_t)j * E + ecol[i]];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[u], b[u][i], acc[i], 0, 0, 0);
+            }
+        }
+    }
+    // accumulator of a lane: rows (tokens) 4g .. 4g+3 of column (expert) tile * 16 + col
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        if (wave + 4 * i < ntiles) {  // wave-uniform: a wave's last tile may lie past E
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                s_logit[4 * g + r][(wave + 4 * i) * 16 + col] = acc[i][r];
+            }
+        }
+    }
+    __syncthreads();
+    if (logits_out) {
+        for (int idx = threadIdx.x; idx < kGateTile * E; idx += 256) {
+            const int r = idx / E, e = idx - r * E;
+            if (t0 + r < T) {
+                logits_out[(size_t)(t0 + r) * E + e] = s_logit[r][e];
+            }
+        }
+    }
+    for (int rr = 0; rr < 4; ++rr) {
+        const int r = wave * 4 + rr, t = t0 + r;
+        if (t >= T) {  // wave-uniform
+            break;
+        }
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = lane + 64 * i < E ? s_logit[r][lane + 64 * i] : -INFINITY;
+        }
+        float all = 0.f;   // softmax over every expert (norm_topk == 0): needs the maximum, which is round 0's winner
+        float mx = 0.f, sel_v = -INFINITY;
+        int   sel_i = 0;
+        for (int j = 0; j < k; ++j) {
+            float bv = v[0];
+            int   bi = lane;
+#pragma unroll
+            for (int i = 1; i < 4; ++i) {
+                if (v[i] > bv) {
+                    bv = v[i];
+                    bi = lane + 64 * i;
+                }
+            }
+            wave_argmax(bv, bi);
+            if (j == 0) {
+                mx = bv;
+                if (!norm_topk) {
+                    all = (__builtin_expf(v[0] - mx) + __builtin_expf(v[1] - mx)) + (__builtin_expf(v[2] - mx) + __builtin_expf(v[3] - mx));
+                    all = group_sum<64>(all);
+                }
+            }
+            if (lane == j) {
+                sel_v = bv;
+                sel_i = bi;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (bi == lane + 64 * i) {
+                    v[i] = -INFINITY;
+                }
+            }
+        }
+        const float p     = lane < k ? __builtin_expf(sel_v - mx) : 0.f;
+        const float denom = norm_topk ? group_sum<64>(p) : all;
+        const float inv   = 1.0f / denom;
+        if (lane < k) {
+            topk_ids[(size_t)t * k + lane] = min(sel_i, E - 1);  // (in range whatever the logits are: the tables index by it)
+            topk_w[(size_t)t * k + lane]   = p * inv * routed_scale;
+        }
+    }
+}
+
+// Routing tables, one workgroup per expert, no walk over E: the waves split the token-major pair list into contiguous segments.
+// Pass 1 counts, per wave, the pairs of lower experts (-> offsets[e]) and of this expert; one barrier; pass 2 places this expert's
+// pairs by __ballot + popcount prefix behind the waves before it, so the tokens of an expert come in ascending order and the
+// tables are those of moe_route_kernel on the same ids.  No atomics: the placement does not depend on timing.
+__global__ __launch_bounds__(1024) void moe_route_wide_kernel(int* __restrict__ offsets, int* __restrict__ f2n, int* __restrict__ en2f,
+                                                              const int* __restrict__ topk_ids, int T, int E, int k)
+{
+    __shared__ int s_lt[16], s_eq[16];
+    const int      e = blockIdx.x;
+    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int      P     = T * k;
+    const int      seg   = ((P + waves - 1) / waves + 63) / 64 * 64;  // pairs per wave, whole 64-pair chunks
+    const int      begin = min(wave * seg, P), end = min(begin + seg, P);
+    int            lt = 0, eq = 0;
+    for (int p0 = begin; p0 < end; p0 += 64) {
+        const int p  = p0 + lane;
+        const int id = p < end ? topk_ids[p] : E;
+        lt += id < e;
+        eq += id == e;
+    }
+    lt = wave_sum_i32(lt);
+    eq = wave_sum_i32(eq);
+    if (lane == 0) {
+        s_lt[wave] = lt;
+        s_eq[wave] = eq;
+    }
+    __syncthreads();
+    int base = 0, total = 0;
+    for (int w = 0; w < waves; ++w) {
+        base += s_lt[w] + (w < wave ? s_eq[w] : 0);
+        total += s_lt[w];
+    }
+    if (threadIdx.x == 0) {
+        offsets[e] = total;
+        if (e == E - 1) {
+            offsets[E] = P;
+        }
+    }
+    for (int p0 = begin; p0 < end; p0 += 64) {
+        const int      p    = p0 + lane;
+        const bool     hit  = p < end && topk_ids[p] == e;
+        const uint64_t mask = __ballot(hit);
+        if (hit) {
+            const int f = base + __popcll(mask & ((1ull << lane) - 1));
+            const int t = p / k;
+            f2n[f]      = t;
+            en2f[(size_t)(p - t * k) * T + t] = f;
+        }
+        base += __popcll(mask);
+    }
+}
+
 // out[t][h] = fp16( sum_j w[t][j] * y[en2f[j][t]][h] ); 8 columns per thread
 __global__ __launch_bounds__(256) void moe_combine_kernel(half_t* __restrict__ out, int ldo, const half_t* __restrict__ y, int ldy,
                                                           const float* __restrict__ topk_w, const int* __restrict__ en2f, int T,
@@ -191,11 +407,50 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(half_t* __restrict__ o
     *(half8_t*)(out + (size_t)t * ldo + h) = o;
 }
 
+// TM_MOE_ROUTER: auto (default) = the serial kernels up to 64 experts and the wide ones above, wide = the wide ones for every
+// expert count.  Read once; tm_debug_set_moe_router overrides it for A/B runs in one process (a plain global read by every launch:
+// not thread-safe, for tests and the benchmark tool only, set while no forward is being enqueued).
+static int g_moe_router_override = -1;
+void moe_router_override(int mode)
+{
+    g_moe_router_override = mode;
+}
+bool moe_router_wide(int E)
+{
+    static const bool env_wide = [] {
+        const char* v = getenv("TM_MOE_ROUTER");
+        return v && std::string(v) == "wide";
+    }();
+    return E > kMaxExperts || (g_moe_router_override >= 0 ? g_moe_router_override == 1 : env_wide);
+}
+
 int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_t* x, int ldx, const half_t* wg, int T, int H,
                     int E, int k, bool norm_topk, float routed_scale, hipStream_t st)
 {
-    TM_REQUIRE(E >= 1 && E <= kMaxExperts && k >= 1 && k <= kMaxTopK && k <= E, "moe: 1 <= top_k <= experts <= 64, top_k <= 8");
+    TM_REQUIRE(E >= 1 && E <= kMaxExpertsWide && k >= 1 && k <= kMaxTopK && k <= E, "moe: 1 <= top_k <= experts <= 256, top_k <= 8");
     if (T == 0) {
+        return 0;
+    }
+    if (moe_router_wide(E)) {
+        TM_REQUIRE(H % 128 == 0 && ldx % 8 == 0, "moe wide router: hidden % 128 == 0 and 16-byte aligned rows of x");
+        const dim3 grid((T + kGateTile - 1) / kGateTile);
+        const int  nt = ((E + 15) / 16 + 3) / 4;  // column tiles per wave
+#define TM_GATE_WIDE(NT) \
+    moe_gate_wide_kernel<NT><<<grid, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, T, H, E, k, norm_topk ? 1 : 0, routed_scale)
+        if (nt == 1) {
+            TM_GATE_WIDE(1);
+        }
+        else if (nt == 2) {
+            TM_GATE_WIDE(2);
+        }
+        else if (nt == 3) {
+            TM_GATE_WIDE(3);
+        }
+        else {
+            TM_GATE_WIDE(4);
+        }
+#undef TM_GATE_WIDE
+        TM_HIP_CHECK(hipGetLastError());
         return 0;
     }
     moe_gate_kernel<<<T, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, H, E, k, norm_topk ? 1 : 0, routed_scale);
@@ -205,6 +460,12 @@ int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_
 
 int launch_moe_route(int* offsets, int* f2n, int* en2f, const int* topk_ids, int T, int E, int k, hipStream_t st)
 {
+    if (moe_router_wide(E)) {
+        // one workgroup per expert; four waves are enough to walk a decode-sized pair list
+        moe_route_wide_kernel<<<E, (size_t)T * k <= 4096 ? 256 : 1024, 0, st>>>(offsets, f2n, en2f, topk_ids, T, E, k);
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     moe_route_kernel<<<1, 1024, 0, st>>>(offsets, f2n, en2f, topk_ids, T, E, k);
     TM_HIP_CHECK(hipGetLastError());
     return 0;
@@ -266,8 +527,10 @@ int moe_prepare(MoeBlock& m, hipStream_t st)
 }
 
 // out[t] = sum_j w_j * W2_e( silu(W1_e x_t) * (W3_e x_t) ) over the top_k experts e of token t
+// `stages` (kMoeGate .. kMoeCombine) selects the launches: every one of them is a whole forward; a subset runs on the tables and
+// activations an earlier forward left in the same workspace (tools/bench_moe_router.py times the launches one by one)
 int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ldx, int tokens, void* workspace, int* topk_ids_out,
-                float* topk_w_out, hipStream_t st)
+                float* topk_w_out, hipStream_t st, unsigned stages)
 {
     TM_REQUIRE(m.groups13 && m.groups2, "moe: not prepared");
     if (tokens == 0) {
@@ -284,8 +547,12 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
     half_t*      act   = (half_t*)(w + o);
     o                  = (o + pairs * m.inter * 2 + 255) / 256 * 256;
     half_t*      y2    = (half_t*)(w + o);
-    TM_TRY_RC(launch_moe_gate(ids, tw, nullptr, x, ldx, m.gate, tokens, m.hidden, m.experts, m.top_k, m.norm_topk, m.routed_scale, st));
-    TM_TRY_RC(launch_moe_route(offs, f2n, en2f, ids, tokens, m.experts, m.top_k, st));
+    if (stages & kMoeGate) {
+        TM_TRY_RC(launch_moe_gate(ids, tw, nullptr, x, ldx, m.gate, tokens, m.hidden, m.experts, m.top_k, m.norm_topk, m.routed_scale, st));
+    }
+    if (stages & kMoeRoute) {
+        TM_TRY_RC(launch_moe_route(offs, f2n, en2f, ids, tokens, m.experts, m.top_k, st));
+    }
     // expert FFNs: gathered rows of x -> act (gated SiLU fused) -> y2, both grouped over the experts
     const int hint = (int)((pairs + m.experts - 1) / m.experts);  // expected rows per expert
     if (m.groups13_p8) {
@@ -300,19 +567,29 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
         const int    ldsx2 = ((int)pairs + 3) / 4 * 4;
         float*       sx2   = (float*)(aq + pairs * m.inter);
         TM_REQUIRE(ldx == m.hidden || tokens == 1, "moe fp8: x must be row-contiguous");
-        TM_TRY_RC(launch_quant_fp8_rows(xq, sx1, x, ldx, tokens, m.hidden, ldsx1, st));
-        TM_TRY_RC(launch_linear_fp8_grouped(m.w13[0], m.groups13_p8, m.experts, xq, sx1, ldsx1, tokens, act, m.inter, tokens, hint, true,
-                                            offs, f2n, st));
-        TM_TRY_RC(launch_quant_fp8_rows(aq, sx2, act, m.inter, (int)pairs, m.inter, ldsx2, st));
-        TM_TRY_RC(launch_linear_fp8_grouped(m.w2[0], m.groups2_p8, m.experts, aq, sx2, ldsx2, (int)pairs, y2, m.hidden, tokens, hint, false,
-                                            offs, nullptr, st));
+        if (stages & kMoeW13) {
+            TM_TRY_RC(launch_quant_fp8_rows(xq, sx1, x, ldx, tokens, m.hidden, ldsx1, st));
+            TM_TRY_RC(launch_linear_fp8_grouped(m.w13[0], m.groups13_p8, m.experts, xq, sx1, ldsx1, tokens, act, m.inter, tokens, hint, true,
+                                                offs, f2n, st));
+        }
+        if (stages & kMoeW2) {
+            TM_TRY_RC(launch_quant_fp8_rows(aq, sx2, act, m.inter, (int)pairs, m.inter, ldsx2, st));
+            TM_TRY_RC(launch_linear_fp8_grouped(m.w2[0], m.groups2_p8, m.experts, aq, sx2, ldsx2, (int)pairs, y2, m.hidden, tokens, hint, false,
+                                                offs, nullptr, st));
+        }
     }
     else {
-        TM_TRY_RC(launch_linear_grouped(m.w13[0], m.groups13, m.experts, x, ldx, tokens, act, m.inter, tokens, hint, true, offs, f2n, st));
-        TM_TRY_RC(launch_linear_grouped(m.w2[0], m.groups2, m.experts, act, m.inter, (int)pairs, y2, m.hidden, tokens, hint, false, offs,
-                                        nullptr, st));
+        if (stages & kMoeW13) {
+            TM_TRY_RC(launch_linear_grouped(m.w13[0], m.groups13, m.experts, x, ldx, tokens, act, m.inter, tokens, hint, true, offs, f2n, st));
+        }
+        if (stages & kMoeW2) {
+            TM_TRY_RC(launch_linear_grouped(m.w2[0], m.groups2, m.experts, act, m.inter, (int)pairs, y2, m.hidden, tokens, hint, false, offs,
+                                            nullptr, st));
+        }
     }
-    TM_TRY_RC(launch_moe_combine(out, ldo, y2, m.hidden, tw, en2f, tokens, m.hidden, m.top_k, st));
+    if (stages & kMoeCombine) {
+        TM_TRY_RC(launch_moe_combine(out, ldo, y2, m.hidden, tw, en2f, tokens, m.hidden, m.top_k, st));
+    }
     if (topk_ids_out) {
         TM_HIP_CHECK(hipMemcpyAsync(topk_ids_out, ids, pairs * 4, hipMemcpyDeviceToDevice, st));
     }

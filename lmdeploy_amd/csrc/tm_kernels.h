@@ -315,8 +315,9 @@ struct MoeBlock {
 };
 size_t moe_workspace_bytes(const MoeBlock& m, int tokens);
 int    moe_prepare(MoeBlock& m, hipStream_t st);
+enum : unsigned { kMoeGate = 1, kMoeRoute = 2, kMoeW13 = 4, kMoeW2 = 8, kMoeCombine = 16, kMoeAll = 31 };  // launches of moe_forward
 int    moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ldx, int tokens, void* workspace, int* topk_ids_out,
-                   float* topk_w_out, hipStream_t st);
+                   float* topk_w_out, hipStream_t st, unsigned stages = kMoeAll);
 void   moe_free(MoeBlock& m);
 // mixture of experts (moe.hip, grouped GEMM in gemm_w4a16.hip)
 int moe_build_groups(void** d_groups, const LinearWeight* experts, int E, hipStream_t st);
@@ -325,6 +326,9 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
                           hipStream_t st);
 int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_t* x, int ldx, const half_t* wg, int T, int H,
                     int E, int k, bool norm_topk, float routed_scale, hipStream_t st);
+// router choice (TM_MOE_ROUTER): mode -1 = the environment's, 0 = auto (serial kernels up to 64 experts), 1 = wide for every E
+void moe_router_override(int mode);
+bool moe_router_wide(int E);
 int launch_moe_route(int* offsets, int* f2n, int* en2f, const int* topk_ids, int T, int E, int k, hipStream_t st);
 int launch_moe_combine(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, int T, int H, int k,
                        hipStream_t st);

@@ -1,9 +1,10 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
-Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 with AWQ (W4A16 g128), FP8 (e4m3,
-128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights:
+Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen3-MoE with AWQ (W4A16 g128),
+FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (MoE experts: AWQ or FP8 only):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
-                                     qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head)
+                                     qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head;
+                                     Qwen3-MoE: mlp.gate router + mlp.experts.X.{gate,up,down}_proj, qwen3.py:110-121)
   * FP8 normalize / dequant          lmdeploy/turbomind/weight_format.py:349-384 (HF [out, in] -> [in, out], scales alike)
   * AWQ normalize (unpack order)     lmdeploy/turbomind/weight_format.py:200-234
   * RoPE q/k channel permutation     lmdeploy/turbomind/models/utils.py:306-373 (weight, scales and zeros alike)
@@ -60,8 +61,32 @@ class ModelConfig:
     tie_word_embeddings: bool = False
 
 
-# dense Qwen decoders: the Llama layout plus the attention prologue (exact names: the MoE variants stay refused)
-QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM')
+# Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
+# in every layer) is served, Qwen2-MoE (shared expert behind a sigmoid gate: a different block) stays refused
+QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM')
+QWEN3_MOE_KEYS = ('num_experts', 'num_experts_per_tok', 'moe_intermediate_size')
+
+
+def _qwen3_moe_fields(arch: str, c: dict, quantized: bool) -> dict:
+    """the MoE fields of a Qwen3MoeForCausalLM config, or NotImplementedError with the reason.  The three geometry keys must be in
+    config.json: a library default would describe some other checkpoint."""
+    missing = [k for k in QWEN3_MOE_KEYS if c.get(k) is None]
+    if missing:
+        raise NotImplementedError(f'{arch}: config.json lacks {", ".join(missing)}')
+    E, k = int(c['num_experts']), int(c['num_experts_per_tok'])
+    if c.get('mlp_only_layers'):
+        raise NotImplementedError(f'{arch} with mlp_only_layers {c["mlp_only_layers"]}: dense layers among the sparse ones are not '
+                                  f'implemented (the MoE switch is model-wide)')
+    if int(c.get('decoder_sparse_step', 1)) != 1:
+        raise NotImplementedError(f'{arch} with decoder_sparse_step {c["decoder_sparse_step"]}: every layer must be sparse (the MoE '
+                                  f'switch is model-wide)')
+    if not 1 <= E <= 256 or not 1 <= k <= 8 or k > E:
+        raise NotImplementedError(f'{arch} with num_experts {E}, num_experts_per_tok {k}: the router serves up to 256 experts, top-8')
+    if not quantized:
+        raise NotImplementedError(f'{arch} with fp16 / bf16 experts: the grouped expert GEMM serves AWQ (u4) and block-128 FP8 (e4m3) '
+                                  f'weights only')
+    return dict(inter=int(c['moe_intermediate_size']), moe_experts=E, moe_top_k=k,
+                moe_norm_topk=bool(c.get('norm_topk_prob', False)), moe_routed_scale=1.0)
 
 
 def read_config(model_path: str) -> ModelConfig:
@@ -72,13 +97,13 @@ def read_config(model_path: str) -> ModelConfig:
     qwen = arch in QWEN_ARCHS
     if kind == 'llama' and not qwen and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
         raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 '
-                                  f'dense decoders')
+                                  f'decoders and Qwen3-MoE')
     H = c['hidden_size']
     heads = c['num_attention_heads']
     D = c.get('head_dim') or H // heads
     attn_bias = qk_norm = 0
     if qwen:
-        kind = 'qwen3' if arch == 'Qwen3ForCausalLM' else 'qwen2'
+        kind = 'qwen2' if arch == 'Qwen2ForCausalLM' else 'qwen3'
         if c.get('use_sliding_window'):
             raise NotImplementedError(f'{arch} with use_sliding_window: sliding-window attention is not implemented')
         if D != 128:
@@ -119,13 +144,16 @@ def read_config(model_path: str) -> ModelConfig:
             merged += [t for t in (ge if isinstance(ge, (list, tuple)) else [ge]) if t not in merged]
             eos = merged if len(merged) > 1 else merged[0]
     c = dict(c, eos_token_id=eos)
+    if arch == 'Qwen3MoeForCausalLM':
+        moe = _qwen3_moe_fields(arch, c, q is not None)
+    else:
+        moe = dict(inter=c['intermediate_size'], moe_experts=int(c.get('num_local_experts', 0) or 0) if 'Mixtral' in arch else 0,
+                   moe_top_k=int(c.get('num_experts_per_tok', 0) or 0) if 'Mixtral' in arch else 0)
     return ModelConfig(hidden=H, layers=c['num_hidden_layers'], q_heads=heads,
-                       kv_heads=c.get('num_key_value_heads', heads), head_dim=D, inter=c['intermediate_size'],
+                       kv_heads=c.get('num_key_value_heads', heads), head_dim=D,
                        vocab=c['vocab_size'], rms_eps=float(c.get('rms_norm_eps', 1e-5)), rope=rope, arch=kind,
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
-                       max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt,
-                       moe_experts=int(c.get('num_local_experts', 0) or 0) if 'Mixtral' in arch else 0,
-                       moe_top_k=int(c.get('num_experts_per_tok', 0) or 0) if 'Mixtral' in arch else 0,
+                       max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, **moe,
                        attn_bias=attn_bias, qk_norm=qk_norm, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
@@ -204,11 +232,14 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
             v = _linear(t, p + '.self_attn.v_proj', cfg.quantized)
             wo = _linear(t, p + '.self_attn.o_proj', cfg.quantized)
             moe = None
-            if cfg.moe_experts:      # Mixtral (models/mixtral.py:73-106): router + per-expert w1 / w3 / w2
-                m = p + '.block_sparse_moe'
+            if cfg.moe_experts:      # router [E, H] (unquantised also in AWQ checkpoints) -> fp16 [H][E]; per-expert w1 / w3 / w2
+                # Mixtral (models/mixtral.py:73-106): block_sparse_moe.experts.X.w1 / w3 / w2; Qwen3-MoE (models/qwen3.py:110-121):
+                # mlp.experts.X.gate_proj / up_proj / down_proj
+                m, names = ((p + '.mlp', ('gate_proj', 'up_proj', 'down_proj')) if cfg.arch == 'qwen3'
+                            else (p + '.block_sparse_moe', ('w1', 'w3', 'w2')))
                 moe = dict(moe_gate=np.ascontiguousarray(t.get(m + '.gate.weight').astype(np.float16).T), experts=[])
                 for x in range(cfg.moe_experts):
-                    e1, e3, e2 = (_linear(t, f'{m}.experts.{x}.{n}', cfg.quantized) for n in ('w1', 'w3', 'w2'))
+                    e1, e3, e2 = (_linear(t, f'{m}.experts.{x}.{n}', cfg.quantized) for n in names)
                     moe['experts'].append(dict(w1w3=_fuse_w1w3(e1, e3), w2=e2))
                 w1 = w3 = w2 = None
             else:

@@ -124,6 +124,10 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
         _emit(slots, p + '.attention.w_qkv', _shard_linear(L['w_qkv'], 'col', tp, rank, G, qkv_slices))
         _emit(slots, p + '.attention.wo', _shard_linear(L['wo'], 'row', tp, rank, G))
         if 'experts' in L:     # mixture of experts: replicated router, every expert sharded like the dense FFN
+            if tp > 1 and i_l % 128:
+                # the rank's half of a *.w1w3.scales row is i_l / 128 blocks, and the fp8 gated linear needs N = 2 * i_l % 256 == 0
+                raise ValueError(f'moe experts of width {I} do not shard over tp = {tp}: {I} / {tp} = {I / tp:g} is not a multiple '
+                                 f'of 128')
             slots[p + '.moe_ffn.gate.weight'] = np.ascontiguousarray(L['moe_gate'], dtype=np.float16)
             for x, E_ in enumerate(L['experts']):
                 q = f'{p}.moe_ffn.experts.{x}'
