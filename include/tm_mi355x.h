@@ -259,17 +259,31 @@ int    tm_linear_destroy(tm_linear* w);
  * flat row); the tokens of an expert are in ascending order.
  * tm_moe_forward_stages enqueues a subset of tm_moe_forward's launches (bits: gate + top-k 1, routing tables 2, grouped w1w3 with its
  * activation quantisation 4, grouped w2 8, combine 16; 31 = tm_moe_forward) on what an earlier forward of the same x and tokens
- * left in `workspace`: the measurement tool times the launches one by one with it. */
+ * left in `workspace`: the measurement tool times the launches one by one with it.
+ * Shared expert (Qwen2-MoE: the layer has a routed MoE AND a dense feed_forward, the shared expert, whose output the combine scales per
+ * token by a sigmoid gate before the routed experts are added -- models/llama/unified_decoder.cc:295-318, moe_ffn_layer.cc:295-325,
+ * invokeMoeCombine kernels/gemm/moe_utils_v2.cu:1032-1105; weights lmdeploy/turbomind/models/qwen2.py:110-128):
+ * tm_moe_set_shared_gate copies the gate vector (device fp16 [hidden]) into the block; from then on the block is run by
+ * tm_moe_forward_shared, whose `shared` (device fp16 [tokens][hidden]) is the shared expert's FFN output for the same x:
+ *   out[t] = fp16( float(shared[t]) * sigmoid(x_t . gate) + sum_e w_e(t) * float(y_e(t)) )
+ * with the logit and the sum in fp32, in ONE combine launch.  `shared` may equal `out` (the reference combines in place); x must not.
+ * tm_moe_forward / tm_moe_forward_stages on such a block return TM_INVALID instead of dropping the term;
+ * tm_moe_forward_shared_stages is tm_moe_forward_stages for it (`shared` is read by the combine stage only). */
 typedef struct tm_moe tm_moe;
 int    tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk,
                      float routed_scale);
 int    tm_moe_set_gate(tm_moe* m, const void* gate, tm_stream_t st);
+int    tm_moe_set_shared_gate(tm_moe* m, const void* gate_fp16_hidden, tm_stream_t st);
 int    tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void* w13_scales, const void* w13_zeros,
                          const void* w2_weight, const void* w2_scales, const void* w2_zeros, tm_stream_t st);
 size_t tm_moe_workspace(const tm_moe* m, int tokens);
 int    tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* workspace, int* topk_ids_out, float* topk_w_out,
                       tm_stream_t st);
 int    tm_moe_forward_stages(tm_moe* m, void* out, const void* x, int tokens, void* workspace, unsigned stages, tm_stream_t st);
+int    tm_moe_forward_shared(tm_moe* m, void* out, const void* x, const void* shared, int tokens, void* workspace, int* topk_ids_out,
+                             float* topk_w_out, tm_stream_t st);
+int    tm_moe_forward_shared_stages(tm_moe* m, void* out, const void* x, const void* shared, int tokens, void* workspace,
+                                    int* topk_ids_out, float* topk_w_out, unsigned stages, tm_stream_t st);
 int    tm_moe_router(tm_moe* m, const void* x, int tokens, int* topk_ids, float* topk_w, float* logits_out, int* offsets, int* f2n,
                      int* en2f, tm_stream_t st);
 int    tm_moe_destroy(tm_moe* m);
@@ -390,6 +404,11 @@ typedef struct tm_model_config {
      * `inter` (sharded over tp like the dense FFN), `moe_top_k` per token (Mixtral: 8 / 2, norm_topk = 1) */
     int   moe_experts, moe_top_k, moe_norm_topk;
     float moe_routed_scale;
+    /* Qwen2-MoE shared expert (0 = none; needs moe_experts > 0): every MoE layer ALSO has a dense FFN of this width (sharded over tp like
+     * the dense FFN; moe_shared_inter / tp % 128 == 0) in the slots "layers.{i}.feed_forward.w1w3.*" / ".w2.*" -- the reference's names:
+     * the shared expert is the layer's feed_forward -- and a gate "layers.{i}.moe_ffn.shared_gate.weight" fp16 [hidden], replicated.
+     * FFN output = sigmoid(x . gate) * feed_forward(x) + the routed experts (tm_moe_forward_shared). */
+    int   moe_shared_inter;
     /* Qwen attention prologue (0 = off): attn_bias -> slot "layers.{i}.attention.w_qkv.bias" fp16 [local qkv columns] added to
      * q / k / v (Qwen2); qk_norm -> slots "layers.{i}.attention.{q,k}_norm.weight" fp16 [head_dim], per-head RMSNorm of q / k with
      * rms_eps (Qwen3).  Order: norm -> bias -> RoPE. */

@@ -56,7 +56,7 @@ class ModelConfig(C.Structure):
                 ('rope_type', c_int), ('rope_factor', c_float), ('rope_low_freq_factor', c_float),
                 ('rope_high_freq_factor', c_float), ('rope_original_max_position', c_int), ('group_size', c_int),
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
-                ('moe_routed_scale', c_float), ('attn_bias', c_int), ('qk_norm', c_int)]
+                ('moe_routed_scale', c_float), ('moe_shared_inter', c_int), ('attn_bias', c_int), ('qk_norm', c_int)]
 
 
 class EngineConfig(C.Structure):
@@ -100,9 +100,13 @@ _SIGNATURES = {
     'tm_sample_workspace': (c_size_t, [c_int]),
     'tm_moe_create': (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int, c_float]),
     'tm_moe_set_gate': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'tm_moe_set_shared_gate': (c_int, [c_void_p, c_void_p, c_void_p]),
     'tm_moe_set_expert': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_moe_workspace': (c_size_t, [c_void_p, c_int]),
     'tm_moe_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_moe_forward_shared': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_moe_forward_shared_stages': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, C.c_uint,
+                                             c_void_p]),
     'tm_moe_forward_stages': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, C.c_uint, c_void_p]),
     'tm_moe_router': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_moe_destroy': (c_int, [c_void_p]),

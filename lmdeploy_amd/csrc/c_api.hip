@@ -612,6 +612,17 @@ int tm_moe_set_gate(tm_moe* m, const void* gate, tm_stream_t st)
     return 0;
 }
 
+int tm_moe_set_shared_gate(tm_moe* m, const void* gate, tm_stream_t st)
+{
+    TM_REQUIRE(m && gate, "null pointer");
+    const size_t bytes = (size_t)m->m.hidden * 2;
+    if (!m->m.shared_gate) {
+        TM_HIP_CHECK(hipMalloc((void**)&m->m.shared_gate, bytes));
+    }
+    TM_HIP_CHECK(hipMemcpyAsync(m->m.shared_gate, gate, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st));
+    return 0;
+}
+
 int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void* w13_scales, const void* w13_zeros,
                       const void* w2_weight, const void* w2_scales, const void* w2_zeros, tm_stream_t st)
 {
@@ -638,6 +649,7 @@ int tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* worksp
                    tm_stream_t st)
 {
     TM_REQUIRE(m && out && x && workspace, "null pointer");
+    TM_REQUIRE(!m->m.shared_gate, "moe: the block has a shared gate: tm_moe_forward_shared takes the shared expert's output");
     if (!m->prepared) {
         TM_TRY_RC(moe_prepare(m->m, (hipStream_t)st));
         m->prepared = true;
@@ -646,10 +658,32 @@ int tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* worksp
                        (hipStream_t)st);
 }
 
+int tm_moe_forward_shared_stages(tm_moe* m, void* out, const void* x, const void* shared, int tokens, void* workspace, int* topk_ids_out,
+                                 float* topk_w_out, unsigned stages, tm_stream_t st)
+{
+    TM_REQUIRE(m && out && x && shared && workspace, "null pointer");
+    TM_REQUIRE(m->m.shared_gate, "moe: no shared gate set (tm_moe_set_shared_gate)");
+    TM_REQUIRE(stages >= 1 && stages <= kMoeAll, "moe stages: a non-empty subset of gate 1, route 2, w1w3 4, w2 8, combine 16");
+    TM_REQUIRE(x != out, "moe: x is read by the combine and must not be the output");
+    if (!m->prepared) {
+        TM_TRY_RC(moe_prepare(m->m, (hipStream_t)st));
+        m->prepared = true;
+    }
+    return moe_forward(m->m, (half_t*)out, m->m.hidden, (const half_t*)x, m->m.hidden, tokens, workspace, topk_ids_out, topk_w_out,
+                       (hipStream_t)st, stages, (const half_t*)shared);
+}
+
+int tm_moe_forward_shared(tm_moe* m, void* out, const void* x, const void* shared, int tokens, void* workspace, int* topk_ids_out,
+                          float* topk_w_out, tm_stream_t st)
+{
+    return tm_moe_forward_shared_stages(m, out, x, shared, tokens, workspace, topk_ids_out, topk_w_out, kMoeAll, st);
+}
+
 int tm_moe_forward_stages(tm_moe* m, void* out, const void* x, int tokens, void* workspace, unsigned stages, tm_stream_t st)
 {
     TM_REQUIRE(m && out && x && workspace, "null pointer");
     TM_REQUIRE(stages >= 1 && stages <= kMoeAll, "moe stages: a non-empty subset of gate 1, route 2, w1w3 4, w2 8, combine 16");
+    TM_REQUIRE(!m->m.shared_gate, "moe: the block has a shared gate: tm_moe_forward_shared_stages takes the shared expert's output");
     if (!m->prepared) {
         TM_TRY_RC(moe_prepare(m->m, (hipStream_t)st));
         m->prepared = true;

@@ -106,14 +106,18 @@ static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, 
 // gemm_w4a16.hip): add_linear cannot report an error, so engine creation refuses such a model up front
 static int check_linear_images(const tm_model_config& m, int tp)
 {
-    const int q = m.q_heads / tp, kv = std::max(1, m.kv_heads / tp), inter = m.inter / tp;
+    const int q = m.q_heads / tp, kv = std::max(1, m.kv_heads / tp), inter = m.inter / tp, shared = m.moe_shared_inter / tp;
     const struct {
         const char* name;
         int         K, N, type;
     } lin[] = {{"w_qkv", m.hidden, (q + 2 * kv) * m.head_dim, m.weight_type}, {"wo", q * m.head_dim, m.hidden, m.weight_type},
                {"w1w3", m.hidden, 2 * inter, m.weight_type}, {"w2", inter, m.hidden, m.weight_type},
-               {"lm_head", m.hidden, m.vocab / tp, TM_WEIGHT_F16}};
+               {"lm_head", m.hidden, m.vocab / tp, TM_WEIGHT_F16},
+               {"shared w1w3", m.hidden, 2 * shared, m.weight_type}, {"shared w2", shared, m.hidden, m.weight_type}};
     for (const auto& l : lin) {
+        if (l.K == 0 || l.N == 0) {  // no shared expert
+            continue;
+        }
         const size_t bytes = gemm_general_image_bytes(l.K, l.N, l.type);
         TM_REQUIRE(bytes < kGeneralImageLimit, std::string(l.name) + " " + std::to_string(l.K) + " x " + std::to_string(l.N)
                                                    + ": its general-kernel image of " + std::to_string(bytes)
@@ -209,6 +213,9 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8, "weight_type");
     TM_REQUIRE(c->max_batch_size >= 1 && c->max_batch_size <= 1024 && c->session_len >= 1,
                "1 <= max_batch_size <= 1024, session_len >= 1");
+    TM_REQUIRE(m.moe_shared_inter >= 0 && (m.moe_shared_inter == 0 || m.moe_experts > 0), "moe_shared_inter needs moe_experts > 0");
+    TM_REQUIRE(m.moe_shared_inter % c->tp == 0 && (m.moe_shared_inter / c->tp) % 128 == 0,
+               "moe_shared_inter / tp must be a multiple of 128");
     TM_TRY(check_linear_images(m, c->tp));
     TM_HIP_CHECK(hipSetDevice(c->device));
 
@@ -218,6 +225,7 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     e->q_heads     = m.q_heads / c->tp;
     e->kv_heads    = std::max(1, m.kv_heads / c->tp);
     e->inter       = m.inter / c->tp;
+    e->shared_inter = m.moe_shared_inter / c->tp;
     e->vocab_local = m.vocab / c->tp;
     {
         const char* fc = getenv("TM_FORCE_COMM");
@@ -254,6 +262,12 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
                 const std::string q = p + ".moe_ffn.experts." + std::to_string(x);
                 add_linear(e, L.ex13[x], q + ".w1w3", m.hidden, 2 * e->inter, m.weight_type);
                 add_linear(e, L.ex2[x], q + ".w2", e->inter, m.hidden, m.weight_type);
+            }
+            if (e->shared_inter > 0) {  // the shared expert: the layer's dense feed_forward at its own width + the sigmoid gate [H]
+                L.has_shared = true;
+                add_linear(e, L.w13, p + ".feed_forward.w1w3", m.hidden, 2 * e->shared_inter, m.weight_type, 3);
+                add_linear(e, L.w2, p + ".feed_forward.w2", e->shared_inter, m.hidden, m.weight_type, 4);
+                e->slots[p + ".moe_ffn.shared_gate.weight"].bytes = (int64_t)m.hidden * 2;  // fp16 [H], replicated
             }
         }
         else {
@@ -377,6 +391,11 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
                 TM_TRY(linear(L.ex13[x]));
                 TM_TRY(linear(L.ex2[x]));
             }
+            if (L.has_shared) {
+                TM_TRY(linear(L.w13));
+                TM_TRY(linear(L.w2));
+                TM_TRY(vec(p + ".moe_ffn.shared_gate.weight", m.hidden, 0.f, 0.05f));
+            }
         }
         else {
             TM_TRY(linear(L.w13));
@@ -448,6 +467,17 @@ int tm_engine_process_weights(tm_engine* e)
             TM_REQUIRE(g.filled, "weight not loaded: " + p + ".moe_ffn.gate.weight");
             L.moe.gate = (half_t*)g.dev;  // used in place (freed by moe_free)
             g.dev      = nullptr;
+            if (L.has_shared) {
+                for (LinearSlots* l : {&L.w13, &L.w2}) {
+                    if (!l->w.packed && !l->w.packed32) {
+                        TM_TRY(prepare_linear(e, *l));
+                    }
+                }
+                Slot& sg = e->slots[p + ".moe_ffn.shared_gate.weight"];
+                TM_REQUIRE(sg.filled, "weight not loaded: " + p + ".moe_ffn.shared_gate.weight");
+                L.moe.shared_gate = (half_t*)sg.dev;  // used in place (freed by moe_free)
+                sg.dev            = nullptr;
+            }
             TM_TRY(moe_prepare(L.moe, e->stream));
         }
         else {
@@ -499,17 +529,21 @@ int tm_engine_start(tm_engine* e)
     TM_TRY(dmalloc(&e->d_tmp, T * e->hidden));
     TM_TRY(dmalloc(&e->d_qkv, T * e->qkv_n));
     TM_TRY(dmalloc(&e->d_attn, T * e->q_heads * e->D));
-    TM_TRY(dmalloc(&e->d_act, T * e->inter));
+    TM_TRY(dmalloc(&e->d_act, T * std::max(e->inter, e->shared_inter)));
+    if (e->shared_inter > 0) {
+        TM_TRY(dmalloc(&e->d_shared, T * e->hidden));
+    }
     TM_TRY(dmalloc(&e->d_logits, (size_t)B * e->vocab_local));
     TM_TRY(dmalloc(&e->d_last, (size_t)B * e->hidden));
     // split-K workspace: decode-sized problems only (M <= 64 rows x widest N x 16 slabs)
-    e->gemm_ws_bytes = (size_t)16 * 64 * std::max(std::max(e->qkv_n, 2 * e->inter), e->hidden) * sizeof(float);
+    const int wide_n = std::max(std::max(e->qkv_n, 2 * std::max(e->inter, e->shared_inter)), e->hidden);  // widest linear output
+    e->gemm_ws_bytes = (size_t)16 * 64 * wide_n * sizeof(float);
     TM_HIP_CHECK(hipMalloc((void**)&e->d_gemm_ws, e->gemm_ws_bytes));
     {
         const size_t tiles = (size_t)(e->hidden + 63) / 64;
         TM_TRY(dmalloc(&e->d_ss, tiles * kFoldMaxRows));
         // arrival counters: one per (column tile, row block) of the widest decode linear at its narrowest tile (64 columns, 32 rows)
-        const size_t ntk = (size_t)(std::max(std::max(e->qkv_n, 2 * e->inter), e->hidden) + 63) / 64 * (kFoldMaxRows / 32);
+        const size_t ntk = (size_t)(wide_n + 63) / 64 * (kFoldMaxRows / 32);
         const char* fm   = getenv("TM_FOLD_MAX_M");
         // default 64: at batch 128 (BASELINE config 3) the folded layer is parity-green but measured SLOWER than the reduce-norm launches it
         // removes (InternLM2-20B: 10.83 .. 10.91 vs 10.43 ms per step, profiles/r06_fold128_*): its producers are limited to the 32-row-block
@@ -762,8 +796,10 @@ int tm_engine_destroy(tm_engine* e)
             moe_free(L.moe);
         }
     }
-    if (e->d_moe_ws) {
-        (void)hipFree(e->d_moe_ws);
+    for (void* q : {e->d_moe_ws, (void*)e->d_shared}) {
+        if (q) {
+            (void)hipFree(q);
+        }
     }
     linear_weight_free(e->output.w);
     for (auto& kv : e->slots) {

@@ -530,8 +530,16 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
         TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O));
         if (L.is_moe) {
             // router + grouped expert FFNs + combine -> d_tmp, then (all-reduce +) residual + RMSNorm as for the dense FFN
+            const half_t* shared = nullptr;
+            if (L.has_shared) {
+                // Qwen2-MoE: the shared expert is the layer's dense FFN (unified_decoder.cc:295-318); its output waits in d_shared for
+                // the combine, which scales it by sigmoid(x . shared_gate) and adds the routed experts (moe_combine_shared_kernel)
+                TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->shared_inter, M, true)));
+                TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act, e->shared_inter, e->d_shared, e->hidden, M, false)));
+                shared = e->d_shared;
+            }
             TM_PROF(P_GEMM_GATE_UP, TM_TRY(moe_forward(L.moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr,
-                                                       nullptr, st)));
+                                                       nullptr, st, kMoeAll, shared)));
             TM_TRY(reduce_residual_norm(e, M, next_norm));
             continue;
         }

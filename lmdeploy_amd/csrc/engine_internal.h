@@ -65,8 +65,10 @@ struct Layer {
     half_t*     qkv_bias  = nullptr;
     half_t*     q_norm    = nullptr;
     half_t*     k_norm    = nullptr;
-    // mixture of experts: the dense w13 / w2 are unused; gate slot + per-expert slots feed `moe`
+    // mixture of experts: gate slot + per-expert slots feed `moe`; the dense w13 / w2 are unused unless the layer has a shared
+    // expert (tm_model_config.moe_shared_inter: Qwen2-MoE), which IS the dense FFN at the shared width, gated inside moe's combine
     bool                     is_moe = false;
+    bool                     has_shared = false;
     std::vector<LinearSlots> ex13, ex2;
     MoeBlock                 moe;
 };
@@ -79,6 +81,8 @@ struct tm_engine {
     tm_engine_config cfg{};
     // local (per-rank) dims
     int q_heads = 0, kv_heads = 0, inter = 0, vocab_local = 0, hidden = 0, D = 128;
+    int shared_inter = 0;  // Qwen2-MoE: this rank's width of the shared expert (0: none)
+    int ffn_inter() const { return shared_inter > 0 ? shared_inter : inter; }  // width of the DENSE w1w3 / w2 slots of a layer
     int qkv_n = 0;
 
     hipStream_t  stream = nullptr;
@@ -227,6 +231,7 @@ struct tm_engine {
     half_t*   d_logits_gather = nullptr;  // tp > 1 + sampling: [tp][max_batch][vocab / tp] all-gathered shards ...
     half_t*   d_logits_full   = nullptr;  // ... and the full rows [max_batch][vocab] every rank samples from
     void*     d_moe_ws    = nullptr;  // routing tables + expert activations of one forward (moe_workspace_bytes)
+    half_t*   d_shared    = nullptr;  // [max_tokens][hidden] the shared expert's FFN output of one forward (moe_shared_inter > 0)
     // logprobs of the generated tokens (tm_engine_set_logprobs, static batch): records [batch][max_new] x [cap] next to d_generated
     int    logprobs_next = 0, logprobs_n = 0;
     bool   logprobs_on = false, graph_logprobs = false;

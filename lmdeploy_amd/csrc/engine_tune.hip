@@ -11,7 +11,8 @@ extern "C" {
 // ------------------------------------------------------------------------------------------------------------------
 // Measured GEMM dispatch (reference: the warm-up tuning of turbomind.cc:363-487 -> gemm::Gemm::Run's DispatchCache,
 // kernels/gemm/gemm.cu:92-224; TM_GEMM_TUNE / TM_GEMM_EXPORT / TM_GEMM_IMPORT).  For the decode batch M <= 256 every
-// dense linear role of the model (w_qkv, wo, w1w3, w2) is timed with every (workgroup shape, split-K) candidate of the
+// dense linear role of the model (w_qkv, wo, w1w3, w2; on a MoE model with a shared expert w1w3 / w2 are that expert's, its w2
+// followed by the MoE combine) is timed with every (workgroup shape, split-K) candidate of the
 // decode kernel as ONE hipGraph over the model's own layers -- distinct weights per node, more bytes than the Infinity
 // Cache holds, as in a decode step -- and each node is followed by the kernel that consumes its result (the fused split-K
 // reduce + residual + RMSNorm for wo / w2, the slab reduce standing in for the attention prologue for w_qkv): a split-K
@@ -24,6 +25,12 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
                "tuning: 1 <= M <= 256 (a decode batch) or a prefill size class 512, 1024, ... 8192, within max_prefill_token_num");
     half_t* const norm_out = M <= e->cfg.max_batch_size ? e->d_last : e->d_x;  // (d_x is the INPUT of w_qkv / w1w3 only)
     hipStream_t st = e->stream;
+    // Qwen2-MoE: roles w1w3 / w2 are the shared expert (the layer's dense FFN at the shared width).  Its w2 writes d_shared and is
+    // consumed by the MoE combine, not by the reduce-norm: it is timed with that launch behind it, on the routing tables one whole
+    // MoE forward of the stand-in activations leaves in the workspace first
+    const bool    shared_ffn = !e->layers.empty() && e->layers[0].has_shared;
+    const int     ffw        = e->ffn_inter();
+    half_t* const w2_out     = shared_ffn ? e->d_shared : e->d_tmp;
     struct Role {
         const char*   name;
         int           which;  // 0 qkv, 1 wo, 2 w13, 3 w2
@@ -35,8 +42,8 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
     };
     const Role roles[4] = {{"w_qkv", 0, e->d_x, e->hidden, e->d_qkv, e->qkv_n, false},
                            {"wo", 1, e->d_attn, e->q_heads * e->D, e->d_tmp, e->hidden, false},
-                           {"w1w3", 2, e->d_x, e->hidden, e->d_act, e->inter, true},
-                           {"w2", 3, e->d_act, e->inter, e->d_tmp, e->hidden, false}};
+                           {"w1w3", 2, e->d_x, e->hidden, e->d_act, ffw, true},
+                           {"w2", 3, e->d_act, ffw, w2_out, e->hidden, false}};
     hipEvent_t e0, e1;
     TM_HIP_CHECK(hipEventCreate(&e0));
     TM_HIP_CHECK(hipEventCreate(&e1));
@@ -45,14 +52,18 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
     // run ~45 % faster than on real data and mis-rank the compute-bound candidates (launch_fill_uniform_f16)
     TM_TRY(launch_fill_uniform_f16(e->d_x, (size_t)M * e->hidden, 1.7f, 1u, st));
     TM_TRY(launch_fill_uniform_f16(e->d_attn, (size_t)M * e->q_heads * e->D, 0.5f, 2u, st));
-    TM_TRY(launch_fill_uniform_f16(e->d_act, (size_t)M * e->inter, 0.5f, 3u, st));
+    TM_TRY(launch_fill_uniform_f16(e->d_act, (size_t)M * ffw, 0.5f, 3u, st));
+    if (shared_ffn) {
+        TM_TRY(launch_fill_uniform_f16(e->d_shared, (size_t)M * e->hidden, 0.5f, 5u, st));
+        TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st, kMoeAll, e->d_shared));
+    }
     TM_HIP_CHECK(hipMemsetAsync(e->d_resid, 0, (size_t)M * e->hidden * 2, st));
     TM_HIP_CHECK(hipMemsetAsync(e->d_ss, 0x3f, (size_t)(e->hidden / 64) * kFoldMaxRows * sizeof(float), st));  // finite stand-in sums of squares (0.747)
     int rc = 0;
     for (const Role& r : roles) {
         std::vector<const LinearWeight*> ws;
         for (Layer& L : e->layers) {
-            if (r.which >= 2 && L.is_moe) {
+            if (r.which >= 2 && L.is_moe && !L.has_shared) {
                 continue;
             }
             const LinearWeight* w = r.which == 0 ? &L.qkv.w : r.which == 1 ? &L.wo.w : r.which == 2 ? &L.w13.w : &L.w2.w;
@@ -92,7 +103,7 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
             if (gemm_workspace_bytes(M, w0.N, cfg.splits) > e->gemm_ws_bytes) {
                 continue;
             }
-            const bool norm_consumer = (r.which == 1 || r.which == 3) && !e->use_comm;
+            const bool norm_consumer = (r.which == 1 || (r.which == 3 && !shared_ffn)) && !e->use_comm;
             // decode batches of an engine that folds the RMSNorm into the GEMMs (linear_fold_*): the candidates are timed as they
             // will run -- wo / w2 with the residual / sums-of-squares epilogue (and the in-launch slab merge) instead of the
             // reduce-norm launch, w_qkv / w1w3 with the row factor from d_ss -- and only tiles whose kernel carries that code
@@ -135,6 +146,10 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
                     if (norm_consumer) {
                         TM_TRY(launch_residual_rmsnorm(norm_out, e->d_resid, slabs > 1 ? nullptr : e->d_tmp, slabs > 1 ? e->d_gemm_ws : nullptr,
                                                        slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st));
+                    }
+                    else if (r.which == 3 && shared_ffn) {  // the shared expert's consumer: the combine launch
+                        TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st,
+                                           kMoeCombine, e->d_shared));
                     }
                 }
                 return 0;
@@ -282,6 +297,10 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
     hipStream_t st = e->stream;
     const int   Mb = dec32_m_bucket(M);
     int         tv[4];
+    // Qwen2-MoE: the shared expert's w2 is consumed by the MoE combine (see tune_decode_gemms)
+    const bool    shared_ffn = !e->layers.empty() && e->layers[0].has_shared;
+    const int     ffw        = e->ffn_inter();
+    half_t* const w2_out     = shared_ffn ? e->d_shared : e->d_tmp;
     // ---- dense linears of the general kernel: per role over the layers (with the consumer of wo / w2), then the lm_head ----
     struct Role {
         const char*   name;
@@ -295,12 +314,16 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
     half_t* const norm_out = M <= e->cfg.max_batch_size ? e->d_last : e->d_x;
     const Role roles[5] = {{"w_qkv", 0, e->d_x, e->hidden, e->d_qkv, e->qkv_n, false},
                            {"wo", 1, e->d_attn, e->q_heads * e->D, e->d_tmp, e->hidden, false},
-                           {"w1w3", 2, e->d_x, e->hidden, e->d_act, e->inter, true},
-                           {"w2", 3, e->d_act, e->inter, e->d_tmp, e->hidden, false},
+                           {"w1w3", 2, e->d_x, e->hidden, e->d_act, ffw, true},
+                           {"w2", 3, e->d_act, ffw, w2_out, e->hidden, false},
                            {"lm_head", 4, e->d_last, e->hidden, e->d_logits, e->vocab_local, false}};
     TM_TRY(launch_fill_uniform_f16(e->d_x, (size_t)M * e->hidden, 1.7f, 1u, st));
     TM_TRY(launch_fill_uniform_f16(e->d_attn, (size_t)M * e->q_heads * e->D, 0.5f, 2u, st));
-    TM_TRY(launch_fill_uniform_f16(e->d_act, (size_t)M * e->inter, 0.5f, 3u, st));
+    TM_TRY(launch_fill_uniform_f16(e->d_act, (size_t)M * ffw, 0.5f, 3u, st));
+    if (shared_ffn) {
+        TM_TRY(launch_fill_uniform_f16(e->d_shared, (size_t)M * e->hidden, 0.5f, 5u, st));
+        TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st, kMoeAll, e->d_shared));
+    }
     for (const Role& r : roles) {
         std::vector<const LinearWeight*> ws;
         if (r.which == 4) {
@@ -311,7 +334,7 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
         }
         else {
             for (Layer& L : e->layers) {
-                if (r.which >= 2 && L.is_moe) {
+                if (r.which >= 2 && L.is_moe && !L.has_shared) {
                     continue;
                 }
                 const LinearWeight* w = r.which == 0 ? &L.qkv.w : r.which == 1 ? &L.wo.w : r.which == 2 ? &L.w13.w : &L.w2.w;
@@ -341,7 +364,7 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
         if (!has) {
             cand[nc++] = heur;
         }
-        const bool norm_consumer = (r.which == 1 || r.which == 3) && !e->use_comm;
+        const bool norm_consumer = (r.which == 1 || (r.which == 3 && !shared_ffn)) && !e->use_comm;
         float      best = 1e30f, t_heur = 1e30f;
         GemmConfig bc = heur;
         for (int i = 0; i < nc; ++i) {
@@ -356,6 +379,10 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
                     if (norm_consumer) {
                         TM_TRY(launch_residual_rmsnorm(norm_out, e->d_resid, slabs > 1 ? nullptr : e->d_tmp, slabs > 1 ? e->d_gemm_ws : nullptr,
                                                        slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st));
+                    }
+                    else if (r.which == 3 && shared_ffn) {  // the shared expert's consumer: the combine launch
+                        TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st,
+                                           kMoeCombine, e->d_shared));
                     }
                     else if (r.which == 4) {  // the head's consumer
                         TM_TRY(launch_argmax(e->d_next_ids, nullptr, e->d_logits, M, e->vocab_local, e->vocab_local, 0, st));
@@ -401,7 +428,8 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
     if (moe.size() >= 2 && e->d_moe_ws) {
         auto chain = [&]() -> int {
             for (Layer* L : moe) {
-                TM_TRY(moe_forward(L->moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st));
+                TM_TRY(moe_forward(L->moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st, kMoeAll,
+                                   L->has_shared ? e->d_shared : nullptr));
             }
             return 0;
         };

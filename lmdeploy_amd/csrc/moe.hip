@@ -10,6 +10,9 @@
 //   route:  for every expert the tokens that selected it, in ascending token order:
 //           offsets[e] .. offsets[e+1] index the flat pair list; f2n[f] = token; en2f[j][t] = f.
 //   combine: out[t] = fp16( sum_j w[t][j] * float(y[en2f[j][t]]) ).
+//   shared expert (Qwen2-MoE; unified_decoder.cc:295-318, moe_ffn_layer.cc:295-325, moe_utils_v2.cu:1032-1105): the layer's dense
+//           feed_forward output `shared` is scaled per token by sigmoid(x . w_shared_gate) and the routed sum is added on top, in
+//           the same launch (moe_combine_shared_kernel): out[t] = fp16( float(shared[t]) * sigma_t + sum_j w[t][j] * float(y[..]) ).
 // Two routers fill the same tables: the serial kernels (8-expert Mixtral, the default for experts <= 64) and the wide ones
 // (moe_gate_wide_kernel / moe_route_wide_kernel, 1 <= experts <= 256: Qwen3-MoE), chosen by the expert count or TM_MOE_ROUTER.
 #include "tm_common.h"
@@ -407,6 +410,66 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(half_t* __restrict__ o
     *(half8_t*)(out + (size_t)t * ldo + h) = o;
 }
 
+// The combine of a block with a shared expert (Qwen2-MoE), gate and combine in ONE launch:
+//   logit[t] = sum_h f32(x[t][h]) * f32(g[h]),  sigma = 1 / (1 + expf(-logit))   (expf overflow: 1 / inf = 0, no NaN)
+//   out[t][h] = fp16( fma(w[t][k-1], y[..], ... fma(w[t][0], y[en2f[0][t]][h], f32(shared[t][h]) * sigma)) )
+// i.e. moe_combine_kernel's chain started from the shared term instead of zero (MoeReduceKernel).  Same grid as moe_combine_kernel
+// (2048 columns per workgroup); EVERY workgroup of a token computes the token's whole logit with one summation tree that does not
+// depend on the grid: thread i sums its 8-channel chunks i, i + 256, ... in channel order (fma chain), the 64 lanes of a wave
+// combine by the group_sum<64> butterfly, the four wave sums as (p0 + p1) + (p2 + p3) -- so all workgroups of a token, and all
+// launches, scale by the same bits.  x and g come from L2 for every workgroup but the first (2 H bytes each per token).
+// `out` may alias `shared` (the reference combines in place): a thread reads its 8 shared columns before it writes them.
+__global__ __launch_bounds__(256) void moe_combine_shared_kernel(half_t* out, int ldo, const half_t* __restrict__ y, int ldy,
+                                                                 const float* __restrict__ topk_w, const int* __restrict__ en2f,
+                                                                 const half_t* shared, int lds, const half_t* __restrict__ x, int ldx,
+                                                                 const half_t* __restrict__ g, int T, int H, int k)
+{
+    __shared__ float part[4];
+    const int        t  = blockIdx.y;
+    const half_t*    xr = x + (size_t)t * ldx;
+    float            lg = 0.f;
+    for (int c = threadIdx.x * 8; c < H; c += 256 * 8) {
+        const half8_t xv = *(const half8_t*)(xr + c);
+        const half8_t gv = *(const half8_t*)(g + c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            lg = __builtin_fmaf((float)xv[e], (float)gv[e], lg);
+        }
+    }
+    lg = group_sum<64>(lg);
+    if ((threadIdx.x & 63) == 0) {
+        part[threadIdx.x >> 6] = lg;
+    }
+    __syncthreads();
+    const float logit = (part[0] + part[1]) + (part[2] + part[3]);
+    const float sigma = 1.0f / (1.0f + __builtin_expf(-logit));
+    const int   h     = (blockIdx.x * 256 + threadIdx.x) * 8;
+    if (h >= H) {
+        return;
+    }
+    const half8_t sv = *(const half8_t*)(shared + (size_t)t * lds + h);
+    float         acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] = (float)sv[e] * sigma;
+    }
+    for (int j = 0; j < k; ++j) {
+        const int     f = en2f[(size_t)j * T + t];
+        const float   w = topk_w[(size_t)t * k + j];
+        const half8_t v = *(const half8_t*)(y + (size_t)f * ldy + h);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            acc[e] = __builtin_fmaf(w, (float)v[e], acc[e]);
+        }
+    }
+    half8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        o[e] = (half_t)acc[e];
+    }
+    *(half8_t*)(out + (size_t)t * ldo + h) = o;
+}
+
 // TM_MOE_ROUTER: auto (default) = the serial kernels up to 64 experts and the wide ones above, wide = the wide ones for every
 // expert count.  Read once; tm_debug_set_moe_router overrides it for A/B runs in one process (a plain global read by every launch:
 // not thread-safe, for tests and the benchmark tool only, set while no forward is being enqueued).
@@ -483,6 +546,20 @@ int launch_moe_combine(half_t* out, int ldo, const half_t* y, int ldy, const flo
     return 0;
 }
 
+int launch_moe_combine_shared(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, const half_t* shared,
+                              int lds, const half_t* x, int ldx, const half_t* gate, int T, int H, int k, hipStream_t st)
+{
+    TM_REQUIRE(H % 8 == 0 && ldo % 8 == 0 && ldy % 8 == 0 && lds % 8 == 0 && ldx % 8 == 0, "moe combine: H and the row strides % 8 == 0");
+    TM_REQUIRE(shared && x && gate, "moe combine: shared expert output, x and the shared gate");
+    if (T == 0) {
+        return 0;
+    }
+    moe_combine_shared_kernel<<<dim3((H / 8 + 255) / 256, T), 256, 0, st>>>(out, ldo, y, ldy, topk_w, en2f, shared, lds, x, ldx, gate, T,
+                                                                            H, k);
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---- one MoE FFN block (host object shared by the C-ABI operator and the engine) -------------------------------------
 size_t moe_workspace_bytes(const MoeBlock& m, int tokens)
 {
@@ -527,12 +604,16 @@ int moe_prepare(MoeBlock& m, hipStream_t st)
 }
 
 // out[t] = sum_j w_j * W2_e( silu(W1_e x_t) * (W3_e x_t) ) over the top_k experts e of token t
+// (+ sigmoid(x_t . shared_gate) * shared[t] when the block has a shared gate: `shared` [tokens][ld = ldo] is the shared expert's FFN
+// output, required exactly then, read by the combine stage only, and may be `out`)
 // `stages` (kMoeGate .. kMoeCombine) selects the launches: every one of them is a whole forward; a subset runs on the tables and
 // activations an earlier forward left in the same workspace (tools/bench_moe_router.py times the launches one by one)
 int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ldx, int tokens, void* workspace, int* topk_ids_out,
-                float* topk_w_out, hipStream_t st, unsigned stages)
+                float* topk_w_out, hipStream_t st, unsigned stages, const half_t* shared)
 {
     TM_REQUIRE(m.groups13 && m.groups2, "moe: not prepared");
+    TM_REQUIRE((m.shared_gate != nullptr) == (shared != nullptr),
+               "moe: the shared expert's output is required exactly when the block has a shared gate");
     if (tokens == 0) {
         return 0;
     }
@@ -587,7 +668,11 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
                                             nullptr, st));
         }
     }
-    if (stages & kMoeCombine) {
+    if ((stages & kMoeCombine) && m.shared_gate) {
+        TM_TRY_RC(launch_moe_combine_shared(out, ldo, y2, m.hidden, tw, en2f, shared, ldo, x, ldx, m.shared_gate, tokens, m.hidden, m.top_k,
+                                            st));
+    }
+    else if (stages & kMoeCombine) {
         TM_TRY_RC(launch_moe_combine(out, ldo, y2, m.hidden, tw, en2f, tokens, m.hidden, m.top_k, st));
     }
     if (topk_ids_out) {
@@ -607,12 +692,12 @@ void moe_free(MoeBlock& m)
     for (auto& l : m.w2) {
         linear_weight_free(l);
     }
-    for (void* q : {(void*)m.gate, m.groups13, m.groups2, m.groups13_p8, m.groups2_p8}) {
+    for (void* q : {(void*)m.gate, (void*)m.shared_gate, m.groups13, m.groups2, m.groups13_p8, m.groups2_p8}) {
         if (q) {
             (void)hipFree(q);
         }
     }
-    m.gate = nullptr;
+    m.gate = m.shared_gate = nullptr;
     m.groups13 = m.groups2 = nullptr;
     m.groups13_p8 = m.groups2_p8 = nullptr;
 }

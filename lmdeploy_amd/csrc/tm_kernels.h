@@ -309,6 +309,7 @@ struct MoeBlock {
     bool                      norm_topk    = true;
     float                     routed_scale = 1.f;
     half_t*                   gate         = nullptr;  // device fp16 [hidden][experts]
+    half_t*                   shared_gate  = nullptr;  // device fp16 [hidden] (Qwen2-MoE: the shared expert's sigmoid gate) or nullptr; owned
     std::vector<LinearWeight> w13, w2;                 // per expert: gated (gate_j, up_j)-interleaved [H][2I], [I][H]
     void *                    groups13 = nullptr, *groups2 = nullptr;
     void *                    groups13_p8 = nullptr, *groups2_p8 = nullptr;  // fp8 experts: P8 unit pointers (gemm_fp8.hip)
@@ -317,7 +318,7 @@ size_t moe_workspace_bytes(const MoeBlock& m, int tokens);
 int    moe_prepare(MoeBlock& m, hipStream_t st);
 enum : unsigned { kMoeGate = 1, kMoeRoute = 2, kMoeW13 = 4, kMoeW2 = 8, kMoeCombine = 16, kMoeAll = 31 };  // launches of moe_forward
 int    moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ldx, int tokens, void* workspace, int* topk_ids_out,
-                   float* topk_w_out, hipStream_t st, unsigned stages = kMoeAll);
+                   float* topk_w_out, hipStream_t st, unsigned stages = kMoeAll, const half_t* shared = nullptr);
 void   moe_free(MoeBlock& m);
 // mixture of experts (moe.hip, grouped GEMM in gemm_w4a16.hip)
 int moe_build_groups(void** d_groups, const LinearWeight* experts, int E, hipStream_t st);
@@ -332,6 +333,9 @@ bool moe_router_wide(int E);
 int launch_moe_route(int* offsets, int* f2n, int* en2f, const int* topk_ids, int T, int E, int k, hipStream_t st);
 int launch_moe_combine(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, int T, int H, int k,
                        hipStream_t st);
+// the same with a shared expert: out = fp16(f32(shared) * sigmoid(x . gate) + the routed sum); out may alias shared
+int launch_moe_combine_shared(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, const half_t* shared,
+                              int lds, const half_t* x, int ldx, const half_t* gate, int T, int H, int k, hipStream_t st);
 
 extern uint64_t* g_gemm_dbg;  // gemm_w4a16.hip: optional per-workgroup timing stamps (tm_debug_set_gemm_trace)
 // The trace buffer holds kTraceMaxWorkgroups x 8 stamps; a launch with more workgroups is not traced.  (The only unbounded

@@ -1,10 +1,11 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
-Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen3-MoE with AWQ (W4A16 g128),
+Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
 FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (MoE experts: AWQ or FP8 only):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
                                      qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head;
-                                     Qwen3-MoE: mlp.gate router + mlp.experts.X.{gate,up,down}_proj, qwen3.py:110-121)
+                                     Qwen3-MoE: mlp.gate router + mlp.experts.X.{gate,up,down}_proj, qwen3.py:110-121;
+                                     Qwen2-MoE adds mlp.shared_expert.* and mlp.shared_expert_gate, qwen2.py:110-128)
   * FP8 normalize / dequant          lmdeploy/turbomind/weight_format.py:349-384 (HF [out, in] -> [in, out], scales alike)
   * AWQ normalize (unpack order)     lmdeploy/turbomind/weight_format.py:200-234
   * RoPE q/k channel permutation     lmdeploy/turbomind/models/utils.py:306-373 (weight, scales and zeros alike)
@@ -58,19 +59,22 @@ class ModelConfig:
     max_position_embeddings: int = 8192
     attn_bias: int = 0                 # Qwen2 (and Qwen3 with attention_bias): q / k / v projections carry a bias
     qk_norm: int = 0                   # Qwen3: per-head RMSNorm of q and k before RoPE
+    moe_shared_inter: int = 0          # Qwen2-MoE: width of the shared expert (a dense FFN behind a sigmoid gate in every MoE layer)
     tie_word_embeddings: bool = False
 
 
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
-# in every layer) is served, Qwen2-MoE (shared expert behind a sigmoid gate: a different block) stays refused
-QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM')
+# in every layer) and Qwen2-MoE (the Qwen2 prologue; routed experts plus a shared expert behind a sigmoid gate in every layer)
+QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM', 'Qwen2MoeForCausalLM')
+QWEN2_ARCHS = ('Qwen2ForCausalLM', 'Qwen2MoeForCausalLM')
 QWEN3_MOE_KEYS = ('num_experts', 'num_experts_per_tok', 'moe_intermediate_size')
+QWEN2_MOE_KEYS = QWEN3_MOE_KEYS + ('shared_expert_intermediate_size',)
 
 
-def _qwen3_moe_fields(arch: str, c: dict, quantized: bool) -> dict:
-    """the MoE fields of a Qwen3MoeForCausalLM config, or NotImplementedError with the reason.  The three geometry keys must be in
-    config.json: a library default would describe some other checkpoint."""
-    missing = [k for k in QWEN3_MOE_KEYS if c.get(k) is None]
+def _qwen3_moe_fields(arch: str, c: dict, quantized: bool, keys: tuple = QWEN3_MOE_KEYS) -> dict:
+    """the MoE fields of a Qwen3MoeForCausalLM (or, with QWEN2_MOE_KEYS, Qwen2MoeForCausalLM) config, or NotImplementedError with the
+    reason.  The geometry keys must be in config.json: a library default would describe some other checkpoint."""
+    missing = [k for k in keys if c.get(k) is None]
     if missing:
         raise NotImplementedError(f'{arch}: config.json lacks {", ".join(missing)}')
     E, k = int(c['num_experts']), int(c['num_experts_per_tok'])
@@ -85,8 +89,12 @@ def _qwen3_moe_fields(arch: str, c: dict, quantized: bool) -> dict:
     if not quantized:
         raise NotImplementedError(f'{arch} with fp16 / bf16 experts: the grouped expert GEMM serves AWQ (u4) and block-128 FP8 (e4m3) '
                                   f'weights only')
+    shared = int(c['shared_expert_intermediate_size']) if 'shared_expert_intermediate_size' in keys else 0
+    if shared < 0 or shared % 128:
+        raise NotImplementedError(f'{arch} with shared_expert_intermediate_size {shared}: the shared expert\'s width must be a '
+                                  f'multiple of 128')
     return dict(inter=int(c['moe_intermediate_size']), moe_experts=E, moe_top_k=k,
-                moe_norm_topk=bool(c.get('norm_topk_prob', False)), moe_routed_scale=1.0)
+                moe_norm_topk=bool(c.get('norm_topk_prob', False)), moe_routed_scale=1.0, moe_shared_inter=shared)
 
 
 def read_config(model_path: str) -> ModelConfig:
@@ -97,13 +105,13 @@ def read_config(model_path: str) -> ModelConfig:
     qwen = arch in QWEN_ARCHS
     if kind == 'llama' and not qwen and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
         raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 '
-                                  f'decoders and Qwen3-MoE')
+                                  f'decoders, Qwen2-MoE and Qwen3-MoE')
     H = c['hidden_size']
     heads = c['num_attention_heads']
     D = c.get('head_dim') or H // heads
     attn_bias = qk_norm = 0
     if qwen:
-        kind = 'qwen2' if arch == 'Qwen2ForCausalLM' else 'qwen3'
+        kind = 'qwen2' if arch in QWEN2_ARCHS else 'qwen3'
         if c.get('use_sliding_window'):
             raise NotImplementedError(f'{arch} with use_sliding_window: sliding-window attention is not implemented')
         if D != 128:
@@ -146,6 +154,8 @@ def read_config(model_path: str) -> ModelConfig:
     c = dict(c, eos_token_id=eos)
     if arch == 'Qwen3MoeForCausalLM':
         moe = _qwen3_moe_fields(arch, c, q is not None)
+    elif arch == 'Qwen2MoeForCausalLM':
+        moe = _qwen3_moe_fields(arch, c, q is not None, QWEN2_MOE_KEYS)
     else:
         moe = dict(inter=c['intermediate_size'], moe_experts=int(c.get('num_local_experts', 0) or 0) if 'Mixtral' in arch else 0,
                    moe_top_k=int(c.get('num_experts_per_tok', 0) or 0) if 'Mixtral' in arch else 0)
@@ -233,14 +243,26 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
             wo = _linear(t, p + '.self_attn.o_proj', cfg.quantized)
             moe = None
             if cfg.moe_experts:      # router [E, H] (unquantised also in AWQ checkpoints) -> fp16 [H][E]; per-expert w1 / w3 / w2
-                # Mixtral (models/mixtral.py:73-106): block_sparse_moe.experts.X.w1 / w3 / w2; Qwen3-MoE (models/qwen3.py:110-121):
-                # mlp.experts.X.gate_proj / up_proj / down_proj
-                m, names = ((p + '.mlp', ('gate_proj', 'up_proj', 'down_proj')) if cfg.arch == 'qwen3'
+                # Mixtral (models/mixtral.py:73-106): block_sparse_moe.experts.X.w1 / w3 / w2; Qwen3-MoE (models/qwen3.py:110-121) and
+                # Qwen2-MoE (models/qwen2.py:110-128): mlp.experts.X.gate_proj / up_proj / down_proj
+                m, names = ((p + '.mlp', ('gate_proj', 'up_proj', 'down_proj')) if cfg.arch in ('qwen2', 'qwen3')
                             else (p + '.block_sparse_moe', ('w1', 'w3', 'w2')))
                 moe = dict(moe_gate=np.ascontiguousarray(t.get(m + '.gate.weight').astype(np.float16).T), experts=[])
                 for x in range(cfg.moe_experts):
                     e1, e3, e2 = (_linear(t, f'{m}.experts.{x}.{n}', cfg.quantized) for n in names)
                     moe['experts'].append(dict(w1w3=_fuse_w1w3(e1, e3), w2=e2))
+                if getattr(cfg, 'moe_shared_inter', 0):
+                    # Qwen2-MoE: the shared expert is a dense FFN (the engine's feed_forward slots), its gate an unquantised [1, H] row
+                    sg = m + '.shared_expert_gate'
+                    if (sg + '.qweight') in t or (sg + '.weight_scale_inv') in t:
+                        raise NotImplementedError(f'{sg}: a quantised shared-expert gate is not implemented (the gate is read as '
+                                                  f'fp16 / bf16 [1, hidden])')
+                    s1, s3, s2 = (_linear(t, f'{m}.shared_expert.{n}', cfg.quantized) for n in names)
+                    gate = t.get(sg + '.weight')
+                    if gate.dtype == np.uint8 or gate.size != cfg.hidden:
+                        raise NotImplementedError(f'{sg}.weight: expected fp16 / bf16 [1, {cfg.hidden}], got {gate.dtype} '
+                                                  f'{tuple(gate.shape)}')
+                    moe.update(w1w3=_fuse_w1w3(s1, s3), w2=s2, shared_gate=np.ascontiguousarray(gate.astype(np.float16).reshape(-1)))
                 w1 = w3 = w2 = None
             else:
                 w1 = _linear(t, p + '.mlp.gate_proj', cfg.quantized)

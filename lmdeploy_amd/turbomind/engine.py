@@ -19,13 +19,15 @@ _ROPE_TYPES = {'default': 0, 'linear': 1, 'llama3': 2}
 
 def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     """cfg: any object with hidden, layers, q_heads, kv_heads, head_dim, inter, vocab, rms_eps, rope(.dim,.base,.type,
-    .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings), group; optional moe_*, attn_bias, qk_norm."""
+    .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings), group; optional moe_* (moe_shared_inter: Qwen2-MoE's
+    shared expert), attn_bias, qk_norm."""
     r = cfg.rope
     return _ffi.ModelConfig(cfg.hidden, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, cfg.inter, cfg.vocab,
                             cfg.rms_eps, r.base, _ROPE_TYPES[r.type], r.factor, r.low_freq_factor, r.high_freq_factor,
                             r.original_max_position_embeddings, cfg.group, weight_type,
                             int(getattr(cfg, 'moe_experts', 0) or 0), int(getattr(cfg, 'moe_top_k', 0) or 0),
                             int(bool(getattr(cfg, 'moe_norm_topk', True))), float(getattr(cfg, 'moe_routed_scale', 1.0)),
+                            int(getattr(cfg, 'moe_shared_inter', 0) or 0),
                             int(bool(getattr(cfg, 'attn_bias', 0))), int(bool(getattr(cfg, 'qk_norm', 0))))
 
 

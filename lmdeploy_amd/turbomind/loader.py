@@ -102,7 +102,9 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     """weights (unsharded, TM layout): {'tok_embeddings' [V,H], 'norm' [H], 'output' [H,V],
     'layers': [{'attn_norm','ffn_norm', 'w_qkv','wo','w1w3','w2': linear dicts}]} with w_qkv = [Q|K|V] along N and
     w1w3 already (gate_j, up_j)-interleaved; Qwen layers add 'qkv_bias' [Hq*D + 2*Hkv*D] (q / k permuted like w_qkv) and /
-    or 'q_norm', 'k_norm' [D].  Returns {slot name: contiguous numpy array} for this rank."""
+    or 'q_norm', 'k_norm' [D]; MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
+    all of them: w1w3 / w2 are then the shared expert (width cfg.moe_shared_inter) next to its 'shared_gate' [H].
+    Returns {slot name: contiguous numpy array} for this rank."""
     D = cfg.head_dim
     Hq, Hkv, I, G = cfg.q_heads, cfg.kv_heads, cfg.inter, cfg.group
     assert Hq % tp == 0 and I % tp == 0 and cfg.vocab % tp == 0
@@ -118,6 +120,8 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     qkv_slices = [(q0 * D, (q0 + hq_l) * D), (nq + kv0 * D, nq + (kv0 + hkv_l) * D),
                   (nq + nkv + kv0 * D, nq + nkv + (kv0 + hkv_l) * D)]
     i_l = I // tp
+    S = int(getattr(cfg, 'moe_shared_inter', 0) or 0)
+    s_l = S // tp
     slots = {}
     for li, L in enumerate(weights['layers']):
         p = f'layers.{li}'
@@ -128,7 +132,15 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
                 # the rank's half of a *.w1w3.scales row is i_l / 128 blocks, and the fp8 gated linear needs N = 2 * i_l % 256 == 0
                 raise ValueError(f'moe experts of width {I} do not shard over tp = {tp}: {I} / {tp} = {I / tp:g} is not a multiple '
                                  f'of 128')
+            if S and (S % tp or s_l % 128):
+                raise ValueError(f'shared expert of width {S} does not shard over tp = {tp}: {S} / {tp} = {S / tp:g} is not a multiple '
+                                 f'of 128')
             slots[p + '.moe_ffn.gate.weight'] = np.ascontiguousarray(L['moe_gate'], dtype=np.float16)
+            if S:              # Qwen2-MoE: the shared expert sharded like the dense FFN, its gate vector replicated
+                _emit(slots, p + '.feed_forward.w1w3',
+                      _shard_linear(L['w1w3'], 'col', tp, rank, G, [(2 * rank * s_l, 2 * (rank + 1) * s_l)]))
+                _emit(slots, p + '.feed_forward.w2', _shard_linear(L['w2'], 'row', tp, rank, G))
+                slots[p + '.moe_ffn.shared_gate.weight'] = np.ascontiguousarray(L['shared_gate'], dtype=np.float16)
             for x, E_ in enumerate(L['experts']):
                 q = f'{p}.moe_ffn.experts.{x}'
                 _emit(slots, q + '.w1w3', _shard_linear(E_['w1w3'], 'col', tp, rank, G, [(2 * rank * i_l, 2 * (rank + 1) * i_l)]))
