@@ -58,7 +58,9 @@ int launch_gather_rows(half_t* out, const half_t* in, const int* rows, int n, in
     return 0;
 }
 
-// greedy: argmax over fp32-cast logits, lowest index wins ties. One 1024-thread workgroup per row.
+// greedy: argmax over fp32-cast logits.  One 1024-thread workgroup per row; columns [V, ld) are never read.
+// Contract: NaN never wins (every comparison with it is false); the result is the LOWEST index of the maximum over the
+// remaining entries; a row with no entry above -inf (all -inf, or -inf and NaN) gives id 0 and value -inf.
 __global__ __launch_bounds__(1024) void argmax_kernel(int* __restrict__ out_ids,
                                                       half_t* __restrict__ out_val,
                                                       const half_t* __restrict__ logits,
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(int* __restrict__ out_ids,
     }
     for (int i = nvec * 8 + threadIdx.x; i < V; i += 1024) {
         const float f = (float)lp[i];
-        if (f > best || (f == best && i < bi)) {
+        if (f > best) {  // i is above every index this thread has seen: a tie keeps the earlier one, -inf keeps "none"
             best = f;
             bi   = i;
         }

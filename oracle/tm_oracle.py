@@ -658,8 +658,10 @@ def lm_head(hidden: np.ndarray, w_out: np.ndarray) -> np.ndarray:
 
 
 def greedy(logits: np.ndarray) -> np.ndarray:
-    """top_k = 1 on fp32-cast logits (generation/sampling.cc:92-183). Ties: lowest index here;
-    the reference does not guarantee tie order => tests avoid exact ties."""
+    """top_k = 1 on fp32-cast logits (generation/sampling.cc:92-183). Ties: lowest index, here and in argmax_kernel
+    (the reference does not guarantee a tie order; ours is tested, tests/test_gpu_row_ops.py::test_argmax_edges).
+    The kernel's contract goes further than this function: NaN never wins there and a row with nothing above -inf gives
+    id 0, i.e. it is greedy() of the logits with NaN replaced by -inf; np.argmax would return the first NaN."""
     return np.asarray(logits).astype(f32).argmax(-1).astype(np.int32)
 
 

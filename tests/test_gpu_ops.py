@@ -180,22 +180,38 @@ def test_flatten_kv(tm, cuda, bits, transpose_v):
         o.process_kv(oc, tables[b], layer, k, v, None, None, 0)
     dc = DevCache(L, total, tables)
     dc.upload(oc)
-    koff = np.concatenate([[0], np.cumsum([nb * 64 for nb in nblk])]).astype(np.int32)
-    stride = int(koff[-1])
-    kf = torch.zeros((Hkv, stride, 128), dtype=torch.float16, device='cuda')
-    vf = torch.zeros((Hkv, 128, stride) if transpose_v else (Hkv, stride, 128), dtype=torch.float16, device='cuda')
+    # every sequence owns a 64-aligned region of the scratch; one region between them and one behind them belong to no
+    # sequence of this call (the engine's scratch holds earlier chunks there)
+    pad = [nb * 64 for nb in nblk]
+    koff = np.asarray([0, pad[0], pad[0] + pad[1] + 64], np.int32)
+    stride = int(koff[-1]) + pad[2] + 64
+    # the scratch is reused across prefill chunks and never cleared: poison it (fp16 NaN 0x7e00) so that every byte the kernel
+    # is relied on to write has to be written by THIS call
+    kf = torch.full((Hkv, stride, 128), 0x7e00, dtype=torch.int16, device='cuda').view(torch.float16)
+    vf = torch.full((Hkv, 128, stride) if transpose_v else (Hkv, stride, 128), 0x7e00, dtype=torch.int16,
+                    device='cuda').view(torch.float16)
     _ffi.check(tm.tm_flatten_kv(kf.data_ptr(), vf.data_ptr(), transpose_v, dev(koff).data_ptr(),
                                 dev(np.asarray(klen, np.int32)).data_ptr(), len(klen), max(klen), stride, dc.view(layer),
                                 st()))
     K, V = host(kf), host(vf)
     if transpose_v:
         V = V.transpose(0, 2, 1)
+    k_written = np.zeros(stride, bool)
+    v_written = np.zeros(stride, bool)
     for b, n in enumerate(klen):
         kr, vr = o.flatten_kv(oc, tables[b], layer, n)
         assert np.array_equal(K[:, koff[b]:koff[b] + n].view(np.uint16), kr.view(np.uint16))
         assert np.array_equal(V[:, koff[b]:koff[b] + n].view(np.uint16), vr.view(np.uint16))
         if transpose_v:   # padding up to the 64-token tile must be zero (prefill attention relies on it)
-            assert not V[:, koff[b] + n:koff[b + 1]].any()
+            assert not V[:, koff[b] + n:koff[b] + pad[b]].view(np.uint16).any()
+        k_written[koff[b]:koff[b] + n] = True
+        v_written[koff[b]:koff[b] + (pad[b] if transpose_v else n)] = True
+    # Contract of the scratch: the call writes K rows [0, klen) and V rows [0, klen) of each sequence's region, and for
+    # transposed V also zeros in [klen, klen_pad) -- the prefill kernel multiplies masked probabilities (0) by that tail, so
+    # it must not hold a stale NaN.  The K tail [klen, klen_pad) stays STALE by contract (its scores are masked before use),
+    # and so does everything outside the regions of the sequences flattened here.
+    assert (K[:, ~k_written].view(np.uint16) == 0x7e00).all(), 'K rows outside [0, klen) of a flattened sequence were written'
+    assert (V[:, ~v_written].view(np.uint16) == 0x7e00).all(), 'V outside the flattened sequences\' regions was written'
 
 
 # ------------------------------------------------------------------------------------------------
@@ -409,8 +425,19 @@ def test_decode_attention_block_table_permutation_invariance(tm, cuda):
 
 @pytest.mark.parametrize('Hq,Hkv,qlens,hist', [(4, 2, [70, 5, 129], [0, 0, 0]), (8, 8, [33], [95]), (6, 2, [1, 64], [0, 64]),
                                                (8, 2, [200, 37], [0, 10]), (32, 8, [130], [62]), (16, 2, [64, 96], [0, 32]),
-                                               (32, 8, [1024, 700], [0, 324]), (8, 4, [300], [1000])])
+                                               (32, 8, [1024, 700], [0, 324]), (8, 4, [300], [1000]),
+                                               # GQA groups 6 and 7: two heads / one head per wave (28 / 4 is Qwen2.5-7B)
+                                               (12, 2, [33, 64, 1], [31, 0, 64]), (28, 4, [33, 64, 1], [31, 0, 64])])
 def test_prefill_attention(tm, cuda, Hq, Hkv, qlens, hist):
+    _check_prefill_attention(tm, Hq, Hkv, qlens, hist, None)
+
+
+def test_prefill_attention_softmax_scale(tm, cuda):
+    """an explicit softmax scale (every other case passes 0.0 = the default 1 / sqrt(128)), given to kernel and oracle alike"""
+    _check_prefill_attention(tm, 8, 2, [70], [10], 0.05)
+
+
+def _check_prefill_attention(tm, Hq, Hkv, qlens, hist, softmax_scale):
     rng = np.random.default_rng(Hq + sum(qlens))
     B = len(qlens)
     klen = [h + n for h, n in zip(hist, qlens)]
@@ -433,10 +460,11 @@ def test_prefill_attention(tm, cuda, Hq, Hkv, qlens, hist):
     out = torch.zeros((T, Hq * 128), dtype=torch.float16, device='cuda')
     _ffi.check(tm.tm_prefill_attention(out.data_ptr(), dev(q).data_ptr(), Hq * 128, dev(K).data_ptr(), dev(Vt).data_ptr(),
                                        stride, dev(cu).data_ptr(), dev(koff).data_ptr(),
-                                       dev(np.asarray(klen, np.int32)).data_ptr(), B, max(qlens), Hq, Hkv, 0.0, st()))
+                                       dev(np.asarray(klen, np.int32)).data_ptr(), B, max(qlens), Hq, Hkv,
+                                       0.0 if softmax_scale is None else softmax_scale, st()))
     got = host(out)
     for b, n in enumerate(qlens):
-        ref = o.prefill_attention(q[cu[b]:cu[b + 1]].reshape(n, Hq, 128), Ks[b], Vs[b], hist[b]).reshape(n, -1)
+        ref = o.prefill_attention(q[cu[b]:cu[b + 1]].reshape(n, Hq, 128), Ks[b], Vs[b], hist[b], softmax_scale).reshape(n, -1)
         err = np.abs(got[cu[b]:cu[b + 1]].astype(np.float32) - ref.astype(np.float32))
         assert np.all(err <= 1e-2 * np.abs(ref.astype(np.float32)) + 2e-3), f'seq {b}: max err {err.max()}'
 
