@@ -246,9 +246,10 @@ int    tm_linear_destroy(tm_linear* w);
  * kernels/gemm/moe_utils_v2.cu:355-690; grouped linear LlamaLinear.cu:67-127) -------------------------------------
  * out[t] = sum over the top_k experts e of token t of w_e(t) * W2_e( silu(W1_e x_t) * (W3_e x_t) ), with
  * logits = x Wg (fp32), top-k on the logits (ties: lower expert id), w = softmax over the selected experts
- * (norm_topk != 0) or over all experts, times routed_scale.  Expert weights: weight_type TM_WEIGHT_U4 / TM_WEIGHT_FP8,
- * boundary layouts of tm_linear_prepare; w13 = [hidden][2*inter] with (gate_j, up_j) column-interleaved, w2 =
- * [inter][hidden].  FP8 w13: w1 and w3 are block-quantised separately in a checkpoint, so the scale row of w13 is
+ * (norm_topk != 0) or over all experts, times routed_scale.  Expert weights: weight_type TM_WEIGHT_U4 / TM_WEIGHT_FP8 /
+ * TM_WEIGHT_F16, boundary layouts of tm_linear_prepare; w13 = [hidden][2*inter] with (gate_j, up_j) column-interleaved, w2 =
+ * [inter][hidden].  TM_WEIGHT_F16: the weights are fp16 [K][N], scales = zeros = NULL, and the forward has no activation-quantisation
+ * stage.  FP8 w13: w1 and w3 are block-quantised separately in a checkpoint, so the scale row of w13 is
  * [w1's inter/128 blocks | w3's inter/128 blocks] (inter % 128 == 0) -- also for the engine's *.w1w3.scales slots.  gate: fp16 [hidden][experts].  All pointers device.  topk_ids_out / topk_w_out (device
  * [tokens][top_k], may be NULL) expose the routing for tests.
  * Bounds: 1 <= top_k <= 8, top_k <= experts <= 256 (Mixtral 8 / 2, Qwen3-MoE 128 / 8).  Up to 64 experts the router is the serial
@@ -362,7 +363,7 @@ int tm_debug_pick_tiling(int K, int N, int M, int use_table, int* shape, int* sp
  * config4 = {tiles per wave, split-K, waves, k-phases} -- the measured entry (tm_engine_tune_gemm / tm_gemm_import, `G` lines)
  * first, then the heuristic.  Reference: the same DispatchCache serves every GEMM of the model (gemm.cu:92-224). */
 int tm_debug_pick_general(int weight_type, int role, int K, int N, int M, int* config4);
-/* Host-only: the measured row-tile height of the grouped expert GEMMs (u4: 16 / 32 / 64, e4m3 on the fp8 matrix cores: 32 / 64)
+/* Host-only: the measured row-tile height of the grouped expert GEMMs (u4 and fp16: 16 / 32 / 64, e4m3 on the fp8 matrix cores: 32 / 64)
  * for `tokens` rows per forward; *rows = 0: no entry, the launcher's own rule (twice the expected rows per expert) applies. */
 int tm_debug_grouped_tile(int weight_type, int K, int N, int tokens, int* rows);
 /* Host-only: every (shape, splits) pair the start-up tuner (tm_engine_tune_gemm; gemm::Gemm::Run's dispatch candidates,
@@ -380,7 +381,7 @@ int tm_debug_general_candidates(int weight_type, int K, int N, int M, int64_t wo
  * (cu_block_nums must say the same); 0 = ragged (default).  The engine's own table is rectangular and always takes this
  * path: the decode kernel then needs no dependent pointer loads (test hook for that path). */
 int tm_debug_set_block_stride(int stride);
-/* Grouped expert GEMMs launched by the CALLING thread (tm_moe_forward) use `rows`-row tiles: u4 / fp8 weight-only 16, 32 or
+/* Grouped expert GEMMs launched by the CALLING thread (tm_moe_forward) use `rows`-row tiles: u4 / fp16 / fp8 weight-only 16, 32 or
  * 64 (decode-sized forwards, tokens <= 64), e4m3 on the fp8 matrix cores 32 or 64 (any size); 0 = off, the measured entry or
  * the launcher's own rule (test hook: every row tile against the oracle, whatever the routing). */
 int tm_debug_set_grouped_rows(int rows);

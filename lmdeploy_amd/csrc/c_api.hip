@@ -580,7 +580,8 @@ struct tm_moe {
 int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk, float routed_scale)
 {
     TM_REQUIRE(out, "null pointer");
-    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8, "moe experts: u4 or fp8 weights");
+    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_F16,
+               "moe experts: u4, fp8 or fp16 weights");
     TM_REQUIRE(hidden % 128 == 0 && inter % 128 == 0 && experts >= 1 && experts <= 256 && top_k >= 1 && top_k <= 8 && top_k <= experts,
                "moe geometry");
     auto* o         = new tm_moe();
@@ -626,9 +627,14 @@ int tm_moe_set_shared_gate(tm_moe* m, const void* gate, tm_stream_t st)
 int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void* w13_scales, const void* w13_zeros,
                       const void* w2_weight, const void* w2_scales, const void* w2_zeros, tm_stream_t st)
 {
-    TM_REQUIRE(m && w13_weight && w13_scales && w2_weight && w2_scales, "null pointer");
+    TM_REQUIRE(m && w13_weight && w2_weight, "null pointer");
     TM_REQUIRE(expert >= 0 && expert < m->m.experts, "expert index");
     m->prepared = false;
+    if (m->type == TM_WEIGHT_F16) {  // fp16 [K][N], no scales / zeros: the 16-column image of the plain fp16 linears
+        TM_TRY_RC(linear_weight_prepare_f16(m->m.w13[expert], (const half_t*)w13_weight, (hipStream_t)st));
+        return linear_weight_prepare_f16(m->m.w2[expert], (const half_t*)w2_weight, (hipStream_t)st);
+    }
+    TM_REQUIRE(w13_scales && w2_scales, "null pointer");
     if (m->type == TM_WEIGHT_U4) {
         TM_REQUIRE(w13_zeros && w2_zeros, "u4 experts need zeros");
         TM_TRY_RC(linear_weight_prepare_u4(m->m.w13[expert], (const int32_t*)w13_weight, (const half_t*)w13_scales,
@@ -977,7 +983,7 @@ int tm_debug_pick_general(int weight_type, int role, int K, int N, int M, int* c
 
 int tm_debug_grouped_tile(int weight_type, int K, int N, int tokens, int* rows)
 {
-    TM_REQUIRE(rows && K > 0 && N > 0 && tokens > 0 && (weight_type == 0 || weight_type == 2), "arguments");
+    TM_REQUIRE(rows && K > 0 && N > 0 && tokens > 0 && weight_type >= 0 && weight_type <= 2, "arguments");
     int tv[4];
     *rows = gen_table_get(kGenGrouped + weight_type, 0, K, N, dec32_m_bucket(tokens), tv) ? tv[0] : 0;
     return 0;

@@ -238,9 +238,8 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     e->qkv_n       = (e->q_heads + 2 * e->kv_heads) * e->D;
     TM_REQUIRE((e->inter * 1) % 128 == 0 && (e->q_heads * e->D) % 128 == 0 && m.hidden % 128 == 0,
                "K dims must be multiples of 128 after TP sharding");
-    TM_REQUIRE(m.moe_experts == 0 || (m.moe_experts <= 256 && m.moe_top_k >= 1 && m.moe_top_k <= 8 && m.moe_top_k <= m.moe_experts
-                                      && m.weight_type != TM_WEIGHT_F16),
-               "moe: 1 <= top_k <= experts <= 256, top_k <= 8, u4 or fp8 expert weights");
+    TM_REQUIRE(m.moe_experts == 0 || (m.moe_experts <= 256 && m.moe_top_k >= 1 && m.moe_top_k <= 8 && m.moe_top_k <= m.moe_experts),
+               "moe: 1 <= top_k <= experts <= 256, top_k <= 8 (u4, fp8 or fp16 expert weights)");
     // the grouped expert GEMMs put experts x 64-row blocks of one forward on grid.z: refuse here what the first large prefill would hit
     TM_REQUIRE(m.moe_experts == 0
                    || (int64_t)m.moe_experts * ((std::max(c->max_batch_size, std::max(64, c->max_prefill_token_num)) + 63) / 64) <= 65535,

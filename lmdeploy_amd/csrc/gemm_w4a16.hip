@@ -879,7 +879,7 @@ static bool gen_entry_valid(int kind, int role, int K, int N, int M, const int v
         return (v[0] == 1 || v[0] == 2 || v[0] == 4) && v[1] >= 1 && v[1] <= 16 && (v[2] == 4 || v[2] == 8 || v[2] == 16)
                && (v[3] == 1 || v[3] == 2);
     }
-    if (kind == kGenGrouped) {  // u4 experts: 16 / 32 / 64-row tiles (decode batches only)
+    if (kind == kGenGrouped || kind == kGenGrouped + 1) {  // u4 / fp16 experts: 16 / 32 / 64-row tiles (decode batches only)
         return (v[0] == 16 || v[0] == 32 || v[0] == 64) && M <= 64;
     }
     if (kind == kGenGrouped + 2) {  // e4m3 experts on the fp8 matrix cores: 32 / 64-row tiles
@@ -931,7 +931,7 @@ int gen_dense_candidates(const LinearWeight& w, int M, size_t workspace_bytes, G
 int gen_grouped_candidates(const LinearWeight& proto, int m_cap, int* rows_out, int cap)
 {
     int n = 0;
-    if (proto.type == 0 && m_cap <= 64) {
+    if ((proto.type == 0 || proto.type == 1) && m_cap <= 64) {
         for (int r : {16, 32, 64}) {
             if (n < cap && (r == 16 || r / 2 < m_cap)) {
                 rows_out[n++] = r;
@@ -1351,7 +1351,7 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
                           half_t* y, int ldy, int m_cap, int m_hint, bool gated_silu, const int* seg, const int* row_idx,
                           hipStream_t st)
 {
-    TM_REQUIRE(proto.type == 0 || proto.type == 2, "grouped GEMM: u4 or fp8 expert weights");
+    TM_REQUIRE(proto.type == 0 || proto.type == 1 || proto.type == 2, "grouped GEMM: u4, fp8 or fp16 expert weights");
     TM_REQUIRE(ldx % 8 == 0 && (!gated_silu || proto.N % 32 == 0), "grouped GEMM: alignment");
     if (m_cap == 0 || E == 0) {
         return 0;
@@ -1389,8 +1389,13 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
         }
         p.zper         = (m_cap + 16 * mt - 1) / (16 * mt);
         TM_REQUIRE((int64_t)E * p.zper <= 65535, "grouped linear: experts x row blocks exceed grid.z (65535): split the forward into fewer tokens");
-        dim3 grid((ntiles + 7) / 8, 1, E * p.zper);
-        if (proto.type == 0) {
+        // u4 / fp8: 8 waves of one column tile each; fp16: the 4-wave form of the plain kernel (launch_mt<1, MT>)
+        dim3 grid(proto.type == 1 ? (ntiles + 3) / 4 : (ntiles + 7) / 8, 1, E * p.zper);
+        if (proto.type == 1) {
+            rc = mt == 1 ? launch_one<1, 1, 1, 4, 1, 1, 4, 0, true>(p, grid, st) : mt == 2 ? launch_one<1, 2, 1, 4, 1, 1, 4, 0, true>(p, grid, st) :
+                                                                                    launch_one<1, 4, 1, 4, 1, 1, 4, 0, true>(p, grid, st);
+        }
+        else if (proto.type == 0) {
             rc = mt == 1 ? launch_one<0, 1, 1, 8, 1, 1, 4, 0, true>(p, grid, st) : mt == 2 ? launch_one<0, 2, 1, 8, 1, 1, 4, 0, true>(p, grid, st) :
                                                                                     launch_one<0, 4, 1, 8, 1, 1, 4, 0, true>(p, grid, st);
         }
@@ -1402,8 +1407,10 @@ int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E
     else {  // prefill: 64-row blocks x 2 tiles per wave; blocks past an expert's segment exit at once
         p.zper = (m_cap + 63) / 64;
         TM_REQUIRE((int64_t)E * p.zper <= 65535, "grouped linear: experts x row blocks exceed grid.z (65535): split the forward into fewer tokens");
-        dim3 grid((ntiles + 15) / 16, 1, E * p.zper);
-        rc = proto.type == 0 ? launch_one<0, 4, 2, 8, 1, 1, 4, 0, true>(p, grid, st) : launch_one<2, 4, 2, 8, 1, 1, 2, 0, true>(p, grid, st);
+        dim3 grid(proto.type == 1 ? (ntiles + 7) / 8 : (ntiles + 15) / 16, 1, E * p.zper);  // fp16: 4 waves x 2 tiles
+        rc = proto.type == 0 ? launch_one<0, 4, 2, 8, 1, 1, 4, 0, true>(p, grid, st) :
+             proto.type == 1 ? launch_one<1, 4, 2, 4, 1, 1, 2, 0, true>(p, grid, st) :
+                               launch_one<2, 4, 2, 8, 1, 1, 2, 0, true>(p, grid, st);
     }
     return rc;
 }

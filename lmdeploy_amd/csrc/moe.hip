@@ -3,7 +3,8 @@
 // Replaces: MoeFfnLayerImpl::Gate, invokeMoeGate_V2 (softmax / top-k / norm_topk / routed_scale and the f2n / en2f /
 // offsets tables) and invokeMoeCombine (src/turbomind/models/llama/moe_ffn_layer.cc:43-53,133-325;
 // kernels/gemm/moe_utils_v2.cu:355-690).  The expert FFNs run as grouped GEMMs (gemm_w4a16.hip, `groups` descriptors)
-// over the token rows listed per expert.
+// over the token rows listed per expert: u4 (AWQ) and fp16 experts in gemm_kernel's grouped mode, e4m3 experts on the fp8 matrix
+// cores (gemm_fp8.hip; x and the gated-SiLU output are quantised per row first) or, with TM_FP8_MFMA=0, weight-only in gemm_kernel.
 //   gate:   logits[t][e] = sum_h x[t][h] * Wg[h][e] in fp32; top-k on the logits (ties: lower expert id);
 //           norm_topk: w_j = exp(l_j - max) / sum over the SELECTED experts, else softmax over all experts;
 //           w_j *= routed_scale.
@@ -575,7 +576,7 @@ size_t moe_workspace_bytes(const MoeBlock& m, int tokens)
     b  = (b + 255) / 256 * 256;
     b += pairs * m.hidden * 2;       // y2   [pairs][H]
     b  = (b + 255) / 256 * 256;
-    // fp8 x fp8 experts: codes + scales of x (per token) and of the gated-SiLU output (per (token, expert) row)
+    // fp8 x fp8 experts: codes + scales of x (per token) and of the gated-SiLU output (per (token, expert) row); unused by u4 / fp16
     b += fp8_act_workspace_bytes(tokens, m.hidden) + fp8_act_workspace_bytes((int)pairs, m.inter);
     return b + 256;
 }

@@ -205,7 +205,7 @@ int    dec32_m_bucket(int M);  // table key of a forward with M rows: M itself u
 // Measured dispatch of everything that is NOT a P32 kernel (reference: gemm.cu:92-224 caches every problem the
 // warm-up of turbomind.cc:363-487 meets, not only the dense u4 ones).  One table, key (kind, role, K, N, M bucket):
 //   kind kGenDense + type   : gemm_kernel of a dense linear (fp16 lm_head, e4m3 weight-only, u4 with N % 32 != 0) -> {nt, splits, waves, kphases}
-//   kind kGenGrouped + type : row-tile height of the grouped expert GEMMs (u4: 16 / 32 / 64 rows, fp8 MFMA: 32 / 64) -> {rows, 0, 0, 0}
+//   kind kGenGrouped + type : row-tile height of the grouped expert GEMMs (u4 and f16: 16 / 32 / 64 rows, fp8 MFMA: 32 / 64) -> {rows, 0, 0, 0}
 // Text form (same file as the P32 table): `G kind role K N M a b c d`.  role 5 = lm_head; grouped entries use role 0.
 constexpr int kGenDense   = 16;
 constexpr int kGenGrouped = 32;

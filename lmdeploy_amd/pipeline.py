@@ -33,6 +33,9 @@ SYNTHETIC = {
                        rope=checkpoint.RopeConfig(128, 500000.0, 'llama3', 8.0, 1.0, 4.0, 8192)),
     'tiny': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=512, vocab=1024,
                  rope=checkpoint.RopeConfig(128, 10000.0)),
+    # a mixture-of-experts twin of `tiny`: 8 experts of width 128, top-2 (u4, fp8 or -- model_format='hf' -- fp16 experts)
+    'tiny_moe': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=128, vocab=1024,
+                     rope=checkpoint.RopeConfig(128, 10000.0), moe_experts=8, moe_top_k=2),
 }
 
 

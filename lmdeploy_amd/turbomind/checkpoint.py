@@ -1,7 +1,7 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
 Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
-FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (MoE experts: AWQ or FP8 only):
+FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (dense linears and MoE experts alike):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
                                      qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head;
                                      Qwen3-MoE: mlp.gate router + mlp.experts.X.{gate,up,down}_proj, qwen3.py:110-121;
@@ -87,8 +87,14 @@ def _qwen3_moe_fields(arch: str, c: dict, quantized: bool, keys: tuple = QWEN3_M
     if not 1 <= E <= 256 or not 1 <= k <= 8 or k > E:
         raise NotImplementedError(f'{arch} with num_experts {E}, num_experts_per_tok {k}: the router serves up to 256 experts, top-8')
     if not quantized:
-        raise NotImplementedError(f'{arch} with fp16 / bf16 experts: the grouped expert GEMM serves AWQ (u4) and block-128 FP8 (e4m3) '
-                                  f'weights only')
+        # unquantised experts run as fp16 (a bf16 tensor is narrowed like the dense linears).  The config must say that the checkpoint is
+        # fp16 / bf16 -- as every published one does (`torch_dtype`, `dtype` in newer exports): a config.json with neither a
+        # quantization_config nor a 16-bit dtype describes float32 experts, or a quantised export whose quantization_config was lost
+        dt = str(c.get('torch_dtype', c.get('dtype'))).replace('torch.', '')
+        if dt not in ('float16', 'bfloat16'):
+            raise NotImplementedError(f'{arch} without a quantization_config and with torch_dtype {dt}: unquantised experts are served '
+                                      f'from float16 / bfloat16 checkpoints (config.json must say so); quantised experts need their '
+                                      f'quantization_config (AWQ or block-128 FP8)')
     shared = int(c['shared_expert_intermediate_size']) if 'shared_expert_intermediate_size' in keys else 0
     if shared < 0 or shared % 128:
         raise NotImplementedError(f'{arch} with shared_expert_intermediate_size {shared}: the shared expert\'s width must be a '
@@ -243,6 +249,7 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
             wo = _linear(t, p + '.self_attn.o_proj', cfg.quantized)
             moe = None
             if cfg.moe_experts:      # router [E, H] (unquantised also in AWQ checkpoints) -> fp16 [H][E]; per-expert w1 / w3 / w2
+                # (AWQ, FP8 or, in the checkpoints as published, fp16 / bf16 -> fp16 [K][N] like the dense linears)
                 # Mixtral (models/mixtral.py:73-106): block_sparse_moe.experts.X.w1 / w3 / w2; Qwen3-MoE (models/qwen3.py:110-121) and
                 # Qwen2-MoE (models/qwen2.py:110-128): mlp.experts.X.gate_proj / up_proj / down_proj
                 m, names = ((p + '.mlp', ('gate_proj', 'up_proj', 'down_proj')) if cfg.arch in ('qwen2', 'qwen3')
