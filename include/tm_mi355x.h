@@ -79,6 +79,31 @@ int tm_residual_rmsnorm(void* y, void* resid, const void* hidden, const float* p
 int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rope_type, float factor,
                   float low_freq_factor, float high_freq_factor, int original_max_position);
 
+/* The same recipe for every RoPE type (RopeConfig, init_rope_kernel_param: attention_weight.cc:37-93; rotary_embedding.h:11-110):
+ * type 0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic.  yarn: inv_freq = freq - freq * alpha * (1 - 1 / factor) with alpha the ramp
+ * between the correction dimensions of yarn_beta_fast / yarn_beta_slow rotations over max_position_embeddings, and cos / sin scaled by
+ * yarn_attention_factor in fp32 before the cast to fp16.  dynamic: the default recipe of `base` (the caller passes the SEQUENCE's
+ * base, tm_rope_dynamic_base); factor and max_position_embeddings only feed that function. */
+typedef struct tm_rope_param {
+    int   dim;
+    float base;
+    int   type;
+    float factor, low_freq_factor, high_freq_factor;
+    int   original_max_position;
+    int   max_position_embeddings;
+    float yarn_beta_fast, yarn_beta_slow, yarn_attention_factor;
+} tm_rope_param;
+/* tm_rope_table for every type: fp32 products, exp2 / sin / cos in double on those fp32 values, rounded fp32 -> fp16 */
+int tm_rope_table_ex(void* host_out, int max_pos, const tm_rope_param* p);
+/* the same table built on the DEVICE (asynchronous on `st`; inverse frequencies from the host recipe, angles / cos / sin per entry
+ * as on the host) */
+int tm_rope_table_device(void* dev_out, int max_pos, const tm_rope_param* p, tm_stream_t st);
+/* dynamic NTK (init_dynamic_ntk, unified_attention_layer.cc:228-243): factor > 1 and prompt_len > max_position_embeddings
+ * -> base * s ^ (dim / (dim - 2)) with s = factor * prompt_len / max_position_embeddings - (factor - 1) in float as the reference has
+ * it, the power in double and rounded to float once (the reference's powf with a float exponent lies up to ~5 fp32 ulps from the
+ * formula's value); else base.  The engine fixes a sequence's base with exactly this function when the sequence is admitted. */
+float tm_rope_dynamic_base(float base, float factor, int dim, int max_position_embeddings, int prompt_len);
+
 /* RoPE(q,k) + quantise-and-store K/V of the new tokens into the paged cache (ProcessKV_v2 / decode prologue).
  * qkv fp16 [total_tokens][(q_heads + 2 kv_heads)*128]; q is rotated in place.
  * cu_q_len [batch+1], k_len [batch] = context length of each sequence AFTER adding its new tokens (device).
@@ -92,6 +117,11 @@ int tm_kv_rope_store(void* qkv, int q_heads, const int* cu_q_len, const int* k_l
 int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                         const void* cos_sin, int max_pos, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
                         const tm_kv_cache* cache, tm_stream_t st);
+/* tm_kv_rope_store_qk with per-sequence tables: rope_row0 device int [batch] (NULL = tm_kv_rope_store_qk), sequence b reads table row
+ * rope_row0[b] + min(pos, max_pos - 1) -- cos_sin holds several regions of max_pos rows, an offset of 0 is the first (shared) one. */
+int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                         const void* cos_sin, int max_pos, const int* rope_row0, const void* qkv_bias, const void* q_norm,
+                         const void* k_norm, float qk_eps, const tm_kv_cache* cache, tm_stream_t st);
 /* FlattenKV_v2: dequantise the whole context into linear fp16 scratch.  k_out [kv_heads][k_stride][128];
  * v_out the same, or transposed [kv_heads][128][k_stride] when transpose_v != 0.  Sequence b starts at
  * cu_k_off[b] (device; must be 64-aligned when transposing). */
@@ -396,9 +426,13 @@ typedef struct tm_model_config {
     int   hidden, layers, q_heads, kv_heads, head_dim, inter, vocab;
     float rms_eps;
     float rope_base;
-    int   rope_type; /* 0 default, 1 linear, 2 llama3 */
+    int   rope_type; /* 0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic (tm_rope_param) */
     float rope_factor, rope_low_freq_factor, rope_high_freq_factor;
     int   rope_original_max_position;
+    /* yarn: the correction range's length; dynamic: prompts longer than this take a base of their own (an engine whose session_len
+     * does not exceed it runs exactly as rope_type 0) */
+    int   rope_max_position_embeddings;
+    float rope_yarn_beta_fast, rope_yarn_beta_slow, rope_yarn_attention_factor;
     int   group_size;   /* 128 */
     int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16 or TM_WEIGHT_FP8 for the decoder linears; lm_head is fp16 */
     /* mixture of experts (0 experts = dense FFN): every layer's FFN is a router + `moe_experts` expert FFNs of width
@@ -435,6 +469,9 @@ typedef struct tm_engine_config {
 typedef struct tm_engine tm_engine;
 
 int tm_engine_create(tm_engine** out, const tm_engine_config* cfg);
+/* after tm_engine_start: *per_seq_tables = 1 when the engine keeps one RoPE table region per batch slot behind the shared one
+ * (rope_type 4 with rope_factor > 1 and session_len > rope_max_position_embeddings), *table_bytes = bytes of those regions (0 without) */
+int tm_engine_rope_info(tm_engine* e, int* per_seq_tables, int64_t* table_bytes);
 int tm_engine_destroy(tm_engine* e);
 /* RCCL bootstrap for tp > 1: rank 0 calls tm_comm_unique_id (128 bytes, host), broadcasts it out of band
  * (torch.distributed / TCPStore), then every rank calls tm_engine_comm_init. */

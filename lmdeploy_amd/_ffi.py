@@ -49,12 +49,21 @@ class KvCache(C.Structure):
                 ('kv_heads', c_int), ('head_dim', c_int), ('block_len', c_int), ('bits', c_int)]
 
 
+class RopeParam(C.Structure):
+    """struct tm_rope_param"""
+    _fields_ = [('dim', c_int), ('base', c_float), ('type', c_int), ('factor', c_float), ('low_freq_factor', c_float),
+                ('high_freq_factor', c_float), ('original_max_position', c_int), ('max_position_embeddings', c_int),
+                ('yarn_beta_fast', c_float), ('yarn_beta_slow', c_float), ('yarn_attention_factor', c_float)]
+
+
 class ModelConfig(C.Structure):
     """struct tm_model_config"""
     _fields_ = [('hidden', c_int), ('layers', c_int), ('q_heads', c_int), ('kv_heads', c_int), ('head_dim', c_int),
                 ('inter', c_int), ('vocab', c_int), ('rms_eps', c_float), ('rope_base', c_float),
                 ('rope_type', c_int), ('rope_factor', c_float), ('rope_low_freq_factor', c_float),
-                ('rope_high_freq_factor', c_float), ('rope_original_max_position', c_int), ('group_size', c_int),
+                ('rope_high_freq_factor', c_float), ('rope_original_max_position', c_int),
+                ('rope_max_position_embeddings', c_int), ('rope_yarn_beta_fast', c_float), ('rope_yarn_beta_slow', c_float),
+                ('rope_yarn_attention_factor', c_float), ('group_size', c_int),
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
                 ('moe_routed_scale', c_float), ('moe_shared_inter', c_int), ('attn_bias', c_int), ('qk_norm', c_int)]
 
@@ -77,6 +86,12 @@ _SIGNATURES = {
     'tm_residual_rmsnorm': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                     c_int, c_int, c_void_p]),
     'tm_rope_table': (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_float, c_int]),
+    'tm_rope_table_ex': (c_int, [c_void_p, c_int, POINTER(RopeParam)]),
+    'tm_rope_table_device': (c_int, [c_void_p, c_int, POINTER(RopeParam), c_void_p]),
+    'tm_rope_dynamic_base': (c_float, [c_float, c_float, c_int, c_int, c_int]),
+    'tm_kv_rope_store_seq': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_float, POINTER(KvCache), c_void_p]),
+    'tm_engine_rope_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     'tm_kv_rope_store': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                  POINTER(KvCache), c_void_p]),
     'tm_kv_rope_store_qk': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,

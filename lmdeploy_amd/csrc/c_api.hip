@@ -40,41 +40,90 @@ static KvCacheView to_view(const tm_kv_cache* c)
     return v;
 }
 
-// Host-side (cos, sin) table.  Deterministic recipe shared with the oracle: freq and the angle are fp32
-// products, exp2 / sin / cos are evaluated in double on those fp32 values and rounded fp32 -> fp16.
-int build_rope_table(half_t* out, int max_pos, int dim, float base, int type, float factor, float low, float high,
-                     int orig_max_pos)
+// Per-pair inverse frequencies of one RoPE recipe (init_rope_kernel_param, attention_weight.cc:37-93 + the init_* functions of
+// rotary_embedding.h:11-52).  Deterministic recipe shared with the oracle: freq is an fp32 product run through exp2 in double and
+// rounded to fp32; everything behind it is stated in fp32 operation by operation.
+int rope_inv_freq(RopeInvFreq* out, const tm_rope_param& p)
 {
-    TM_REQUIRE(dim > 0 && dim % 2 == 0, "rope dim");
-    TM_REQUIRE(type >= 0 && type <= 2, "rope_type in {0 default, 1 linear, 2 llama3}");
-    const float        scale_factor = (float)(-std::log2((double)base) / dim);
-    std::vector<float> inv(dim / 2);
+    const int dim = p.dim;
+    TM_REQUIRE(dim > 0 && dim % 2 == 0 && dim / 2 <= kRopeMaxPairs, "rope dim: even, at most 128");
+    TM_REQUIRE(p.type >= 0 && p.type <= 4, "rope_type in {0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic}");
+    TM_REQUIRE(p.base > 0.f, "rope base");
+    const float scale_factor = (float)(-std::log2((double)p.base) / dim);
+    // dynamic NTK: the default recipe at the base the caller passes (the sequence's own, tm_rope_dynamic_base)
+    const float inv_factor   = (p.type == 4 || p.factor == 0.f) ? 1.f : (float)(1.0 / p.factor);
+    float       div_2 = 0.f, mul_min = 0.f;
+    if (p.type == 3) {
+        // YaRN correction range: the dimensions between beta_fast and beta_slow rotations over max_position_embeddings
+        TM_REQUIRE(p.max_position_embeddings > 0 && p.yarn_beta_fast > 0.f && p.yarn_beta_slow > 0.f && p.base != 1.f,
+                   "yarn: max_position_embeddings, beta_fast, beta_slow > 0");
+        const auto corr = [&](float rot) {
+            return (dim * std::log((double)p.max_position_embeddings / ((double)rot * 2.0 * M_PI))) / (2.0 * std::log((double)p.base));
+        };
+        float low  = (float)std::floor(corr(p.yarn_beta_fast));
+        float high = (float)std::ceil(corr(p.yarn_beta_slow));
+        low        = std::max(low, 0.f);
+        high       = std::min(high, dim - 1.f);
+        if (low == high) {
+            high += 0.001f;
+        }
+        div_2   = (float)(1.0 / (double)(high - low) / 2.0);
+        mul_min = (float)(1.0 / (double)(high - low) * (double)low);
+    }
     for (int i = 0; i < dim; i += 2) {
         const float prod = (float)i * scale_factor;
         const float freq = (float)std::exp2((double)prod);
         float       f    = freq;
-        if (type == 1) {
-            f = (float)(1.0 / factor) * freq;
+        if (p.type == 1) {
+            f = inv_factor * freq;
         }
-        else if (type == 2) {
-            const double inv_diff   = 1.0 / ((double)high - (double)low);
-            const float  alpha      = (float)((double)orig_max_pos / (2.0 * M_PI) * inv_diff);
-            const float  beta       = (float)((double)low * inv_diff);
-            const float  inv_factor = (float)(1.0 / factor);
-            float        smooth     = alpha * freq - beta;
-            smooth                  = smooth < 0.f ? 0.f : (smooth > 1.f ? 1.f : smooth);
-            f                       = (1.f - smooth) * freq * inv_factor + smooth * freq;
+        else if (p.type == 2) {
+            const double inv_diff = 1.0 / ((double)p.high_freq_factor - (double)p.low_freq_factor);
+            const float  alpha    = (float)((double)p.original_max_position / (2.0 * M_PI) * inv_diff);
+            const float  beta     = (float)((double)p.low_freq_factor * inv_diff);
+            float        smooth   = alpha * freq - beta;
+            smooth                = smooth < 0.f ? 0.f : (smooth > 1.f ? 1.f : smooth);
+            f                     = (1.f - smooth) * freq * inv_factor + smooth * freq;
         }
-        inv[i / 2] = f;
+        else if (p.type == 3) {
+            float alpha = (float)i * div_2 - mul_min;
+            alpha       = alpha < 0.f ? 0.f : (alpha > 1.f ? 1.f : alpha);
+            f           = freq - freq * alpha * (1.f - inv_factor);
+        }
+        out->inv[i / 2] = f;
     }
+    for (int i = dim / 2; i < kRopeMaxPairs; ++i) {
+        out->inv[i] = 0.f;
+    }
+    out->attention_factor = p.type == 3 ? p.yarn_attention_factor : 1.f;
+    return 0;
+}
+
+// Host-side (cos, sin) table: the angle is an fp32 product, sin / cos are evaluated in double on that fp32 value, rounded to fp32,
+// scaled by the YaRN attention factor in fp32 (1 for every other type: exact) and rounded to fp16.
+int build_rope_table_ex(half_t* out, int max_pos, const tm_rope_param& p)
+{
+    RopeInvFreq f;
+    TM_TRY_RC(rope_inv_freq(&f, p));
+    const int pairs = p.dim / 2;
     for (int t = 0; t < max_pos; ++t) {
-        for (int i = 0; i < dim / 2; ++i) {
-            const float ang                        = (float)t * inv[i];
-            out[((size_t)t * (dim / 2) + i) * 2]   = (half_t)(float)std::cos((double)ang);
-            out[((size_t)t * (dim / 2) + i) * 2 + 1] = (half_t)(float)std::sin((double)ang);
+        for (int i = 0; i < pairs; ++i) {
+            const float ang                    = (float)t * f.inv[i];
+            out[((size_t)t * pairs + i) * 2]     = (half_t)((float)std::cos((double)ang) * f.attention_factor);
+            out[((size_t)t * pairs + i) * 2 + 1] = (half_t)((float)std::sin((double)ang) * f.attention_factor);
         }
     }
     return 0;
+}
+
+int build_rope_table(half_t* out, int max_pos, int dim, float base, int type, float factor, float low, float high,
+                     int orig_max_pos)
+{
+    TM_REQUIRE(type >= 0 && type <= 2, "rope_type in {0 default, 1 linear, 2 llama3}");
+    tm_rope_param p{};
+    p.dim = dim, p.base = base, p.type = type, p.factor = factor, p.low_freq_factor = low, p.high_freq_factor = high;
+    p.original_max_position = orig_max_pos;
+    return build_rope_table_ex(out, max_pos, p);
 }
 
 }  // namespace tmk
@@ -134,6 +183,33 @@ int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rop
                             high_freq_factor, original_max_position);
 }
 
+int tm_rope_table_ex(void* host_out, int max_pos, const tm_rope_param* p)
+{
+    TM_REQUIRE(host_out && p && max_pos >= 1, "null pointer / max_pos");
+    return build_rope_table_ex((half_t*)host_out, max_pos, *p);
+}
+
+float tm_rope_dynamic_base(float base, float factor, int dim, int max_position_embeddings, int prompt_len)
+{
+    // init_dynamic_ntk (unified_attention_layer.cc:228-243).  The reference evaluates base * powf(s, dim / (dim - 2.f)) in float; the
+    // float exponent alone is off by 6e-8, which at s = 190 (prompt 4096 over 64 positions, factor 3) already moves the result 4.8 fp32
+    // ulps away from the formula's value.  Here s is the reference's float expression and the power is taken in double and rounded
+    // once: within 1 ulp of the formula, within the reference's own evaluation error of the reference.
+    if (factor > 1.f && max_position_embeddings > 0 && prompt_len > max_position_embeddings) {
+        const float s = factor * prompt_len / max_position_embeddings - (factor - 1);
+        return (float)((double)base * std::pow((double)s, (double)dim / ((double)dim - 2.0)));
+    }
+    return base;
+}
+
+int tm_rope_table_device(void* dev_out, int max_pos, const tm_rope_param* p, tm_stream_t st)
+{
+    TM_REQUIRE(dev_out && p && max_pos >= 1, "null pointer / max_pos");
+    RopeInvFreq f;
+    TM_TRY_RC(rope_inv_freq(&f, *p));
+    return launch_rope_table((half2_t*)dev_out, max_pos, p->dim, f, (hipStream_t)st);
+}
+
 int tm_kv_rope_store(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                      const void* cos_sin, int max_pos, const tm_kv_cache* cache, tm_stream_t st)
 {
@@ -145,10 +221,18 @@ int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* 
                         const void* cos_sin, int max_pos, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
                         const tm_kv_cache* cache, tm_stream_t st)
 {
+    return tm_kv_rope_store_seq(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, nullptr, qkv_bias, q_norm, k_norm,
+                                qk_eps, cache, st);
+}
+
+int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                         const void* cos_sin, int max_pos, const int* rope_row0, const void* qkv_bias, const void* q_norm,
+                         const void* k_norm, float qk_eps, const tm_kv_cache* cache, tm_stream_t st)
+{
     TM_REQUIRE(qkv && cu_q_len && k_len && cache, "null pointer");
     return launch_kv_rope_store((half_t*)qkv, q_heads, cu_q_len, k_len, batch, total_tokens, (const half2_t*)cos_sin,
                                 max_pos, to_view(cache), (hipStream_t)st, (const half_t*)qkv_bias, (const half_t*)q_norm,
-                                (const half_t*)k_norm, qk_eps);
+                                (const half_t*)k_norm, qk_eps, rope_row0);
 }
 
 int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,

@@ -70,6 +70,64 @@ __global__ void fill_const_f32_kernel(float* out, size_t n, float v)
     }
 }
 
+__global__ void set_int_kernel(int* dst, int v)
+{
+    *dst = v;
+}
+
+static tm_rope_param model_rope_param(const tm_engine* e)
+{
+    const tm_model_config& m = e->cfg.model;
+    tm_rope_param          p{};
+    p.dim = e->D, p.base = m.rope_base, p.type = m.rope_type, p.factor = m.rope_factor;
+    p.low_freq_factor = m.rope_low_freq_factor, p.high_freq_factor = m.rope_high_freq_factor;
+    p.original_max_position   = m.rope_original_max_position;
+    p.max_position_embeddings = m.rope_max_position_embeddings;
+    p.yarn_beta_fast = m.rope_yarn_beta_fast, p.yarn_beta_slow = m.rope_yarn_beta_slow;
+    p.yarn_attention_factor = m.rope_yarn_attention_factor;
+    return p;
+}
+
+// Admission of a sequence into batch slot `slot` (static prefill, continuous-batching admit, scoring): its RoPE base is fixed from its
+// prompt length (init_dynamic_ntk, unified_attention_layer.cc:228-243) and never changes while it generates.  A base of its own ->
+// the slot's table region is rebuilt on the engine stream, in front of the sequence's first forward, and the slot's row offset points
+// at it; the model's base -> offset 0, the shared table.  No-op on an engine with one table.
+int rope_admit(tm_engine* e, int slot, int prompt_len)
+{
+    if (!e->d_rope_row0) {
+        return 0;
+    }
+    const tm_model_config& m = e->cfg.model;
+    TM_REQUIRE(slot >= 0 && slot < e->cfg.max_batch_size, "internal: rope_admit slot");
+    const float base = tm_rope_dynamic_base(m.rope_base, m.rope_factor, e->D, m.rope_max_position_embeddings, prompt_len);
+    int         row0 = 0;
+    if (base != m.rope_base) {
+        row0            = (1 + slot) * e->rope_max_pos;
+        tm_rope_param p = model_rope_param(e);
+        p.base          = base;
+        RopeInvFreq f;
+        TM_TRY(rope_inv_freq(&f, p));
+        TM_TRY(launch_rope_table(e->d_rope + (size_t)row0 * (e->D / 2), e->rope_max_pos, e->D, f, e->stream));
+    }
+    if (row0 != e->h_rope_row0[slot]) {
+        set_int_kernel<<<1, 1, 0, e->stream>>>(e->d_rope_row0 + slot, row0);
+        TM_HIP_CHECK(hipGetLastError());
+        e->h_rope_row0[slot] = row0;
+    }
+    return 0;
+}
+
+// the slots [slot0, slot0 + n) go back to the shared table (release, a parked slot, the end of a scoring call)
+int rope_reset(tm_engine* e, int slot0, int n)
+{
+    if (!e->d_rope_row0 || n <= 0) {
+        return 0;
+    }
+    TM_HIP_CHECK(hipMemsetAsync(e->d_rope_row0 + slot0, 0, (size_t)n * sizeof(int), e->stream));
+    std::fill(e->h_rope_row0.begin() + slot0, e->h_rope_row0.begin() + slot0 + n, 0);
+    return 0;
+}
+
 static int64_t slot_bytes_linear(const tm_engine* e, int K, int N, const char* part)
 {
     if (!strcmp(part, "qweight")) return (int64_t)K * N / 2;
@@ -207,6 +265,7 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(c->tp >= 1 && c->rank >= 0 && c->rank < c->tp, "0 <= rank < tp");
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
     TM_REQUIRE(m.kv_heads % c->tp == 0 || c->tp % m.kv_heads == 0, "kv_heads vs tp");
+    TM_REQUIRE(m.rope_type >= 0 && m.rope_type <= 4, "rope_type in {0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic}");
     TM_REQUIRE(c->quant_policy == 0 || c->quant_policy == 4 || c->quant_policy == 8,
                "quant_policy in {0,4,8} (lmdeploy/messages.py:351-358)");
     TM_REQUIRE(c->cache_block_seq_len == 64, "cache_block_seq_len must be 64");
@@ -569,10 +628,25 @@ int tm_engine_start(tm_engine* e)
     e->rope_max_pos = c.session_len + 1;
     {
         std::vector<half_t> tab((size_t)e->rope_max_pos * e->D);
-        TM_TRY(build_rope_table(tab.data(), e->rope_max_pos, e->D, m.rope_base, m.rope_type, m.rope_factor,
-                                m.rope_low_freq_factor, m.rope_high_freq_factor, m.rope_original_max_position));
-        TM_TRY(dmalloc(&e->d_rope, tab.size() / 2));
+        TM_TRY(build_rope_table_ex(tab.data(), e->rope_max_pos, model_rope_param(e)));
+        // dynamic NTK: only a prompt longer than rope_max_position_embeddings takes a base of its own, so an engine whose session_len
+        // does not exceed it keeps the one table (type 4 at the model's base IS the default table) and everything that goes with it
+        const bool per_seq = m.rope_type == 4 && m.rope_factor > 1.f && m.rope_max_position_embeddings > 0
+                             && c.session_len > m.rope_max_position_embeddings;
+        const size_t regions = per_seq ? (size_t)1 + B : 1;
+        TM_REQUIRE(regions * e->rope_max_pos < ((size_t)1 << 31), "per-sequence RoPE tables: (1 + max_batch_size) x (session_len + 1) rows reach 2^31");
+        // (allocated in front of the KV pool: the pool is derived from what is free after this)
+        if (hipMalloc((void**)&e->d_rope, regions * tab.size() * sizeof(half_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_last_error("RoPE table allocation failed");
+            return TM_OOM;
+        }
         TM_HIP_CHECK(hipMemcpy(e->d_rope, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+        if (per_seq) {
+            TM_TRY(dmalloc(&e->d_rope_row0, (size_t)B));
+            TM_HIP_CHECK(hipMemset(e->d_rope_row0, 0, (size_t)B * sizeof(int)));
+            e->h_rope_row0.assign(B, 0);
+        }
     }
 
     TM_TRY(dmalloc(&e->d_ids, (size_t)B));
@@ -710,6 +784,15 @@ int tm_engine_debug_read(tm_engine* e, int what, int a, int b, void* host_out, i
     return 1;
 }
 
+int tm_engine_rope_info(tm_engine* e, int* per_seq_tables, int64_t* table_bytes)
+{
+    TM_REQUIRE(e && e->started, "null pointer / engine not started");
+    const bool on = e->d_rope_row0 != nullptr;
+    if (per_seq_tables) *per_seq_tables = on ? 1 : 0;
+    if (table_bytes) *table_bytes = on ? (int64_t)e->cfg.max_batch_size * e->rope_max_pos * e->D * (int64_t)sizeof(half_t) : 0;
+    return 0;
+}
+
 tm_stream_t tm_engine_stream(tm_engine* e)
 {
     return e ? (tm_stream_t)e->stream : nullptr;
@@ -809,7 +892,8 @@ int tm_engine_destroy(tm_engine* e)
     void* bufs[] = {e->pool, e->d_block_ptrs, e->d_cu_block_nums, e->d_resid, e->d_x, e->d_qkv, e->d_attn, e->d_act,
                     e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
-                    e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets};
+                    e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
+                    e->d_rope_row0};
     for (void* p : bufs) {
         if (p) {
             (void)hipFree(p);

@@ -198,7 +198,8 @@ static int forward_tail_two_halves(tm_engine* e, Layer& L, int M, int Ma, const 
 // hide AR(wo A) only under wo B and AR(w2 B) only under the next w_qkv A; here every exchange has a third to a half of the other
 // micro-batch's layer to hide under (measured with the 1-rank exchange stand-in: profiles/r05_prefill_overlap_emulated_exchange.txt).
 // Same kernels and per-row arithmetic as the unsplit forward; dense layers only.
-static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int max_q_len, int max_k_len, int kflat_stride, float scale_log2)
+static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int max_q_len, int max_k_len, int kflat_stride, float scale_log2,
+                                           const int* rope_row0)
 {
     const tm_model_config& m  = e->cfg.model;
     hipStream_t            st = e->stream;
@@ -227,7 +228,7 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             KvCacheView cv = cache_view(e, li);
             cv.block_ptrs += (size_t)P.s0 * e->max_blocks_per_seq;  // cu_block_nums[b] = b * max_blocks_per_seq: the part's sequence 0
             TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv, e->q_heads, P.cu_q, e->d_k_len + P.s0, P.nseq, P.rows, e->d_rope, e->rope_max_pos,
-                                                           cv, st, L.qkv_bias, L.q_norm, L.k_norm, eps)));
+                                                           cv, st, L.qkv_bias, L.q_norm, L.k_norm, eps, rope_row0 ? rope_row0 + P.s0 : nullptr)));
             TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + P.s0, e->d_k_len + P.s0, P.nseq, max_k_len,
                                                         kflat_stride, cv, st)));
             PrefillAttnParams p{};
@@ -354,6 +355,9 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     hipStream_t            st = e->stream;
     const int              nd = md ? md->rows : 0;  // leading decode rows of a mixed forward
     TM_REQUIRE(!md || (!decode && nd > 0 && nd < M), "internal: mixed forward");
+    // per-sequence RoPE tables: the row offsets are indexed by batch slot, this forward's sequence 0 sits in slot0
+    const int* const rope_row0 = e->d_rope_row0 ? e->d_rope_row0 + slot0 : nullptr;
+    TM_REQUIRE(!rope_row0 || !e->fuse_qkv, "internal: fused decode prologue with per-sequence RoPE tables");
     half_t* const qkv_p  = e->d_qkv + (size_t)nd * e->qkv_n;            // first prefill row
     half_t* const attn_p = e->d_attn + (size_t)nd * e->q_heads * e->D;
     TM_PROF(P_EMBED, TM_TRY(launch_embedding(e->d_resid, e->tok_embeddings, d_ids, M, e->hidden, m.vocab, st)));
@@ -370,7 +374,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     }
     if (two_mb) {
         e->pipe_mb_forwards += 1;
-        TM_TRY(forward_layers_two_microbatches(e, M, nseq, max_q_len, max_k_len, kflat_stride, scale_log2));
+        TM_TRY(forward_layers_two_microbatches(e, M, nseq, max_q_len, max_k_len, kflat_stride, scale_log2, rope_row0));
     }
     bool        qkv_done = false;  // the previous layer's two-halves tail already projected this layer's QKV
     int         ss_tiles   = 0;  // > 0: d_x holds r . g of a folded producer, d_ss its sums of squares (the next GEMM applies the row factor)
@@ -388,7 +392,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             ss_tiles = 0;
             if (!fuse_qkv) {
                 TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                               e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
+                                                               e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps, rope_row0)));
             }
         }
         else if (fuse_qkv) {
@@ -405,7 +409,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             }
             qkv_done = false;
             TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                           e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
+                                                           e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps, rope_row0)));
         }
         if (md) {
             // decode rows: (fused prologue: RoPE + K/V quantise-store) + attention on the fp16 projection rows; they share
@@ -432,7 +436,8 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             }
             else {  // fp16 KV (no fused prologue): RoPE + store of the decode rows' K/V first
                 TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(e->d_qkv, e->q_heads, md->cu_q, md->k_len, nd, nd, e->d_rope,
-                                                               e->rope_max_pos, cvd, dst, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps)));
+                                                               e->rope_max_pos, cvd, dst, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps,
+                                                               e->d_rope_row0)));  // decode rows = batch slots 0 .. nd-1
             }
             p.q              = e->d_qkv;
             p.q_stride       = e->qkv_n;
@@ -821,7 +826,10 @@ void setup_decode(tm_engine* e, int batch)
     e->decode_splits = std::min(std::max(splits, 1), 16);
     const char* valu = getenv("TM_ATTN_VALU");
     const char* fuse = getenv("TM_FUSE_QKV");
-    e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse));
+    // per-sequence RoPE tables (dynamic NTK active): the fused prologue reads the one shared table, so such an engine runs the unfused
+    // decode path -- kv_rope_store with the row offsets, then plain decode attention
+    e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse))
+                  && !e->d_rope_row0;
 }
 
 // Chunked prefill of `batch` sequences into the batch slots [slot0, slot0 + batch): whole sequences,
@@ -963,6 +971,7 @@ int tm_engine_release(tm_engine* e)
         TM_HIP_CHECK(hipStreamSynchronize(e->stream));
     }
     e->pending.valid = false;  // a look-ahead decode step of the session that ends here: its tokens belong to nobody
+    TM_TRY(rope_reset(e, 0, e->cfg.max_batch_size));
     for (auto& blks : e->h_blocks) {
         for (int b : blks) {
             e->free_blocks.push_back(b);
@@ -1083,6 +1092,9 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
         e->logits_on = true;
     }
     e->h_ttft_ms.assign(batch, 0.f);
+    for (int b = 0; b < batch; ++b) {
+        TM_TRY(rope_admit(e, b, host_lens[b]));
+    }
     {
         std::vector<const int*> seq_ids(batch);
         int                     off = 0;
@@ -1186,10 +1198,15 @@ int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int
     auto run = [&]() -> int {
         TM_HIP_CHECK(hipMemcpyAsync(e->d_block_ptrs, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice, e->stream));
         TM_HIP_CHECK(hipMemcpyAsync(e->d_score_tgt, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, e->stream));
+        for (int b = 0; b < batch; ++b) {
+            TM_TRY(rope_admit(e, b, host_lens[b]));
+        }
         e->scoring  = true;
         const int r = prefill_slots(e, seq_ids.data(), host_lens, batch, 0, nullptr);
         e->scoring  = false;
+        const int rr = rope_reset(e, 0, batch);  // also behind a failed forward: the slots go back to the shared table
         TM_TRY(r);
+        TM_TRY(rr);
         TM_HIP_CHECK(hipMemcpyAsync(nll.data(), e->d_score_nll, nll.size() * 4, hipMemcpyDeviceToHost, e->stream));
         TM_HIP_CHECK(hipStreamSynchronize(e->stream));
         return 0;

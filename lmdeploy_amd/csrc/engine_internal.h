@@ -25,8 +25,8 @@
 
 namespace tmk {
 
-int build_rope_table(half_t* out, int max_pos, int dim, float base, int type, float factor, float low, float high,
-                     int orig_max_pos);
+int build_rope_table_ex(half_t* out, int max_pos, const tm_rope_param& p);
+int rope_inv_freq(RopeInvFreq* out, const tm_rope_param& p);
 
 #define TM_NCCL_CHECK(expr)                                                                        \
     do {                                                                                           \
@@ -158,6 +158,12 @@ struct tm_engine {
     int     kflat_stride = 0;
     half2_t* d_rope = nullptr;
     int      rope_max_pos = 0;
+    // dynamic NTK (rope_type 4 with rope_factor > 1 and session_len > rope_max_position_embeddings): d_rope holds 1 + max_batch_size
+    // regions of rope_max_pos rows -- the shared table of the model's base, then one region per batch slot -- and d_rope_row0
+    // [max_batch_size] the first row of every slot's table (0 = the shared one).  A sequence's base is fixed when it is admitted
+    // (rope_admit); a persistent device array, so a captured decode step sees the updates like it sees d_k_len.  nullptr: one table.
+    int*             d_rope_row0 = nullptr;
+    std::vector<int> h_rope_row0;
 
     // batch state (device)
     int *d_next_ids = nullptr;
@@ -349,6 +355,8 @@ inline int dmalloc(T** p, size_t n)
 
 // ---- shared between the engine translation units ----
 int launch_advance_active(int* k_len, const int* active, int n, hipStream_t st);
+int rope_admit(tm_engine* e, int slot, int prompt_len);
+int rope_reset(tm_engine* e, int slot0, int n);
 size_t prof_event(tm_engine* e);
 void p2p_tables(tm_engine* e, half_t** data, uint32_t** flags);
 int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w);

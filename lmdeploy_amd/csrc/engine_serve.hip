@@ -95,7 +95,7 @@ static int cb_park_slot(tm_engine* e, int slot)
     e->h_active[slot] = 0;
     park_slot_kernel<<<1, 1, 0, e->stream>>>(e->d_active, e->d_k_len, e->d_block_ptrs + (size_t)slot * e->max_blocks_per_seq, slot, dp);
     TM_HIP_CHECK(hipGetLastError());
-    return 0;
+    return rope_reset(e, slot, 1);
 }
 
 // prefill the newly admitted requests (contiguous slot runs share one chunked prefill), hand over their first tokens
@@ -123,6 +123,7 @@ static int cb_prefill_admitted(tm_engine* e, const std::vector<SchedAdmit>& admi
             TM_REQUIRE(r && r->running, "internal: admitted request vanished");
             ids[k]  = r->prompt.data();
             lens[k] = (int)r->prompt.size();
+            TM_TRY(rope_admit(e, slot0 + k, lens[k]));
             if (e->sampling_on) {  // greedy rows are top_k = 1 rows of the sampling kernels
                 auto              it = e->cb_sampling.find(r->id);
                 const tm_sampling sp = it == e->cb_sampling.end() ? tm_sampling{1.f, 1, 1.f, 0.f, 0} : it->second;

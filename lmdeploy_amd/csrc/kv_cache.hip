@@ -43,7 +43,9 @@ __device__ __forceinline__ float row16_max(float v)
 
 // QKX: the Qwen prologue (per-head RMSNorm of q / k, then the q / k / v bias; either may be nullptr) in front of RoPE.
 // One 16-lane row holds one head of one token, so the head's sum of squares is a row16 DPP reduction like row16_max.
-template<int BITS, bool QKX>
+// SEQ: per-sequence RoPE tables (dynamic NTK) -- sequence b reads the rows [rope_row0[b], rope_row0[b] + max_pos) of cos_sin; the
+// position is clamped first, so a position past the end stays inside the sequence's own region.  Without SEQ rope_row0 is not read.
+template<int BITS, bool QKX, bool SEQ = false>
 __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__ qkv,
                                                             int q_heads,
                                                             const int* __restrict__ cu_q_len,
@@ -56,7 +58,8 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
                                                             const half_t* __restrict__ qkv_bias,
                                                             const half_t* __restrict__ q_norm,
                                                             const half_t* __restrict__ k_norm,
-                                                            float qk_eps)
+                                                            float qk_eps,
+                                                            const int* __restrict__ rope_row0)
 {
     constexpr int  D       = 128;
     const KvLayout L       = cache.layout;
@@ -95,7 +98,11 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
     if ((is_q || is_k) && cos_sin != nullptr) {
         // interleaved pairs (x[2i], x[2i+1]); c,s already cast to fp16; fp16 mul/sub/add, no fma
         const int     p  = pos < max_pos ? pos : max_pos - 1;
-        const half8_t cs = *(const half8_t*)(cos_sin + (size_t)p * (D / 2) + lane16 * 4);
+        size_t        row = (size_t)p;
+        if constexpr (SEQ) {
+            row += (size_t)rope_row0[b];  // 64-bit: max_batch x (session_len + 1) rows of 256 B pass 2 GiB
+        }
+        const half8_t cs = *(const half8_t*)(cos_sin + row * (D / 2) + lane16 * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const half_t c  = cs[2 * i];
@@ -183,9 +190,11 @@ int launch_kv_rope_store(half_t*        qkv,
                          const half_t*  qkv_bias,
                          const half_t*  q_norm,
                          const half_t*  k_norm,
-                         float          qk_eps)
+                         float          qk_eps,
+                         const int*     rope_row0)
 {
     TM_REQUIRE(cache.layout.head_dim == 128, "head_dim must be 128");
+    TM_REQUIRE(rope_row0 == nullptr || cos_sin != nullptr, "rope_row0 needs a table");
     TM_REQUIRE(cache.layout.bits == 16 || cache.layout.bits == 8 || cache.layout.bits == 4, "kv bits in {16,8,4}");
     TM_REQUIRE((q_norm == nullptr) == (k_norm == nullptr), "q_norm and k_norm come together");
     if (total_tokens == 0) {
@@ -193,9 +202,17 @@ int launch_kv_rope_store(half_t*        qkv,
     }
     dim3 grid((total_tokens + 15) / 16, q_heads + 2 * cache.layout.kv_heads);
     const bool qkx = qkv_bias != nullptr || q_norm != nullptr;
-#define TM_KV_STORE(B_, X_)                                                                                                 \
-    kv_rope_store_kernel<B_, X_><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, \
-                                                       cache, qkv_bias, q_norm, k_norm, qk_eps)
+#define TM_KV_STORE(B_, X_)                                                                                                       \
+    do {                                                                                                                          \
+        if (rope_row0 != nullptr) {                                                                                               \
+            kv_rope_store_kernel<B_, X_, true><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, \
+                                                                     max_pos, cache, qkv_bias, q_norm, k_norm, qk_eps, rope_row0); \
+        }                                                                                                                         \
+        else {                                                                                                                    \
+            kv_rope_store_kernel<B_, X_><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin,       \
+                                                               max_pos, cache, qkv_bias, q_norm, k_norm, qk_eps, nullptr);        \
+        }                                                                                                                         \
+    } while (0)
     switch (cache.layout.bits) {
         case 16:
             if (qkx) TM_KV_STORE(16, true);
@@ -210,6 +227,37 @@ int launch_kv_rope_store(half_t*        qkv,
             else TM_KV_STORE(4, false);
     }
 #undef TM_KV_STORE
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// (cos, sin) table on the device: the table of tm_rope_table_ex for inverse frequencies the host computed by the shared recipe.
+// One thread = one (position, pair): angle = one fp32 product, cos / sin in double of that fp32 value, rounded fp32 (x the YaRN
+// attention factor, in fp32) -> fp16; one half2 store per thread, consecutive threads consecutive pairs.  Runs once per admission of a
+// sequence that takes a base of its own (dynamic NTK), on the engine stream.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rope_table_kernel(half2_t* __restrict__ out, int64_t entries, int pairs, RopeInvFreq f)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= entries) {
+        return;
+    }
+    const int   t   = (int)(idx / pairs);
+    const int   i   = (int)(idx - (int64_t)t * pairs);
+    const float ang = (float)t * f.inv[i];
+    const float c   = (float)cos((double)ang) * f.attention_factor;  // a factor of 1 is exact
+    const float s   = (float)sin((double)ang) * f.attention_factor;
+    half2_t     o   = {(half_t)c, (half_t)s};
+    out[idx]  = o;
+}
+
+int launch_rope_table(half2_t* out, int max_pos, int dim, const RopeInvFreq& f, hipStream_t st)
+{
+    TM_REQUIRE(out != nullptr && max_pos >= 1, "rope table: null pointer / max_pos");
+    TM_REQUIRE(dim > 0 && dim % 2 == 0 && dim / 2 <= kRopeMaxPairs, "rope dim: even, at most 128");
+    const int64_t entries = (int64_t)max_pos * (dim / 2);
+    rope_table_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(out, entries, dim / 2, f);
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }

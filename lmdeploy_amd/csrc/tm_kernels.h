@@ -53,7 +53,16 @@ int launch_residual_rmsnorm(half_t* y, half_t* resid, const half_t* hidden, cons
 int launch_kv_rope_store(half_t* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                          const half2_t* cos_sin, int max_pos, KvCacheView cache, hipStream_t st,
                          const half_t* qkv_bias = nullptr, const half_t* q_norm = nullptr, const half_t* k_norm = nullptr,
-                         float qk_eps = 0.f);
+                         float qk_eps = 0.f, const int* rope_row0 = nullptr);
+
+// per-pair inverse frequencies of one RoPE recipe (rope_inv_freq, c_api.hip) + the factor on cos / sin (YaRN; 1 otherwise): what the
+// host table builder and rope_table_kernel share, so both build the same table
+constexpr int kRopeMaxPairs = 64;
+struct RopeInvFreq {
+    float inv[kRopeMaxPairs];
+    float attention_factor;
+};
+int launch_rope_table(half2_t* out, int max_pos, int dim, const RopeInvFreq& f, hipStream_t st);
 // Gather + dequantise (two-rounding "flatten" form) the whole context of every sequence into linear
 // scratch: K [kv_heads][k_stride][D]; V either [kv_heads][k_stride][D] or transposed [kv_heads][D][k_stride].
 int launch_flatten_kv(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,

@@ -16,6 +16,7 @@ HF linears are [out, in]; TM layout is [in, out] (= AWQ's native [K, N/8] packin
 from __future__ import annotations
 
 import json
+import math
 import os
 from dataclasses import dataclass, field
 from glob import glob
@@ -34,6 +35,13 @@ class RopeConfig:
     low_freq_factor: float = 1.0
     high_freq_factor: float = 4.0
     original_max_position_embeddings: int = 8192
+    # yarn: the length the correction range is taken over; dynamic: prompts longer than this take a base of their own.  Both hold
+    # the MODEL's max_position_embeddings (what the reference's copy_rope_config hands to the engine, also for yarn checkpoints that
+    # carry original_max_position_embeddings: that key only sets the factor)
+    max_position_embeddings: int = 0
+    beta_fast: float = 32.0
+    beta_slow: float = 1.0
+    attention_factor: float = 1.0
 
 
 @dataclass
@@ -103,15 +111,38 @@ def _qwen3_moe_fields(arch: str, c: dict, quantized: bool, keys: tuple = QWEN3_M
                 moe_norm_topk=bool(c.get('norm_topk_prob', False)), moe_routed_scale=1.0, moe_shared_inter=shared)
 
 
+def _yarn_mscale(scale: float, mscale: float = 1.0) -> float:
+    return 1.0 if scale <= 1 else 0.1 * mscale * math.log(scale) + 1.0
+
+
+def _scaled_rope(t: str, rs: dict, D: int, base: float, max_pos: int) -> RopeConfig:
+    """rope_scaling `dynamic` / `yarn` of a Llama / InternLM config as the reference parses it (lmdeploy/turbomind/models/utils.py:76-187)"""
+    factor = float(rs.get('factor', 0.0))
+    if t == 'dynamic':
+        return RopeConfig(D, base, 'dynamic', factor, max_position_embeddings=max_pos)
+    af = rs.get('attention_factor')
+    if af is None:
+        ms, ms_all = rs.get('mscale'), rs.get('mscale_all_dim')
+        af = _yarn_mscale(factor, ms) / _yarn_mscale(factor, ms_all) if ms is not None and ms_all is not None else _yarn_mscale(factor)
+    if 'original_max_position_embeddings' in rs:
+        factor = max_pos / rs['original_max_position_embeddings']
+    return RopeConfig(D, base, 'yarn', float(factor), max_position_embeddings=max_pos, beta_fast=float(rs.get('beta_fast', 32.0)),
+                      beta_slow=float(rs.get('beta_slow', 1.0)), attention_factor=float(af))
+
+
 def read_config(model_path: str) -> ModelConfig:
     with open(os.path.join(model_path, 'config.json')) as f:
         c = json.load(f)
     arch = (c.get('architectures') or ['LlamaForCausalLM'])[0]
     kind = 'internlm2' if 'InternLM2' in arch else 'llama'
     qwen = arch in QWEN_ARCHS
-    if kind == 'llama' and not qwen and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
-        raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 '
-                                  f'decoders, Qwen2-MoE and Qwen3-MoE')
+    internlm3 = arch == 'InternLM3ForCausalLM'      # a plain Llama (the reference: supported_models.py) -- without projection biases
+    if internlm3 and (c.get('bias') or c.get('qkv_bias')):
+        raise NotImplementedError(f'{arch} with bias {c.get("bias")} / qkv_bias {c.get("qkv_bias")}: the Llama reader carries no '
+                                  f'projection biases')
+    if kind == 'llama' and not qwen and not internlm3 and not any(a in arch for a in ('Llama', 'Mistral', 'Mixtral')):
+        raise NotImplementedError(f'architecture {arch}: the MI355X hot path covers Llama / InternLM2 / InternLM3 / Mixtral / Qwen2 / '
+                                  f'Qwen3 decoders, Qwen2-MoE and Qwen3-MoE')
     H = c['hidden_size']
     heads = c['num_attention_heads']
     D = c.get('head_dim') or H // heads
@@ -145,6 +176,8 @@ def read_config(model_path: str) -> ModelConfig:
                               float(rs.get('high_freq_factor', 4.0)), int(rs.get('original_max_position_embeddings', 8192)))
         elif t == 'linear':
             rope = RopeConfig(D, rope.base, 'linear', float(rs['factor']))
+        elif t in ('dynamic', 'yarn') and not qwen:
+            rope = _scaled_rope(t, rs, D, rope.base, int(c.get('max_position_embeddings', 0)))
         elif t not in (None, 'default'):
             raise NotImplementedError(f'rope_scaling type {t}')
     # eos ids: config.json + generation_config.json (GenerationConfig.update_from_hf_gen_cfg, lmdeploy/messages.py:176-199)

@@ -14,17 +14,20 @@ import numpy as np
 
 from .. import _ffi
 
-_ROPE_TYPES = {'default': 0, 'linear': 1, 'llama3': 2}
+_ROPE_TYPES = {'default': 0, 'linear': 1, 'llama3': 2, 'yarn': 3, 'dynamic': 4}
 
 
 def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     """cfg: any object with hidden, layers, q_heads, kv_heads, head_dim, inter, vocab, rms_eps, rope(.dim,.base,.type,
-    .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings), group; optional moe_* (moe_shared_inter: Qwen2-MoE's
-    shared expert), attn_bias, qk_norm."""
+    .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings; optional .max_position_embeddings, .beta_fast,
+    .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert), attn_bias,
+    qk_norm."""
     r = cfg.rope
     return _ffi.ModelConfig(cfg.hidden, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, cfg.inter, cfg.vocab,
                             cfg.rms_eps, r.base, _ROPE_TYPES[r.type], r.factor, r.low_freq_factor, r.high_freq_factor,
-                            r.original_max_position_embeddings, cfg.group, weight_type,
+                            r.original_max_position_embeddings, int(getattr(r, 'max_position_embeddings', 0) or 0),
+                            float(getattr(r, 'beta_fast', 32.0)), float(getattr(r, 'beta_slow', 1.0)),
+                            float(getattr(r, 'attention_factor', 1.0)), cfg.group, weight_type,
                             int(getattr(cfg, 'moe_experts', 0) or 0), int(getattr(cfg, 'moe_top_k', 0) or 0),
                             int(bool(getattr(cfg, 'moe_norm_topk', True))), float(getattr(cfg, 'moe_routed_scale', 1.0)),
                             int(getattr(cfg, 'moe_shared_inter', 0) or 0),
@@ -353,6 +356,13 @@ class Engine:
         wb, kv, nb, sp = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
         _ffi.check(self._lib.tm_engine_stats(self._h, C.byref(wb), C.byref(kv), C.byref(nb), C.byref(sp)))
         return dict(weight_bytes=wb.value, kv_bytes_per_token=kv.value, num_blocks=nb.value, decode_splits=sp.value)
+
+    def rope_info(self) -> dict:
+        """per_seq_tables: the engine keeps one RoPE table per batch slot (dynamic NTK with session_len > max_position_embeddings)
+        and runs the unfused decode prologue; table_bytes: what those tables take"""
+        on, nb = C.c_int(), C.c_int64()
+        _ffi.check(self._lib.tm_engine_rope_info(self._h, C.byref(on), C.byref(nb)))
+        return dict(per_seq_tables=bool(on.value), table_bytes=nb.value)
 
     def comm_info(self) -> dict:
         """which communicator the tensor-parallel data path runs on, its own rank count, graph replay or eager"""
