@@ -56,7 +56,7 @@ typedef struct tm_kv_cache {
     const int*      cu_block_nums; /* device [batch+1]: first block of each sequence in block_ptrs */
     int64_t         layer_offset;  /* bytes: layer * tm_kv_layer_size()                            */
     int             kv_heads;      /* local kv heads                                               */
-    int             head_dim;      /* 128                                                          */
+    int             head_dim;      /* 64 | 128                                                     */
     int             block_len;     /* 64 tokens (lmdeploy/messages.py:323)                         */
     int             bits;          /* quant_policy: 16 (none) | 8 | 4 (lmdeploy/messages.py:20-27) */
 } tm_kv_cache;
@@ -105,15 +105,16 @@ int tm_rope_table_device(void* dev_out, int max_pos, const tm_rope_param* p, tm_
 float tm_rope_dynamic_base(float base, float factor, int dim, int max_position_embeddings, int prompt_len);
 
 /* RoPE(q,k) + quantise-and-store K/V of the new tokens into the paged cache (ProcessKV_v2 / decode prologue).
- * qkv fp16 [total_tokens][(q_heads + 2 kv_heads)*128]; q is rotated in place.
+ * qkv fp16 [total_tokens][(q_heads + 2 kv_heads)*head_dim]; q is rotated in place.  cache->head_dim is 64 or 128 (cos_sin rows
+ * of head_dim / 2 pairs).
  * cu_q_len [batch+1], k_len [batch] = context length of each sequence AFTER adding its new tokens (device).
  * cos_sin may be NULL (no rotation). */
 int tm_kv_rope_store(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                      const void* cos_sin, int max_pos, const tm_kv_cache* cache, tm_stream_t st);
 /* The same with the Qwen attention prologue in front of RoPE, each part optional (NULL = off): q_norm / k_norm fp16 [128]
  * (both or neither) -> per-head RMSNorm of every q / k head, y = h(h(f32(x) * inv) * w), inv = 1 / sqrt(sum f32(x)^2 / 128 + eps)
- * (Qwen3); then qkv_bias fp16 [(q_heads + 2 kv_heads)*128] added to q, k and v in fp16 (Qwen2).  With all three NULL this is
- * tm_kv_rope_store. */
+ * (Qwen3; head_dim 128 only: with head_dim 64 the norm returns TM_INVALID); then qkv_bias fp16 [(q_heads + 2 kv_heads)*head_dim]
+ * added to q, k and v in fp16 (Qwen2; head_dim 64 or 128).  With all three NULL this is tm_kv_rope_store. */
 int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                         const void* cos_sin, int max_pos, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
                         const tm_kv_cache* cache, tm_stream_t st);
@@ -122,15 +123,17 @@ int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* 
 int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                          const void* cos_sin, int max_pos, const int* rope_row0, const void* qkv_bias, const void* q_norm,
                          const void* k_norm, float qk_eps, const tm_kv_cache* cache, tm_stream_t st);
-/* FlattenKV_v2: dequantise the whole context into linear fp16 scratch.  k_out [kv_heads][k_stride][128];
- * v_out the same, or transposed [kv_heads][128][k_stride] when transpose_v != 0.  Sequence b starts at
+/* FlattenKV_v2: dequantise the whole context into linear fp16 scratch.  k_out [kv_heads][k_stride][head_dim];
+ * v_out the same, or transposed [kv_heads][head_dim][k_stride] when transpose_v != 0 (head_dim 64 or 128; the transposed rows are
+ * zero-filled from k_len up to the next multiple of 64).  Sequence b starts at
  * cu_k_off[b] (device; must be 64-aligned when transposing). */
 int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
                   int max_k_len, int k_stride, const tm_kv_cache* cache, tm_stream_t st);
 
 /* Paged flash-decode, one query token per sequence (dispatchDecoding).  q fp16 [batch][q_stride] already
- * rotated (head h at h*128), out fp16 [batch][q_heads*128].  splits >= 1; workspace of
- * tm_decode_attention_workspace() bytes needed when splits > 1.  softmax_scale <= 0 -> 1/sqrt(128).
+ * rotated (head h at h*head_dim), out fp16 [batch][q_heads*head_dim], head_dim = cache->head_dim (64 or 128).  splits >= 1;
+ * workspace of tm_decode_attention_workspace() bytes needed when splits > 1 (sized for head_dim 128, which is enough for 64).
+ * softmax_scale <= 0 -> 1/sqrt(head_dim).  head_dim 64 runs the VALU kernel for every KV width.
  * Every k_len[b] >= 1 and the first block-table entry of every sequence is a mapped block (the engine parks free batch slots on a
  * dummy block with k_len = 1); a k_len = 0 entry reads that first block and produces no meaningful row. */
 size_t tm_decode_attention_workspace(int batch, int q_heads, int splits);
@@ -141,7 +144,8 @@ int    tm_decode_attention(void* out, const void* q, int q_stride, const int* k_
  * kernel itself applies RoPE to q/k and quantises + stores the new K/V).  int8 / int4 KV.  Input is the raw QKV
  * projection of the new token of every sequence: qkv_splits == 0 -> `qkv` is fp16 [batch][qkv_n]; qkv_splits >= 1
  * -> `qkv` is fp32 split-K slabs [qkv_splits][batch][qkv_n] which are summed in order and rounded to fp16 first.
- * Row layout [Q heads | K heads | V heads] x 128.  k_len INCLUDES the new token.  Cache bytes/params written are
+ * Row layout [Q heads | K heads | V heads] x 128: head_dim 128 only, a cache of head_dim 64 returns TM_INVALID (run
+ * tm_kv_rope_store + tm_decode_attention).  k_len INCLUDES the new token.  Cache bytes/params written are
  * bit-identical to tm_kv_rope_store; `out` equals tm_decode_attention on that cache. */
 int tm_decode_attention_fused(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
                               const int* k_len, int batch, int q_heads, float softmax_scale, int splits,
@@ -152,10 +156,16 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
                                  const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps, const int* k_len,
                                  int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
                                  tm_stream_t st);
-/* Causal prefill attention over flattened KV (dispatchAttention).  vt is the transposed V of tm_flatten_kv. */
+/* Causal prefill attention over flattened KV (dispatchAttention).  vt is the transposed V of tm_flatten_kv.  head_dim 128;
+ * softmax_scale <= 0 -> 1/sqrt(128). */
 int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
                          const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                          int q_heads, int kv_heads, float softmax_scale, tm_stream_t st);
+/* The same for head_dim 64 or 128 (q heads at h*head_dim, k [kv_heads][k_stride][head_dim], vt [kv_heads][head_dim][k_stride]);
+ * softmax_scale <= 0 -> 1/sqrt(head_dim).  tm_prefill_attention is the head_dim = 128 case. */
+int tm_prefill_attention_hd(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
+                            const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
+                            int q_heads, int kv_heads, int head_dim, float softmax_scale, tm_stream_t st);
 
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st);
 /* greedy top-1 on fp32-cast logits (generation/sampling.cc:92-183); out_val (fp16 [batch]) may be NULL */
@@ -423,6 +433,8 @@ int tm_debug_set_moe_router(int mode);
  * Engine level (static batcher around LanguageModel::Forward)
  * --------------------------------------------------------------------------------------------*/
 typedef struct tm_model_config {
+    /* head_dim: 64 or 128; q_heads / tp * head_dim must be a multiple of 128.  head_dim 64 decodes on the VALU attention kernel behind
+     * tm_kv_rope_store (no fused prologue) for every quant_policy; qk_norm needs head_dim 128. */
     int   hidden, layers, q_heads, kv_heads, head_dim, inter, vocab;
     float rms_eps;
     float rope_base;

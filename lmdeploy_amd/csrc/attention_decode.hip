@@ -19,51 +19,75 @@
 //     share a token (wavefront-level reduction, no LDS), the P.V products accumulate per lane in fp32 and are
 //     reduced across lanes once per workgroup;
 //   * grid = (kv_heads * head_chunks, batch, splits) -> 512..2048 workgroups for the metric shape.
+//
+// Head dimension: the kernel is templated on D (64 | 128).  At D = 64 every KV width keeps CPT = 8 lanes per token (E = 8 dims per
+// lane: 16-byte loads for fp16, 8-byte for int8, 4-byte for int4), so the DPP butterflies (group_sum<8>, upper_sum<8>) are the ones
+// the fp16 D = 128 path already runs; CPT = 4 (16 dims per lane) has no butterfly in tm_common.h and does not compile.  Head_dim 64
+// decodes here for all three widths: the MFMA kernel (attention_decode_mfma.hip) and its fused prologue are D = 128 only.
 #include "tm_common.h"
 #include "tm_kernels.h"
 #include <stdlib.h>
 
 namespace tmk {
 
-template<int BITS>
+template<int BITS, int D = 128>
 struct KvTraits;
 template<>
-struct KvTraits<8> {
+struct KvTraits<8, 128> {
     static constexpr int LOAD_BYTES = 16;  // per lane per instruction
     static constexpr int E          = 16;  // head dims per lane
     static constexpr int TILE       = 32;  // tokens per online-softmax step (register budget: 2+ waves/SIMD)
 };
 template<>
-struct KvTraits<16> {
+struct KvTraits<16, 128> {
     static constexpr int LOAD_BYTES = 16;
     static constexpr int E          = 8;
     static constexpr int TILE       = 32;  // 256-B rows: keep the register tile at 8 loads
 };
 template<>
-struct KvTraits<4> {
+struct KvTraits<4, 128> {
     static constexpr int LOAD_BYTES = 8;
     static constexpr int E          = 16;
     static constexpr int TILE       = 32;
 };
+// D = 64: E = 8 for every width, so a token keeps CPT = 8 lanes (see the file header)
+template<>
+struct KvTraits<8, 64> {
+    static constexpr int LOAD_BYTES = 8;
+    static constexpr int E          = 8;
+    static constexpr int TILE       = 32;
+};
+template<>
+struct KvTraits<16, 64> {
+    static constexpr int LOAD_BYTES = 16;
+    static constexpr int E          = 8;
+    static constexpr int TILE       = 32;
+};
+template<>
+struct KvTraits<4, 64> {
+    static constexpr int LOAD_BYTES = 4;
+    static constexpr int E          = 8;
+    static constexpr int TILE       = 32;
+};
 
-// Dequantise one lane-load into E/2 half2 pairs (decode form: single-rounding fma).
-template<int BITS>
-__device__ __forceinline__ void dequant_chunk(const uint32_t (&raw)[KvTraits<BITS>::LOAD_BYTES / 4],
+// Dequantise one lane-load of LW dwords into half2 pairs (decode form: single-rounding fma): 2 LW dims at 16 bits, 4 LW at 8, 8 LW at 4.
+template<int BITS, int LW>
+__device__ __forceinline__ void dequant_chunk(const uint32_t (&raw)[LW],
                                               half2_t s2,
                                               half2_t z2,
-                                              half2_t (&out)[KvTraits<BITS>::E / 2])
+                                              half2_t (&out)[LW * (BITS == 16 ? 1 : BITS == 8 ? 2 : 4)])
 {
     const half2_t k1024 = {(half_t)1024.0f, (half_t)1024.0f};
     if constexpr (BITS == 16) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < LW; ++i) {
             out[i] = bit_cast<half2_t>(raw[i]);
         }
     }
     else if constexpr (BITS == 8) {
         // bytes b0..b3 of a dword are dims 4i..4i+3: 0x64bb is fp16(1024 + b)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < LW; ++i) {
             const uint32_t lo = __builtin_amdgcn_perm(0x64646464u, raw[i], 0x04010400u);
             const uint32_t hi = __builtin_amdgcn_perm(0x64646464u, raw[i], 0x04030402u);
             out[2 * i]        = h2_fma(bit_cast<half2_t>(lo) - k1024, s2, z2);
@@ -73,7 +97,7 @@ __device__ __forceinline__ void dequant_chunk(const uint32_t (&raw)[KvTraits<BIT
     else {
         // nibble i (i<4) = element 2i, nibble 4+i = element 2i+1 of each group of 8
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < LW; ++i) {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const uint32_t t = ((raw[i] >> (4 * p)) & 0x000f000fu) | 0x64006400u;
@@ -83,13 +107,31 @@ __device__ __forceinline__ void dequant_chunk(const uint32_t (&raw)[KvTraits<BIT
     }
 }
 
-template<int BITS, int HPW>
+// raw bytes of one lane-load; streaming policy: every byte is read once per launch
+template<int LW>
+__device__ __forceinline__ void load_raw(uint32_t (&raw)[LW], const char* ptr)
+{
+    static_assert(LW == 1 || LW == 2 || LW == 4, "4-, 8- or 16-byte lane loads");
+    if constexpr (LW == 4) {
+        const u32x4 t = __builtin_nontemporal_load((const u32x4*)ptr);
+        raw[0] = t[0], raw[1] = t[1], raw[2] = t[2], raw[3] = t[3];
+    }
+    else if constexpr (LW == 2) {
+        const u32x2 t = __builtin_nontemporal_load((const u32x2*)ptr);
+        raw[0] = t[0], raw[1] = t[1];
+    }
+    else {
+        raw[0] = __builtin_nontemporal_load((const uint32_t*)ptr);
+    }
+}
+
+template<int BITS, int HPW, int D = 128>
 __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnParams p, int head_chunks)
 {
-    using Tr                 = KvTraits<BITS>;
-    constexpr int D          = 128;
+    using Tr                 = KvTraits<BITS, D>;
     constexpr int E          = Tr::E;
     constexpr int CPT        = D / E;       // lanes sharing a token (8 or 16)
+    static_assert(CPT == 8 || CPT == 16, "a token's lanes reduce with the 8- / 16-lane butterflies of tm_common.h");
     constexpr int TILE       = Tr::TILE;
     constexpr int TPI        = 64 / CPT;    // tokens per load instruction (8 or 4)
     constexpr int IPT        = TILE / TPI;  // load instructions per tile (8)
@@ -168,15 +210,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
         uint32_t kraw[IPT][LW];
 #pragma unroll
         for (int r = 0; r < IPT; ++r) {
-            const char* ptr = kdata + (size_t)(r * TPI + tg) * TOKB + c * Tr::LOAD_BYTES;
-            if constexpr (LW == 4) {
-                const u32x4 t = __builtin_nontemporal_load((const u32x4*)ptr);  // read once per launch: streaming policy
-                kraw[r][0] = t[0], kraw[r][1] = t[1], kraw[r][2] = t[2], kraw[r][3] = t[3];
-            }
-            else {
-                const u32x2 t = __builtin_nontemporal_load((const u32x2*)ptr);
-                kraw[r][0] = t[0], kraw[r][1] = t[1];
-            }
+            load_raw<LW>(kraw[r], kdata + (size_t)(r * TPI + tg) * TOKB + c * Tr::LOAD_BYTES);
         }
         float S[IPT][HPW];
 #pragma unroll
@@ -189,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
                 z2                = half2_t{pp[1], pp[1]};
             }
             half2_t kd[E / 2];
-            dequant_chunk<BITS>(kraw[r], s2, z2, kd);
+            dequant_chunk<BITS, LW>(kraw[r], s2, z2, kd);
             const bool valid = r * TPI + tg < ntok;
 #pragma unroll
             for (int h = 0; h < HPW; ++h) {
@@ -207,15 +241,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
         uint32_t vraw[IPT][LW];
 #pragma unroll
         for (int r = 0; r < IPT; ++r) {
-            const char* ptr = vdata + (size_t)(r * TPI + tg) * TOKB + c * Tr::LOAD_BYTES;
-            if constexpr (LW == 4) {
-                const u32x4 t = __builtin_nontemporal_load((const u32x4*)ptr);  // read once per launch: streaming policy
-                vraw[r][0] = t[0], vraw[r][1] = t[1], vraw[r][2] = t[2], vraw[r][3] = t[3];
-            }
-            else {
-                const u32x2 t = __builtin_nontemporal_load((const u32x2*)ptr);
-                vraw[r][0] = t[0], vraw[r][1] = t[1];
-            }
+            load_raw<LW>(vraw[r], vdata + (size_t)(r * TPI + tg) * TOKB + c * Tr::LOAD_BYTES);
         }
 
         // ---- online softmax ---------------------------------------------------------------
@@ -256,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
                 z2                = half2_t{pp[1], pp[1]};
             }
             half2_t vd[E / 2];
-            dequant_chunk<BITS>(vraw[r], s2, z2, vd);
+            dequant_chunk<BITS, LW>(vraw[r], s2, z2, vd);
             const bool valid = r * TPI + tg < ntok;
             if constexpr (BITS == 16) {
                 if (!valid) {  // raw fp16 garbage past the context must not reach the accumulators
@@ -335,10 +361,10 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
     }
 }
 
-// split-K merge: one 128-thread workgroup per (sequence, query head)
-__global__ __launch_bounds__(128) void decode_reduce_kernel(DecodeAttnParams p)
+// split-K merge: one D-thread workgroup per (sequence, query head)
+template<int D>
+__global__ __launch_bounds__(D) void decode_reduce_kernel(DecodeAttnParams p)
 {
-    constexpr int D    = 128;
     const int     hq   = blockIdx.x;
     const int     b    = blockIdx.y;
     const int     d    = threadIdx.x;
@@ -362,7 +388,7 @@ size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, in
     return (size_t)batch * q_heads * splits * (head_dim + 2) * sizeof(float);
 }
 
-template<int BITS>
+template<int BITS, int D = 128>
 static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
 {
     const int group = p.q_heads / p.cache.layout.kv_heads;
@@ -377,20 +403,20 @@ static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
     dim3      grid(p.cache.layout.kv_heads * chunks, p.batch, p.splits);
     switch (hpw) {
         case 4:
-            decode_attention_kernel<BITS, 4><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 4, D><<<grid, 256, 0, st>>>(p, chunks);
             break;
         case 3:
-            decode_attention_kernel<BITS, 3><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 3, D><<<grid, 256, 0, st>>>(p, chunks);
             break;
         case 2:
-            decode_attention_kernel<BITS, 2><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 2, D><<<grid, 256, 0, st>>>(p, chunks);
             break;
         default:
-            decode_attention_kernel<BITS, 1><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 1, D><<<grid, 256, 0, st>>>(p, chunks);
     }
     TM_HIP_CHECK(hipGetLastError());
     if (p.splits > 1) {
-        decode_reduce_kernel<<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
+        decode_reduce_kernel<D><<<dim3(p.q_heads, p.batch), D, 0, st>>>(p);
         TM_HIP_CHECK(hipGetLastError());
     }
     return 0;
@@ -399,7 +425,7 @@ static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
 {
     const KvLayout& L = p.cache.layout;
-    TM_REQUIRE(L.head_dim == 128 && L.block_len == 64, "decode attention: head_dim 128, block_len 64");
+    TM_REQUIRE((L.head_dim == 64 || L.head_dim == 128) && L.block_len == 64, "decode attention: head_dim 64 or 128, block_len 64");
     TM_REQUIRE(p.q_heads % L.kv_heads == 0, "q_heads % kv_heads");
     TM_REQUIRE(p.splits >= 1 && p.splits <= 128, "1 <= splits <= 128 (kMaxKVSplits)");
     TM_REQUIRE(p.splits == 1 || (p.partial_o && p.partial_ml), "split-K needs a workspace");
@@ -410,6 +436,19 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     TM_REQUIRE(!fused || L.bits == 8 || L.bits == 4, "fused decode prologue: int8 / int4 KV only");
     // the Qwen prologue (bias / q-k norm) exists only in the fused MFMA path; unfused kernels read q after launch_kv_rope_store applied it
     TM_REQUIRE(fused || (!p.qkv_bias && !p.q_norm && !p.k_norm), "qkv bias / q-k norm need the fused decode prologue");
+    if (L.head_dim == 64) {
+        // before TM_ATTN_VALU is looked at: head_dim 64 has the VALU kernel only, for every KV width
+        TM_REQUIRE(!fused, "fused decode prologue (MFMA kernel): head_dim must be 128, head_dim 64 runs kv_rope_store + tm_decode_attention");
+        switch (L.bits) {
+            case 16:
+                return launch_bits<16, 64>(p, st);
+            case 8:
+                return launch_bits<8, 64>(p, st);
+            case 4:
+                return launch_bits<4, 64>(p, st);
+        }
+        TM_REQUIRE(false, "kv bits in {16,8,4}");
+    }
     switch (L.bits) {
         case 16:
             return launch_bits<16>(p, st);
@@ -426,7 +465,7 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
                 return rc;
             }
             if (p.splits > 1) {
-                decode_reduce_kernel<<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
+                decode_reduce_kernel<128><<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
                 TM_HIP_CHECK(hipGetLastError());
             }
             return 0;
@@ -443,7 +482,7 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
                 return rc;
             }
             if (p.splits > 1) {
-                decode_reduce_kernel<<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
+                decode_reduce_kernel<128><<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
                 TM_HIP_CHECK(hipGetLastError());
             }
             return 0;

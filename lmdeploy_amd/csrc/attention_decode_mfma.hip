@@ -640,6 +640,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(Decode
 
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p_in, hipStream_t st)
 {
+    TM_REQUIRE(p_in.cache.layout.head_dim == 128, "MFMA decode attention: head_dim must be 128 (head_dim 64 runs the VALU kernel)");
     DecodeAttnParams p     = p_in;
     const int        group = p.q_heads / p.cache.layout.kv_heads;
     int       hpw   = group;

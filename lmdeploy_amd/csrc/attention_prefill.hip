@@ -24,6 +24,23 @@
 // bounds it now is the softmax's VALU issue, not memory: per 32-key step and wave 64 MFMAs (1024 matrix-pipe cycles) stand
 // against ~500 VALU slots (32 v_exp_f32 at quarter rate alone are 512 cycles), and the two waves of a SIMD share one VALU.
 // Prefill attention is 8 % of a prefill chunk (the GEMMs are 82 %), so this is where the kernel was left.
+//
+// Head dimension: the kernel is templated on D (64 | 128); everything above describes D = 128, whose instantiations are unchanged.
+// At D = 64 the QK contraction is 2 MFMA k-steps (not 4), the O tile 4 column tiles (not 8), a K-tile row 128 B = 8 chunks of 16 B and a
+// stage 8 KB of K + 8 KB of V^T (32 KB of LDS for both buffers).  The 1 KB DMA pieces: K piece pc = key rows 8pc .. 8pc+7, V^T piece
+// pc = head-dim rows 8pc .. 8pc+7, 8 + 8 pieces per stage, wave w moves pieces w and 4 + w of either tile.
+// LDS reads at D = 64, by the 16-lane service groups of a ds_read_b128 (two neighbouring g, eight score-tile rows each):
+//   * K fragments: rows are 128 B, so two rows span the 64 banks and the bank quad of a read is (row & 1, slot).  The eight rows of a
+//     half group are keys {0..3, 24..27} or {8..11, 16..19} (+4 for tile B, +32 for the second step): same-parity rows differ in
+//     bits 1 and 3, which ksw64() moves to slot bits 1 and 2; slot bit 0 is g's.  16 distinct bank quads per group: conflict-free.
+//   * V^T fragments: the rows, the swizzle (d & 7) and the read addresses are those of the D = 128 tile with half as many rows.  A
+//     group holds eight i16 of one g and the other eight of its neighbour: either eight cover all eight slots ((4 sub + g) ^ (i16 & 7)),
+//     and two lanes of different g on one slot have i16 of different parity, i.e. rows in different halves of the bank row:
+//     conflict-free, as at D = 128.
+//   * The V^T transpose pass of flatten_kv_kernel and the LDS-DMA writes (lane L to slot L of a 1 KB piece) are not ds_read_b128
+//     fragment reads; they were not analysed.
+// Both statements follow the bank rule (bank = byte address / 4 mod 64, conflicts inside a service group only); no counter run has
+// confirmed them at D = 64.
 #include "tm_common.h"
 #include "tm_kernels.h"
 
@@ -64,14 +81,23 @@ __device__ __forceinline__ float sum_xor16_xor32(float v)
     return __builtin_bit_cast(float, (unsigned)q[0]) + __builtin_bit_cast(float, (unsigned)q[1]);
 }
 
+// The same for the 128-byte K rows of head_dim 64 (8 slots, 3-bit term): see the file header.
+__device__ __forceinline__ int ksw64(int r)
+{
+    return (r & 2) | ((r & 8) >> 1);
+}
+
 // Running maxima start at a large negative FINITE value: every difference / product in the online softmax then stays finite
 // or is a clean -inf (masked score -> exp2(-inf) = 0), and the "-inf so far" selects around each exp disappear.
 constexpr float kMinScore = -1.0e30f;
 
-template<int G>
+template<int G, int D = 128>
 __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnParams p)
 {
-    constexpr int D     = 128;
+    static_assert(D == 64 || D == 128, "head_dim 64 or 128");
+    constexpr int NDD   = D / 32;       // MFMA k-steps of the QK contraction
+    constexpr int NDT   = D / 16;       // 16-column tiles of O
+    constexpr int KROW  = D * 2;        // bytes of a K-tile row
     constexpr int KS    = 64;           // keys per stage
     constexpr int KTILE = KS * D * 2;   // bytes of a K tile (and of a V^T tile)
     constexpr int STG   = 2 * KTILE;
@@ -101,11 +127,11 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
     // Q^T fragments (B operand): lane (j = query row, g) holds Q[q0+j][32*dd + 8g .. +8) of head hq0 + h
     const int     qrow = min(q0 + i16, qlen - 1);
     const half_t* qptr = p.q + (size_t)(q_beg + qrow) * p.q_stride + (size_t)hq0 * D;
-    half8_t       qf[G][4];
+    half8_t       qf[G][NDD];
 #pragma unroll
     for (int h = 0; h < G; ++h) {
 #pragma unroll
-        for (int dd = 0; dd < 4; ++dd) {
+        for (int dd = 0; dd < NDD; ++dd) {
             qf[h][dd] = *(const half8_t*)(qptr + h * D + dd * 32 + g * 8);
         }
     }
@@ -121,18 +147,19 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
     // (128 B each, 8 chunks); wave w moves pieces 4r + w, r = 0..3.  Lane L lands in slot L: it fetches the chunk that belongs there.
     // piece 4r + w: K rows 16r + 4w + (L >> 4), V^T rows 32r + 8w + (L >> 3) -- the swizzle terms (row & 15, d & 7) do not depend on
     // r (ksw looks at bits 3 and 1..0 only), so one per-lane offset each serves all four pieces and r moves into the scalar offset
-    const int krow0 = 4 * wave + (lane >> 4);
-    const int kdo   = krow0 * 256 + (((lane & 15) ^ ksw(krow0)) << 4);
+    // D = 64: K piece 4r + w = key rows 32r + 8w + (L >> 3), r = 0..1; ksw64 looks at row bits 3 and 1 only, so again one per-lane offset
+    const int krow0 = D == 128 ? 4 * wave + (lane >> 4) : 8 * wave + (lane >> 3);
+    const int kdo   = D == 128 ? krow0 * 256 + (((lane & 15) ^ ksw(krow0)) << 4) : krow0 * 128 + (((lane & 7) ^ ksw64(krow0)) << 4);
     const int vrow0 = 8 * wave + (lane >> 3);
     const int vdo   = vrow0 * p.k_stride * 2 + (((lane & 7) ^ (vrow0 & 7)) << 4);
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem);
     auto stage_in = [&](int ks, int buf) __attribute__((always_inline)) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int r = 0; r < NDD; ++r) {
             unsigned       keep;
             const unsigned dk = lds0 + buf * STG + (4 * r + wave) * 1024;
             const unsigned dv = dk + KTILE;
-            const int      sk = ks * D * 2 + r * 16 * 256, sv = ks * 2 + r * 32 * p.k_stride * 2;
+            const int      sk = ks * D * 2 + r * 4096, sv = ks * 2 + r * 32 * p.k_stride * 2;  // 4 pieces on: 4 KB of K, 32 rows of V^T
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
                          "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"
                          "s_mov_b32 m0, %5\n\ts_nop 0\n\t"
@@ -143,14 +170,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
         }
     };
 
-    floatx4 O[G][8];
+    floatx4 O[G][NDT];
     float   m[G], l[G];
 #pragma unroll
     for (int h = 0; h < G; ++h) {
         m[h] = kMinScore;
         l[h] = 0.f;
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
+        for (int dt = 0; dt < NDT; ++dt) {
             O[h][dt] = floatx4{0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -176,13 +203,14 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             if (ks >= kend_w) {  // wave-uniform: causal end of this wave (or an inactive wave)
                 continue;
             }
-            half8_t ka[4], kb[4];
+            half8_t ka[NDD], kb[NDD];
             {
                 const int ra = 32 * sub + krow, rb = ra + 4;
+                const int wa = D == 128 ? ksw(ra) : ksw64(ra), wb = D == 128 ? ksw(rb) : ksw64(rb);
 #pragma unroll
-                for (int dd = 0; dd < 4; ++dd) {
-                    ka[dd] = *(const half8_t*)(kt + ra * 256 + (((4 * dd + g) ^ ksw(ra)) << 4));
-                    kb[dd] = *(const half8_t*)(kt + rb * 256 + (((4 * dd + g) ^ ksw(rb)) << 4));
+                for (int dd = 0; dd < NDD; ++dd) {
+                    ka[dd] = *(const half8_t*)(kt + ra * KROW + (((4 * dd + g) ^ wa) << 4));
+                    kb[dd] = *(const half8_t*)(kt + rb * KROW + (((4 * dd + g) ^ wb) << 4));
                 }
             }
             // the whole 32-key step lies at or below the diagonal for every row of the wave and inside the context:
@@ -194,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             for (int h = 0; h < G; ++h) {
                 floatx4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int dd = 0; dd < 4; ++dd) {
+                for (int dd = 0; dd < NDD; ++dd) {
                     sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka[dd], qf[h][dd], sa, 0, 0, 0);
                     sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(kb[dd], qf[h][dd], sb, 0, 0, 0);
                 }
@@ -240,7 +268,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
                 l[h] = l[h] * alpha + psum;
                 if (__builtin_amdgcn_readfirstlane((int)__any(mnew != m[h]))) {  // wave-uniform: did any row's max move?
 #pragma unroll
-                    for (int dt = 0; dt < 8; ++dt) {
+                    for (int dt = 0; dt < NDT; ++dt) {
                         O[h][dt] *= alpha;
                     }
                 }
@@ -250,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             // (fragments fetched here, not above the softmax: 32 more live registers there would spill at G = 4)
             const char* vrow = vt + i16 * 128 + (((4 * sub + g) ^ (i16 & 7)) << 4);  // row dt*16 + i16: same swizzle term for every dt
 #pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
+            for (int dt = 0; dt < NDT; ++dt) {
                 const half8_t vf = *(const half8_t*)(vrow + dt * 16 * 128);
 #pragma unroll
                 for (int h = 0; h < G; ++h) {
@@ -269,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             half_t*     optr = p.out + (size_t)(q_beg + q0 + i16) * p.q_heads * D + (size_t)(hq0 + h) * D;
             const float inv  = 1.0f / lh;
 #pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
+            for (int dt = 0; dt < NDT; ++dt) {
                 half4_t o = {(half_t)(O[h][dt][0] * inv), (half_t)(O[h][dt][1] * inv), (half_t)(O[h][dt][2] * inv),
                              (half_t)(O[h][dt][3] * inv)};
                 *(half4_t*)(optr + dt * 16 + g * 4) = o;
@@ -282,6 +310,7 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st)
 {
     TM_REQUIRE(p.q_heads % p.kv_heads == 0, "q_heads % kv_heads");
     TM_REQUIRE(p.k_stride % 64 == 0, "k_stride must be a multiple of 64");
+    TM_REQUIRE(p.head_dim == 64 || p.head_dim == 128, "prefill attention: head_dim must be 64 or 128");
     if (p.batch == 0 || p.max_q_len == 0) {
         return 0;
     }
@@ -289,6 +318,25 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st)
     const int G     = group % 4 == 0 ? 4 : (group % 2 == 0 ? 2 : 1);  // query heads per wave (share one kv head); G = 4 spills ~25
                                                                        // registers at two workgroups per CU -- measured equal to G = 2
     dim3      grid((p.max_q_len + 63) / 64, p.q_heads / G, p.batch);
+    if (p.head_dim == 64) {
+        constexpr int lds64 = 2 * 2 * 64 * 64 * 2;
+        const void* const k64 = G == 4 ? (const void*)prefill_attention_kernel<4, 64> :
+                                G == 2 ? (const void*)prefill_attention_kernel<2, 64> : (const void*)prefill_attention_kernel<1, 64>;
+        if (const int rc = ensure_dynamic_lds(k64, lds64)) {
+            return rc;
+        }
+        if (G == 4) {
+            prefill_attention_kernel<4, 64><<<grid, 256, lds64, st>>>(p);
+        }
+        else if (G == 2) {
+            prefill_attention_kernel<2, 64><<<grid, 256, lds64, st>>>(p);
+        }
+        else {
+            prefill_attention_kernel<1, 64><<<grid, 256, lds64, st>>>(p);
+        }
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     constexpr int lds = 2 * 2 * 64 * 128 * 2;  // two stages of (K tile + V^T tile)
     const void* const k = G == 4 ? (const void*)prefill_attention_kernel<4> :
                           G == 2 ? (const void*)prefill_attention_kernel<2> : (const void*)prefill_attention_kernel<1>;

@@ -245,6 +245,7 @@ int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off
 
 size_t tm_decode_attention_workspace(int batch, int q_heads, int splits)
 {
+    // sized for head_dim 128: enough for 64 too (the partial-O slots of a launch follow the cache's head_dim, partial_ml sits behind them)
     return decode_attention_workspace_bytes(batch, q_heads, 128, splits);
 }
 
@@ -259,11 +260,11 @@ int tm_decode_attention(void* out, const void* q, int q_stride, const int* k_len
     p.k_len      = k_len;
     p.batch      = batch;
     p.q_heads    = q_heads;
-    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt(128.0f);
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)cache->head_dim);
     p.scale_log2 = s * 1.4426950408889634f;
     p.splits     = splits < 1 ? 1 : splits;
     p.partial_o  = (float*)workspace;
-    p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * 128 : nullptr;
+    p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * cache->head_dim : nullptr;
     p.cache      = to_view(cache);
     return launch_decode_attention(p, (hipStream_t)st);
 }
@@ -282,6 +283,8 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
                                  tm_stream_t st)
 {
     TM_REQUIRE(out && qkv && k_len && cache, "null pointer");
+    TM_REQUIRE(cache->head_dim == 128,
+               "fused decode prologue: head_dim must be 128 (head_dim 64: tm_kv_rope_store + tm_decode_attention)");
     TM_REQUIRE(cache->bits == 8 || cache->bits == 4, "fused decode prologue: int8 / int4 KV only");
     TM_REQUIRE(qkv_n == (q_heads + 2 * cache->kv_heads) * 128, "qkv_n != (q_heads + 2 kv_heads) * 128");
     DecodeAttnParams p{};
@@ -289,11 +292,11 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
     p.k_len      = k_len;
     p.batch      = batch;
     p.q_heads    = q_heads;
-    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt(128.0f);
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)cache->head_dim);
     p.scale_log2 = s * 1.4426950408889634f;
     p.splits     = splits < 1 ? 1 : splits;
     p.partial_o  = (float*)workspace;
-    p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * 128 : nullptr;
+    p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * cache->head_dim : nullptr;
     p.cache      = to_view(cache);
     p.qkv_slabs  = qkv_splits > 0 ? (const float*)qkv : nullptr;
     p.qkv_f16    = qkv_splits > 0 ? nullptr : (const half_t*)qkv;
@@ -312,7 +315,16 @@ int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, 
                          const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                          int q_heads, int kv_heads, float softmax_scale, tm_stream_t st)
 {
+    return tm_prefill_attention_hd(out, q, q_stride, k, vt, k_stride, cu_q_len, cu_k_off, k_len, batch, max_q_len, q_heads, kv_heads, 128,
+                                   softmax_scale, st);
+}
+
+int tm_prefill_attention_hd(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
+                            const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
+                            int q_heads, int kv_heads, int head_dim, float softmax_scale, tm_stream_t st)
+{
     TM_REQUIRE(out && q && k && vt && cu_q_len && cu_k_off && k_len, "null pointer");
+    TM_REQUIRE(head_dim == 64 || head_dim == 128, "prefill attention: head_dim must be 64 or 128");
     PrefillAttnParams p{};
     p.q          = (const half_t*)q;
     p.q_stride   = q_stride;
@@ -327,7 +339,8 @@ int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, 
     p.max_q_len  = max_q_len;
     p.q_heads    = q_heads;
     p.kv_heads   = kv_heads;
-    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt(128.0f);
+    p.head_dim   = head_dim;
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)head_dim);
     p.scale_log2 = s * 1.4426950408889634f;
     return launch_prefill_attention(p, (hipStream_t)st);
 }

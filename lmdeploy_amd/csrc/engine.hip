@@ -260,7 +260,8 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
 {
     TM_REQUIRE(out && c, "null pointer");
     const tm_model_config& m = c->model;
-    TM_REQUIRE(m.head_dim == 128, "head_dim must be 128");
+    TM_REQUIRE(m.head_dim == 64 || m.head_dim == 128, "head_dim must be 64 or 128");
+    TM_REQUIRE(m.head_dim == 128 || !m.qk_norm, "qk_norm (per-head q/k RMSNorm) needs head_dim 128: not built for head_dim 64");
     TM_REQUIRE(m.group_size == 128, "AWQ group size must be 128");
     TM_REQUIRE(c->tp >= 1 && c->rank >= 0 && c->rank < c->tp, "0 <= rank < tp");
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
@@ -294,6 +295,7 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
         e->mixed_steps_on = !(ms && !atoi(ms));
         e->graph_comm     = !(gc && !atoi(gc));
     }
+    e->D           = m.head_dim;
     e->qkv_n       = (e->q_heads + 2 * e->kv_heads) * e->D;
     TM_REQUIRE((e->inter * 1) % 128 == 0 && (e->q_heads * e->D) % 128 == 0 && m.hidden % 128 == 0,
                "K dims must be multiples of 128 after TP sharding");

@@ -246,6 +246,7 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             p.q_heads    = e->q_heads;
             p.kv_heads   = e->kv_heads;
             p.scale_log2 = scale_log2;
+            p.head_dim   = e->D;
             TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
             TM_PROF(P_GEMM_O, TM_TRY(linear_plain(e, L.wo, e->d_attn + (size_t)P.r0 * kq, kq, e->d_tmp + off, H, P.rows, false)));
             TM_TRY(allreduce_rows_side(e, P.r0, P.rows, &done[h]));
@@ -500,6 +501,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             p.q_heads    = e->q_heads;
             p.kv_heads   = e->kv_heads;
             p.scale_log2 = scale_log2;
+            p.head_dim   = e->D;
             TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
             if (md && e->mixed_two_streams && e->aux_stream) {
                 TM_HIP_CHECK(hipStreamWaitEvent(st, e->ev_aux_join, 0));  // join: wo reads the decode rows' attention output too
@@ -794,7 +796,8 @@ void setup_decode(tm_engine* e, int batch)
         // count of TP = 8 (profiles/r04_gemm_experiments_session2.txt, call25): 64 x 4 workgroups 1.485 ms per step against
         // 1.547 .. 1.587 with 64 x 8 (Llama-3-8B shard), 5.06 against 5.26 (Llama-3-70B shard).  fp16 KV (VALU kernel, <= 4
         // heads per workgroup): two workgroups per CU as before.
-        const bool mfma  = e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4;
+        // head_dim 64 decodes on the VALU kernel for every KV width: its head-per-workgroup rule
+        const bool mfma  = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128;
         const int  group = e->q_heads / e->kv_heads;
         int        hpw   = 1;
         if (mfma) {
@@ -828,8 +831,9 @@ void setup_decode(tm_engine* e, int batch)
     const char* fuse = getenv("TM_FUSE_QKV");
     // per-sequence RoPE tables (dynamic NTK active): the fused prologue reads the one shared table, so such an engine runs the unfused
     // decode path -- kv_rope_store with the row offsets, then plain decode attention
+    // head_dim 64: no MFMA kernel, so no fused prologue either -- the same unfused path
     e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse))
-                  && !e->d_rope_row0;
+                  && !e->d_rope_row0 && e->D == 128;
 }
 
 // Chunked prefill of `batch` sequences into the batch slots [slot0, slot0 + batch): whole sequences,

@@ -9,8 +9,10 @@
 //   inv = h(1/f32(scale)); q = sat_u8(rne(h(h(x-zero)*inv))); b==4: min(q,15), nibbles [0,2,4,6,1,3,5,7].
 // Byte layout of a block: kernels/attention/block.h:126-219 (KvLayout in tm_kernels.h).
 //
-// Work mapping: 16 lanes own one 128-wide head row (8 halves = 16 B each, coalesced 256 B per row);
-// min/max are wave-level DPP reductions inside the 16-lane row -- no LDS.  HBM-bound byte work.
+// Work mapping: D/8 lanes own one D-wide head row (8 halves = 16 B each, one coalesced row): 16 lanes (256 B) at head_dim 128,
+// 8 lanes (128 B) at head_dim 64; min/max are wave-level DPP reductions inside that lane row -- no LDS.  HBM-bound byte work.
+// Both kernels are templated on D (64 | 128): the 8-lane row reduces with xor1, xor2, half-mirror only (the row_ror:8 step of the
+// 16-lane row would mix two tokens), a 256-thread workgroup holds 2048 / D token rows.
 #include "tm_common.h"
 #include "tm_kernels.h"
 
@@ -32,20 +34,26 @@ __device__ __forceinline__ int find_seq(const int* cu, int batch, int token)
     return lo;
 }
 
-__device__ __forceinline__ float row16_max(float v)
+// max over the LPR (8 | 16) lanes of one head row
+template<int LPR>
+__device__ __forceinline__ float row_max(float v)
 {
+    static_assert(LPR == 8 || LPR == 16, "head rows of 8 or 16 lanes");
     v = fmaxf(v, dpp_f32<DPP_XOR1>(v));
     v = fmaxf(v, dpp_f32<DPP_XOR2>(v));
     v = fmaxf(v, dpp_f32<DPP_HMIRR>(v));
-    v = fmaxf(v, dpp_f32<DPP_ROR8>(v));
+    if constexpr (LPR == 16) {
+        v = fmaxf(v, dpp_f32<DPP_ROR8>(v));
+    }
     return v;
 }
 
 // QKX: the Qwen prologue (per-head RMSNorm of q / k, then the q / k / v bias; either may be nullptr) in front of RoPE.
-// One 16-lane row holds one head of one token, so the head's sum of squares is a row16 DPP reduction like row16_max.
+// One 16-lane row holds one 128-wide head of one token, so the head's sum of squares is a row DPP reduction like row_max.  The norm
+// exists at D = 128 only (head_norm8 fixes 1/128 and the 16-partial tree); the launcher refuses it at D = 64, the bias works there.
 // SEQ: per-sequence RoPE tables (dynamic NTK) -- sequence b reads the rows [rope_row0[b], rope_row0[b] + max_pos) of cos_sin; the
 // position is clamped first, so a position past the end stays inside the sequence's own region.  Without SEQ rope_row0 is not read.
-template<int BITS, bool QKX, bool SEQ = false>
+template<int BITS, bool QKX, bool SEQ = false, int D = 128>
 __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__ qkv,
                                                             int q_heads,
                                                             const int* __restrict__ cu_q_len,
@@ -61,14 +69,15 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
                                                             float qk_eps,
                                                             const int* __restrict__ rope_row0)
 {
-    constexpr int  D       = 128;
+    static_assert(D == 64 || D == 128, "head_dim 64 or 128");
+    constexpr int  LPR     = D / 8;  // lanes per head row
     const KvLayout L       = cache.layout;
-    const int      lane16  = threadIdx.x & 15;
-    const int      token   = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int      lane16  = threadIdx.x & (LPR - 1);  // lane inside the head row (0..7 at D = 64)
+    const int      token   = blockIdx.x * (256 / LPR) + threadIdx.x / LPR;
     const int      head    = blockIdx.y;  // [0,Hq): q   [Hq,Hq+Hkv): k   [Hq+Hkv, Hq+2Hkv): v
     const int      kv_heads = L.kv_heads;
     if (token >= total_tokens) {
-        return;  // whole 16-lane rows exit together; DPP rows are 16 lanes
+        return;  // whole head rows (LPR lanes, one token) exit together; the DPP reductions stay inside a head row
     }
     const int stride = (q_heads + 2 * kv_heads) * D;
     half_t*   src    = qkv + (size_t)token * stride + (size_t)head * D + lane16 * 8;
@@ -83,11 +92,13 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
     const bool is_k = !is_q && head < q_heads + kv_heads;
 
     if constexpr (QKX) {
-        if (q_norm != nullptr) {  // grid-uniform; V rows reduce too (whole rows stay in step) and keep x
-            const float   ss = group_sum<16>(sumsq8(x));
-            const half8_t w  = *(const half8_t*)((is_q ? q_norm : k_norm) + lane16 * 8);
-            if (is_q || is_k) {
-                x = head_norm8(x, ss, w, qk_eps);
+        if constexpr (D == 128) {
+            if (q_norm != nullptr) {  // grid-uniform; V rows reduce too (whole rows stay in step) and keep x
+                const float   ss = group_sum<16>(sumsq8(x));
+                const half8_t w  = *(const half8_t*)((is_q ? q_norm : k_norm) + lane16 * 8);
+                if (is_q || is_k) {
+                    x = head_norm8(x, ss, w, qk_eps);
+                }
             }
         }
         if (qkv_bias != nullptr) {
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
         const int     p  = pos < max_pos ? pos : max_pos - 1;
         size_t        row = (size_t)p;
         if constexpr (SEQ) {
-            row += (size_t)rope_row0[b];  // 64-bit: max_batch x (session_len + 1) rows of 256 B pass 2 GiB
+            row += (size_t)rope_row0[b];  // 64-bit: max_batch x (session_len + 1) rows of 2 D bytes pass 2 GiB
         }
         const half8_t cs = *(const half8_t*)(cos_sin + row * (D / 2) + lane16 * 4);
 #pragma unroll
@@ -139,8 +150,8 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
             mx            = fmaxf(mx, f);
             mnn           = fmaxf(mnn, -f);
         }
-        mx             = row16_max(mx);
-        mnn            = row16_max(mnn);
+        mx             = row_max<LPR>(mx);
+        mnn            = row_max<LPR>(mnn);
         const float mn = -mnn;
         // fp16 min/max are exact in f32
         const float  inv_q_max = 1.0f / (float)((1 << BITS) - 1);
@@ -193,24 +204,32 @@ int launch_kv_rope_store(half_t*        qkv,
                          float          qk_eps,
                          const int*     rope_row0)
 {
-    TM_REQUIRE(cache.layout.head_dim == 128, "head_dim must be 128");
+    const int hd = cache.layout.head_dim;
+    TM_REQUIRE(hd == 64 || hd == 128, "kv_rope_store: head_dim must be 64 or 128");
+    TM_REQUIRE(hd == 128 || (q_norm == nullptr && k_norm == nullptr), "kv_rope_store: q/k RMSNorm (qk_norm) needs head_dim 128");
     TM_REQUIRE(rope_row0 == nullptr || cos_sin != nullptr, "rope_row0 needs a table");
     TM_REQUIRE(cache.layout.bits == 16 || cache.layout.bits == 8 || cache.layout.bits == 4, "kv bits in {16,8,4}");
     TM_REQUIRE((q_norm == nullptr) == (k_norm == nullptr), "q_norm and k_norm come together");
     if (total_tokens == 0) {
         return 0;
     }
-    dim3 grid((total_tokens + 15) / 16, q_heads + 2 * cache.layout.kv_heads);
+    const int  tpw = 2048 / hd;  // token rows per 256-thread workgroup: 16 | 32
+    dim3       grid((total_tokens + tpw - 1) / tpw, q_heads + 2 * cache.layout.kv_heads);
     const bool qkx = qkv_bias != nullptr || q_norm != nullptr;
+#define TM_KV_STORE_D(B_, X_, S_, D_)                                                                                             \
+    kv_rope_store_kernel<B_, X_, S_, D_><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, max_pos, \
+                                                               cache, qkv_bias, q_norm, k_norm, qk_eps, rope_row0)
 #define TM_KV_STORE(B_, X_)                                                                                                       \
     do {                                                                                                                          \
-        if (rope_row0 != nullptr) {                                                                                               \
-            kv_rope_store_kernel<B_, X_, true><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, \
-                                                                     max_pos, cache, qkv_bias, q_norm, k_norm, qk_eps, rope_row0); \
+        if (hd == 64) {                                                                                                           \
+            if (rope_row0 != nullptr) TM_KV_STORE_D(B_, X_, true, 64);                                                            \
+            else TM_KV_STORE_D(B_, X_, false, 64);                                                                                \
+        }                                                                                                                         \
+        else if (rope_row0 != nullptr) {                                                                                          \
+            TM_KV_STORE_D(B_, X_, true, 128);                                                                                     \
         }                                                                                                                         \
         else {                                                                                                                    \
-            kv_rope_store_kernel<B_, X_><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin,       \
-                                                               max_pos, cache, qkv_bias, q_norm, k_norm, qk_eps, nullptr);        \
+            TM_KV_STORE_D(B_, X_, false, 128);                                                                                    \
         }                                                                                                                         \
     } while (0)
     switch (cache.layout.bits) {
@@ -227,6 +246,7 @@ int launch_kv_rope_store(half_t*        qkv,
             else TM_KV_STORE(4, false);
     }
 #undef TM_KV_STORE
+#undef TM_KV_STORE_D
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -301,7 +321,7 @@ __device__ __forceinline__ half8_t load_dequant_flatten(const char* data, const 
     }
 }
 
-template<int BITS, bool VT>
+template<int BITS, bool VT, int D = 128>
 __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_out,
                                                          half_t* __restrict__ v_out,
                                                          const int* __restrict__ cu_k_off,
@@ -309,7 +329,9 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
                                                          int         k_stride,
                                                          KvCacheView cache)
 {
-    constexpr int  D  = 128;
+    static_assert(D == 64 || D == 128, "head_dim 64 or 128");
+    constexpr int  LPR  = D / 8;      // lanes per token row (as in kv_rope_store_kernel)
+    constexpr int  ROWS = 256 / LPR;  // token rows per pass: 16 | 32
     const KvLayout L  = cache.layout;
     const int      b  = blockIdx.z;
     const int      hd = blockIdx.y;
@@ -320,14 +342,14 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
     }
     __shared__ half_t vt_smem[VT ? 64 * (D + 8) : 1];
 
-    const int    lane16 = threadIdx.x & 15;
-    const int    row    = threadIdx.x >> 4;  // 16 token rows per pass
+    const int    lane16 = threadIdx.x & (LPR - 1);
+    const int    row    = threadIdx.x / LPR;  // ROWS token rows per pass
     const char*  block  = (const char*)cache.block_ptrs[cache.cu_block_nums[b] + blockIdx.x] + cache.layer_offset;
     const size_t obase  = (size_t)hd * k_stride + cu_k_off[b];
 
 #pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int  ti    = pass * 16 + row;
+    for (int pass = 0; pass < 64 / ROWS; ++pass) {
+        const int  ti    = pass * ROWS + row;
         const bool valid = t0 + ti < n;
         half8_t    kk = {}, vv = {};
         if (valid) {
@@ -344,12 +366,12 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
     }
     if constexpr (VT) {
         __syncthreads();
-        // thread -> (d = tid & 127, token octets); 64 tokens x 128 d = 1024 16-B vectors / 256 thr = 4 each
+        // thread -> (d = vec & (D - 1), token octets); 64 tokens x D d = 8 D 16-B vectors / 256 thr = D / 32 each
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
+        for (int it = 0; it < D / 32; ++it) {
             const int vec = threadIdx.x + it * 256;
-            const int d   = vec & 127;
-            const int to  = vec >> 7;  // 0..7 token octet
+            const int d   = vec & (D - 1);
+            const int to  = vec / D;  // 0..7 token octet
             half8_t   o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -373,14 +395,19 @@ int launch_flatten_kv(half_t*     k_out,
                       KvCacheView cache,
                       hipStream_t st)
 {
-    TM_REQUIRE(cache.layout.head_dim == 128, "head_dim must be 128");
+    const int hd = cache.layout.head_dim;
+    TM_REQUIRE(hd == 64 || hd == 128, "flatten_kv: head_dim must be 64 or 128");
     TM_REQUIRE(cache.layout.block_len == 64, "block_len must be 64");
     TM_REQUIRE(!transpose_v || k_stride % 64 == 0, "transposed V needs a 64-aligned k_stride");
     if (batch == 0 || max_k_len == 0) {
         return 0;
     }
     dim3 grid((max_k_len + 63) / 64, cache.layout.kv_heads, batch);
-#define TM_FLATTEN(B_, T_) flatten_kv_kernel<B_, T_><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache)
+#define TM_FLATTEN(B_, T_)                                                                                 \
+    do {                                                                                                   \
+        if (hd == 64) flatten_kv_kernel<B_, T_, 64><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache); \
+        else flatten_kv_kernel<B_, T_, 128><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache);         \
+    } while (0)
     const int bits = cache.layout.bits;
     if (transpose_v) {
         if (bits == 16) TM_FLATTEN(16, true);

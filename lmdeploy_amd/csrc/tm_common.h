@@ -75,6 +75,7 @@ constexpr int DPP_ROR8  = 0x128;  // row_ror:8      (lane i <- i^8 in each 16)
 template<int N>
 __device__ __forceinline__ float group_sum(float v)
 {
+    static_assert(N == 8 || N == 16 || N == 64, "group_sum: groups of 8, 16 or 64 lanes only");
     v += dpp_f32<DPP_XOR1>(v);
     v += dpp_f32<DPP_XOR2>(v);
     v += dpp_f32<DPP_HMIRR>(v);
@@ -90,6 +91,7 @@ __device__ __forceinline__ float group_sum(float v)
 template<int N>
 __device__ __forceinline__ float group_max(float v)
 {
+    static_assert(N == 8 || N == 16 || N == 64, "group_max: groups of 8, 16 or 64 lanes only");
     v = fmaxf(v, dpp_f32<DPP_XOR1>(v));
     v = fmaxf(v, dpp_f32<DPP_XOR2>(v));
     v = fmaxf(v, dpp_f32<DPP_HMIRR>(v));
@@ -133,6 +135,7 @@ __device__ __forceinline__ half8_t head_norm8(half8_t x, float ss, half8_t w, fl
 template<int LOW>
 __device__ __forceinline__ float upper_sum(float v)
 {
+    static_assert(LOW == 8 || LOW == 16, "upper_sum: 8 or 16 distinct low lanes only");
     if constexpr (LOW <= 8) {
         v += dpp_f32<DPP_ROR8>(v);
     }
@@ -143,6 +146,7 @@ __device__ __forceinline__ float upper_sum(float v)
 template<int LOW>
 __device__ __forceinline__ float upper_max(float v)
 {
+    static_assert(LOW == 8 || LOW == 16, "upper_max: 8 or 16 distinct low lanes only");
     if constexpr (LOW <= 8) {
         v = fmaxf(v, dpp_f32<DPP_ROR8>(v));
     }

@@ -9,7 +9,7 @@ namespace tmk {
 // ---- paged KV cache geometry (reference: kernels/attention/block.h:126-219) ----------------
 struct KvLayout {
     int kv_heads;
-    int head_dim;   // 128
+    int head_dim;   // 64 | 128
     int block_len;  // 64
     int bits;       // 16 | 8 | 4
     __host__ __device__ int token_data_size() const { return bits * head_dim / 8; }
@@ -119,6 +119,7 @@ struct PrefillAttnParams {
     int           q_heads;
     int           kv_heads;
     float         scale_log2;
+    int           head_dim = 128;  // D: 64 | 128
 };
 int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 

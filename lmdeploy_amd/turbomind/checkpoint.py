@@ -155,12 +155,22 @@ def read_config(model_path: str) -> ModelConfig:
             raise NotImplementedError(f'{arch} with head_dim {D}: the attention kernels need head_dim 128')
         attn_bias = 1 if kind == 'qwen2' else int(bool(c.get('attention_bias', False)))
         qk_norm = 1 if kind == 'qwen3' else 0
+    else:
+        # the Llama reader (Llama / Mistral / Mixtral / InternLM): attention and KV-cache kernels exist for head_dim 64 and 128
+        if D not in (64, 128):
+            raise NotImplementedError(f'{arch} with head_dim {D}: the attention kernels support head_dim 64 and 128')
+        if heads * D % 128:
+            raise NotImplementedError(f'{arch} with {heads} attention heads of head_dim {D}: num_attention_heads * head_dim = '
+                                      f'{heads * D} must be a multiple of 128 (the K dimension of the o projection)')
     q = c.get('quantization_config')
     wfmt = 'f16'
     if q is not None:
         if q.get('quant_method') == 'fp8':       # converter.py:186-187; block size fixed at 128 (converter.py:82,90)
             if list(q.get('weight_block_size') or [128, 128]) != [128, 128]:
                 raise NotImplementedError(f'quantization_config {q}: fp8 needs 128x128 weight blocks')
+            if D == 64:
+                raise NotImplementedError(f'{arch} with fp8 weights and head_dim 64: the 128-column scale blocks of the q / k / v '
+                                          f'projections straddle heads; fp8 needs head_dim 128')
             wfmt = 'fp8'
         elif q.get('quant_method') != 'awq' or q.get('bits', 4) != 4 or q.get('group_size', 128) != 128:
             raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128 or block-128 FP8 '

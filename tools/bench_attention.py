@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Time the paged decode attention kernel at the metric shape (B=64, 32 q / 8 kv heads, int8 KV) on random cache
-contents.  python tools/bench_attention.py [--ctx 1536] [--bits 8] [--splits 1,2,4]"""
+contents.  python tools/bench_attention.py [--ctx 1536] [--bits 8] [--splits 1,2,4] [--head-dim 128]
+--head-dim 64 times the head_dim 64 kernel (VALU, every KV width); set TM_ATTN_VALU=1 to time the same kernel family at head_dim 128.
+--engine-decode times whole decode steps of a SYNTHETIC Llama-3.2-1B geometry instead (tm_engine_init_synthetic weights, int8 KV)."""
 import argparse
 import os
 import sys
@@ -19,6 +21,9 @@ def main():
     ap.add_argument('--hq', type=int, default=32)
     ap.add_argument('--hkv', type=int, default=8)
     ap.add_argument('--bits', type=int, default=8)
+    ap.add_argument('--head-dim', type=int, default=128, choices=[64, 128])
+    ap.add_argument('--engine-decode', action='store_true',
+                    help='decode tok/s of a synthetic Llama-3.2-1B geometry (2048 / 16 layers / 32 x 8 heads of 64 / 8192 / 128256)')
     ap.add_argument('--splits', default='1,2,4')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--trace', action='store_true')
@@ -26,10 +31,12 @@ def main():
     ap.add_argument('--layout', default='block', choices=['block', 'layer'],
                     help='block: [block][layer] (reference: all layers of a block contiguous); layer: [layer][block]')
     a = ap.parse_args()
+    if a.engine_decode:
+        return engine_decode(a.batch, a.ctx, a.bits)
     tm = _ffi.load()
-    B, Hq, Hkv, ctx, bits = a.batch, a.hq, a.hkv, a.ctx, a.bits
+    B, Hq, Hkv, ctx, bits, D = a.batch, a.hq, a.hkv, a.ctx, a.bits, a.head_dim
     layers = a.layers   # several layers so that consecutive launches touch different (cold) cache bytes
-    lsz = tm.tm_kv_layer_size(Hkv, 128, 64, bits)
+    lsz = tm.tm_kv_layer_size(Hkv, D, 64, bits)
     nblk = (ctx + 63) // 64
     pool = torch.randint(0, 255, (B * nblk, layers * lsz), dtype=torch.uint8, device='cuda')
     # make the per-token (scale, zero) params finite fp16 values
@@ -49,10 +56,10 @@ def main():
     ptrs = tables[0]
     cu = torch.arange(0, (B + 1) * nblk, nblk, dtype=torch.int32, device='cuda')
     klen = torch.full((B,), ctx, dtype=torch.int32, device='cuda')
-    q = torch.randn((B, Hq * 128), device='cuda').half()
-    out = torch.empty((B, Hq * 128), device='cuda').half()
+    q = torch.randn((B, Hq * D), device='cuda').half()
+    out = torch.empty((B, Hq * D), device='cuda').half()
     st = torch.cuda.current_stream().cuda_stream
-    bytes_per_launch = B * ctx * 2 * Hkv * (128 * bits // 8 + (4 if bits < 16 else 0))
+    bytes_per_launch = B * ctx * 2 * Hkv * (D * bits // 8 + (4 if bits < 16 else 0))
     if a.trace:
         # in-kernel phase stamps (100 MHz): start / prologue done (q ready, first block issued) / wave 0 done /
         # all waves done / end, per workgroup
@@ -63,8 +70,8 @@ def main():
             dbg.zero_()
             torch.cuda.synchronize()
             tm.tm_debug_set_gemm_trace(dbg.data_ptr())
-            view = _ffi.KvCache(tables[it % layers].data_ptr(), cu.data_ptr(), off_of(it % layers), Hkv, 128, 64, bits)
-            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * 128, klen.data_ptr(), B, Hq, 0.0, splits,
+            view = _ffi.KvCache(tables[it % layers].data_ptr(), cu.data_ptr(), off_of(it % layers), Hkv, D, 64, bits)
+            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits,
                                               ws.data_ptr(), view, st))
             tm.tm_debug_set_gemm_trace(None)
             torch.cuda.synchronize()
@@ -98,17 +105,51 @@ def main():
     for splits in [int(s) for s in a.splits.split(',')]:
         ws = torch.empty(max(1, tm.tm_decode_attention_workspace(B, Hq, splits)), dtype=torch.uint8, device='cuda')
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+        for i in range(4):   # warm-up: code-object load and clocks, outside the timed launches
+            view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
+            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits,
+                                              ws.data_ptr(), view, st))
+        torch.cuda.synchronize()
         for i, (e0, e1) in enumerate(ev):
-            view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, 128, 64, bits)
+            view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
             e0.record()
-            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * 128, klen.data_ptr(), B, Hq, 0.0, splits,
+            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits,
                                               ws.data_ptr(), view, st))
             e1.record()
         torch.cuda.synchronize()
         ts = sorted(x.elapsed_time(y) for x, y in ev)
         med = ts[len(ts) // 2]
-        print(f'ctx={ctx} bits={bits} splits={splits}: {med*1e3:8.1f} us  {bytes_per_launch/(med*1e-3)/1e9:7.0f} GB/s '
+        gbs = bytes_per_launch / (med * 1e-3) / 1e9
+        print(f'head_dim={D} ctx={ctx} bits={bits} splits={splits}: {med*1e3:8.1f} us  {gbs:7.0f} GB/s = {gbs / 8000:.3f} of 8 TB/s '
               f'({bytes_per_launch/1e6:.1f} MB/launch)  layout={a.layout} layers={layers}', flush=True)
+
+
+def engine_decode(batch, ctx, bits, warmup=8, steps=64, rounds=3):
+    """decode steps of a synthetic Llama-3.2-1B geometry (random u4 weights: the speed of the shape, not of a checkpoint)"""
+    import time
+
+    from lmdeploy_amd.turbomind.engine import Engine
+    from oracle import tm_oracle as o
+    cfg = o.ModelConfig(hidden=2048, layers=16, q_heads=32, kv_heads=8, head_dim=64, inter=8192, vocab=128256, kv_bits=bits,
+                        rope=o.RopeParam(64, 500000.0, 'llama3', 32.0, 1.0, 4.0, 8192))
+    eng = Engine.from_model_config(cfg, max_batch_size=batch, session_len=ctx + warmup + rounds * steps + 8,
+                                   quant_policy=0 if bits == 16 else bits, max_prefill_token_num=8192, use_graph=1)
+    eng.init_synthetic(seed=1)
+    eng.start()
+    rng = np.random.default_rng(0)
+    eng.prefill([rng.integers(0, cfg.vocab, ctx).astype(np.int32) for _ in range(batch)], max_new_tokens=warmup + rounds * steps + 1)
+    eng.decode(warmup)
+    ms = []
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.decode(steps)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3 / steps)
+    eng.close()
+    med = sorted(ms)[len(ms) // 2]
+    print(f'synthetic Llama-3.2-1B geometry, head_dim 64, batch {batch}, ctx {ctx}, kv bits {bits}: {med:.3f} ms per decode step '
+          f'(rounds {[round(x, 3) for x in ms]}) = {batch / med * 1e3:.0f} tok/s', flush=True)
 
 
 if __name__ == '__main__':
