@@ -141,7 +141,7 @@ def _argmax_rows(rng, V):
     return x
 
 
-@pytest.mark.parametrize('V,ld', [(7, 8), (8, 8), (1003, 1008), (4099, 4104), (8200, 8200), (8207, 8208)])
+@pytest.mark.parametrize('V,ld', [(7, 8), (8, 8), (1003, 1008), (4099, 4104), (8200, 8200), (8207, 8208), (151936, 152064)])
 def test_argmax_edges(tm, cuda, V, ld):
     """Contract of tm_argmax (argmax_kernel, misc.hip):
       * NaN never wins;
