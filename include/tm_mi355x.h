@@ -156,6 +156,16 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
                                  const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps, const int* k_len,
                                  int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
                                  tm_stream_t st);
+/* tm_decode_attention with a sliding window and attention sinks (AttentionParams::window_size / ::sinks,
+ * src/turbomind/kernels/attention/attention_params.h:55-72; the tile skip of decoding_template.h:29 and
+ * attention_universal.h:411,474-480; the sink term L += expf(sink - M * scale) of attention_universal.h:529-535).
+ * window > 0: the query at k_len - 1 sees the keys j with k_len - 1 - j < window, i.e. the last min(k_len, window) tokens; cache
+ * tiles wholly before them are not read.  sinks (device fp16 [q_heads], may be NULL): one natural-log logit per head that joins
+ * the softmax denominator and contributes no value.  Runs the VALU kernel for every KV width and head_dim (never the MFMA
+ * kernel or its fused prologue).  window == 0 && sinks == NULL is tm_decode_attention, bit for bit; window < 0: TM_INVALID. */
+int tm_decode_attention_window(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
+                               float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
+                               const void* sinks, tm_stream_t st);
 /* Causal prefill attention over flattened KV (dispatchAttention).  vt is the transposed V of tm_flatten_kv.  head_dim 128;
  * softmax_scale <= 0 -> 1/sqrt(128). */
 int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
@@ -166,6 +176,15 @@ int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, 
 int tm_prefill_attention_hd(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
                             const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                             int q_heads, int kv_heads, int head_dim, float softmax_scale, tm_stream_t st);
+/* tm_prefill_attention_hd with a sliding window and attention sinks (attention_params.h:55-72; the per-row mask
+ * 0 <= q_pos - k_pos < window_size of mainloop_sm80.h:558-566; tile skip attention_universal.h:411,474-480; sink term :529-535):
+ * the row at absolute position q sees the keys t with 0 <= q - t < window; key steps no row of a workgroup sees are skipped.
+ * sinks as in tm_decode_attention_window.  window == 0 && sinks == NULL is tm_prefill_attention_hd, bit for bit; window < 0:
+ * TM_INVALID. */
+int tm_prefill_attention_window(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
+                                const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
+                                int q_heads, int kv_heads, int head_dim, float softmax_scale, int window, const void* sinks,
+                                tm_stream_t st);
 
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st);
 /* greedy top-1 on fp32-cast logits (generation/sampling.cc:92-183); out_val (fp16 [batch]) may be NULL */
@@ -456,6 +475,12 @@ typedef struct tm_model_config {
      * the shared expert is the layer's feed_forward -- and a gate "layers.{i}.moe_ffn.shared_gate.weight" fp16 [hidden], replicated.
      * FFN output = sigmoid(x . gate) * feed_forward(x) + the routed experts (tm_moe_forward_shared). */
     int   moe_shared_inter;
+    /* Sliding-window attention and attention sinks (AttentionParams::window_size / ::sinks, kernels/attention/attention_params.h:55-72).
+     * attn_window: the window of every layer, 0 = none (tm_engine_set_layer_windows overrides it per layer); a window >= session_len is
+     * full attention.  attn_sinks != 0 -> slot "layers.{i}.attention.sinks" fp16 [q_heads / tp], one natural-log logit per local head.
+     * An engine with a windowed layer or sinks decodes like head_dim 64: tm_kv_rope_store + the VALU attention kernel, no fused
+     * prologue, no folded norm.  KV blocks older than the window stay allocated. */
+    int   attn_window, attn_sinks;
     /* Qwen attention prologue (0 = off): attn_bias -> slot "layers.{i}.attention.w_qkv.bias" fp16 [local qkv columns] added to
      * q / k / v (Qwen2); qk_norm -> slots "layers.{i}.attention.{q,k}_norm.weight" fp16 [head_dim], per-head RMSNorm of q / k with
      * rms_eps (Qwen3).  Order: norm -> bias -> RoPE. */
@@ -485,6 +510,9 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* cfg);
  * (rope_type 4 with rope_factor > 1 and session_len > rope_max_position_embeddings), *table_bytes = bytes of those regions (0 without) */
 int tm_engine_rope_info(tm_engine* e, int* per_seq_tables, int64_t* table_bytes);
 int tm_engine_destroy(tm_engine* e);
+/* Per-layer sliding windows (gpt-oss alternates sliding and full layers): window[i] replaces attn_window for layer i, 0 = full
+ * attention.  Before tm_engine_start; layers must equal the model's; a negative window is TM_INVALID. */
+int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers);
 /* RCCL bootstrap for tp > 1: rank 0 calls tm_comm_unique_id (128 bytes, host), broadcasts it out of band
  * (torch.distributed / TCPStore), then every rank calls tm_engine_comm_init. */
 int tm_comm_unique_id(void* host_out128);

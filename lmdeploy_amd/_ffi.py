@@ -65,7 +65,8 @@ class ModelConfig(C.Structure):
                 ('rope_max_position_embeddings', c_int), ('rope_yarn_beta_fast', c_float), ('rope_yarn_beta_slow', c_float),
                 ('rope_yarn_attention_factor', c_float), ('group_size', c_int),
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
-                ('moe_routed_scale', c_float), ('moe_shared_inter', c_int), ('attn_bias', c_int), ('qk_norm', c_int)]
+                ('moe_routed_scale', c_float), ('moe_shared_inter', c_int), ('attn_window', c_int), ('attn_sinks', c_int),
+                ('attn_bias', c_int), ('qk_norm', c_int)]
 
 
 class EngineConfig(C.Structure):
@@ -92,6 +93,7 @@ _SIGNATURES = {
     'tm_kv_rope_store_seq': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_float, POINTER(KvCache), c_void_p]),
     'tm_engine_rope_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
+    'tm_engine_set_layer_windows': (c_int, [c_void_p, c_void_p, c_int]),
     'tm_kv_rope_store': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                  POINTER(KvCache), c_void_p]),
     'tm_kv_rope_store_qk': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
@@ -101,6 +103,8 @@ _SIGNATURES = {
     'tm_decode_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
     'tm_decode_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                     POINTER(KvCache), c_void_p]),
+    'tm_decode_attention_window': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
+                                           POINTER(KvCache), c_int, c_void_p, c_void_p]),
     'tm_decode_attention_fused': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_float, c_int, c_void_p, POINTER(KvCache), c_void_p]),
     'tm_decode_attention_fused_qk': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
@@ -110,6 +114,8 @@ _SIGNATURES = {
                                      c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'tm_prefill_attention_hd': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    'tm_prefill_attention_window': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     'tm_embedding': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'tm_argmax': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'tm_cross_entropy': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -125,7 +125,11 @@ __device__ __forceinline__ void load_raw(uint32_t (&raw)[LW], const char* ptr)
     }
 }
 
-template<int BITS, int HPW, int D = 128>
+// WS = true: the sliding-window / attention-sink variant (DecodeAttnParams::window, ::sinks; reference: attention_params.h:55-72,
+// decoding_template.h:29, attention_universal.h:411,474-480,529-535).  A compile-time variant, so the plain instantiations keep their
+// registers: tiles that lie wholly before ctx - window are neither loaded nor counted in the split-K partition, the one tile the
+// window starts in is masked the way the tokens past the context are, and the sink joins l once, after the last merge.
+template<int BITS, int HPW, int D = 128, bool WS = false>
 __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnParams p, int head_chunks)
 {
     using Tr                 = KvTraits<BITS, D>;
@@ -152,10 +156,15 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
     const int tg   = lane / CPT;  // token inside a load instruction
 
     const int ctx        = p.k_len[b];
-    const int tiles      = (ctx + TILE - 1) / TILE;
+    int       wbeg       = 0;  // first token the query at ctx - 1 sees: ctx - 1 - j < window
+    if constexpr (WS) {
+        wbeg = p.window > 0 ? max(ctx - p.window, 0) : 0;
+    }
+    const int tile_lo    = wbeg / TILE;  // tiles before it are skipped, not masked
+    const int tiles      = (ctx + TILE - 1) / TILE - tile_lo;
     const int per_split  = (tiles + p.splits - 1) / p.splits;
-    const int tile_begin = split * per_split;
-    const int tile_end   = min(tile_begin + per_split, tiles);
+    const int tile_begin = tile_lo + split * per_split;
+    const int tile_end   = min(tile_begin + per_split, tile_lo + tiles);
 
     // ---- queries: q[h][E dims of chunk c] as half2 pairs, kept in registers ------------------
     half2_t qv[HPW][E / 2];
@@ -200,7 +209,15 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
         if constexpr (BITS != 16) {
             kpar = *(const uint32_t*)(base + L.k_param(kv_head, toff + (lane & (TILE - 1))));
             vpar = *(const uint32_t*)(base + L.v_param(kv_head, toff + (lane & (TILE - 1))));
-            if (lane >= ntok) {
+            if constexpr (WS) {
+                // the same zeroing, also for the tokens before the window, as a bit mask: with the two-sided condition as a branch the
+                // compiler sinks the two loads into it and waits for them in front of the K loads (measured: 113 against 99 us at
+                // head_dim 64, int8, batch 64, context 4096)
+                const uint32_t keep = (lane < ntok && tok0 + lane >= wbeg) ? ~0u : 0u;
+                kpar &= keep;
+                vpar &= keep;
+            }
+            else if (lane >= ntok) {
                 kpar = 0;  // scale = zero = 0 -> dequantised value 0, never NaN
                 vpar = 0;
             }
@@ -224,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
             }
             half2_t kd[E / 2];
             dequant_chunk<BITS, LW>(kraw[r], s2, z2, kd);
-            const bool valid = r * TPI + tg < ntok;
+            const bool valid = r * TPI + tg < ntok && (!WS || tok0 + r * TPI + tg >= wbeg);
 #pragma unroll
             for (int h = 0; h < HPW; ++h) {
                 float acc = 0.f;
@@ -283,9 +300,9 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
             }
             half2_t vd[E / 2];
             dequant_chunk<BITS, LW>(vraw[r], s2, z2, vd);
-            const bool valid = r * TPI + tg < ntok;
+            const bool valid = r * TPI + tg < ntok && (!WS || tok0 + r * TPI + tg >= wbeg);
             if constexpr (BITS == 16) {
-                if (!valid) {  // raw fp16 garbage past the context must not reach the accumulators
+                if (!valid) {  // raw fp16 garbage past the context (or before the window) must not reach the accumulators
 #pragma unroll
                     for (int i = 0; i < E / 2; ++i) {
                         vd[i] = half2_t{};
@@ -348,6 +365,11 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
         }
         const int hq = head0 + h;
         if (p.splits == 1) {
+            if constexpr (WS) {
+                if (p.sinks) {  // the sink logit joins the denominator once and carries no value
+                    l += fast_exp2((float)p.sinks[hq] * 1.4426950408889634f - ms * sc);
+                }
+            }
             p.out[(size_t)b * p.q_heads * D + (size_t)hq * D + d] = (half_t)(o / l);
         }
         else {
@@ -362,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void decode_attention_kernel(DecodeAttnPara
 }
 
 // split-K merge: one D-thread workgroup per (sequence, query head)
-template<int D>
+template<int D, bool WS = false>
 __global__ __launch_bounds__(D) void decode_reduce_kernel(DecodeAttnParams p)
 {
     const int     hq   = blockIdx.x;
@@ -380,6 +402,11 @@ __global__ __launch_bounds__(D) void decode_reduce_kernel(DecodeAttnParams p)
         o += wt * p.partial_o[(slot + s) * D + d];
         l += wt * p.partial_ml[(slot + s) * 2 + 1];
     }
+    if constexpr (WS) {
+        if (p.sinks) {  // never per split: here, behind the merge
+            l += fast_exp2((float)p.sinks[hq] * 1.4426950408889634f - ms * p.scale_log2);
+        }
+    }
     p.out[(size_t)b * p.q_heads * D + (size_t)hq * D + d] = (half_t)(o / l);
 }
 
@@ -388,7 +415,7 @@ size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, in
     return (size_t)batch * q_heads * splits * (head_dim + 2) * sizeof(float);
 }
 
-template<int BITS, int D = 128>
+template<int BITS, int D = 128, bool WS = false>
 static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
 {
     const int group = p.q_heads / p.cache.layout.kv_heads;
@@ -403,23 +430,38 @@ static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
     dim3      grid(p.cache.layout.kv_heads * chunks, p.batch, p.splits);
     switch (hpw) {
         case 4:
-            decode_attention_kernel<BITS, 4, D><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 4, D, WS><<<grid, 256, 0, st>>>(p, chunks);
             break;
         case 3:
-            decode_attention_kernel<BITS, 3, D><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 3, D, WS><<<grid, 256, 0, st>>>(p, chunks);
             break;
         case 2:
-            decode_attention_kernel<BITS, 2, D><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 2, D, WS><<<grid, 256, 0, st>>>(p, chunks);
             break;
         default:
-            decode_attention_kernel<BITS, 1, D><<<grid, 256, 0, st>>>(p, chunks);
+            decode_attention_kernel<BITS, 1, D, WS><<<grid, 256, 0, st>>>(p, chunks);
     }
     TM_HIP_CHECK(hipGetLastError());
     if (p.splits > 1) {
-        decode_reduce_kernel<D><<<dim3(p.q_heads, p.batch), D, 0, st>>>(p);
+        decode_reduce_kernel<D, WS><<<dim3(p.q_heads, p.batch), D, 0, st>>>(p);
         TM_HIP_CHECK(hipGetLastError());
     }
     return 0;
+}
+
+// window / sinks: the VALU kernel's WS variant for every KV width, whatever TM_ATTN_VALU says
+template<int D>
+static int launch_window(const DecodeAttnParams& p, hipStream_t st)
+{
+    switch (p.cache.layout.bits) {
+        case 16:
+            return launch_bits<16, D, true>(p, st);
+        case 8:
+            return launch_bits<8, D, true>(p, st);
+        case 4:
+            return launch_bits<4, D, true>(p, st);
+    }
+    TM_REQUIRE(false, "kv bits in {16,8,4}");
 }
 
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
@@ -436,6 +478,12 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     TM_REQUIRE(!fused || L.bits == 8 || L.bits == 4, "fused decode prologue: int8 / int4 KV only");
     // the Qwen prologue (bias / q-k norm) exists only in the fused MFMA path; unfused kernels read q after launch_kv_rope_store applied it
     TM_REQUIRE(fused || (!p.qkv_bias && !p.q_norm && !p.k_norm), "qkv bias / q-k norm need the fused decode prologue");
+    TM_REQUIRE(p.window >= 0, "decode attention: window must be >= 0 (0 = full attention)");
+    if (p.window > 0 || p.sinks) {
+        // the MFMA kernel and its fused prologue know neither: such a call runs kv_rope_store + the VALU kernel
+        TM_REQUIRE(!fused, "fused decode prologue with a sliding window or attention sinks: run kv_rope_store + tm_decode_attention_window");
+        return L.head_dim == 64 ? launch_window<64>(p, st) : launch_window<128>(p, st);
+    }
     if (L.head_dim == 64) {
         // before TM_ATTN_VALU is looked at: head_dim 64 has the VALU kernel only, for every KV width
         TM_REQUIRE(!fused, "fused decode prologue (MFMA kernel): head_dim must be 128, head_dim 64 runs kv_rope_store + tm_decode_attention");

@@ -91,7 +91,11 @@ __device__ __forceinline__ int ksw64(int r)
 // or is a clean -inf (masked score -> exp2(-inf) = 0), and the "-inf so far" selects around each exp disappear.
 constexpr float kMinScore = -1.0e30f;
 
-template<int G, int D = 128>
+// WS = true: the sliding-window / attention-sink variant (PrefillAttnParams::window, ::sinks; reference: attention_params.h:55-72,
+// mainloop_sm80.h:558-566, attention_universal.h:411,474-480,529-535), compiled apart so that the plain instantiations stay as they are.
+// The key loop starts at the first stage a row of the workgroup can see, a wave skips the 32-key steps before its first row's window,
+// the rest is masked per row, and the sink joins each row's l before the divide.
+template<int G, int D = 128, bool WS = false>
 __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnParams p)
 {
     static_assert(D == 64 || D == 128, "head_dim 64 or 128");
@@ -186,12 +190,16 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
     const int   kend_w  = active ? min(klen, hist + q0 + 16) : 0;       // keys visible to the last row of this wave
     const int   kend_wg = min(klen, hist + bx * 64 + 64);               // ... of this workgroup
     const int   krow    = 8 * (i16 >> 2) + (i16 & 3);                   // key (within the 32-key step) of score-tile-A row i16; tile B: +4
+    // window: first key the first row of this wave / workgroup sees (the rows below it see later ones only)
+    const int   win     = WS ? p.window : 0;
+    const int   kbeg_w  = win > 0 ? max(hist + q0 - win + 1, 0) : 0;
+    const int   kbeg_wg = win > 0 ? max(hist + bx * 64 - win + 1, 0) / KS * KS : 0;
 
-    stage_in(0, 0);
+    stage_in(kbeg_wg, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int buf = 0;
-    for (int ks0 = 0; ks0 < kend_wg; ks0 += KS, buf ^= 1) {
+    for (int ks0 = kbeg_wg; ks0 < kend_wg; ks0 += KS, buf ^= 1) {
         if (ks0 + KS < kend_wg) {
             stage_in(ks0 + KS, buf ^ 1);  // every wave is past the barrier behind its reads of that buffer
         }
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
 #pragma nounroll
         for (int sub = 0; sub < 2; ++sub) {
             const int ks = ks0 + 32 * sub;
-            if (ks >= kend_w) {  // wave-uniform: causal end of this wave (or an inactive wave)
+            if (ks >= kend_w || (WS && ks + 32 <= kbeg_w)) {  // wave-uniform: causal end of this wave (or an inactive wave); before its window
                 continue;
             }
             half8_t ka[NDD], kb[NDD];
@@ -215,7 +223,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             }
             // the whole 32-key step lies at or below the diagonal for every row of the wave and inside the context:
             // no masking needed (wave-uniform; true for all but the last one or two steps)
-            const bool full = ks + 32 <= klen && ks + 31 <= hist + q0;
+            // window: ... and the step's first key is still inside the window of the wave's last row
+            const bool full = ks + 32 <= klen && ks + 31 <= hist + q0 && (!WS || win <= 0 || hist + q0 + 15 - ks < win);
             half8_t    pf[G];
             floatx4    sa_[G], sb_[G];
 #pragma unroll
@@ -246,7 +255,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const int t = ks + 8 * g + e;
-                        s[e]        = (t < klen && t <= qpos) ? s[e] : -INFINITY;
+                        s[e]        = (t < klen && t <= qpos && (!WS || win <= 0 || qpos - t < win)) ? s[e] : -INFINITY;
                     }
                 }
                 float tmax = s[0];
@@ -293,7 +302,12 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
     if (active && q0 + i16 < qlen) {
 #pragma unroll
         for (int h = 0; h < G; ++h) {
-            const float lh = sum_xor16_xor32(l[h]);
+            float lh = sum_xor16_xor32(l[h]);
+            if constexpr (WS) {
+                if (p.sinks) {  // m is the row's max over its keys: uniform in the four lanes of a row
+                    lh += fast_exp2((float)p.sinks[hq0 + h] * 1.4426950408889634f - m[h] * sc);
+                }
+            }
             half_t*     optr = p.out + (size_t)(q_beg + q0 + i16) * p.q_heads * D + (size_t)(hq0 + h) * D;
             const float inv  = 1.0f / lh;
 #pragma unroll
@@ -304,6 +318,28 @@ __global__ __launch_bounds__(256, 2) void prefill_attention_kernel(PrefillAttnPa
             }
         }
     }
+}
+
+template<int D>
+static int launch_prefill_ws(const PrefillAttnParams& p, int G, dim3 grid, hipStream_t st)
+{
+    constexpr int     lds = 2 * 2 * 64 * D * 2;  // two stages of (K tile + V^T tile)
+    const void* const k   = G == 4 ? (const void*)prefill_attention_kernel<4, D, true> :
+                            G == 2 ? (const void*)prefill_attention_kernel<2, D, true> : (const void*)prefill_attention_kernel<1, D, true>;
+    if (const int rc = ensure_dynamic_lds(k, lds)) {
+        return rc;
+    }
+    if (G == 4) {
+        prefill_attention_kernel<4, D, true><<<grid, 256, lds, st>>>(p);
+    }
+    else if (G == 2) {
+        prefill_attention_kernel<2, D, true><<<grid, 256, lds, st>>>(p);
+    }
+    else {
+        prefill_attention_kernel<1, D, true><<<grid, 256, lds, st>>>(p);
+    }
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st)
@@ -318,6 +354,10 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st)
     const int G     = group % 4 == 0 ? 4 : (group % 2 == 0 ? 2 : 1);  // query heads per wave (share one kv head); G = 4 spills ~25
                                                                        // registers at two workgroups per CU -- measured equal to G = 2
     dim3      grid((p.max_q_len + 63) / 64, p.q_heads / G, p.batch);
+    TM_REQUIRE(p.window >= 0, "prefill attention: window must be >= 0 (0 = causal only)");
+    if (p.window > 0 || p.sinks) {
+        return p.head_dim == 64 ? launch_prefill_ws<64>(p, G, grid, st) : launch_prefill_ws<128>(p, G, grid, st);
+    }
     if (p.head_dim == 64) {
         constexpr int lds64 = 2 * 2 * 64 * 64 * 2;
         const void* const k64 = G == 4 ? (const void*)prefill_attention_kernel<4, 64> :

@@ -252,8 +252,18 @@ size_t tm_decode_attention_workspace(int batch, int q_heads, int splits)
 int tm_decode_attention(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
                         float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st)
 {
+    return tm_decode_attention_window(out, q, q_stride, k_len, batch, q_heads, softmax_scale, splits, workspace, cache, 0, nullptr, st);
+}
+
+int tm_decode_attention_window(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
+                               float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
+                               const void* sinks, tm_stream_t st)
+{
     TM_REQUIRE(out && q && k_len && cache, "null pointer");
+    TM_REQUIRE(window >= 0, "tm_decode_attention_window: window must be >= 0 (0 = full attention)");
     DecodeAttnParams p{};
+    p.window     = window;
+    p.sinks      = (const half_t*)sinks;
     p.q          = (const half_t*)q;
     p.q_stride   = q_stride;
     p.out        = (half_t*)out;
@@ -323,9 +333,21 @@ int tm_prefill_attention_hd(void* out, const void* q, int q_stride, const void* 
                             const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                             int q_heads, int kv_heads, int head_dim, float softmax_scale, tm_stream_t st)
 {
+    return tm_prefill_attention_window(out, q, q_stride, k, vt, k_stride, cu_q_len, cu_k_off, k_len, batch, max_q_len, q_heads, kv_heads,
+                                       head_dim, softmax_scale, 0, nullptr, st);
+}
+
+int tm_prefill_attention_window(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
+                                const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
+                                int q_heads, int kv_heads, int head_dim, float softmax_scale, int window, const void* sinks,
+                                tm_stream_t st)
+{
     TM_REQUIRE(out && q && k && vt && cu_q_len && cu_k_off && k_len, "null pointer");
     TM_REQUIRE(head_dim == 64 || head_dim == 128, "prefill attention: head_dim must be 64 or 128");
+    TM_REQUIRE(window >= 0, "tm_prefill_attention_window: window must be >= 0 (0 = causal only)");
     PrefillAttnParams p{};
+    p.window     = window;
+    p.sinks      = (const half_t*)sinks;
     p.q          = (const half_t*)q;
     p.q_stride   = q_stride;
     p.out        = (half_t*)out;

@@ -262,6 +262,7 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     const tm_model_config& m = c->model;
     TM_REQUIRE(m.head_dim == 64 || m.head_dim == 128, "head_dim must be 64 or 128");
     TM_REQUIRE(m.head_dim == 128 || !m.qk_norm, "qk_norm (per-head q/k RMSNorm) needs head_dim 128: not built for head_dim 64");
+    TM_REQUIRE(m.attn_window >= 0, "attn_window must be >= 0 (0 = full attention)");
     TM_REQUIRE(m.group_size == 128, "AWQ group size must be 128");
     TM_REQUIRE(c->tp >= 1 && c->rank >= 0 && c->rank < c->tp, "0 <= rank < tp");
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
@@ -339,6 +340,9 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
         if (m.attn_bias) {  // this rank's Q | K | V columns, q / k channel-permuted like the weights
             e->slots[p + ".attention.w_qkv.bias"].bytes = (int64_t)e->qkv_n * 2;
         }
+        if (m.attn_sinks) {  // this rank's q heads
+            e->slots[p + ".attention.sinks"].bytes = (int64_t)e->q_heads * 2;
+        }
         if (m.qk_norm) {  // one head, permuted like one head of q / k; replicated over the ranks
             e->slots[p + ".attention.q_norm.weight"].bytes = (int64_t)e->D * 2;
             e->slots[p + ".attention.k_norm.weight"].bytes = (int64_t)e->D * 2;
@@ -348,6 +352,18 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     e->slots["norm.weight"].bytes           = (int64_t)m.hidden * 2;
     add_linear(e, e->output, "output", m.hidden, e->vocab_local, TM_WEIGHT_F16, 5);
     *out = e;
+    return 0;
+}
+
+int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers)
+{
+    TM_REQUIRE(e && window, "null pointer");
+    TM_REQUIRE(!e->started, "tm_engine_set_layer_windows: call before tm_engine_start");
+    TM_REQUIRE(layers == e->cfg.model.layers, "tm_engine_set_layer_windows: one window per layer of the model");
+    for (int i = 0; i < layers; ++i) {
+        TM_REQUIRE(window[i] >= 0, "tm_engine_set_layer_windows: window must be >= 0 (0 = full attention)");
+    }
+    e->layer_windows.assign(window, window + layers);
     return 0;
 }
 
@@ -466,6 +482,9 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
         if (m.attn_bias) {
             TM_TRY(vec(p + ".attention.w_qkv.bias", e->qkv_n, 0.f, 0.02f));
         }
+        if (m.attn_sinks) {
+            TM_TRY(vec(p + ".attention.sinks", e->q_heads, 0.f, 1.f));
+        }
         if (m.qk_norm) {
             TM_TRY(vec(p + ".attention.q_norm.weight", e->D, 1.f, 0.05f));
             TM_TRY(vec(p + ".attention.k_norm.weight", e->D, 1.f, 0.05f));
@@ -552,6 +571,9 @@ int tm_engine_process_weights(tm_engine* e)
         if (m.attn_bias) {
             TM_TRY(norm(p + ".attention.w_qkv.bias", &L.qkv_bias));
         }
+        if (m.attn_sinks) {
+            TM_TRY(norm(p + ".attention.sinks", &L.sinks));
+        }
         if (m.qk_norm) {
             TM_TRY(norm(p + ".attention.q_norm.weight", &L.q_norm));
             TM_TRY(norm(p + ".attention.k_norm.weight", &L.k_norm));
@@ -617,6 +639,19 @@ int tm_engine_start(tm_engine* e)
         // (profiles/r06_fold_ab.txt).  TM_FOLD_NORM=3 runs it (bit 0: wo -> w1w3, bit 1: w2 -> w_qkv); every test of it stays.
         const char* fold = getenv("TM_FOLD_NORM");
         e->fold_norm     = (!e->use_comm && m.weight_type == 0 && m.moe_experts == 0 && e->hidden % 64 == 0) ? (fold ? atoi(fold) & 3 : 0) : 0;
+    }
+    {
+        // sliding windows: a window that covers the whole session is full attention; an engine left without a windowed layer and without
+        // sinks is the engine it was before the feature (fused MFMA path, same launches)
+        e->windowed = m.attn_sinks != 0;
+        for (int i = 0; i < m.layers; ++i) {
+            const int w         = e->layer_windows.empty() ? m.attn_window : e->layer_windows[i];
+            e->layers[i].window = w >= c.session_len ? 0 : w;
+            e->windowed |= e->layers[i].window > 0;
+        }
+        if (e->windowed) {
+            e->fold_norm = 0;
+        }
     }
     if (m.moe_experts > 0) {
         TM_HIP_CHECK(hipMalloc(&e->d_moe_ws, moe_workspace_bytes(e->layers[0].moe, e->max_tokens)));

@@ -247,6 +247,8 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             p.kv_heads   = e->kv_heads;
             p.scale_log2 = scale_log2;
             p.head_dim   = e->D;
+            p.window     = L.window;
+            p.sinks      = L.sinks;
             TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
             TM_PROF(P_GEMM_O, TM_TRY(linear_plain(e, L.wo, e->d_attn + (size_t)P.r0 * kq, kq, e->d_tmp + off, H, P.rows, false)));
             TM_TRY(allreduce_rows_side(e, P.r0, P.rows, &done[h]));
@@ -451,6 +453,8 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             p.partial_o      = e->d_attn_ws;
             p.partial_ml     = e->d_attn_ws + (size_t)nd * e->q_heads * e->decode_splits * e->D;
             p.cache          = cvd;
+            p.window         = L.window;
+            p.sinks          = L.sinks;
             TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, dst)));
             if (dst != st) {
                 TM_HIP_CHECK(hipEventRecord(e->ev_aux_join, dst));
@@ -481,6 +485,8 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             p.partial_o  = e->d_attn_ws;
             p.partial_ml = e->d_attn_ws + (size_t)nseq * e->q_heads * e->decode_splits * e->D;
             p.cache      = cv;
+            p.window     = L.window;
+            p.sinks      = L.sinks;
             TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, st)));
         }
         else {
@@ -502,6 +508,8 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             p.kv_heads   = e->kv_heads;
             p.scale_log2 = scale_log2;
             p.head_dim   = e->D;
+            p.window     = L.window;
+            p.sinks      = L.sinks;
             TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
             if (md && e->mixed_two_streams && e->aux_stream) {
                 TM_HIP_CHECK(hipStreamWaitEvent(st, e->ev_aux_join, 0));  // join: wo reads the decode rows' attention output too
@@ -797,7 +805,7 @@ void setup_decode(tm_engine* e, int batch)
         // 1.547 .. 1.587 with 64 x 8 (Llama-3-8B shard), 5.06 against 5.26 (Llama-3-70B shard).  fp16 KV (VALU kernel, <= 4
         // heads per workgroup): two workgroups per CU as before.
         // head_dim 64 decodes on the VALU kernel for every KV width: its head-per-workgroup rule
-        const bool mfma  = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128;
+        const bool mfma  = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128 && !e->windowed;
         const int  group = e->q_heads / e->kv_heads;
         int        hpw   = 1;
         if (mfma) {
@@ -832,8 +840,9 @@ void setup_decode(tm_engine* e, int batch)
     // per-sequence RoPE tables (dynamic NTK active): the fused prologue reads the one shared table, so such an engine runs the unfused
     // decode path -- kv_rope_store with the row offsets, then plain decode attention
     // head_dim 64: no MFMA kernel, so no fused prologue either -- the same unfused path
+    // a sliding window or attention sinks (e->windowed): the VALU kernel's variant serves them, the same unfused path for every layer
     e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse))
-                  && !e->d_rope_row0 && e->D == 128;
+                  && !e->d_rope_row0 && e->D == 128 && !e->windowed;
 }
 
 // Chunked prefill of `batch` sequences into the batch slots [slot0, slot0 + batch): whole sequences,

@@ -65,6 +65,9 @@ struct Layer {
     half_t*     qkv_bias  = nullptr;
     half_t*     q_norm    = nullptr;
     half_t*     k_norm    = nullptr;
+    // sliding window of this layer after clamping (0: full attention) and its sink logits [q_heads] (nullptr: none); tm_engine_start
+    int         window    = 0;
+    half_t*     sinks     = nullptr;
     // mixture of experts: gate slot + per-expert slots feed `moe`; the dense w13 / w2 are unused unless the layer has a shared
     // expert (tm_model_config.moe_shared_inter: Qwen2-MoE), which IS the dense FFN at the shared width, gated inside moe's combine
     bool                     is_moe = false;
@@ -185,6 +188,10 @@ struct tm_engine {
 
     int            decode_splits = 1;
     bool           fuse_qkv      = false;  // decode: qkv GEMM output -> attention kernel directly (int8 KV, MFMA kernel)
+    // some layer has a sliding window shorter than session_len, or the model has attention sinks: the whole engine runs head_dim 64's
+    // arrangement (kv_rope_store + VALU decode kernel, no fused prologue, no folded norm).  false: exactly the engine without the feature
+    bool             windowed = false;
+    std::vector<int> layer_windows;  // tm_engine_set_layer_windows (empty: attn_window for every layer)
     hipGraphExec_t graph = nullptr;
     // per-kernel-category HIP event profiling (tm_engine_profile_decode)
     bool                                            prof_on = false;

@@ -98,6 +98,11 @@ struct DecodeAttnParams {
     const half_t*  q_norm   = nullptr;
     const half_t*  k_norm   = nullptr;
     float          qk_eps   = 0.f;
+    // Sliding window and attention sinks (VALU kernel only, never with the fused prologue; reference: attention_params.h:55-72).
+    // window > 0: the query at k_len - 1 sees keys j with k_len - 1 - j < window (0 = all).  sinks [q_heads]: natural-log logits that
+    // join the softmax denominator and carry no value (nullptr = none).
+    int            window = 0;
+    const half_t*  sinks  = nullptr;
 };
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip
@@ -120,6 +125,8 @@ struct PrefillAttnParams {
     int           kv_heads;
     float         scale_log2;
     int           head_dim = 128;  // D: 64 | 128
+    int           window   = 0;        // > 0: row at position q sees keys t with 0 <= q - t < window (0 = causal only)
+    const half_t* sinks    = nullptr;  // [q_heads] natural-log sink logits (nullptr = none)
 };
 int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 

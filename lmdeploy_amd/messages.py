@@ -177,7 +177,9 @@ class TurbomindEngineConfig:
     """TurboMind Engine config -- same field names and defaults as the reference (lmdeploy/messages.py:302-343).
 
     Models: the attention path serves head_dim 128 and, through the Llama reader (Llama-3.2-1B, TinyLlama, SmolLM2: fp16 / bf16 or
-    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' needs head_dim 128."""
+    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' needs head_dim 128.  Mistral / Mixtral
+    checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
+    on the VALU attention kernel for every quant_policy, and KV blocks older than the window stay allocated."""
     dtype: str = 'auto'
     model_format: str | None = None
     tp: int = 1

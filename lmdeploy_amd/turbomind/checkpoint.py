@@ -69,6 +69,7 @@ class ModelConfig:
     qk_norm: int = 0                   # Qwen3: per-head RMSNorm of q and k before RoPE
     moe_shared_inter: int = 0          # Qwen2-MoE: width of the shared expert (a dense FFN behind a sigmoid gate in every MoE layer)
     tie_word_embeddings: bool = False
+    window: int = 0                    # Mistral / Mixtral `sliding_window`: a query sees the last `window` keys (0 = all)
 
 
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
@@ -162,6 +163,13 @@ def read_config(model_path: str) -> ModelConfig:
         if heads * D % 128:
             raise NotImplementedError(f'{arch} with {heads} attention heads of head_dim {D}: num_attention_heads * head_dim = '
                                       f'{heads * D} must be a multiple of 128 (the K dimension of the o projection)')
+    window = 0
+    if 'Mistral' in arch or 'Mixtral' in arch:      # sliding_window: null, absent or 0 = full attention (Mistral-7B-v0.1: 4096)
+        sw = c.get('sliding_window')
+        if sw is not None:
+            if isinstance(sw, bool) or not isinstance(sw, int) or sw < 0:
+                raise ValueError(f'{arch}: sliding_window {sw!r} must be a non-negative integer or null')
+            window = sw
     q = c.get('quantization_config')
     wfmt = 'f16'
     if q is not None:
@@ -213,7 +221,7 @@ def read_config(model_path: str) -> ModelConfig:
                        vocab=c['vocab_size'], rms_eps=float(c.get('rms_norm_eps', 1e-5)), rope=rope, arch=kind,
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
                        max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, **moe,
-                       attn_bias=attn_bias, qk_norm=qk_norm, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
+                       attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
 class _Tensors:

@@ -21,7 +21,7 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     """cfg: any object with hidden, layers, q_heads, kv_heads, head_dim, inter, vocab, rms_eps, rope(.dim,.base,.type,
     .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings; optional .max_position_embeddings, .beta_fast,
     .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert), attn_bias,
-    qk_norm."""
+    qk_norm, window (sliding window of every layer, 0 = none), attn_sinks."""
     r = cfg.rope
     return _ffi.ModelConfig(cfg.hidden, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, cfg.inter, cfg.vocab,
                             cfg.rms_eps, r.base, _ROPE_TYPES[r.type], r.factor, r.low_freq_factor, r.high_freq_factor,
@@ -31,6 +31,7 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
                             int(getattr(cfg, 'moe_experts', 0) or 0), int(getattr(cfg, 'moe_top_k', 0) or 0),
                             int(bool(getattr(cfg, 'moe_norm_topk', True))), float(getattr(cfg, 'moe_routed_scale', 1.0)),
                             int(getattr(cfg, 'moe_shared_inter', 0) or 0),
+                            int(getattr(cfg, 'window', 0) or 0), int(bool(getattr(cfg, 'attn_sinks', 0))),
                             int(bool(getattr(cfg, 'attn_bias', 0))), int(bool(getattr(cfg, 'qk_norm', 0))))
 
 
@@ -51,7 +52,16 @@ class Engine:
 
     @classmethod
     def from_model_config(cls, cfg, weight_type: int = 0, **kw) -> 'Engine':
-        return cls(make_model_config(cfg, weight_type), **kw)
+        eng = cls(make_model_config(cfg, weight_type), **kw)
+        layer_windows = getattr(cfg, 'layer_windows', None)
+        if layer_windows is not None:
+            eng.set_layer_windows(layer_windows)
+        return eng
+
+    def set_layer_windows(self, windows: Sequence[int]):
+        """one sliding window per layer (0 = full attention), replacing the model config's window; before start()"""
+        arr = (C.c_int * len(windows))(*[int(w) for w in windows])
+        _ffi.check(self._lib.tm_engine_set_layer_windows(self._h, arr, len(windows)))
 
     # ---- weights ---------------------------------------------------------------------------------
     def load_weights(self, slots: dict):

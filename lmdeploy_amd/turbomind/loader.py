@@ -102,7 +102,7 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     """weights (unsharded, TM layout): {'tok_embeddings' [V,H], 'norm' [H], 'output' [H,V],
     'layers': [{'attn_norm','ffn_norm', 'w_qkv','wo','w1w3','w2': linear dicts}]} with w_qkv = [Q|K|V] along N and
     w1w3 already (gate_j, up_j)-interleaved; Qwen layers add 'qkv_bias' [Hq*D + 2*Hkv*D] (q / k permuted like w_qkv) and /
-    or 'q_norm', 'k_norm' [D]; MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
+    or 'q_norm', 'k_norm' [D]; layers with attention sinks add 'sinks' [Hq]; MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
     all of them: w1w3 / w2 are then the shared expert (width cfg.moe_shared_inter) next to its 'shared_gate' [H].
     Returns {slot name: contiguous numpy array} for this rank."""
     D = cfg.head_dim
@@ -152,6 +152,9 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
         if 'qkv_bias' in L:    # the same column slices as w_qkv (replicated kv heads included)
             slots[p + '.attention.w_qkv.bias'] = np.ascontiguousarray(
                 np.concatenate([L['qkv_bias'][lo:hi] for lo, hi in qkv_slices]), dtype=np.float16)
+        if 'sinks' in L:       # one logit per q head: this rank's heads (the reference: 'sinks': SplitSide.OUTPUT)
+            hq_l = Hq // tp
+            slots[p + '.attention.sinks'] = np.ascontiguousarray(L['sinks'][rank * hq_l:(rank + 1) * hq_l], dtype=np.float16)
         if 'q_norm' in L:      # one head: replicated
             slots[p + '.attention.q_norm.weight'] = np.ascontiguousarray(L['q_norm'], dtype=np.float16)
             slots[p + '.attention.k_norm.weight'] = np.ascontiguousarray(L['k_norm'], dtype=np.float16)

@@ -2,6 +2,8 @@
 """Time the paged decode attention kernel at the metric shape (B=64, 32 q / 8 kv heads, int8 KV) on random cache
 contents.  python tools/bench_attention.py [--ctx 1536] [--bits 8] [--splits 1,2,4] [--head-dim 128]
 --head-dim 64 times the head_dim 64 kernel (VALU, every KV width); set TM_ATTN_VALU=1 to time the same kernel family at head_dim 128.
+--window W times tm_decode_attention_window (the VALU kernel's sliding-window variant, both head dims): the bytes per launch are those
+of the last min(ctx, W) tokens.
 --engine-decode times whole decode steps of a SYNTHETIC Llama-3.2-1B geometry instead (tm_engine_init_synthetic weights, int8 KV)."""
 import argparse
 import os
@@ -24,6 +26,7 @@ def main():
     ap.add_argument('--head-dim', type=int, default=128, choices=[64, 128])
     ap.add_argument('--engine-decode', action='store_true',
                     help='decode tok/s of a synthetic Llama-3.2-1B geometry (2048 / 16 layers / 32 x 8 heads of 64 / 8192 / 128256)')
+    ap.add_argument('--window', type=int, default=0, help='sliding window (0 = none): tm_decode_attention_window')
     ap.add_argument('--splits', default='1,2,4')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--trace', action='store_true')
@@ -59,7 +62,14 @@ def main():
     q = torch.randn((B, Hq * D), device='cuda').half()
     out = torch.empty((B, Hq * D), device='cuda').half()
     st = torch.cuda.current_stream().cuda_stream
-    bytes_per_launch = B * ctx * 2 * Hkv * (D * bits // 8 + (4 if bits < 16 else 0))
+    seen = min(ctx, a.window) if a.window > 0 else ctx
+    bytes_per_launch = B * seen * 2 * Hkv * (D * bits // 8 + (4 if bits < 16 else 0))
+
+    def attend(splits, ws, view):
+        if a.window > 0:
+            return tm.tm_decode_attention_window(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits, ws.data_ptr(),
+                                                 view, a.window, None, st)
+        return tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits, ws.data_ptr(), view, st)
     if a.trace:
         # in-kernel phase stamps (100 MHz): start / prologue done (q ready, first block issued) / wave 0 done /
         # all waves done / end, per workgroup
@@ -107,20 +117,18 @@ def main():
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
         for i in range(4):   # warm-up: code-object load and clocks, outside the timed launches
             view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
-            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits,
-                                              ws.data_ptr(), view, st))
+            _ffi.check(attend(splits, ws, view))
         torch.cuda.synchronize()
         for i, (e0, e1) in enumerate(ev):
             view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
             e0.record()
-            _ffi.check(tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits,
-                                              ws.data_ptr(), view, st))
+            _ffi.check(attend(splits, ws, view))
             e1.record()
         torch.cuda.synchronize()
         ts = sorted(x.elapsed_time(y) for x, y in ev)
         med = ts[len(ts) // 2]
         gbs = bytes_per_launch / (med * 1e-3) / 1e9
-        print(f'head_dim={D} ctx={ctx} bits={bits} splits={splits}: {med*1e3:8.1f} us  {gbs:7.0f} GB/s = {gbs / 8000:.3f} of 8 TB/s '
+        print(f'head_dim={D} ctx={ctx} window={a.window} bits={bits} splits={splits}: {med*1e3:8.1f} us  {gbs:7.0f} GB/s = {gbs / 8000:.3f} of 8 TB/s '
               f'({bytes_per_launch/1e6:.1f} MB/launch)  layout={a.layout} layers={layers}', flush=True)
 
 
