@@ -244,7 +244,7 @@ int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st
 
 /* ---- Linear (mirrors _tm.LinearWeight / LlamaLinear.forward_dense / QuantizeGroupwise) -------- */
 typedef struct tm_linear tm_linear;
-enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2 };
+enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* MoE expert weights only */ };
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size);
 /* Boundary ("TM") layout, device pointers: qweight int32 [K][N/8] (nibble j of word c = column 8c+j,
  * lmdeploy/turbomind/weight_format.py:63-74), scales / zeros fp16 [K/g][N].  For TM_WEIGHT_F16: weight fp16
@@ -328,7 +328,20 @@ int    tm_linear_destroy(tm_linear* w);
  *   out[t] = fp16( float(shared[t]) * sigmoid(x_t . gate) + sum_e w_e(t) * float(y_e(t)) )
  * with the logit and the sum in fp32, in ONE combine launch.  `shared` may equal `out` (the reference combines in place); x must not.
  * tm_moe_forward / tm_moe_forward_stages on such a block return TM_INVALID instead of dropping the term;
- * tm_moe_forward_shared_stages is tm_moe_forward_stages for it (`shared` is read by the combine stage only). */
+ * tm_moe_forward_shared_stages is tm_moe_forward_stages for it (`shared` is read by the combine stage only).
+ * MXFP4 experts and the gpt-oss block (lmdeploy/turbomind/models/gpt_oss.py; src/turbomind/kernels/activation.cu:17-24,
+ * kernels/gemm/transform.h:83-90, kernels/gemm/cast.cu:220-227, models/llama/moe_ffn_layer.cc:43-53,272-275,310-313):
+ * weight_type TM_WEIGHT_MXFP4: tm_moe_set_expert takes the checkpoint layout -- weight = blocks uint8 [N][K/2] (N = output channels,
+ * the low nibble of a byte is the even k) and scales = uint8 [N][K/32] (one ue8m0 byte per 32 k), zeros unused (NULL); w13's N rows are
+ * (gate_j, up_j)-interleaved.  Code c is sign c >> 3 and magnitude {0, .5, 1, 1.5, 2, 3, 4, 6}[c & 7]; scale byte s is the fp16 with
+ * exponent field clamp(s - 112, 0, 30); w = fp16(value * scale), exact when finite; from there on the arithmetic of fp16 experts.
+ * tm_mxfp4_dequant_f16 writes that operand, as the grouped GEMM builds it from the repacked image, to out_kn fp16 [K][N].
+ * tm_moe_set_activation: 0 = SiLU (default), 1 = gpt-oss: g = min(g, 7), u = clamp(u, -7, 7), g * sigmoid(1.702 g) * (1 + u) in fp32 on
+ * the fp16-rounded (and biased) gate / up.  tm_moe_set_gate_bias: device fp32 [experts], added to the router logits before the top-k (NULL: none again; any expert format).
+ * tm_moe_set_expert_bias: device fp16 b13 [2 * inter] ((gate_j, up_j)-interleaved, added in fp16 to the w1w3 output before the
+ * activation; needs activation 1) and b2 [hidden] (added in fp16 to every routed row of that expert before the weighted combine);
+ * experts never given a bias have zero biases.  The activation and the biases are built for TM_WEIGHT_F16 and TM_WEIGHT_MXFP4 experts;
+ * the setters return TM_INVALID for u4 / fp8 blocks, and blocks that never call them launch exactly what they launched before. */
 typedef struct tm_moe tm_moe;
 int    tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk,
                      float routed_scale);
@@ -336,6 +349,10 @@ int    tm_moe_set_gate(tm_moe* m, const void* gate, tm_stream_t st);
 int    tm_moe_set_shared_gate(tm_moe* m, const void* gate_fp16_hidden, tm_stream_t st);
 int    tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void* w13_scales, const void* w13_zeros,
                          const void* w2_weight, const void* w2_scales, const void* w2_zeros, tm_stream_t st);
+int    tm_moe_set_activation(tm_moe* m, int kind);
+int    tm_moe_set_gate_bias(tm_moe* m, const void* bias_fp32_experts, tm_stream_t st);
+int    tm_moe_set_expert_bias(tm_moe* m, int expert, const void* b13_fp16, const void* b2_fp16, tm_stream_t st);
+int    tm_mxfp4_dequant_f16(void* out_kn, const void* blocks, const void* scales, int K, int N, tm_stream_t st);
 size_t tm_moe_workspace(const tm_moe* m, int tokens);
 int    tm_moe_forward(tm_moe* m, void* out, const void* x, int tokens, void* workspace, int* topk_ids_out, float* topk_w_out,
                       tm_stream_t st);
@@ -470,6 +487,14 @@ typedef struct tm_model_config {
      * `inter` (sharded over tp like the dense FFN), `moe_top_k` per token (Mixtral: 8 / 2, norm_topk = 1) */
     int   moe_experts, moe_top_k, moe_norm_topk;
     float moe_routed_scale;
+    /* gpt-oss MoE block (all 0 = the engine as before).  moe_expert_format: 0 = the experts follow weight_type, 3 = TM_WEIGHT_MXFP4
+     * experts whatever the other linears are (gpt-oss: fp16 attention, MXFP4 experts) in the slots "layers.{i}.moe_ffn.experts.{x}.
+     * w1w3.blocks" uint8 [2 * inter][hidden / 2] / ".w1w3.scales" uint8 [2 * inter][hidden / 32] / ".w2.blocks" uint8 [hidden][inter / 2] /
+     * ".w2.scales" uint8 [hidden][inter / 32] (tm_moe_set_expert's layout).  moe_act: tm_moe_set_activation's kind.  moe_bias != 0 ->
+     * slots "...experts.{x}.w1w3.bias" fp16 [2 * inter], "...experts.{x}.w2.bias" fp16 [hidden] and "layers.{i}.moe_ffn.gate.bias" fp32
+     * [experts]; needs moe_act 1.  moe_act / moe_bias need fp16 or MXFP4 experts; MXFP4 experts and moe_bias need tp == 1 (the w2 bias
+     * would need a per-rank rule). */
+    int   moe_expert_format, moe_act, moe_bias;
     /* Qwen2-MoE shared expert (0 = none; needs moe_experts > 0): every MoE layer ALSO has a dense FFN of this width (sharded over tp like
      * the dense FFN; moe_shared_inter / tp % 128 == 0) in the slots "layers.{i}.feed_forward.w1w3.*" / ".w2.*" -- the reference's names:
      * the shared expert is the layer's feed_forward -- and a gate "layers.{i}.moe_ffn.shared_gate.weight" fp16 [hidden], replicated.

@@ -65,7 +65,8 @@ class ModelConfig(C.Structure):
                 ('rope_max_position_embeddings', c_int), ('rope_yarn_beta_fast', c_float), ('rope_yarn_beta_slow', c_float),
                 ('rope_yarn_attention_factor', c_float), ('group_size', c_int),
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
-                ('moe_routed_scale', c_float), ('moe_shared_inter', c_int), ('attn_window', c_int), ('attn_sinks', c_int),
+                ('moe_routed_scale', c_float), ('moe_expert_format', c_int), ('moe_act', c_int), ('moe_bias', c_int),
+                ('moe_shared_inter', c_int), ('attn_window', c_int), ('attn_sinks', c_int),
                 ('attn_bias', c_int), ('qk_norm', c_int)]
 
 
@@ -125,6 +126,10 @@ _SIGNATURES = {
     'tm_moe_set_gate': (c_int, [c_void_p, c_void_p, c_void_p]),
     'tm_moe_set_shared_gate': (c_int, [c_void_p, c_void_p, c_void_p]),
     'tm_moe_set_expert': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_moe_set_activation': (c_int, [c_void_p, c_int]),
+    'tm_moe_set_gate_bias': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'tm_moe_set_expert_bias': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'tm_mxfp4_dequant_f16': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'tm_moe_workspace': (c_size_t, [c_void_p, c_int]),
     'tm_moe_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_moe_forward_shared': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

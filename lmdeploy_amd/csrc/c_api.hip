@@ -699,8 +699,8 @@ struct tm_moe {
 int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk, float routed_scale)
 {
     TM_REQUIRE(out, "null pointer");
-    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_F16,
-               "moe experts: u4, fp8 or fp16 weights");
+    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_MXFP4,
+               "moe experts: u4, fp8, fp16 or mxfp4 weights");
     TM_REQUIRE(hidden % 128 == 0 && inter % 128 == 0 && experts >= 1 && experts <= 256 && top_k >= 1 && top_k <= 8 && top_k <= experts,
                "moe geometry");
     auto* o         = new tm_moe();
@@ -754,6 +754,10 @@ int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void*
         return linear_weight_prepare_f16(m->m.w2[expert], (const half_t*)w2_weight, (hipStream_t)st);
     }
     TM_REQUIRE(w13_scales && w2_scales, "null pointer");
+    if (m->type == TM_WEIGHT_MXFP4) {  // blocks uint8 [N][K/2] + scales uint8 [N][K/32] (the checkpoint layout); zeros unused
+        TM_TRY_RC(linear_weight_prepare_mxfp4(m->m.w13[expert], (const uint8_t*)w13_weight, (const uint8_t*)w13_scales, (hipStream_t)st));
+        return linear_weight_prepare_mxfp4(m->m.w2[expert], (const uint8_t*)w2_weight, (const uint8_t*)w2_scales, (hipStream_t)st);
+    }
     if (m->type == TM_WEIGHT_U4) {
         TM_REQUIRE(w13_zeros && w2_zeros, "u4 experts need zeros");
         TM_TRY_RC(linear_weight_prepare_u4(m->m.w13[expert], (const int32_t*)w13_weight, (const half_t*)w13_scales,
@@ -763,6 +767,70 @@ int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void*
     }
     TM_TRY_RC(linear_weight_prepare_fp8(m->m.w13[expert], (const uint8_t*)w13_weight, (const float*)w13_scales, true, (hipStream_t)st));
     return linear_weight_prepare_fp8(m->m.w2[expert], (const uint8_t*)w2_weight, (const float*)w2_scales, false, (hipStream_t)st);
+}
+
+int tm_moe_set_activation(tm_moe* m, int kind)
+{
+    TM_REQUIRE(m, "null pointer");
+    TM_REQUIRE(kind == 0 || kind == 1, "moe activation: 0 (SiLU) or 1 (gpt-oss)");
+    TM_REQUIRE(kind == 0 || m->type == TM_WEIGHT_F16 || m->type == TM_WEIGHT_MXFP4,
+               "moe: the gpt-oss activation is built for fp16 and MXFP4 experts only (not u4 / fp8)");
+    m->m.act    = kind;
+    m->prepared = false;
+    return 0;
+}
+
+int tm_moe_set_gate_bias(tm_moe* m, const void* bias, tm_stream_t st)
+{
+    TM_REQUIRE(m, "null pointer");
+    if (!bias) {  // NULL: no router bias (the block launches the routers without the add again)
+        if (m->m.gate_bias) {
+            TM_HIP_CHECK(hipStreamSynchronize((hipStream_t)st));
+            TM_HIP_CHECK(hipFree(m->m.gate_bias));
+            m->m.gate_bias = nullptr;
+        }
+        return 0;
+    }
+    const size_t bytes = (size_t)m->m.experts * 4;
+    if (!m->m.gate_bias) {
+        TM_HIP_CHECK(hipMalloc((void**)&m->m.gate_bias, bytes));
+    }
+    TM_HIP_CHECK(hipMemcpyAsync(m->m.gate_bias, bias, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st));
+    return 0;
+}
+
+int tm_moe_set_expert_bias(tm_moe* m, int expert, const void* b13, const void* b2, tm_stream_t st)
+{
+    TM_REQUIRE(m && b13 && b2, "null pointer");
+    TM_REQUIRE(expert >= 0 && expert < m->m.experts, "expert index");
+    TM_REQUIRE(m->type == TM_WEIGHT_F16 || m->type == TM_WEIGHT_MXFP4,
+               "moe: expert biases are built for fp16 and MXFP4 experts only (not u4 / fp8)");
+    const size_t n13 = (size_t)2 * m->m.inter, n2 = (size_t)m->m.hidden;
+    if (!m->m.b13) {  // biases of experts never set are zero
+        TM_HIP_CHECK(hipMalloc((void**)&m->m.b13, n13 * m->m.experts * 2));
+        TM_HIP_CHECK(hipMalloc((void**)&m->m.b2, n2 * m->m.experts * 2));
+        TM_HIP_CHECK(hipMemsetAsync(m->m.b13, 0, n13 * m->m.experts * 2, (hipStream_t)st));
+        TM_HIP_CHECK(hipMemsetAsync(m->m.b2, 0, n2 * m->m.experts * 2, (hipStream_t)st));
+    }
+    TM_HIP_CHECK(hipMemcpyAsync(m->m.b13 + n13 * expert, b13, n13 * 2, hipMemcpyDeviceToDevice, (hipStream_t)st));
+    TM_HIP_CHECK(hipMemcpyAsync(m->m.b2 + n2 * expert, b2, n2 * 2, hipMemcpyDeviceToDevice, (hipStream_t)st));
+    m->prepared = false;
+    return 0;
+}
+
+int tm_mxfp4_dequant_f16(void* out_kn, const void* blocks, const void* scales, int K, int N, tm_stream_t st)
+{
+    TM_REQUIRE(out_kn && blocks && scales, "null pointer");
+    TM_REQUIRE(K >= 128 && K % 128 == 0 && N >= 16 && N % 16 == 0, "mxfp4 dequant: K % 128 == 0 and N % 16 == 0");
+    LinearWeight w;
+    w.K = K, w.N = N;
+    int rc = linear_weight_prepare_mxfp4(w, (const uint8_t*)blocks, (const uint8_t*)scales, (hipStream_t)st);
+    if (!rc) {
+        rc = launch_dequant_mxfp4_f16((half_t*)out_kn, w, (hipStream_t)st);
+    }
+    (void)hipStreamSynchronize((hipStream_t)st);  // the image is freed below
+    linear_weight_free(w);
+    return rc;
 }
 
 size_t tm_moe_workspace(const tm_moe* m, int tokens)
@@ -823,7 +891,7 @@ int tm_moe_router(tm_moe* m, const void* x, int tokens, int* topk_ids, float* to
     TM_REQUIRE(m && x && topk_ids && topk_w && offsets && f2n && en2f, "null pointer");
     TM_REQUIRE(m->m.gate && tokens >= 1, "moe router: gate set, tokens >= 1");
     TM_TRY_RC(launch_moe_gate(topk_ids, topk_w, logits_out, (const half_t*)x, m->m.hidden, m->m.gate, tokens, m->m.hidden, m->m.experts,
-                              m->m.top_k, m->m.norm_topk, m->m.routed_scale, (hipStream_t)st));
+                              m->m.top_k, m->m.norm_topk, m->m.routed_scale, (hipStream_t)st, m->m.gate_bias));
     return launch_moe_route(offsets, f2n, en2f, topk_ids, tokens, m->m.experts, m->m.top_k, (hipStream_t)st);
 }
 
@@ -1102,7 +1170,7 @@ int tm_debug_pick_general(int weight_type, int role, int K, int N, int M, int* c
 
 int tm_debug_grouped_tile(int weight_type, int K, int N, int tokens, int* rows)
 {
-    TM_REQUIRE(rows && K > 0 && N > 0 && tokens > 0 && weight_type >= 0 && weight_type <= 2, "arguments");
+    TM_REQUIRE(rows && K > 0 && N > 0 && tokens > 0 && weight_type >= 0 && weight_type <= 3, "arguments");
     int tv[4];
     *rows = gen_table_get(kGenGrouped + weight_type, 0, K, N, dec32_m_bucket(tokens), tv) ? tv[0] : 0;
     return 0;

@@ -62,6 +62,24 @@ __global__ void fill_fp8_kernel(uint8_t* out, size_t n, uint64_t seed)
     }
 }
 
+// synthetic MXFP4 experts: uniform code bytes, or scale bytes in {base - 1, base, base + 1}
+__global__ void fill_mxfp4_kernel(uint8_t* out, size_t n, uint64_t seed, int scale_base)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const uint64_t z = splitmix64(seed ^ ((i + 1) * 0x9E3779B97F4A7C15ull));
+        out[i]           = scale_base ? (uint8_t)(scale_base - 1 + (int)((z >> 33) % 3)) : (uint8_t)(z >> 33);
+    }
+}
+
+__global__ void f16_to_f32_kernel(float* out, const half_t* in, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        out[i] = (float)in[i];
+    }
+}
+
 __global__ void fill_const_f32_kernel(float* out, size_t n, float v)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -151,6 +169,10 @@ static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, 
             e->slots[prefix + "." + part].bytes = slot_bytes_linear(e, K, N, part);
         }
     }
+    else if (type == TM_WEIGHT_MXFP4) {  // the checkpoint layout: e2m1 codes [N][K/2] + one ue8m0 byte per 32 k [N][K/32]
+        e->slots[prefix + ".blocks"].bytes = (int64_t)N * (K / 2);
+        e->slots[prefix + ".scales"].bytes = (int64_t)N * (K / 32);
+    }
     else if (type == TM_WEIGHT_FP8) {  // e4m3 [K][N] + fp32 128x128 block scales (weight_format.py:349-393)
         e->slots[prefix + ".weight"].bytes = slot_bytes_linear(e, K, N, "weight_fp8");
         e->slots[prefix + ".scales"].bytes = slot_bytes_linear(e, K, N, "scales_fp8");
@@ -230,6 +252,16 @@ static int prepare_linear(tm_engine* e, LinearSlots& l)
             p->dev = nullptr;
         }
     }
+    else if (l.w.type == TM_WEIGHT_MXFP4) {
+        Slot &w = e->slots[l.prefix + ".blocks"], &s = e->slots[l.prefix + ".scales"];
+        TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
+        TM_TRY(linear_weight_prepare_mxfp4(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+        for (Slot* p : {&w, &s}) {
+            TM_HIP_CHECK(hipFree(p->dev));
+            p->dev = nullptr;
+        }
+    }
     else if (l.w.type == TM_WEIGHT_FP8) {
         Slot &w = e->slots[l.prefix + ".weight"], &s = e->slots[l.prefix + ".scales"];
         TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
@@ -277,6 +309,16 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.moe_shared_inter >= 0 && (m.moe_shared_inter == 0 || m.moe_experts > 0), "moe_shared_inter needs moe_experts > 0");
     TM_REQUIRE(m.moe_shared_inter % c->tp == 0 && (m.moe_shared_inter / c->tp) % 128 == 0,
                "moe_shared_inter / tp must be a multiple of 128");
+    TM_REQUIRE(m.moe_expert_format == 0 || m.moe_expert_format == TM_WEIGHT_MXFP4, "moe_expert_format: 0 (follow weight_type) or 3 (MXFP4)");
+    TM_REQUIRE((m.moe_expert_format == 0 && m.moe_act == 0 && m.moe_bias == 0) || m.moe_experts > 0,
+               "moe_expert_format / moe_act / moe_bias need moe_experts > 0");
+    TM_REQUIRE(m.moe_act == 0 || m.moe_act == 1, "moe_act: 0 (SiLU) or 1 (gpt-oss)");
+    TM_REQUIRE((m.moe_act == 0 && m.moe_bias == 0) || m.moe_expert_format == TM_WEIGHT_MXFP4 || m.weight_type == TM_WEIGHT_F16,
+               "moe_act / moe_bias: the gpt-oss activation and expert biases are built for fp16 and MXFP4 experts only (not u4 / fp8)");
+    TM_REQUIRE(m.moe_bias == 0 || m.moe_act == 1, "moe_bias needs moe_act = 1 (the gpt-oss activation)");
+    TM_REQUIRE((m.moe_act == 0 && m.moe_bias == 0) || m.moe_shared_inter == 0, "moe_act / moe_bias with a shared expert is not built");
+    TM_REQUIRE((m.moe_expert_format != TM_WEIGHT_MXFP4 && m.moe_bias == 0) || c->tp == 1,
+               "MXFP4 experts / expert biases with tp > 1 are not built: the w2 bias would need a per-rank rule (run with tp = 1)");
     TM_TRY(check_linear_images(m, c->tp));
     TM_HIP_CHECK(hipSetDevice(c->device));
 
@@ -321,8 +363,16 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
             e->slots[p + ".moe_ffn.gate.weight"].bytes = (int64_t)m.hidden * m.moe_experts * 2;  // fp16 [H][E], replicated
             for (int x = 0; x < m.moe_experts; ++x) {
                 const std::string q = p + ".moe_ffn.experts." + std::to_string(x);
-                add_linear(e, L.ex13[x], q + ".w1w3", m.hidden, 2 * e->inter, m.weight_type);
-                add_linear(e, L.ex2[x], q + ".w2", e->inter, m.hidden, m.weight_type);
+                const int xt = m.moe_expert_format ? m.moe_expert_format : m.weight_type;
+                add_linear(e, L.ex13[x], q + ".w1w3", m.hidden, 2 * e->inter, xt);
+                add_linear(e, L.ex2[x], q + ".w2", e->inter, m.hidden, xt);
+                if (m.moe_bias) {
+                    e->slots[q + ".w1w3.bias"].bytes = (int64_t)2 * e->inter * 2;  // fp16, (gate_j, up_j)-interleaved
+                    e->slots[q + ".w2.bias"].bytes   = (int64_t)m.hidden * 2;
+                }
+            }
+            if (m.moe_bias) {
+                e->slots[p + ".moe_ffn.gate.bias"].bytes = (int64_t)m.moe_experts * 4;  // fp32 [E], replicated
             }
             if (e->shared_inter > 0) {  // the shared expert: the layer's dense feed_forward at its own width + the sigmoid gate [H]
                 L.has_shared = true;
@@ -410,6 +460,19 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
             w->filled = true;
             return 0;
         }
+        if (l.w.type == TM_WEIGHT_MXFP4) {
+            // uniform e2m1 codes (E|value| = 2.25) under scale bytes around 127 - 6: weights of the other synthetic formats' magnitude
+            Slot *w = nullptr, *sc = nullptr;
+            TM_TRY(ensure_slot(e, l.prefix + ".blocks", &w));
+            TM_TRY(ensure_slot(e, l.prefix + ".scales", &sc));
+            fill_mxfp4_kernel<<<((size_t)w->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)w->dev, (size_t)w->bytes, ++sd, 0);
+            TM_HIP_CHECK(hipGetLastError());
+            fill_mxfp4_kernel<<<((size_t)sc->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)sc->dev, (size_t)sc->bytes, ++sd, 127 - 6);
+            TM_HIP_CHECK(hipGetLastError());
+            w->filled = sc->filled = true;
+            TM_TRY(prepare_linear(e, l));
+            return 0;
+        }
         if (l.w.type == TM_WEIGHT_FP8) {
             // random e4m3 codes (no NaN), one constant block scale: E|code value| ~ 30 -> weights ~ 0.1 / sqrt(K)
             Slot *w = nullptr, *sc = nullptr;
@@ -466,6 +529,22 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
             for (int x = 0; x < m.moe_experts; ++x) {
                 TM_TRY(linear(L.ex13[x]));
                 TM_TRY(linear(L.ex2[x]));
+                if (m.moe_bias) {
+                    TM_TRY(vec(L.ex13[x].prefix + ".bias", (size_t)2 * e->inter, 0.f, 0.05f));
+                    TM_TRY(vec(L.ex2[x].prefix + ".bias", m.hidden, 0.f, 0.02f));
+                }
+            }
+            if (m.moe_bias) {  // fp32 [E]: drawn in fp16, then widened
+                Slot* gb = nullptr;
+                TM_TRY(ensure_slot(e, p + ".moe_ffn.gate.bias", &gb));
+                half_t* tmp = nullptr;
+                TM_HIP_CHECK(hipMalloc((void**)&tmp, (size_t)m.moe_experts * 2));
+                TM_TRY(fill_normal(e, tmp, m.moe_experts, 0.f, 0.5f, ++sd));
+                f16_to_f32_kernel<<<(m.moe_experts + 255) / 256, 256, 0, e->stream>>>((float*)gb->dev, tmp, m.moe_experts);
+                TM_HIP_CHECK(hipGetLastError());
+                TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+                TM_HIP_CHECK(hipFree(tmp));
+                gb->filled = true;
             }
             if (L.has_shared) {
                 TM_TRY(linear(L.w13));
@@ -541,6 +620,29 @@ int tm_engine_process_weights(tm_engine* e)
                 L.moe.w2[x]  = L.ex2[x].w;
                 L.ex13[x].w.packed = nullptr, L.ex13[x].w.sz = nullptr, L.ex13[x].w.packed32 = nullptr, L.ex13[x].w.packed8 = nullptr;
                 L.ex2[x].w.packed = nullptr, L.ex2[x].w.sz = nullptr, L.ex2[x].w.packed32 = nullptr, L.ex2[x].w.packed8 = nullptr;
+            }
+            L.moe.act = m.moe_act;
+            if (m.moe_bias) {  // the experts' biases side by side ([E][2I], [E][H]: what the grouped GEMM and the combine index)
+                const size_t n13 = (size_t)2 * e->inter, n2 = (size_t)m.hidden;
+                TM_HIP_CHECK(hipMalloc((void**)&L.moe.b13, n13 * m.moe_experts * 2));
+                TM_HIP_CHECK(hipMalloc((void**)&L.moe.b2, n2 * m.moe_experts * 2));
+                for (int x = 0; x < m.moe_experts; ++x) {
+                    Slot &s13 = e->slots[L.ex13[x].prefix + ".bias"], &s2 = e->slots[L.ex2[x].prefix + ".bias"];
+                    TM_REQUIRE(s13.filled && s2.filled, "weight not loaded: " + L.ex13[x].prefix + ".bias / " + L.ex2[x].prefix + ".bias");
+                    TM_HIP_CHECK(hipMemcpyAsync(L.moe.b13 + n13 * x, s13.dev, n13 * 2, hipMemcpyDeviceToDevice, e->stream));
+                    TM_HIP_CHECK(hipMemcpyAsync(L.moe.b2 + n2 * x, s2.dev, n2 * 2, hipMemcpyDeviceToDevice, e->stream));
+                }
+                TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+                for (int x = 0; x < m.moe_experts; ++x) {
+                    for (Slot* sl : {&e->slots[L.ex13[x].prefix + ".bias"], &e->slots[L.ex2[x].prefix + ".bias"]}) {
+                        TM_HIP_CHECK(hipFree(sl->dev));
+                        sl->dev = nullptr;
+                    }
+                }
+                Slot& gb = e->slots[p + ".moe_ffn.gate.bias"];
+                TM_REQUIRE(gb.filled, "weight not loaded: " + p + ".moe_ffn.gate.bias");
+                L.moe.gate_bias = (float*)gb.dev;  // used in place (freed by moe_free)
+                gb.dev          = nullptr;
             }
             Slot& g = e->slots[p + ".moe_ffn.gate.weight"];
             TM_REQUIRE(g.filled, "weight not loaded: " + p + ".moe_ffn.gate.weight");

@@ -740,7 +740,7 @@ size_t gemm_workspace_bytes(int M, int N, int splits)
 
 size_t gemm_general_image_bytes(int K, int N, int type)
 {
-    const size_t wv = type == 0 ? 1 : (type == 2 ? 2 : 4);  // u32x4 per (tile, k-block) per lane: u4 / fp8 / f16 (gemm_kernel's WV)
+    const size_t wv = (type == 0 || type == 3) ? 1 : (type == 2 ? 2 : 4);  // u32x4 per (tile, k-block) per lane: u4 / fp8 / f16 (gemm_kernel's WV)
     return (size_t)((K + 127) / 128) * ((N + 15) / 16) * 1024 * wv;
 }
 
@@ -879,7 +879,7 @@ static bool gen_entry_valid(int kind, int role, int K, int N, int M, const int v
         return (v[0] == 1 || v[0] == 2 || v[0] == 4) && v[1] >= 1 && v[1] <= 16 && (v[2] == 4 || v[2] == 8 || v[2] == 16)
                && (v[3] == 1 || v[3] == 2);
     }
-    if (kind == kGenGrouped || kind == kGenGrouped + 1) {  // u4 / fp16 experts: 16 / 32 / 64-row tiles (decode batches only)
+    if (kind == kGenGrouped || kind == kGenGrouped + 1 || kind == kGenGrouped + 3) {  // u4 / fp16 / MXFP4 experts: 16 / 32 / 64-row tiles (decode batches only)
         return (v[0] == 16 || v[0] == 32 || v[0] == 64) && M <= 64;
     }
     if (kind == kGenGrouped + 2) {  // e4m3 experts on the fp8 matrix cores: 32 / 64-row tiles
@@ -931,7 +931,7 @@ int gen_dense_candidates(const LinearWeight& w, int M, size_t workspace_bytes, G
 int gen_grouped_candidates(const LinearWeight& proto, int m_cap, int* rows_out, int cap)
 {
     int n = 0;
-    if ((proto.type == 0 || proto.type == 1) && m_cap <= 64) {
+    if ((proto.type == 0 || proto.type == 1 || proto.type == 3) && m_cap <= 64) {
         for (int r : {16, 32, 64}) {
             if (n < cap && (r == 16 || r / 2 < m_cap)) {
                 rows_out[n++] = r;
@@ -1349,8 +1349,13 @@ int moe_build_groups(void** d_groups, const LinearWeight* experts, int E, hipStr
 
 int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E, const half_t* x, int ldx, int x_rows,
                           half_t* y, int ldy, int m_cap, int m_hint, bool gated_silu, const int* seg, const int* row_idx,
-                          hipStream_t st)
+                          hipStream_t st, int act, const half_t* bias)
 {
+    if (proto.type == 3 || (gated_silu && act == 1)) {  // MXFP4 experts, the gpt-oss epilogue: gemm_mxfp4.hip
+        return launch_linear_grouped_mx(proto, d_groups, E, x, ldx, x_rows, y, ldy, m_cap, m_hint, gated_silu ? (act == 1 ? 3 : 1) : 0, bias, seg,
+                                        row_idx, st);
+    }
+    TM_REQUIRE(bias == nullptr, "grouped GEMM: a bias goes with the gpt-oss epilogue");
     TM_REQUIRE(proto.type == 0 || proto.type == 1 || proto.type == 2, "grouped GEMM: u4, fp8 or fp16 expert weights");
     TM_REQUIRE(ldx % 8 == 0 && (!gated_silu || proto.N % 32 == 0), "grouped GEMM: alignment");
     if (m_cap == 0 || E == 0) {

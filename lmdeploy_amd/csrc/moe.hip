@@ -11,6 +11,10 @@
 //   route:  for every expert the tokens that selected it, in ascending token order:
 //           offsets[e] .. offsets[e+1] index the flat pair list; f2n[f] = token; en2f[j][t] = f.
 //   combine: out[t] = fp16( sum_j w[t][j] * float(y[en2f[j][t]]) ).
+//   gpt-oss block (lmdeploy/turbomind/models/gpt_oss.py; MoeBlock::act / gate_bias / b13 / b2, fp16 and MXFP4 experts): a router bias
+//           (logit += bias[e] in fp32 before the top-k), per-expert biases on both linears and the clamped activation
+//           gate * sigmoid(1.702 gate) * (1 + up) -- the w1w3 bias and the activation in the grouped GEMM's epilogue (gemm_mxfp4.hip),
+//           the w2 bias per routed row in the combine (moe_combine_bias_kernel).  Off by default: nothing else launches differently.
 //   shared expert (Qwen2-MoE; unified_decoder.cc:295-318, moe_ffn_layer.cc:295-325, moe_utils_v2.cu:1032-1105): the layer's dense
 //           feed_forward output `shared` is scaled per token by sigmoid(x . w_shared_gate) and the routed sum is added on top, in
 //           the same launch (moe_combine_shared_kernel): out[t] = fp16( float(shared[t]) * sigma_t + sum_j w[t][j] * float(y[..]) ).
@@ -34,6 +38,8 @@ constexpr int kMaxTopK    = 8;
 constexpr int kMaxExpertsWide = 256;  // the wide router below
 
 // one 256-thread workgroup per token; Wg fp16 [H][E] (input-major like every other weight)
+// BIAS (gpt-oss router): logit[e] += bias[e], one fp32 add before the top-k; compiled out otherwise
+template<bool BIAS>
 __global__ __launch_bounds__(256) void moe_gate_kernel(int* __restrict__ topk_ids,      // [T][k]
                                                        float* __restrict__ topk_w,      // [T][k]
                                                        float* __restrict__ logits_out,  // [T][E] or nullptr
@@ -44,7 +50,8 @@ __global__ __launch_bounds__(256) void moe_gate_kernel(int* __restrict__ topk_id
                                                        int E,
                                                        int k,
                                                        int norm_topk,
-                                                       float routed_scale)
+                                                       float routed_scale,
+                                                       const float* __restrict__ bias)
 {
     __shared__ float part[4][kMaxExperts];
     __shared__ float logit[kMaxExperts];
@@ -65,6 +72,9 @@ __global__ __launch_bounds__(256) void moe_gate_kernel(int* __restrict__ topk_id
     __syncthreads();
     if (threadIdx.x < E) {
         logit[threadIdx.x] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if constexpr (BIAS) {
+            logit[threadIdx.x] += bias[threadIdx.x];
+        }
         if (logits_out) {
             logits_out[(size_t)t * E + threadIdx.x] = logit[threadIdx.x];
         }
@@ -208,7 +218,8 @@ constexpr int kLogitLd  = 260;  // fp32 row stride of the logit tile in LDS: row
 // a lane holds the logits of experts lane, lane + 64, lane + 128, lane + 192 and the k winners come from k wave-wide arg-max rounds.
 // NaN logits (a NaN in x or Wg) are not ordered: no comparison replaces a NaN or takes one, so such a token may list an expert twice;
 // its ids stay in [0, E) and the tables stay consistent (every pair is placed once), its output is NaN through the weights anyway.
-template<int NT>
+// BIAS: as in moe_gate_kernel, added where the accumulators go to the logit tile.
+template<int NT, bool BIAS>
 __global__ __launch_bounds__(256) void moe_gate_wide_kernel(int* __restrict__ topk_ids,      // [T][k]
                                                             float* __restrict__ topk_w,      // [T][k]
                                                             float* __restrict__ logits_out,  // [T][E] or nullptr
@@ -220,7 +231,8 @@ __global__ __launch_bounds__(256) void moe_gate_wide_kernel(int* __restrict__ to
                                                             int E,
                                                             int k,
                                                             int norm_topk,
-                                                            float routed_scale)
+                                                            float routed_scale,
+                                                            const float* __restrict__ bias)
 {
     __shared__ float s_logit[kGateTile][kLogitLd];
     const int        lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -264,9 +276,18 @@ __global__ __launch_bounds__(256) void moe_gate_wide_kernel(int* __restrict__ to
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         if (wave + 4 * i < ntiles) {  // wave-uniform: a wave's last tile may lie past E
+            [[maybe_unused]] float be = 0.f;
+            if constexpr (BIAS) {
+                be = bias[ecol[i]];  // (columns past E read expert 0's: never read back)
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                s_logit[4 * g + r][(wave + 4 * i) * 16 + col] = acc[i][r];
+                if constexpr (BIAS) {
+                    s_logit[4 * g + r][(wave + 4 * i) * 16 + col] = acc[i][r] + be;
+                }
+                else {
+                    s_logit[4 * g + r][(wave + 4 * i) * 16 + col] = acc[i][r];
+                }
             }
         }
     }
@@ -411,6 +432,39 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(half_t* __restrict__ o
     *(half8_t*)(out + (size_t)t * ldo + h) = o;
 }
 
+// The combine of a block whose w2 linears have a bias (gpt-oss; moe_ffn_layer.cc:310-313): the bias of the row's expert is added to the
+// routed row in fp16 first, then moe_combine_kernel's fp32 chain in the order j = 0..k-1:
+//   out[t][h] = fp16( sum_j w[t][j] * f32( h(y[en2f[j][t]][h] + b2[topk_ids[t][j]][h]) ) )
+// The expert of pair (t, j) is topk_ids[t][j] itself, so no flat-row -> expert table is needed and the route kernels stay as they are.
+__global__ __launch_bounds__(256) void moe_combine_bias_kernel(half_t* __restrict__ out, int ldo, const half_t* __restrict__ y, int ldy,
+                                                               const float* __restrict__ topk_w, const int* __restrict__ en2f,
+                                                               const int* __restrict__ topk_ids, const half_t* __restrict__ b2, int T,
+                                                               int H, int k)
+{
+    const int t = blockIdx.y;
+    const int h = (blockIdx.x * 256 + threadIdx.x) * 8;
+    if (h >= H) {
+        return;
+    }
+    float acc[8] = {};
+    for (int j = 0; j < k; ++j) {
+        const int     f = en2f[(size_t)j * T + t];
+        const float   w = topk_w[(size_t)t * k + j];
+        const int     x = topk_ids[(size_t)t * k + j];
+        const half8_t v = *(const half8_t*)(y + (size_t)f * ldy + h) + *(const half8_t*)(b2 + (size_t)x * H + h);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            acc[e] = __builtin_fmaf(w, (float)v[e], acc[e]);
+        }
+    }
+    half8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        o[e] = (half_t)acc[e];
+    }
+    *(half8_t*)(out + (size_t)t * ldo + h) = o;
+}
+
 // The combine of a block with a shared expert (Qwen2-MoE), gate and combine in ONE launch:
 //   logit[t] = sum_h f32(x[t][h]) * f32(g[h]),  sigma = 1 / (1 + expf(-logit))   (expf overflow: 1 / inf = 0, no NaN)
 //   out[t][h] = fp16( fma(w[t][k-1], y[..], ... fma(w[t][0], y[en2f[0][t]][h], f32(shared[t][h]) * sigma)) )
@@ -489,7 +543,7 @@ bool moe_router_wide(int E)
 }
 
 int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_t* x, int ldx, const half_t* wg, int T, int H,
-                    int E, int k, bool norm_topk, float routed_scale, hipStream_t st)
+                    int E, int k, bool norm_topk, float routed_scale, hipStream_t st, const float* bias)
 {
     TM_REQUIRE(E >= 1 && E <= kMaxExpertsWide && k >= 1 && k <= kMaxTopK && k <= E, "moe: 1 <= top_k <= experts <= 256, top_k <= 8");
     if (T == 0) {
@@ -499,8 +553,15 @@ int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_
         TM_REQUIRE(H % 128 == 0 && ldx % 8 == 0, "moe wide router: hidden % 128 == 0 and 16-byte aligned rows of x");
         const dim3 grid((T + kGateTile - 1) / kGateTile);
         const int  nt = ((E + 15) / 16 + 3) / 4;  // column tiles per wave
-#define TM_GATE_WIDE(NT) \
-    moe_gate_wide_kernel<NT><<<grid, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, T, H, E, k, norm_topk ? 1 : 0, routed_scale)
+#define TM_GATE_WIDE(NT)                                                                                                                   \
+    if (bias) {                                                                                                                            \
+        moe_gate_wide_kernel<NT, true><<<grid, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, T, H, E, k, norm_topk ? 1 : 0,    \
+                                                             routed_scale, bias);                                                        \
+    }                                                                                                                                      \
+    else {                                                                                                                                 \
+        moe_gate_wide_kernel<NT, false><<<grid, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, T, H, E, k, norm_topk ? 1 : 0,   \
+                                                              routed_scale, nullptr);                                                    \
+    }
         if (nt == 1) {
             TM_GATE_WIDE(1);
         }
@@ -517,7 +578,12 @@ int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_
         TM_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    moe_gate_kernel<<<T, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, H, E, k, norm_topk ? 1 : 0, routed_scale);
+    if (bias) {
+        moe_gate_kernel<true><<<T, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, H, E, k, norm_topk ? 1 : 0, routed_scale, bias);
+    }
+    else {
+        moe_gate_kernel<false><<<T, 256, 0, st>>>(topk_ids, topk_w, logits_out, x, ldx, wg, H, E, k, norm_topk ? 1 : 0, routed_scale, nullptr);
+    }
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -543,6 +609,19 @@ int launch_moe_combine(half_t* out, int ldo, const half_t* y, int ldy, const flo
         return 0;
     }
     moe_combine_kernel<<<dim3((H / 8 + 255) / 256, T), 256, 0, st>>>(out, ldo, y, ldy, topk_w, en2f, T, H, k);
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_moe_combine_bias(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, const int* topk_ids,
+                            const half_t* b2, int T, int H, int k, hipStream_t st)
+{
+    TM_REQUIRE(H % 8 == 0 && ldo % 8 == 0 && ldy % 8 == 0, "moe combine: H and the row strides % 8 == 0");
+    TM_REQUIRE(topk_ids && b2, "moe combine: the expert ids and the w2 biases");
+    if (T == 0) {
+        return 0;
+    }
+    moe_combine_bias_kernel<<<dim3((H / 8 + 255) / 256, T), 256, 0, st>>>(out, ldo, y, ldy, topk_w, en2f, topk_ids, b2, T, H, k);
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -584,6 +663,13 @@ size_t moe_workspace_bytes(const MoeBlock& m, int tokens)
 int moe_prepare(MoeBlock& m, hipStream_t st)
 {
     TM_REQUIRE((int)m.w13.size() == m.experts && (int)m.w2.size() == m.experts && m.gate, "moe: gate and every expert must be set");
+    const int wt = m.w13[0].type;
+    TM_REQUIRE((m.act == 0 && !m.b13 && !m.b2) || wt == 1 || wt == 3,
+               "moe: the gpt-oss activation and expert biases are built for fp16 and MXFP4 experts only (not u4 / fp8)");
+    TM_REQUIRE(m.act == 0 || m.act == 1, "moe: activation 0 (SiLU) or 1 (gpt-oss)");
+    TM_REQUIRE((m.b13 != nullptr) == (m.b2 != nullptr), "moe: expert biases come for both linears (w1w3 and w2)");
+    TM_REQUIRE(!m.b13 || m.act == 1, "moe: expert biases are built with the gpt-oss activation only");
+    TM_REQUIRE(!m.shared_gate || (!m.b2 && m.act == 0), "moe: a shared expert with the gpt-oss activation or expert biases is not built");
     TM_TRY_RC(moe_build_groups(&m.groups13, m.w13.data(), m.experts, st));
     TM_TRY_RC(moe_build_groups(&m.groups2, m.w2.data(), m.experts, st));
     if (fp8_mfma_supported(m.w13[0]) && fp8_mfma_supported(m.w2[0])) {  // device tables of the experts' P8 unit pointers
@@ -630,7 +716,8 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
     o                  = (o + pairs * m.inter * 2 + 255) / 256 * 256;
     half_t*      y2    = (half_t*)(w + o);
     if (stages & kMoeGate) {
-        TM_TRY_RC(launch_moe_gate(ids, tw, nullptr, x, ldx, m.gate, tokens, m.hidden, m.experts, m.top_k, m.norm_topk, m.routed_scale, st));
+        TM_TRY_RC(launch_moe_gate(ids, tw, nullptr, x, ldx, m.gate, tokens, m.hidden, m.experts, m.top_k, m.norm_topk, m.routed_scale, st,
+                                  m.gate_bias));
     }
     if (stages & kMoeRoute) {
         TM_TRY_RC(launch_moe_route(offs, f2n, en2f, ids, tokens, m.experts, m.top_k, st));
@@ -662,7 +749,8 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
     }
     else {
         if (stages & kMoeW13) {
-            TM_TRY_RC(launch_linear_grouped(m.w13[0], m.groups13, m.experts, x, ldx, tokens, act, m.inter, tokens, hint, true, offs, f2n, st));
+            TM_TRY_RC(launch_linear_grouped(m.w13[0], m.groups13, m.experts, x, ldx, tokens, act, m.inter, tokens, hint, true, offs, f2n, st,
+                                            m.act, m.b13));
         }
         if (stages & kMoeW2) {
             TM_TRY_RC(launch_linear_grouped(m.w2[0], m.groups2, m.experts, act, m.inter, (int)pairs, y2, m.hidden, tokens, hint, false, offs,
@@ -672,6 +760,9 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
     if ((stages & kMoeCombine) && m.shared_gate) {
         TM_TRY_RC(launch_moe_combine_shared(out, ldo, y2, m.hidden, tw, en2f, shared, ldo, x, ldx, m.shared_gate, tokens, m.hidden, m.top_k,
                                             st));
+    }
+    else if ((stages & kMoeCombine) && m.b2) {
+        TM_TRY_RC(launch_moe_combine_bias(out, ldo, y2, m.hidden, tw, en2f, ids, m.b2, tokens, m.hidden, m.top_k, st));
     }
     else if (stages & kMoeCombine) {
         TM_TRY_RC(launch_moe_combine(out, ldo, y2, m.hidden, tw, en2f, tokens, m.hidden, m.top_k, st));
@@ -693,7 +784,8 @@ void moe_free(MoeBlock& m)
     for (auto& l : m.w2) {
         linear_weight_free(l);
     }
-    for (void* q : {(void*)m.gate, (void*)m.shared_gate, m.groups13, m.groups2, m.groups13_p8, m.groups2_p8}) {
+    for (void* q : {(void*)m.gate, (void*)m.shared_gate, m.groups13, m.groups2, m.groups13_p8, m.groups2_p8, (void*)m.gate_bias, (void*)m.b13,
+                    (void*)m.b2}) {
         if (q) {
             (void)hipFree(q);
         }
@@ -701,6 +793,8 @@ void moe_free(MoeBlock& m)
     m.gate = m.shared_gate = nullptr;
     m.groups13 = m.groups2 = nullptr;
     m.groups13_p8 = m.groups2_p8 = nullptr;
+    m.gate_bias = nullptr;
+    m.b13 = m.b2 = nullptr;
 }
 
 }  // namespace tmk

@@ -133,12 +133,13 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 // ---- gemm_w4a16.hip ---------------------------------------------------------------------
 struct LinearWeight {
     int       K = 0, N = 0, group = 128;
-    int       type = 0;          // 0 = u4 (AWQ), 1 = f16 dense, 2 = fp8 e4m3 with 128x128 block scales
+    int       type = 0;          // 0 = u4 (AWQ), 1 = f16 dense, 2 = fp8 e4m3 with 128x128 block scales, 3 = MXFP4 (e2m1 codes, one ue8m0
+                                 // scale byte per 32 k; expert weights only: gemm_mxfp4.hip)
     int       role = 0;          // key of the measured dispatch table next to (K, N, M): 0 = any (operator-level handles, imported
                                  // tables without a role column), 1 w_qkv, 2 wo, 3 w1w3, 4 w2 -- two roles of equal (K, N) are timed
                                  // with DIFFERENT consumers by the tuner and keep separate winners
     void*     packed = nullptr;  // fragment-ordered weights (nullptr for a u4 linear prepared p32_only)
-    uint32_t* sz     = nullptr;  // fragment-ordered (s, -z*s) half2 pairs (u4), (s, 0) (fp8)
+    uint32_t* sz     = nullptr;  // fragment-ordered (s, -z*s) half2 pairs (u4), (s, 0) (fp8), four adjusted scale bytes per k-block (MXFP4)
     size_t    packed_bytes = 0, sz_bytes = 0;
     // u4 only, N % 32 == 0: the decode kernel's layout (gemm_decode.hip, "P32": 2176-byte units of 32 columns x 128 k
     // with their (s, -z*s) pairs); `packed` / `sz` stay the layout of the M > 64 kernels
@@ -330,6 +331,11 @@ struct MoeBlock {
     std::vector<LinearWeight> w13, w2;                 // per expert: gated (gate_j, up_j)-interleaved [H][2I], [I][H]
     void *                    groups13 = nullptr, *groups2 = nullptr;
     void *                    groups13_p8 = nullptr, *groups2_p8 = nullptr;  // fp8 experts: P8 unit pointers (gemm_fp8.hip)
+    // gpt-oss block (all off by default: the block then launches what it always launched); fp16 and MXFP4 experts only
+    int                       act       = 0;        // 0 = SiLU: silu(gate) * up; 1 = gpt-oss: clamped gate * sigmoid(1.702 gate) * (1 + up)
+    float*                    gate_bias = nullptr;  // device fp32 [experts]: added to the router logits before the top-k; owned
+    half_t*                   b13       = nullptr;  // device fp16 [experts][2 * inter], (gate_j, up_j)-interleaved like w13's columns; owned
+    half_t*                   b2        = nullptr;  // device fp16 [experts][hidden]: added per routed row in the combine; owned
 };
 size_t moe_workspace_bytes(const MoeBlock& m, int tokens);
 int    moe_prepare(MoeBlock& m, hipStream_t st);
@@ -339,17 +345,28 @@ int    moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int
 void   moe_free(MoeBlock& m);
 // mixture of experts (moe.hip, grouped GEMM in gemm_w4a16.hip)
 int moe_build_groups(void** d_groups, const LinearWeight* experts, int E, hipStream_t st);
+// act (gated only): 0 = SiLU, 1 = gpt-oss with the optional per-expert bias [E][N]; MXFP4 experts and act 1 run in gemm_mxfp4.hip
 int launch_linear_grouped(const LinearWeight& proto, const void* d_groups, int E, const half_t* x, int ldx, int x_rows,
                           half_t* y, int ldy, int m_cap, int m_hint, bool gated_silu, const int* seg, const int* row_idx,
-                          hipStream_t st);
+                          hipStream_t st, int act = 0, const half_t* bias = nullptr);
+// gemm_mxfp4.hip: MXFP4 expert weights (blocks uint8 [N][K/2], scales uint8 [N][K/32]) and the gpt-oss gated epilogue
+int linear_weight_prepare_mxfp4(LinearWeight& w, const uint8_t* blocks, const uint8_t* scales, hipStream_t st);
+int launch_dequant_mxfp4_f16(half_t* out_kn /*[K][N]*/, const LinearWeight& w, hipStream_t st);  // the operand as the GEMM builds it
+int launch_linear_grouped_mx(const LinearWeight& proto, const void* d_groups, int E, const half_t* x, int ldx, int x_rows, half_t* y,
+                             int ldy, int m_cap, int m_hint, int epilogue /* 0 plain, 1 gated SiLU, 3 gated gpt-oss */,
+                             const half_t* bias, const int* seg, const int* row_idx, hipStream_t st);
+// bias: fp32 [E] added to the logits before the top-k (nullptr: none, the kernels without the add)
 int launch_moe_gate(int* topk_ids, float* topk_w, float* logits_out, const half_t* x, int ldx, const half_t* wg, int T, int H,
-                    int E, int k, bool norm_topk, float routed_scale, hipStream_t st);
+                    int E, int k, bool norm_topk, float routed_scale, hipStream_t st, const float* bias = nullptr);
 // router choice (TM_MOE_ROUTER): mode -1 = the environment's, 0 = auto (serial kernels up to 64 experts), 1 = wide for every E
 void moe_router_override(int mode);
 bool moe_router_wide(int E);
 int launch_moe_route(int* offsets, int* f2n, int* en2f, const int* topk_ids, int T, int E, int k, hipStream_t st);
 int launch_moe_combine(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, int T, int H, int k,
                        hipStream_t st);
+// the same with a per-expert bias of the w2 linear: out[t] = fp16( sum_j w[t][j] * f32( h(y[en2f[j][t]] + b2[topk_ids[t][j]]) ) )
+int launch_moe_combine_bias(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, const int* topk_ids,
+                            const half_t* b2, int T, int H, int k, hipStream_t st);
 // the same with a shared expert: out = fp16(f32(shared) * sigmoid(x . gate) + the routed sum); out may alias shared
 int launch_moe_combine_shared(half_t* out, int ldo, const half_t* y, int ldy, const float* topk_w, const int* en2f, const half_t* shared,
                               int lds, const half_t* x, int ldx, const half_t* gate, int T, int H, int k, hipStream_t st);

@@ -179,7 +179,10 @@ class TurbomindEngineConfig:
     Models: the attention path serves head_dim 128 and, through the Llama reader (Llama-3.2-1B, TinyLlama, SmolLM2: fp16 / bf16 or
     model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' needs head_dim 128.  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
-    on the VALU attention kernel for every quant_policy, and KV blocks older than the window stay allocated."""
+    on the VALU attention kernel for every quant_policy, and KV blocks older than the window stay allocated.
+    The gpt-oss MoE block -- MXFP4 experts (e2m1 codes, one ue8m0 scale byte per 32 weights), router and per-expert biases, the clamped
+    gate * sigmoid(1.702 gate) * (1 + up) activation -- is served with tp = 1 (`synthetic:tiny_gptoss_moe` with model_format='hf' runs
+    it); a published gpt-oss checkpoint is not loadable yet (hidden 2880 is no multiple of 128, no o_proj bias)."""
     dtype: str = 'auto'
     model_format: str | None = None
     tp: int = 1

@@ -36,6 +36,11 @@ SYNTHETIC = {
     # a mixture-of-experts twin of `tiny`: 8 experts of width 128, top-2 (u4, fp8 or -- model_format='hf' -- fp16 experts)
     'tiny_moe': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=128, vocab=1024,
                      rope=checkpoint.RopeConfig(128, 10000.0), moe_experts=8, moe_top_k=2),
+    # the gpt-oss MoE block on tiny_moe's geometry: MXFP4 experts with biases, a router bias and the clamped activation, next to
+    # attention linears of the chosen model_format (gpt-oss itself: model_format='hf', fp16 attention)
+    'tiny_gptoss_moe': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=128, vocab=1024,
+                            rope=checkpoint.RopeConfig(128, 10000.0), moe_experts=8, moe_top_k=2, moe_expert_format=3, moe_act=1,
+                            moe_bias=1),
 }
 
 

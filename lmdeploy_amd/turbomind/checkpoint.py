@@ -70,6 +70,9 @@ class ModelConfig:
     moe_shared_inter: int = 0          # Qwen2-MoE: width of the shared expert (a dense FFN behind a sigmoid gate in every MoE layer)
     tie_word_embeddings: bool = False
     window: int = 0                    # Mistral / Mixtral `sliding_window`: a query sees the last `window` keys (0 = all)
+    moe_expert_format: int = 0         # 0: the experts follow weight_format; 3: MXFP4 experts (gpt-oss) next to fp16 / u4 attention
+    moe_act: int = 0                   # 0: silu(gate) * up; 1: gpt-oss, clamped gate * sigmoid(1.702 gate) * (1 + up)
+    moe_bias: int = 0                  # gpt-oss: router bias [E] and per-expert biases on w1w3 / w2
 
 
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
@@ -135,6 +138,12 @@ def read_config(model_path: str) -> ModelConfig:
     with open(os.path.join(model_path, 'config.json')) as f:
         c = json.load(f)
     arch = (c.get('architectures') or ['LlamaForCausalLM'])[0]
+    if arch == 'GptOssForCausalLM':
+        # the MoE block is served (MXFP4 experts, router / expert biases, the clamped activation: gpt_oss_expert_slots maps the
+        # published tensors), as are sliding windows, sinks and YaRN.  What a published checkpoint still needs:
+        raise NotImplementedError(f'{arch}: not loadable yet -- hidden_size {c.get("hidden_size")} % 128 != 0 is not served (every '
+                                  f'GEMM, norm and router takes K % 128 == 0; gpt-oss has 2880 = 22.5 x 128) and the o_proj bias is '
+                                  f'not implemented')
     kind = 'internlm2' if 'InternLM2' in arch else 'llama'
     qwen = arch in QWEN_ARCHS
     internlm3 = arch == 'InternLM3ForCausalLM'      # a plain Llama (the reference: supported_models.py) -- without projection biases
@@ -222,6 +231,40 @@ def read_config(model_path: str) -> ModelConfig:
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
                        max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, **moe,
                        attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
+
+
+def gpt_oss_expert_slots(tensors: dict, layer: int) -> dict:
+    """The MoE block of layer `layer` of a published gpt-oss checkpoint -> this engine's weight slots (a pure function of numpy arrays).
+    tensors (names as published, transformers' GptOssExperts under the MXFP4 integration):
+      model.layers.{i}.mlp.experts.gate_up_proj_blocks uint8 [E, 2I, H/32, 16]   16 bytes = 32 e2m1 codes, low nibble = even k
+      ...gate_up_proj_scales uint8 [E, 2I, H/32]      ...gate_up_proj_bias [E, 2I]     rows (gate_j, up_j)-interleaved, even = gate:
+                                                                                        this engine's w1w3 column order as published
+      ...down_proj_blocks uint8 [E, H, I/32, 16]      ...down_proj_scales [E, H, I/32] ...down_proj_bias [E, H]
+      model.layers.{i}.mlp.router.weight [E, H]       ...router.bias [E]
+    Blocks and scales keep their bytes: [N, K/32, 16] is [N, K/2] row-major, the layout tm_moe_set_expert takes."""
+    m = f'model.layers.{layer}.mlp'
+    gu_b, gu_s, gu_bias = (np.asarray(tensors[f'{m}.experts.gate_up_proj_{n}']) for n in ('blocks', 'scales', 'bias'))
+    dn_b, dn_s, dn_bias = (np.asarray(tensors[f'{m}.experts.down_proj_{n}']) for n in ('blocks', 'scales', 'bias'))
+    rw, rb = np.asarray(tensors[f'{m}.router.weight']), np.asarray(tensors[f'{m}.router.bias'])
+    E, N13, G, sixteen = gu_b.shape
+    H, I = G * 32, N13 // 2
+    if gu_b.dtype != np.uint8 or gu_s.dtype != np.uint8 or dn_b.dtype != np.uint8 or dn_s.dtype != np.uint8 or sixteen != 16:
+        raise ValueError(f'{m}.experts: blocks / scales must be uint8 with 16-byte blocks')
+    if gu_s.shape != (E, N13, G) or gu_bias.shape != (E, N13) or dn_b.shape != (E, H, I // 32, 16) or dn_s.shape != (E, H, I // 32) \
+            or dn_bias.shape != (E, H) or rw.shape != (E, H) or rb.shape != (E,) or N13 % 2 or I % 32:
+        raise ValueError(f'{m}: tensor shapes do not describe {E} experts of hidden {H}, width {I}')
+    p = f'layers.{layer}.moe_ffn'
+    slots = {p + '.gate.weight': np.ascontiguousarray(rw.astype(np.float16).T),
+             p + '.gate.bias': np.ascontiguousarray(rb, dtype=np.float32)}
+    for x in range(E):
+        q = f'{p}.experts.{x}'
+        slots[q + '.w1w3.blocks'] = np.ascontiguousarray(gu_b[x].reshape(N13, H // 2))
+        slots[q + '.w1w3.scales'] = np.ascontiguousarray(gu_s[x])
+        slots[q + '.w1w3.bias'] = np.ascontiguousarray(gu_bias[x], dtype=np.float16)
+        slots[q + '.w2.blocks'] = np.ascontiguousarray(dn_b[x].reshape(H, I // 2))
+        slots[q + '.w2.scales'] = np.ascontiguousarray(dn_s[x])
+        slots[q + '.w2.bias'] = np.ascontiguousarray(dn_bias[x], dtype=np.float16)
+    return slots
 
 
 class _Tensors:

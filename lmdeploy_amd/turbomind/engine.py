@@ -20,7 +20,8 @@ _ROPE_TYPES = {'default': 0, 'linear': 1, 'llama3': 2, 'yarn': 3, 'dynamic': 4}
 def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     """cfg: any object with hidden, layers, q_heads, kv_heads, head_dim, inter, vocab, rms_eps, rope(.dim,.base,.type,
     .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings; optional .max_position_embeddings, .beta_fast,
-    .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert), attn_bias,
+    .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert;
+    moe_expert_format 3 = MXFP4 experts, moe_act 1 = the gpt-oss activation, moe_bias = router and expert biases), attn_bias,
     qk_norm, window (sliding window of every layer, 0 = none), attn_sinks."""
     r = cfg.rope
     return _ffi.ModelConfig(cfg.hidden, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, cfg.inter, cfg.vocab,
@@ -30,6 +31,8 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
                             float(getattr(r, 'attention_factor', 1.0)), cfg.group, weight_type,
                             int(getattr(cfg, 'moe_experts', 0) or 0), int(getattr(cfg, 'moe_top_k', 0) or 0),
                             int(bool(getattr(cfg, 'moe_norm_topk', True))), float(getattr(cfg, 'moe_routed_scale', 1.0)),
+                            int(getattr(cfg, 'moe_expert_format', 0) or 0), int(getattr(cfg, 'moe_act', 0) or 0),
+                            int(bool(getattr(cfg, 'moe_bias', 0))),
                             int(getattr(cfg, 'moe_shared_inter', 0) or 0),
                             int(getattr(cfg, 'window', 0) or 0), int(bool(getattr(cfg, 'attn_sinks', 0))),
                             int(bool(getattr(cfg, 'attn_bias', 0))), int(bool(getattr(cfg, 'qk_norm', 0))))

@@ -87,7 +87,10 @@ def _shard_linear(lin: dict, kind: str, tp: int, rank: int, group: int, col_slic
 
 
 def _emit(slots: dict, prefix: str, lin: dict):
-    if 'q' in lin:
+    if 'blocks' in lin:      # MXFP4 experts in the checkpoint layout: e2m1 codes [N, K/2] + ue8m0 scale bytes [N, K/32]
+        slots[prefix + '.blocks'] = np.ascontiguousarray(lin['blocks'], dtype=np.uint8)
+        slots[prefix + '.scales'] = np.ascontiguousarray(lin['scales'], dtype=np.uint8)
+    elif 'q' in lin:
         slots[prefix + '.qweight'] = np.ascontiguousarray(pack_u4_row(lin['q']))
         slots[prefix + '.scales'] = np.ascontiguousarray(lin['s'], dtype=np.float16)
         slots[prefix + '.zeros'] = np.ascontiguousarray(lin['z'], dtype=np.float16)
@@ -104,6 +107,9 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     w1w3 already (gate_j, up_j)-interleaved; Qwen layers add 'qkv_bias' [Hq*D + 2*Hkv*D] (q / k permuted like w_qkv) and /
     or 'q_norm', 'k_norm' [D]; layers with attention sinks add 'sinks' [Hq]; MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
     all of them: w1w3 / w2 are then the shared expert (width cfg.moe_shared_inter) next to its 'shared_gate' [H].
+    gpt-oss blocks: an MXFP4 expert linear is {'blocks' uint8 [N, K/2], 'scales' uint8 [N, K/32]} (output-major, the checkpoint
+    layout; w1w3's N rows (gate_j, up_j)-interleaved); with cfg.moe_bias every expert carries 'w1w3_bias' [2I] and 'w2_bias' [H] and the
+    layer 'moe_gate_bias' [E] (fp32).  Neither shards: tp must be 1.
     Returns {slot name: contiguous numpy array} for this rank."""
     D = cfg.head_dim
     Hq, Hkv, I, G = cfg.q_heads, cfg.kv_heads, cfg.inter, cfg.group
@@ -136,6 +142,12 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
                 raise ValueError(f'shared expert of width {S} does not shard over tp = {tp}: {S} / {tp} = {S / tp:g} is not a multiple '
                                  f'of 128')
             slots[p + '.moe_ffn.gate.weight'] = np.ascontiguousarray(L['moe_gate'], dtype=np.float16)
+            bias = bool(getattr(cfg, 'moe_bias', 0))
+            mx = any('blocks' in E_[k] for E_ in L['experts'] for k in ('w1w3', 'w2'))
+            if tp > 1 and (bias or mx):
+                raise ValueError(f'MXFP4 experts / expert biases do not shard over tp = {tp}: the w2 bias would need a per-rank rule')
+            if bias:
+                slots[p + '.moe_ffn.gate.bias'] = np.ascontiguousarray(L['moe_gate_bias'], dtype=np.float32)
             if S:              # Qwen2-MoE: the shared expert sharded like the dense FFN, its gate vector replicated
                 _emit(slots, p + '.feed_forward.w1w3',
                       _shard_linear(L['w1w3'], 'col', tp, rank, G, [(2 * rank * s_l, 2 * (rank + 1) * s_l)]))
@@ -143,6 +155,13 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
                 slots[p + '.moe_ffn.shared_gate.weight'] = np.ascontiguousarray(L['shared_gate'], dtype=np.float16)
             for x, E_ in enumerate(L['experts']):
                 q = f'{p}.moe_ffn.experts.{x}'
+                if bias:
+                    slots[q + '.w1w3.bias'] = np.ascontiguousarray(E_['w1w3_bias'], dtype=np.float16)
+                    slots[q + '.w2.bias'] = np.ascontiguousarray(E_['w2_bias'], dtype=np.float16)
+                if mx:     # output-major byte images: nothing to slice (tp == 1)
+                    _emit(slots, q + '.w1w3', E_['w1w3'])
+                    _emit(slots, q + '.w2', E_['w2'])
+                    continue
                 _emit(slots, q + '.w1w3', _shard_linear(E_['w1w3'], 'col', tp, rank, G, [(2 * rank * i_l, 2 * (rank + 1) * i_l)]))
                 _emit(slots, q + '.w2', _shard_linear(E_['w2'], 'row', tp, rank, G))
         else:
