@@ -31,7 +31,18 @@ Every q head of a GQA group has its own (gate, weight) channel pair, the channel
 prefill the pair also rotates with the query row.  Decode live sets are placed on purpose (_pattern); the slots of the newest block
 behind the context hold rows that LOOK live for every head (a mask that lets one in adds a whole token).  Prefill row i (position
 hist + i) has hist + i and hist + i + 1 live in its pair -- a diagonal off by one in either direction adds or removes a token --
-and live tokens at the 32-key and 64-key boundaries and in the history."""
+and live tokens at the 32-key and 64-key boundaries and in the history.
+
+Window and sinks (build_window; the cases above keep their argument tuples, hence their seeds, operands and bits).  A token is
+visible from max(ctx - W, 0) on.  In decode the window's first token and the newest one are live for every head and the token in
+front of the window looks live (tier B: with the top weight); prefill row at position p has p - W look-alive and p - W + 1 live in
+its pair.  The kernels add exp2(f32(sink) * 1.4426950408889634f - m * scale_log2) to the denominator, m the maximum of the raw
+scores: exact, contracted or not, for a sink of +0, -0, -inf or -65504, or where m * scale_log2 is an integer.  With live scores
+near 8192 a sink of 0 would be nothing, so q gets a third non-zero channel, the one where every K row holds the pinned minimum `lo`:
+every score moves by q_off * lo, relative weights and every assertion stay, and the live maximum sits at exponent 0 (tier A) or
+EXP_B - j (tier B).  Heads take the four sink values in turn; the reference adds the sink's weight 2^(8 - e_s) to the denominator
+only, and V is settled with it in place.  Assertion 7 for these cases is tests/attention_window_reference.py (float64 over the
+cropped context, the sink an extra column)."""
 import functools
 import zlib
 from dataclasses import dataclass, field
@@ -100,6 +111,9 @@ class Case:
     Hkv: int
     tier: str
     seqs: list = field(default_factory=list)
+    window: int = 0          # sliding window (0 = none): the query at position p sees the keys t with 0 <= p - t < window
+    sinks: np.ndarray = None  # fp16 [Hq] sink logits (None = no sinks)
+    q_off: int = 0           # q's value in the channel where every K row holds `lo` (0 = no offset channel, the cases without window)
 
     @property
     def lat(self):
@@ -127,8 +141,38 @@ def _units(case, s, hd):
     return Kq, Vu, vs, vz
 
 
+def _wlo_of(case, ctx):
+    """first visible token of every query row [R]: max(ctx - window, 0), which is decode's wbeg and the prefill row's p - W + 1"""
+    return np.maximum(ctx - case.window, 0) if case.window else np.zeros_like(ctx)
+
+
+def window_splits(n, window, splits, tile=32):
+    """the token ranges of the non-empty splits of the windowed decode kernel: the tiles from the one the window starts in to the
+    newest, ceil(tiles / splits) to a split"""
+    wbeg = max(n - window, 0) if window else 0
+    tlo, tend = wbeg // tile, (n + tile - 1) // tile
+    per = (tend - tlo + splits - 1) // splits
+    out = [(max((tlo + i * per) * tile, wbeg), min((tlo + (i + 1) * per) * tile, n)) for i in range(splits)]
+    return [(a, b) for a, b in out if b > a]
+
+
+def _sink_weight(case, smax, sinks, check):
+    """integer weight 2^(8 - e_s) of the sink of every query column, e_s = m * scale_log2 - sink * log2(e): what the kernels add to
+    the denominator, exp2(f32(sink) * 1.4426950408889634f - m * scale_log2), in the unit of _weights"""
+    mc = smax.astype(f64) * (case.lat.step * float(scale_log2(case.tier, case.D)))
+    sk = sinks.astype(f64)
+    with np.errstate(over='ignore', under='ignore'):
+        ws = np.exp2(JMAX + sk * float(LOG2E) - mc)
+    if check:                                                  # exact whether or not the expression is contracted into an fma
+        assert (np.isin(sk, (0.0, -65504.0)) | np.isneginf(sk)).all(), 'sink logits: +0, -0, -inf, -65504'
+        assert (mc == np.rint(mc)).all() and (case.tier == 'B' or not mc.any()), 'the maximum times scale_log2 must be an integer'
+        assert (ws[sk != 0] == 0).all() and (np.abs(mc) <= JMAX).all()
+    return ws
+
+
 def _weights(case, S, vis, check):
-    """S int64 [n, C] scores in K steps, vis bool [n, C] -> (integer weights 2^(8 - j) [n, C], exponents e [n, C], dead [n, C])"""
+    """S int64 [n, C] scores in K steps, vis bool [n, C] -> (integer weights 2^(8 - j) [n, C], exponents e [n, C], dead [n, C],
+    the visible maximum [C])"""
     lat, c = case.lat, float(scale_log2(case.tier, case.D))
     smax = np.where(vis, S, np.iinfo(np.int64).min // 2).max(0)
     e = (smax[None] - S).astype(f64) * (lat.step * c)
@@ -144,7 +188,7 @@ def _weights(case, S, vis, check):
             m = (smax * lat.step).astype(f32)
             assert ((m * f32(c)).astype(f64) == m.astype(f64) * c).all(), 'tier A: the live score must be a power of two'
     w = np.where(live, np.exp2(JMAX - np.where(live, e, 0.0)), 0.0)
-    return w, e, dead
+    return w, e, dead, smax
 
 
 def _round(N, Dn, A, vlsb):
@@ -181,7 +225,16 @@ def reference(case, s, mut=None, check=False, detail=False):
     R = s.q.shape[0]
     name, arg = mut if mut else (None, None)
     ctx = _ctx_of(case, s)
+    wlo = _wlo_of(case, ctx)
     nalloc = s.K.shape[1]
+    if name == 'win_shift':                                   # -1: let in the token in front of the window; +1: drop its first token
+        sh = wlo + arg
+        wlo = np.where((case.window > 0) & (ctx > case.window) & (sh < ctx), sh, wlo)
+    if name == 'wave_edge':                                   # prefill: every row masked with the lower edge of its wave's first row
+        wlo = wlo[np.arange(R) // 16 * 16]
+    sinks = case.sinks
+    if sinks is not None and name == 'next_sink':             # head h counts head h + 1's sink
+        sinks = np.roll(sinks, -1)
     if name == 'ctx_shift':                                   # -1: drop the newest visible token; +1: let in the one behind it
         sh = ctx + arg
         ok = (sh >= 1) & (sh <= nalloc)
@@ -197,8 +250,8 @@ def reference(case, s, mut=None, check=False, detail=False):
         if name == 'next_head':                               # head h computes with head h + 1's q (its live set)
             qh = np.roll(qh, -1, axis=1)
         S = Kq @ qh.reshape(R * G, -1).T                      # [nalloc, R * G]
-        vis = t[:, None] < np.repeat(ctx, G)[None, :]
-        w, e, dead = _weights(case, S, vis, check)
+        vis = (t[:, None] < np.repeat(ctx, G)[None, :]) & (t[:, None] >= np.repeat(wlo, G)[None, :])
+        w, e, dead, smax = _weights(case, S, vis, check)
         if name == 'tile_factor':                             # arg = (first token, end token, factor): a tile dropped or counted twice
             w = w * np.where((t >= arg[0]) & (t < arg[1]), arg[2], 1.0)[:, None]
         if name == 'dead_weight':                             # a dead token leaks 2^-20
@@ -208,12 +261,24 @@ def reference(case, s, mut=None, check=False, detail=False):
             vs2, vz2 = np.roll(vs, -1), np.roll(vz, -1)
             Vu = (code * vs2[:, None] + vz2[:, None]) / lat.vlsb
         if name == 'skip_rescale':
-            N, Dn = _walk(case, S, vis, Vu.astype(f64), arg)
+            N, Dn, skipped = _walk(case, S, vis, Vu.astype(f64), arg)
             A = np.abs(N)
+            extra['skipped'] = extra.get('skipped', False) or bool(skipped.any())     # whether the error had a place to happen
         else:
             N, Dn, A = w.T @ Vu.astype(f64), w.sum(0), w.T @ np.abs(Vu).astype(f64)
+        ws = None
+        if sinks is not None and name != 'no_sink':           # the sink joins the denominator alone: nothing for N or A
+            ws = _sink_weight(case, smax, np.tile(sinks[hd * G:(hd + 1) * G], R), check)
+            if name == 'sink_per_split':                      # arg = splits: once per non-empty split instead of once
+                ws = ws * len(window_splits(s.n, case.window, arg))
+            if name == 'sink_split_max':                      # arg = splits: against the lowest maximum of a split, not the merged one
+                low = np.min([S[a:b].max(0) for a, b in window_splits(s.n, case.window, arg)], 0)     # all of [a, b) is visible
+                ws = _sink_weight(case, low, np.tile(sinks[hd * G:(hd + 1) * G], R), False)
+            Dn = Dn + ws * (2.0**-JMAX if name == 'skip_rescale' else 1.0)      # _walk's unit is the maximum's weight
         if check:                                             # assertion 5: every partial sum in every order is an fp32 number
             lsb = np.where(w > 0, w, np.inf).min(0)           # the smallest weight of every query
+            if ws is not None:
+                lsb = np.minimum(lsb, np.where(ws > 0, ws, np.inf))
             assert ((w.T @ (np.abs(Vu) + np.abs(vz / lat.vlsb)[:, None])) / lsb[:, None]).max() <= BUDGET and (Dn / lsb).max() < 2.0**24
         b_, s_, g_ = _round(N, Dn, A, lat.vlsb)
         bits[:, hd * G:(hd + 1) * G] = b_.reshape(R, G, -1)
@@ -244,7 +309,7 @@ def _walk(case, S, vis, Vu, direction):
         N = N * alpha[:, None] + p.T @ Vu[a:a + 64]
         Dn = Dn * alpha + p.sum(0)
         m = mnew
-    return N, Dn
+    return N, Dn, skipped
 
 
 # ---- operands -------------------------------------------------------------------------------------------------------------------
@@ -283,7 +348,7 @@ BOUNDARY = (0, 31, 32, 63, 64, 95, 96, 127, 128)
 
 def _build_seq(case, rng, n, R, hist):
     """one sequence: q [R, Hq, D], K / V [Hkv, nalloc, D]"""
-    lat, D, Hkv, G, tier = case.lat, case.D, case.Hkv, case.Hq // case.Hkv, case.tier
+    lat, D, Hkv, G, tier, W = case.lat, case.D, case.Hkv, case.Hq // case.Hkv, case.tier, case.window
     decode = case.kind == 'decode'
     nalloc = (n + 63) // 64 * 64 if decode else n
     P = (D - 2) // 2                                          # (gate, weight) channel pairs; two channels pin the K row's range
@@ -298,9 +363,15 @@ def _build_seq(case, rng, n, R, hist):
         kcode[hd, :, perm[D - 1]] = lat.ncode
         kcode[hd][:, gate] = 0                                # everybody dead ...
         live = [set() for _ in range(P)]
+        look = [set() for _ in range(P)]                      # window: the token in front of the lower edge LOOKS live
+        q[:, hd * G:(hd + 1) * G, perm[D - 2]] = case.q_off   # the offset channel: K holds `lo` there for every token
         if decode:
+            wbeg = max(n - W, 0) if W else 0
             for hg in range(G):
-                live[hg] = set(_pattern(rng, (hg + hd * G + n) % N_PATTERNS, n))
+                live[hg] = set(_pattern(rng, (hg + hd * G + n) % N_PATTERNS, n))    # those in front of the window look live only
+                if W:
+                    live[hg].update((wbeg, n - 1))
+                    look[hg].update(t for t in (wbeg - 1,) if t >= 0)
                 q[0, hd * G + hg, gate[hg]] = QG
                 q[0, hd * G + hg, wch[hg]] = lat.q_w(tier)
         else:
@@ -308,6 +379,9 @@ def _build_seq(case, rng, n, R, hist):
                 for hg in range(G):
                     p = (i * G + hg) % P
                     live[p].update(t for t in (hist + i, hist + i + 1) if t < n)
+                    if W:
+                        live[p].update(t for t in (hist + i - W + 1,) if t >= 0)
+                        look[p].update(t for t in (hist + i - W,) if t >= 0)
                     q[i, hd * G + hg, gate[p]] = QG
                     q[i, hd * G + hg, wch[p]] = lat.q_w(tier)
             cand = sorted({t for t in BOUNDARY + (hist - 1, hist, n - 1) if 0 <= t < n})
@@ -318,6 +392,11 @@ def _build_seq(case, rng, n, R, hist):
             if len(ts):
                 kcode[hd, ts, gate[p]] = lat.ncode
                 kcode[hd, ts, wch[p]] = c0 + 1 if tier == 'A' else c0 - rng.integers(0, JMAX + 1, len(ts))
+        for p in range(P):                                    # in tier B with the top weight
+            ts = np.array(sorted(look[p]), np.int64)
+            if len(ts):
+                kcode[hd, ts, gate[p]] = lat.ncode
+                kcode[hd, ts, wch[p]] = c0 + 1 if tier == 'A' else c0
         kcode[hd, n:, :][:, gate] = lat.ncode                 # behind the context: rows that look live to every head
         kcode[hd, n:, :][:, wch] = c0 + 1 if tier == 'A' else c0
     K = (lat.lo + lat.step * kcode).astype(f16)
@@ -356,6 +435,12 @@ def _settle(case, s):
             ts = [t for t in np.flatnonzero(extra[hd][0][:, r * G + h % G]) if d not in s.vpins[hd, t]]
             if ts:
                 s.vcode[hd, ts[rng.integers(len(ts))], d] = rng.integers(1, lat.ncode)
+            else:                                             # every live token is pinned there: one of them gets its pin elsewhere
+                live = np.flatnonzero(extra[hd][0][:, r * G + h % G])
+                t = live[rng.integers(len(live))]
+                d2 = int(rng.choice([x for x in range(case.D) if x not in s.vpins[hd, t]]))
+                s.vcode[hd, t, [d, d2]] = s.vcode[hd, t, [d2, d]]
+                s.vpins[hd, t][s.vpins[hd, t] == d] = d2
         _set_v(case, s)
     raise AssertionError('the outputs do not settle away from the fp16 rounding boundaries')
 
@@ -380,6 +465,17 @@ def _assert_oracle(case, s):
     o.prefill_attention -- rounds to the bits of the integer computation"""
     scale = None if case.tier == 'A' else float(SCALE_B)
     n = s.n
+    if case.q_off:                                            # window / sinks: float64 over the cropped context, the sink an extra column
+        from tests.attention_window_reference import window_decode, window_prefill
+        if case.kind == 'decode':
+            ref = window_decode(s.q[0], s.K[:, :n], s.V[:, :n], case.window, scale, case.sinks)[None]
+        else:
+            ref = window_prefill(s.q, s.K, s.V, s.hist, case.window, scale, case.sinks)
+        assert not np.isnan(ref).any()
+        ref = ref.view(np.uint16).copy()
+        ref[ref == 0x8000] = 0
+        assert np.array_equal(ref[s.good], s.bits[s.good]) and ulp16(ref, s.bits)[~s.good].max(initial=0) <= 1, case
+        return
     for i in range(s.q.shape[0]):
         ctx = n if case.kind == 'decode' else s.hist + i + 1
         ref = o.attention_reference_unfused(s.q[i], s.K[:, :ctx], s.V[:, :ctx], scale).astype(f16).view(np.uint16).copy()
@@ -395,8 +491,32 @@ def _assert_oracle(case, s):
 @functools.lru_cache(maxsize=None)
 def build(kind, bits, D, Hq, Hkv, tier, shape):
     """shape: decode -> tuple of context lengths; prefill -> (qlens, hist).  Every assertion of the module docstring is made here."""
-    case = Case(kind, bits, D, Hq, Hkv, tier)
-    seed = zlib.crc32(repr((kind, bits, D, Hq, Hkv, tier, shape)).encode())
+    return _build(Case(kind, bits, D, Hq, Hkv, tier), (kind, bits, D, Hq, Hkv, tier, shape))
+
+
+SINK_VALUES = (0.0, -np.inf, -0.0, -65504.0)                  # by head, in turn: neighbouring heads differ by a whole unit of weight
+EXP_B = 3                                                     # tier B: the top live weight sits at exponent 3, the sink (logit 0) at 0
+
+
+@functools.lru_cache(maxsize=None)
+def build_window(kind, bits, D, Hq, Hkv, tier, shape, window, with_sinks):
+    """the same with a sliding window (0 = none), sinks (SINK_VALUES by head) and the offset channel: q holds q_off where every K row
+    holds `lo`, so that the live maximum times scale_log2 is 0 (tier A) or a small integer (tier B, EXP_B for the top weight) and a
+    sink logit of 0 is a weight among the live ones"""
+    lat = Lattice(bits)
+    sinks = np.array([SINK_VALUES[(h + window) % 4] for h in range(Hq)], f16) if with_sinks else None
+    if tier == 'A':
+        q_off = QG * (lat.hi + lat.step) / -lat.lo            # the live score QG * (hi + step) becomes 0
+    else:
+        q_off = (QG * lat.hi - 32 * EXP_B) / -lat.lo          # the score of a live token with weight 2^0 becomes 32 * EXP_B
+    assert q_off == int(q_off) and f16(q_off) == q_off
+    case = Case(kind, bits, D, Hq, Hkv, tier, window=window, sinks=sinks, q_off=int(q_off))
+    return _build(case, (kind, bits, D, Hq, Hkv, tier, shape, window, with_sinks))
+
+
+def _build(case, args):
+    kind, shape = case.kind, args[6]
+    seed = zlib.crc32(repr(args).encode())
     rng = np.random.default_rng(seed)
     todo = [(n, 1, n - 1) for n in shape] if kind == 'decode' else [(h + n, n, h) for n, h in zip(*shape)]
     total = loose = 0
@@ -421,6 +541,50 @@ def decode_case(bits, D, group, tier, klen=KLEN_DECODE):
 
 def prefill_case(D, group, tier, shape):
     return build('prefill', 16, D, group * 2, 2, tier, shape)
+
+
+KLEN_WINDOW = (1, 31, 33, 64, 65, 97, 129, 200, 330, 1089)
+WINDOWS_DECODE = (1, 32, 33, 64, 100, 4096)
+GROUPS_WINDOW = (1, 2, 3, 4, 7, 8)                            # heads per workgroup 1, 2, 3, 4, seven chunks of 1, two chunks of 4
+WINDOWS_PREFILL = (1, 16, 17, 32, 33, 64, 65, 100, 4096)
+
+
+def decode_window_case(bits, D, group, tier, window, with_sinks, klen=KLEN_WINDOW):
+    return build_window('decode', bits, D, group * 2, 2, tier, tuple(klen), window, bool(with_sinks))
+
+
+def prefill_window_case(D, group, tier, shape, window, with_sinks):
+    return build_window('prefill', 16, D, group * 2, 2, tier, shape, window, bool(with_sinks))
+
+
+CONTROL_WINDOW = 33
+KLEN_CONTROL = (64, 65, 97, 129, 200, 330)                    # every context longer than CONTROL_WINDOW + 1
+
+
+def control_case():
+    """the device's negative controls: every window starts inside its context (first tokens 31, 32, 64, 96, 167, 297), so a launch
+    with W + 1 lets in a token that looks live and one with W - 1 drops a live one in every sequence; launched without its sinks it
+    loses a unit of weight in every other head"""
+    return decode_window_case(8, 128, 4, 'B', CONTROL_WINDOW, True, KLEN_CONTROL)
+
+
+def decode_window_cases():
+    """thinned: every window in both tiers with every (head_dim, bits); groups and sinks rotate so that every (head_dim, bits) meets
+    every group, and every window and every group meet sinks off and on"""
+    for di, D in enumerate((128, 64)):
+        for bi, bits in enumerate((8, 4, 16)):
+            for wi, W in enumerate(WINDOWS_DECODE):
+                for ti, tier in enumerate('AB'):
+                    yield bits, D, GROUPS_WINDOW[(wi + 3 * ti + bi + di) % 6], tier, W, (wi // 2 + ti + di) % 2
+
+
+def prefill_window_cases():
+    """thinned: every window with every batch shape at every head_dim; tiers, groups and sinks rotate so that every window meets both
+    tiers and sinks off and on"""
+    for di, D in enumerate((128, 64)):
+        for wi, W in enumerate(WINDOWS_PREFILL):
+            for si, shape in enumerate(PREFILL_SHAPES):
+                yield D, GROUPS_PREFILL[(wi + 2 * si + di) % 5], 'AB'[(wi + si + di) % 2], shape, W, (wi + di + (si + 1) // 2) % 2
 
 
 def decode_cases():
