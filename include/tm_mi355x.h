@@ -129,6 +129,14 @@ int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int*
  * cu_k_off[b] (device; must be 64-aligned when transposing). */
 int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
                   int max_k_len, int k_stride, const tm_kv_cache* cache, tm_stream_t st);
+/* tm_flatten_kv in front of tm_prefill_attention_window: cu_q_len (device, [batch + 1]) are the query rows of the forward, so
+ * sequence b has hist = k_len[b] - q_len[b] cached tokens in front of them.  Every 64-token tile with
+ * t0 + 64 <= max(hist - window + 1, 0) is skipped: its cache block is not read and its part of k_out / v_out is left UNWRITTEN
+ * (nothing is zero-filled) -- the windowed prefill kernel starts its key loop at floor64(max(hist - window + 1, 0)) and never
+ * stages those keys.  Every other tile holds tm_flatten_kv's bytes.  window == 0 is tm_flatten_kv, bit for bit (cu_q_len may
+ * be NULL then); window < 0: TM_INVALID. */
+int tm_flatten_kv_window(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
+                         int max_k_len, int k_stride, const tm_kv_cache* cache, const int* cu_q_len, int window, tm_stream_t st);
 
 /* Paged flash-decode, one query token per sequence (dispatchDecoding).  q fp16 [batch][q_stride] already
  * rotated (head h at h*head_dim), out fp16 [batch][q_heads*head_dim], head_dim = cache->head_dim (64 or 128).  splits >= 1;
@@ -534,6 +542,11 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* cfg);
 /* after tm_engine_start: *per_seq_tables = 1 when the engine keeps one RoPE table region per batch slot behind the shared one
  * (rope_type 4 with rope_factor > 1 and session_len > rope_max_position_embeddings), *table_bytes = bytes of those regions (0 without) */
 int tm_engine_rope_info(tm_engine* e, int* per_seq_tables, int64_t* table_bytes);
+/* after tm_engine_start: *ring_blocks = the KV block ring of a sequence (0: no ring -- a layer without a window, a ring that would
+ * not be shorter than ceil(session_len / 64), or TM_KV_RING=0), *free_blocks = blocks of the pool that no sequence owns right now
+ * (the scheduler's count while a continuous-batching session is open; its parking block is neither free nor owned).
+ * TM_CONFLICT while the engine thread runs. */
+int tm_engine_kv_info(tm_engine* e, int* ring_blocks, int64_t* free_blocks);
 int tm_engine_destroy(tm_engine* e);
 /* Per-layer sliding windows (gpt-oss alternates sliding and full layers): window[i] replaces attn_window for layer i, 0 = full
  * attention.  Before tm_engine_start; layers must equal the model's; a negative window is TM_INVALID. */
@@ -583,7 +596,7 @@ int tm_engine_decode(tm_engine* e, int steps);
  * `batch` sequences (host ids concatenated, host lens) run through chunked prefill with the lm_head over EVERY prompt row and
  * per-row cross-entropy against the next token, from the raw logits (no penalties, bans or sampling).  host_nll receives
  * sum(len_b - 1) floats: sequence by sequence, position p scored against ids[b][p + 1].  Each sequence holds ceil(len / 64)
- * blocks for the call only; on return every block is free again and the engine is idle (batch slots, next ids, logits and
+ * blocks (at most its block ring, tm_engine_kv_info) for the call only; on return every block is free again and the engine is idle (batch slots, next ids, logits and
  * the decode graph untouched; the scoring scratch stays allocated until tm_engine_destroy).  Refusals:
  * TM_CONFLICT (engine thread running), TM_INVALID (a batch admitted / scheduler session open, tp > 1, len < 2, an id
  * outside [0, vocab)), TM_TOO_LONG (len >= session_len), TM_OOM (not enough free KV blocks). */
@@ -673,7 +686,7 @@ int tm_gemm_export(const char* path);
  * Continuous batching.  Replaces ModelRequest.forward / cancel + the engine thread's
  * schedule-forward-update loop (bind.cpp:743-793, engine/engine.cc:434-470,770-870, model_request.cc:36-135):
  * requests are queued, admitted in arrival order when a batch slot and enough KV blocks (prompt + max_new_tokens,
- * 64-token blocks) are free, prefilled (chunked, <= max_prefill_token_num prompt tokens per step) and then decoded
+ * 64-token blocks; at most the block ring of a sliding-window model, tm_engine_kv_info) are free, prefilled (chunked, <= max_prefill_token_num prompt tokens per step) and then decoded
  * together with everything else that is running; a sequence ends on eos_id (eos_id < 0: ignore_eos), at
  * max_new_tokens or on cancel, and its slot / blocks are reused by the next admission.  Greedy sampling.
  * The first tm_engine_submit switches the engine into this mode (no static batch may be admitted);
@@ -727,8 +740,17 @@ int tm_engine_wait(tm_engine* e, int64_t req_id, int have_tokens, int timeout_ms
  * *seqs_a = sequences of the first micro-batch, *rows_a = its rows; 0 / 0: no usable boundary (fewer than two sequences, or the smaller side
  * below min_rows / 2 rows) -- the engine then splits the row-wise part of every layer by rows instead. */
 int tm_prefill_split(const int* cu_q, int nseq, int min_rows, int* seqs_a, int* rows_a);
+/* Host-only: the KV block ring of a model whose every layer has a sliding window.  *ring_blocks =
+ * ceil((window - 1 + chunk_tokens) / 64) + 1, window = the largest layer window, chunk_tokens = the most tokens one sequence
+ * contributes to one prefill forward (the engine: max(max_batch_size, 64, max_prefill_token_num)).  A sequence then owns
+ * min(ceil((prompt + max_new_tokens) / 64), ring_blocks) blocks and its logical block i is its physical block i % ring_blocks. */
+int tm_kv_ring_blocks(int window, int chunk_tokens, int* ring_blocks);
 typedef struct tm_sched tm_sched;
 int tm_sched_create(tm_sched** out, int max_batch, int num_blocks, int session_len);
+/* block ring: every request owns at most ring_blocks blocks (0 = off, whole contexts are reserved: the default).  The never-fits
+ * test of tm_sched_submit, tm_sched_admit and tm_sched_admit_ready count with it; tm_sched_query's n_blocks is what the request
+ * owns.  Before the first tm_sched_submit only, TM_INVALID afterwards.  The engine sets it when it creates its scheduler. */
+int tm_sched_set_ring(tm_sched* s, int ring_blocks);
 int tm_sched_destroy(tm_sched* s);
 int tm_sched_submit(tm_sched* s, const int* ids, int n, int max_new_tokens, int eos_id, int64_t* req_id);
 /* admit waiting requests for one step: writes up to cap (request id, slot) pairs */

@@ -95,12 +95,15 @@ _SIGNATURES = {
                                      c_void_p, c_float, POINTER(KvCache), c_void_p]),
     'tm_engine_rope_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     'tm_engine_set_layer_windows': (c_int, [c_void_p, c_void_p, c_int]),
+    'tm_engine_kv_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     'tm_kv_rope_store': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                  POINTER(KvCache), c_void_p]),
     'tm_kv_rope_store_qk': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_float, POINTER(KvCache), c_void_p]),
     'tm_flatten_kv': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(KvCache),
                               c_void_p]),
+    'tm_flatten_kv_window': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(KvCache),
+                                     c_void_p, c_int, c_void_p]),
     'tm_decode_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
     'tm_decode_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                     POINTER(KvCache), c_void_p]),
@@ -241,6 +244,8 @@ _SIGNATURES = {
     'tm_sched_abort_all': (c_int, [c_void_p, c_int]),
     'tm_sched_create': (c_int, [POINTER(c_void_p), c_int, c_int, c_int]),
     'tm_sched_destroy': (c_int, [c_void_p]),
+    'tm_sched_set_ring': (c_int, [c_void_p, c_int]),
+    'tm_kv_ring_blocks': (c_int, [c_int, c_int, POINTER(c_int)]),
     'tm_sched_submit': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int64)]),
     'tm_sched_admit': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_int)]),
     'tm_sched_on_token': (c_int, [c_void_p, c_int, c_int, POINTER(c_int)]),

@@ -243,6 +243,16 @@ int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off
                              to_view(cache), (hipStream_t)st);
 }
 
+int tm_flatten_kv_window(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
+                         int max_k_len, int k_stride, const tm_kv_cache* cache, const int* cu_q_len, int window, tm_stream_t st)
+{
+    TM_REQUIRE(k_out && v_out && cu_k_off && k_len && cache, "null pointer");
+    TM_REQUIRE(window >= 0, "flatten: window must be >= 0 (0 = the whole context)");
+    TM_REQUIRE(window == 0 || cu_q_len, "flatten: a window needs cu_q_len");
+    return launch_flatten_kv_window((half_t*)k_out, (half_t*)v_out, transpose_v, cu_k_off, k_len, cu_q_len, window, batch,
+                                    max_k_len, k_stride, to_view(cache), (hipStream_t)st);
+}
+
 size_t tm_decode_attention_workspace(int batch, int q_heads, int splits)
 {
     // sized for head_dim 128: enough for 64 too (the partial-O slots of a launch follow the cache's head_dim, partial_ml sits behind them)
@@ -919,6 +929,25 @@ int tm_prefill_split(const int* cu_q, int nseq, int min_rows, int* seqs_a, int* 
     }
     *seqs_a = tmk::prefill_microbatch_split(cu_q, nseq, min_rows);
     *rows_a = *seqs_a > 0 ? cu_q[*seqs_a] : 0;
+    return 0;
+}
+
+int tm_kv_ring_blocks(int window, int chunk_tokens, int* ring_blocks)
+{
+    TM_REQUIRE(ring_blocks, "null pointer");
+    TM_REQUIRE(window >= 1 && chunk_tokens >= 1, "ring size: window and chunk_tokens must be >= 1");
+    *ring_blocks = tmk::kv_ring_blocks(window, chunk_tokens);
+    return 0;
+}
+
+int tm_sched_set_ring(tm_sched* s, int ring_blocks)
+{
+    TM_REQUIRE(s, "null pointer");
+    TM_REQUIRE(ring_blocks >= 0, "ring_blocks must be >= 0 (0 = no ring)");
+    if (!s->impl.set_ring(ring_blocks)) {
+        set_last_error("tm_sched_set_ring: only before the first submit");
+        return TM_INVALID;
+    }
     return 0;
 }
 

@@ -337,6 +337,8 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
         const char* gc    = getenv("TM_GRAPH_COMM");
         e->mixed_steps_on = !(ms && !atoi(ms));
         e->graph_comm     = !(gc && !atoi(gc));
+        const char* kr    = getenv("TM_KV_RING");  // 0: sliding-window models reserve whole contexts too (A/B arm of the block ring)
+        e->kv_ring_on     = !(kr && !atoi(kr));
     }
     e->D           = m.head_dim;
     e->qkv_n       = (e->q_heads + 2 * e->kv_heads) * e->D;
@@ -754,6 +756,19 @@ int tm_engine_start(tm_engine* e)
         if (e->windowed) {
             e->fold_norm = 0;
         }
+        // block ring: only when EVERY layer is windowed (one KV block holds all layers, so one full-attention layer keeps every
+        // block of the context alive); the ring is sized by the largest window and by max_tokens, the most tokens prefill_slots
+        // hands one sequence per forward.  A ring as long as the longest block table row would save nothing: off.
+        int w_max = 0, w_min = m.layers > 0 ? e->layers[0].window : 0;
+        for (int i = 0; i < m.layers; ++i) {
+            w_max = std::max(w_max, e->layers[i].window);
+            w_min = std::min(w_min, e->layers[i].window);
+        }
+        e->ring_blocks = 0;
+        if (e->kv_ring_on && w_min > 0) {
+            const int r    = kv_ring_blocks(w_max, e->max_tokens);
+            e->ring_blocks = r < e->max_blocks_per_seq ? r : 0;
+        }
     }
     if (m.moe_experts > 0) {
         TM_HIP_CHECK(hipMalloc(&e->d_moe_ws, moe_workspace_bytes(e->layers[0].moe, e->max_tokens)));
@@ -820,7 +835,7 @@ int tm_engine_start(tm_engine* e)
         TM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
         const float frac = c.cache_max_entry_count > 0.f ? c.cache_max_entry_count : 0.8f;
         blocks           = (int64_t)((double)free_b * frac / (double)e->block_bytes);
-        const int64_t need = (int64_t)B * e->max_blocks_per_seq;
+        const int64_t need = (int64_t)B * kv_blocks_owned(e->max_blocks_per_seq, e->ring_blocks);  // no sequence can own more
         blocks           = std::min(blocks, need);
     }
     TM_REQUIRE(blocks >= 1, "no memory for KV blocks");
@@ -904,9 +919,16 @@ int tm_engine_debug_read(tm_engine* e, int what, int a, int b, void* host_out, i
         return 0;
     }
     if (what == 1) {  // KV block b of static-batch sequence a (all layers, the reference's block byte layout)
-        TM_REQUIRE(a >= 0 && a < (int)e->h_blocks.size() && b >= 0 && b < (int)e->h_blocks[a].size(), "sequence / block index");
+        // b is a LOGICAL block.  With a block ring h_blocks[a] is the ring: logical block b lives in h_blocks[a][b % R] until logical
+        // block b + R is written over it, i.e. while b >= ceil(ctx / 64) - R (ctx = the tokens cached so far)
+        TM_REQUIRE(a >= 0 && a < (int)e->h_blocks.size() && a < (int)e->h_len.size() && b >= 0, "sequence / block index");
+        const int owned   = (int)e->h_blocks[a].size();
+        const int logical = (e->h_len[a] + e->max_new + 63) / 64;
+        const int written = (e->h_len[a] + std::max(e->steps_done, 1) - 1 + 63) / 64;
+        TM_REQUIRE(owned > 0 && b < logical, "sequence / block index");
+        TM_REQUIRE(b >= written - owned, "KV block was overwritten by the sequence's block ring (it lies in front of the window)");
         TM_REQUIRE(bytes == (int64_t)e->block_bytes, "byte count must be the block size");
-        TM_HIP_CHECK(hipMemcpy(host_out, e->pool + (int64_t)e->h_blocks[a][b] * e->block_bytes, (size_t)bytes, hipMemcpyDeviceToHost));
+        TM_HIP_CHECK(hipMemcpy(host_out, e->pool + (int64_t)e->h_blocks[a][b % owned] * e->block_bytes, (size_t)bytes, hipMemcpyDeviceToHost));
         return 0;
     }
     if (what == 2) {  // int64: scheduler steps whose decode rows rode on a prefill forward (mixed steps)
@@ -929,6 +951,18 @@ int tm_engine_rope_info(tm_engine* e, int* per_seq_tables, int64_t* table_bytes)
     const bool on = e->d_rope_row0 != nullptr;
     if (per_seq_tables) *per_seq_tables = on ? 1 : 0;
     if (table_bytes) *table_bytes = on ? (int64_t)e->cfg.max_batch_size * e->rope_max_pos * e->D * (int64_t)sizeof(half_t) : 0;
+    return 0;
+}
+
+int tm_engine_kv_info(tm_engine* e, int* ring_blocks, int64_t* free_blocks)
+{
+    TM_REQUIRE(e && e->started, "null pointer / engine not started");
+    if (e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    if (ring_blocks) *ring_blocks = e->ring_blocks;
+    if (free_blocks) *free_blocks = e->sched ? (int64_t)e->sched->n_free_blocks() : (int64_t)e->free_blocks.size();
     return 0;
 }
 

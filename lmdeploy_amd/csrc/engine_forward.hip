@@ -229,8 +229,8 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             cv.block_ptrs += (size_t)P.s0 * e->max_blocks_per_seq;  // cu_block_nums[b] = b * max_blocks_per_seq: the part's sequence 0
             TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv, e->q_heads, P.cu_q, e->d_k_len + P.s0, P.nseq, P.rows, e->d_rope, e->rope_max_pos,
                                                            cv, st, L.qkv_bias, L.q_norm, L.k_norm, eps, rope_row0 ? rope_row0 + P.s0 : nullptr)));
-            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + P.s0, e->d_k_len + P.s0, P.nseq, max_k_len,
-                                                        kflat_stride, cv, st)));
+            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + P.s0, e->d_k_len + P.s0, P.cu_q, L.window,
+                                                               P.nseq, max_k_len, kflat_stride, cv, st)));
             PrefillAttnParams p{};
             p.q          = qkv;
             p.q_stride   = e->qkv_n;
@@ -490,8 +490,9 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, st)));
         }
         else {
-            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv(e->d_kflat, e->d_vflat, 1, e->d_cu_koff, e->d_k_len, nseq, max_k_len,
-                                                        kflat_stride, cv, st)));
+            // (a windowed layer flattens from the first 64-key stage of its window on: launch_flatten_kv_window; window 0 = the whole context)
+            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff, e->d_k_len, e->d_cu_q, L.window, nseq,
+                                                               max_k_len, kflat_stride, cv, st)));
             PrefillAttnParams p{};
             p.q          = qkv_p;
             p.q_stride   = e->qkv_n;
@@ -1037,7 +1038,7 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
             set_last_error("prompt + max_new_tokens exceeds session_len");
             return TM_TOO_LONG;
         }
-        need += (host_lens[b] + max_new_tokens + 63) / 64;
+        need += kv_blocks_owned((host_lens[b] + max_new_tokens + 63) / 64, e->ring_blocks);
     }
     if (need > (int64_t)e->free_blocks.size()) {
         set_last_error("out of KV cache blocks");
@@ -1047,12 +1048,11 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     e->h_blocks.assign(batch, {});
     for (int b = 0; b < batch; ++b) {
         const int nb = (host_lens[b] + max_new_tokens + 63) / 64;
-        for (int i = 0; i < nb; ++i) {
-            const int blk = e->free_blocks.back();
+        for (int i = 0; i < kv_blocks_owned(nb, e->ring_blocks); ++i) {
+            e->h_blocks[b].push_back(e->free_blocks.back());
             e->free_blocks.pop_back();
-            e->h_blocks[b].push_back(blk);
-            ptrs[(size_t)b * e->max_blocks_per_seq + i] = (uint64_t)(e->pool + (int64_t)blk * e->block_bytes);
         }
+        kv_table_row(e, ptrs.data() + (size_t)b * e->max_blocks_per_seq, e->h_blocks[b], nb);
     }
     TM_HIP_CHECK(hipMemcpyAsync(e->d_block_ptrs, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice, e->stream));
     TM_HIP_CHECK(hipMemsetAsync(e->d_step, 0, 4, e->stream));
@@ -1166,7 +1166,7 @@ int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int
             set_last_error("input length >= session_len");
             return TM_TOO_LONG;
         }
-        need += (host_lens[b] + 63) / 64;
+        need += kv_blocks_owned((host_lens[b] + 63) / 64, e->ring_blocks);
         total += host_lens[b];
     }
     for (int64_t i = 0; i < total; ++i) {
@@ -1200,12 +1200,14 @@ int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int
         for (int p = 0; p < host_lens[b]; ++p) {
             tgt[off + p] = p + 1 < host_lens[b] ? host_ids[off + p + 1] : -1;
         }
-        for (int i = 0; i < (host_lens[b] + 63) / 64; ++i) {
-            const int blk = e->free_blocks.back();
+        const int        nb = (host_lens[b] + 63) / 64;
+        std::vector<int> own;
+        for (int i = 0; i < kv_blocks_owned(nb, e->ring_blocks); ++i) {
+            own.push_back(e->free_blocks.back());
             e->free_blocks.pop_back();
-            blocks.push_back(blk);
-            ptrs[(size_t)b * e->max_blocks_per_seq + i] = (uint64_t)(e->pool + (int64_t)blk * e->block_bytes);
         }
+        blocks.insert(blocks.end(), own.begin(), own.end());
+        kv_table_row(e, ptrs.data() + (size_t)b * e->max_blocks_per_seq, own, nb);
     }
     std::vector<float> nll(total);
     auto run = [&]() -> int {

@@ -138,6 +138,11 @@ struct tm_engine {
     int64_t   num_blocks  = 0;
     std::vector<int> free_blocks;
     int       max_blocks_per_seq = 0;
+    // KV block ring (scheduler.h: kv_ring_blocks): every layer has a sliding window -> a sequence owns at most
+    // ring_blocks blocks and the block table row of logical blocks i repeats them, ptrs[i] = ring[i % ring_blocks].  0 = off: some
+    // layer is full attention (or TM_KV_RING=0, read at creation) and every sequence reserves its whole context.
+    bool      kv_ring_on  = true;
+    int       ring_blocks = 0;
     uint64_t* d_block_ptrs    = nullptr;  // [max_batch][max_blocks_per_seq]
     int*      d_cu_block_nums = nullptr;  // [max_batch+1]
 
@@ -358,6 +363,17 @@ inline int dmalloc(T** p, size_t n)
 {
     TM_HIP_CHECK(hipMalloc((void**)p, n * sizeof(T)));
     return 0;
+}
+
+// One block table row (host image of max_blocks_per_seq pointers): logical block i < `logical` of a sequence that owns the blocks
+// `owned` is owned[i % owned.size()] -- the identity when the sequence owns its whole context, the block ring otherwise
+// (owned.size() = kv_blocks_owned(logical, ring_blocks), scheduler.h).  The three admission sites (tm_engine_prefill,
+// tm_engine_score, the scheduler's admissions in engine_serve.hip) fill their tables through this; no kernel knows about the ring.
+inline void kv_table_row(const tm_engine* e, uint64_t* row, const std::vector<int>& owned, int logical)
+{
+    for (int i = 0; i < logical && i < e->max_blocks_per_seq && !owned.empty(); ++i) {
+        row[i] = (uint64_t)(e->pool + (int64_t)owned[(size_t)i % owned.size()] * e->block_bytes);
+    }
 }
 
 // ---- shared between the engine translation units ----

@@ -47,6 +47,7 @@ static int cb_enter(tm_engine* e)
     }
     e->dummy_block = (int)e->num_blocks - 1;  // parking block of the free slots; the scheduler owns the others
     e->sched.reset(new BatchScheduler(B, (int)e->num_blocks - 1, e->cfg.session_len, e->cfg.cache_block_seq_len));
+    (void)e->sched->set_ring(e->ring_blocks);  // 0 = off; a fresh scheduler takes it
     e->free_blocks.clear();
     e->h_active.assign(B, 0);
     // read when a continuous-batching session starts.  Default OFF -- measured (profiles/r04_request_stream_device_busy.txt): the device
@@ -134,10 +135,10 @@ static int cb_prefill_admitted(tm_engine* e, const std::vector<SchedAdmit>& admi
                 const tm_logits_param lp = it == e->cb_logits.end() ? kNoLogitsParam : it->second;
                 TM_TRY(logits_upload(e, &lp, &lens[k], &r->eos, slot0 + k, 1));
             }
-            TM_REQUIRE((int)r->blocks.size() <= e->max_blocks_per_seq, "internal: block table row too short");
-            for (size_t q = 0; q < r->blocks.size(); ++q) {
-                ptrs[(size_t)k * e->max_blocks_per_seq + q] = (uint64_t)(e->pool + (int64_t)r->blocks[q] * e->block_bytes);
-            }
+            const int logical = e->sched->blocks_for(lens[k] + r->max_new);  // r->blocks: all of them, or the request's block ring
+            TM_REQUIRE(logical <= e->max_blocks_per_seq && (int)r->blocks.size() == kv_blocks_owned(logical, e->ring_blocks),
+                       "internal: block table row too short");
+            kv_table_row(e, ptrs.data() + (size_t)k * e->max_blocks_per_seq, r->blocks, logical);
         }
         TM_HIP_CHECK(hipMemcpyAsync(e->d_pf_block_ptrs + (size_t)slot0 * e->max_blocks_per_seq, ptrs.data(), ptrs.size() * 8,
                                     hipMemcpyHostToDevice, e->stream));

@@ -15,6 +15,7 @@
 // 16-lane row would mix two tokens), a 256-thread workgroup holds 2048 / D token rows.
 #include "tm_common.h"
 #include "tm_kernels.h"
+#include <tuple>
 
 namespace tmk {
 
@@ -321,14 +322,23 @@ __device__ __forceinline__ half8_t load_dequant_flatten(const char* data, const 
     }
 }
 
-template<int BITS, bool VT, int D = 128>
+// WIN = true: the sliding-window variant (launch_flatten_kv_window).  The prefill kernel behind it starts its key loop at
+// kbeg_wg = max(hist + bx * 64 - window + 1, 0) / 64 * 64 (attention_prefill.hip), smallest for query block bx = 0, and stages K
+// rows and V^T columns [ks, ks + 64) from there on only: a 64-token tile that ends at or below max(hist - window + 1, 0),
+// hist = k_len - q_len, is read by no workgroup.  Such a tile returns here before it loads anything and its part of the scratch is
+// left as it was (not zero-filled).  The variant's two arguments (cu_q_len [batch + 1], window) are the pack W, empty for
+// WIN = false: those instantiations keep the kernel arguments -- and with them, register for register, the code -- they had before
+// the variant existed (an unused or empty trailing argument still moves the kernarg segment and the SGPR count).
+template<int BITS, bool VT, int D = 128, bool WIN = false, typename... W>
 __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_out,
                                                          half_t* __restrict__ v_out,
                                                          const int* __restrict__ cu_k_off,
                                                          const int* __restrict__ k_len,
                                                          int         k_stride,
-                                                         KvCacheView cache)
+                                                         KvCacheView cache,
+                                                         W... win)
 {
+    static_assert(sizeof...(W) == (WIN ? 2 : 0), "WIN: (const int* cu_q_len, int window)");
     static_assert(D == 64 || D == 128, "head_dim 64 or 128");
     constexpr int  LPR  = D / 8;      // lanes per token row (as in kv_rope_store_kernel)
     constexpr int  ROWS = 256 / LPR;  // token rows per pass: 16 | 32
@@ -339,6 +349,13 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
     const int      n  = k_len[b];
     if (t0 >= n) {
         return;
+    }
+    if constexpr (WIN) {
+        const auto [cu_q_len, window] = std::tuple<const int*, int>(win...);
+        const int  hist               = n - (cu_q_len[b + 1] - cu_q_len[b]);
+        if (t0 + 64 <= max(hist - window + 1, 0)) {
+            return;  // workgroup-uniform: in front of every query row's window
+        }
     }
     __shared__ half_t vt_smem[VT ? 64 * (D + 8) : 1];
 
@@ -384,16 +401,19 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
     }
 }
 
-int launch_flatten_kv(half_t*     k_out,
-                      half_t*     v_out,
-                      int         transpose_v,
-                      const int*  cu_k_off,
-                      const int*  k_len,
-                      int         batch,
-                      int         max_k_len,
-                      int         k_stride,
-                      KvCacheView cache,
-                      hipStream_t st)
+template<bool WIN>
+static int launch_flatten_kv_impl(half_t*     k_out,
+                                  half_t*     v_out,
+                                  int         transpose_v,
+                                  const int*  cu_k_off,
+                                  const int*  k_len,
+                                  int         batch,
+                                  int         max_k_len,
+                                  int         k_stride,
+                                  KvCacheView cache,
+                                  const int*  cu_q_len,
+                                  int         window,
+                                  hipStream_t st)
 {
     const int hd = cache.layout.head_dim;
     TM_REQUIRE(hd == 64 || hd == 128, "flatten_kv: head_dim must be 64 or 128");
@@ -403,10 +423,17 @@ int launch_flatten_kv(half_t*     k_out,
         return 0;
     }
     dim3 grid((max_k_len + 63) / 64, cache.layout.kv_heads, batch);
-#define TM_FLATTEN(B_, T_)                                                                                 \
-    do {                                                                                                   \
-        if (hd == 64) flatten_kv_kernel<B_, T_, 64><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache); \
-        else flatten_kv_kernel<B_, T_, 128><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache);         \
+#define TM_FLATTEN_D(B_, T_, D_)                                                                                                    \
+    do {                                                                                                                            \
+        if constexpr (WIN)                                                                                                          \
+            flatten_kv_kernel<B_, T_, D_, true><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache, cu_q_len, window); \
+        else                                                                                                                        \
+            flatten_kv_kernel<B_, T_, D_><<<grid, 256, 0, st>>>(k_out, v_out, cu_k_off, k_len, k_stride, cache);                     \
+    } while (0)
+#define TM_FLATTEN(B_, T_)                      \
+    do {                                        \
+        if (hd == 64) TM_FLATTEN_D(B_, T_, 64); \
+        else TM_FLATTEN_D(B_, T_, 128);         \
     } while (0)
     const int bits = cache.layout.bits;
     if (transpose_v) {
@@ -420,8 +447,46 @@ int launch_flatten_kv(half_t*     k_out,
         else TM_FLATTEN(4, false);
     }
 #undef TM_FLATTEN
+#undef TM_FLATTEN_D
     TM_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int launch_flatten_kv(half_t*     k_out,
+                      half_t*     v_out,
+                      int         transpose_v,
+                      const int*  cu_k_off,
+                      const int*  k_len,
+                      int         batch,
+                      int         max_k_len,
+                      int         k_stride,
+                      KvCacheView cache,
+                      hipStream_t st)
+{
+    return launch_flatten_kv_impl<false>(k_out, v_out, transpose_v, cu_k_off, k_len, batch, max_k_len, k_stride, cache, nullptr, 0, st);
+}
+
+// flatten for a layer with a sliding window: tiles wholly in front of max(k_len - q_len - window + 1, 0) are neither read nor
+// written (flatten_kv_kernel<.., WIN = true>); window == 0 is launch_flatten_kv, launch for launch
+int launch_flatten_kv_window(half_t*     k_out,
+                             half_t*     v_out,
+                             int         transpose_v,
+                             const int*  cu_k_off,
+                             const int*  k_len,
+                             const int*  cu_q_len,
+                             int         window,
+                             int         batch,
+                             int         max_k_len,
+                             int         k_stride,
+                             KvCacheView cache,
+                             hipStream_t st)
+{
+    TM_REQUIRE(window >= 0, "flatten_kv: window must be >= 0 (0 = the whole context)");
+    if (window == 0) {
+        return launch_flatten_kv(k_out, v_out, transpose_v, cu_k_off, k_len, batch, max_k_len, k_stride, cache, st);
+    }
+    TM_REQUIRE(cu_q_len, "flatten_kv: a window needs cu_q_len");
+    return launch_flatten_kv_impl<true>(k_out, v_out, transpose_v, cu_k_off, k_len, batch, max_k_len, k_stride, cache, cu_q_len, window, st);
 }
 
 }  // namespace tmk

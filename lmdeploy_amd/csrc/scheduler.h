@@ -22,6 +22,26 @@
 
 namespace tmk {
 
+// KV block ring of a sliding-window model.  When EVERY layer has a window W > 0 (W = the largest one) no kernel
+// reads a key below hist - W + 1 again, so logical block i of a sequence can live in physical block ring[i % R] and the
+// sequence owns min(ceil((prompt + max_new) / 64), R) blocks.  R = ceil((W - 1 + C) / 64) + 1, C = the most tokens one sequence
+// contributes to one prefill forward (the engine's max_tokens: prefill_slots never takes more per iteration).
+// Invariant: in every forward the keys [hist - W + 1, hist + q) of a sequence, q <= C new tokens behind hist cached ones, are
+// resident at the same time.  They are at most W - 1 + C tokens, which touch at most ceil((W - 1 + C) / 64) + 1 = R consecutive
+// logical blocks (the + 1: neither end is 64-aligned), and R consecutive logical blocks are R different physical ones.
+// kv_rope_store writes the whole chunk before flatten_kv / attention read anything; what it overwrites are logical blocks
+// <= (hist + q - 1) / 64 - R, wholly below floor64(hist - W + 1), the first key any prefill workgroup stages.  Decode (q = 1)
+// reads the tiles from (ctx - W) / 32 on: W + 1 tokens, R * 64 >= W + 64 covers them.
+inline int kv_ring_blocks(int window, int chunk_tokens, int block_len = 64)
+{
+    return (window - 1 + chunk_tokens + block_len - 1) / block_len + 1;
+}
+// blocks a sequence of `logical` 64-token blocks owns: all of them without a ring (ring_blocks == 0), at most the ring with one
+inline int kv_blocks_owned(int logical, int ring_blocks)
+{
+    return ring_blocks > 0 && logical > ring_blocks ? ring_blocks : logical;
+}
+
 struct SchedRequest {
     int64_t          id       = 0;
     std::vector<int> prompt;
@@ -31,7 +51,7 @@ struct SchedRequest {
     int              status   = 0;   // Request::k*: 0 = waiting / running, 7 finished, 8 cancelled
     int              slot     = -1;  // batch slot while running
     bool             running  = false;
-    std::vector<int> blocks;         // KV blocks owned while running
+    std::vector<int> blocks;         // KV blocks owned while running (with a block ring: logical block i is blocks[i % size])
     std::vector<int> out;            // generated tokens so far
     // GenerationConfig.logprobs (set_logprobs): per generated token the first lp_n kept candidates (entries beyond lp_num[t] are
     // padding), their count and the token's own logprob -- the request's logprob_vals / logprob_indexes / logprob_nums outputs
@@ -68,7 +88,7 @@ public:
         if (n + max_new > session_len_) {
             return 6;
         }
-        if (blocks_for(n + max_new) > total_blocks_) {
+        if (owned_for(n + max_new) > total_blocks_) {
             return 11;
         }
         SchedRequest r;
@@ -98,7 +118,7 @@ public:
             }
             SchedRequest& r = it->second;
             const int n    = (int)r.prompt.size();
-            const int need = blocks_for(n + r.max_new);
+            const int need = owned_for(n + r.max_new);
             int       slot = -1;
             for (int b = 0; b < max_batch_; ++b) {
                 if (slot_req_[b] < 0) {
@@ -139,7 +159,7 @@ public:
             for (int b = 0; b < max_batch_ && !slot; ++b) {
                 slot = slot_req_[b] < 0;
             }
-            return slot && blocks_for((int)r.prompt.size() + r.max_new) <= (int)free_blocks_.size();  // head of the line decides
+            return slot && owned_for((int)r.prompt.size() + r.max_new) <= (int)free_blocks_.size();  // head of the line decides
         }
         return false;
     }
@@ -294,6 +314,18 @@ public:
     }
     int n_free_blocks() const { return (int)free_blocks_.size(); }
     int blocks_for(int tokens) const { return (tokens + block_len_ - 1) / block_len_; }
+    // blocks a sequence of `tokens` tokens owns: blocks_for() without a ring, at most ring_blocks with one
+    int owned_for(int tokens) const { return kv_blocks_owned(blocks_for(tokens), ring_blocks_); }
+    int ring_blocks() const { return ring_blocks_; }
+    // KV block ring (kv_ring_blocks above; 0 = off: whole contexts are reserved).  Before the first submit only: false afterwards
+    bool set_ring(int ring_blocks)
+    {
+        if (next_id_ != 1 || ring_blocks < 0) {
+            return false;
+        }
+        ring_blocks_ = ring_blocks;
+        return true;
+    }
 
 private:
     void finish(SchedRequest& r, int status)
@@ -310,7 +342,7 @@ private:
         r.slot    = -1;
     }
 
-    int                             max_batch_, session_len_, block_len_, total_blocks_ = 0;
+    int                             max_batch_, session_len_, block_len_, total_blocks_ = 0, ring_blocks_ = 0;
     int64_t                         next_id_ = 1;
     std::vector<int>                free_blocks_;
     std::vector<int64_t>            slot_req_;

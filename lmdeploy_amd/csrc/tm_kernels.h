@@ -67,6 +67,12 @@ int launch_rope_table(half2_t* out, int max_pos, int dim, const RopeInvFreq& f, 
 // scratch: K [kv_heads][k_stride][D]; V either [kv_heads][k_stride][D] or transposed [kv_heads][D][k_stride].
 int launch_flatten_kv(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
                       int max_k_len, int k_stride, KvCacheView cache, hipStream_t st);
+// The same for a layer with a sliding window (cu_q_len [batch + 1]: the forward's query rows): 64-token tiles that end at or below
+// max(k_len - q_len - window + 1, 0) are skipped -- not read, their scratch left unwritten: the windowed prefill kernel never stages them.
+// window == 0 is launch_flatten_kv.
+int launch_flatten_kv_window(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len,
+                             const int* cu_q_len, int window, int batch, int max_k_len, int k_stride, KvCacheView cache,
+                             hipStream_t st);
 
 // ---- attention_decode.hip ---------------------------------------------------------------
 struct DecodeAttnParams {

@@ -179,7 +179,11 @@ class TurbomindEngineConfig:
     Models: the attention path serves head_dim 128 and, through the Llama reader (Llama-3.2-1B, TinyLlama, SmolLM2: fp16 / bf16 or
     model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' needs head_dim 128.  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
-    on the VALU attention kernel for every quant_policy, and KV blocks older than the window stay allocated.
+    on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
+    R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
+    it owns min(ceil((prompt + max_new_tokens) / 64), R) blocks (Mistral-7B-v0.1 at session_len 32768: 193 instead of 512), and
+    prefill dequantises the window, not the history.  A model with one full-attention layer (gpt-oss alternates) keeps whole contexts;
+    TM_KV_RING=0 at engine creation switches the ring off.
     The gpt-oss MoE block -- MXFP4 experts (e2m1 codes, one ue8m0 scale byte per 32 weights), router and per-expert biases, the clamped
     gate * sigmoid(1.702 gate) * (1 + up) activation -- is served with tp = 1 (`synthetic:tiny_gptoss_moe` with model_format='hf' runs
     it); a published gpt-oss checkpoint is not loadable yet (hidden 2880 is no multiple of 128, no o_proj bias)."""

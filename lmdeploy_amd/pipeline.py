@@ -33,6 +33,9 @@ SYNTHETIC = {
                        rope=checkpoint.RopeConfig(128, 500000.0, 'llama3', 8.0, 1.0, 4.0, 8192)),
     'tiny': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=512, vocab=1024,
                  rope=checkpoint.RopeConfig(128, 10000.0)),
+    # `tiny` with a sliding window of 40 tokens in every layer: sequences keep a KV block ring instead of their whole context
+    'tiny_window': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=512, vocab=1024,
+                        rope=checkpoint.RopeConfig(128, 10000.0), window=40),
     # a mixture-of-experts twin of `tiny`: 8 experts of width 128, top-2 (u4, fp8 or -- model_format='hf' -- fp16 experts)
     'tiny_moe': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=128, vocab=1024,
                      rope=checkpoint.RopeConfig(128, 10000.0), moe_experts=8, moe_top_k=2),
@@ -61,7 +64,8 @@ class Pipeline:
         """tp > 1, the reference's way (lmdeploy/turbomind/turbomind.py:187-217): ONE call -- this process becomes rank 0 and starts
         the other tp - 1 ranks of the node itself (one process per GPU, turbomind/tp_group.py), broadcasts every request to them and
         returns rank 0's responses.  Expert path, unchanged: an externally launched process per GPU (torch.distributed.run, ...)
-        passes its `rank` and the broadcast RCCL id (`comm_unique_id`); `_tp_link` is the worker side of the one-call form."""
+        passes its `rank` and the broadcast RCCL id (`comm_unique_id`); `_tp_link` is the worker side of the one-call form.
+        `cache_blocks=N` (keyword, tp = 1): a KV pool of exactly N 64-token blocks instead of cache_max_entry_count x free memory."""
         if kwargs.get('speculative_config') is not None or kwargs.get('chat_template_config') is not None:
             raise NotImplementedError('speculative decoding / chat templates are outside the MI355X hot path')
         cfg = backend_config or TurbomindEngineConfig()
@@ -91,6 +95,7 @@ class Pipeline:
                                                                         else 'f16'], tp=cfg.tp, rank=rank,
             device=devices[rank % len(devices)], max_batch_size=cfg.max_batch_size or 64, session_len=session_len,
             quant_policy=int(cfg.quant_policy), cache_max_entry_count=cfg.cache_max_entry_count,
+            cache_blocks=int(kwargs.get('cache_blocks') or 0),     # an explicit pool of 64-token KV blocks (0: sized from free memory)
             max_prefill_token_num=cfg.max_prefill_token_num or 8192)
         self._group = None
         if cfg.tp > 1:

@@ -256,7 +256,8 @@ class Engine:
         return out
 
     def fetch_kv_block(self, seq: int, block: int) -> np.ndarray:
-        """parity tests: the bytes of KV block `block` of static-batch sequence `seq` (all layers)"""
+        """parity tests: the bytes of logical KV block `block` of static-batch sequence `seq` (all layers).  With a block ring
+        (kv_info) only a resident block can be read: one that the ring has overwritten raises TmError(TM_INVALID)."""
         out = np.zeros(self.stats()['kv_bytes_per_token'] * 64, np.uint8)
         _ffi.check(self._lib.tm_engine_debug_read(self._h, 1, seq, block, out.ctypes.data, out.nbytes))
         return out
@@ -369,6 +370,13 @@ class Engine:
         wb, kv, nb, sp = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
         _ffi.check(self._lib.tm_engine_stats(self._h, C.byref(wb), C.byref(kv), C.byref(nb), C.byref(sp)))
         return dict(weight_bytes=wb.value, kv_bytes_per_token=kv.value, num_blocks=nb.value, decode_splits=sp.value)
+
+    def kv_info(self) -> dict:
+        """ring_blocks: blocks of a sequence's KV block ring (0 = no ring: a layer without a sliding window, or TM_KV_RING=0);
+        free_blocks: blocks of the pool no sequence owns right now"""
+        ring, free = C.c_int(), C.c_int64()
+        _ffi.check(self._lib.tm_engine_kv_info(self._h, C.byref(ring), C.byref(free)))
+        return dict(ring_blocks=ring.value, free_blocks=free.value)
 
     def rope_info(self) -> dict:
         """per_seq_tables: the engine keeps one RoPE table per batch slot (dynamic NTK with session_len > max_position_embeddings)
