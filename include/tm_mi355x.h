@@ -73,6 +73,13 @@ int tm_rmsnorm(void* y, const void* x, const void* w, float eps, int M, int H, t
  * If `partial` != NULL, hidden is given as `splits` fp32 split-K slabs [splits][M][H] (hidden must be NULL). */
 int tm_residual_rmsnorm(void* y, void* resid, const void* hidden, const float* partial, int splits,
                         const void* bias, const void* w, float eps, int M, int H, tm_stream_t st);
+/* The same two operators over zero-padded rows (a model whose hidden size is served padded to a multiple of 128): only the columns
+ * [0, Hv) are the row, Hv % 8 == 0, 0 < Hv <= H.  The sum of squares runs over them and is divided by Hv; the columns [Hv, H) of x /
+ * resid / hidden / partial are never read -- a NaN there reaches no output -- and y (and resid) receive +0 there.  bias and w are
+ * read on [0, Hv) only.  Hv == H forwards to tm_rmsnorm / tm_residual_rmsnorm. */
+int tm_rmsnorm_valid(void* y, const void* x, const void* w, float eps, int M, int H, int Hv, tm_stream_t st);
+int tm_residual_rmsnorm_valid(void* y, void* resid, const void* hidden, const float* partial, int splits,
+                              const void* bias, const void* w, float eps, int M, int H, int Hv, tm_stream_t st);
 
 /* (cos,sin) fp16 table [max_pos][rope_dim/2][2] on the HOST (rotary_embedding.h:11-52, attention_weight.cc:37-93).
  * rope_type: 0 default, 1 linear, 2 llama3.  The caller uploads it. */
@@ -83,7 +90,10 @@ int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rop
  * type 0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic.  yarn: inv_freq = freq - freq * alpha * (1 - 1 / factor) with alpha the ramp
  * between the correction dimensions of yarn_beta_fast / yarn_beta_slow rotations over max_position_embeddings, and cos / sin scaled by
  * yarn_attention_factor in fp32 before the cast to fp16.  dynamic: the default recipe of `base` (the caller passes the SEQUENCE's
- * base, tm_rope_dynamic_base); factor and max_position_embeddings only feed that function. */
+ * base, tm_rope_dynamic_base); factor and max_position_embeddings only feed that function.
+ * yarn_truncate (yarn only): 1 = the correction dimensions are rounded outwards (floor / ceil: the reference, and transformers'
+ * default); 0 = they stay fractional (transformers' `truncate: false`, gpt-oss).  The clamps to [0, dim - 1] and the low == high guard
+ * apply to both. */
 typedef struct tm_rope_param {
     int   dim;
     float base;
@@ -92,9 +102,13 @@ typedef struct tm_rope_param {
     int   original_max_position;
     int   max_position_embeddings;
     float yarn_beta_fast, yarn_beta_slow, yarn_attention_factor;
+    int   yarn_truncate;
 } tm_rope_param;
 /* tm_rope_table for every type: fp32 products, exp2 / sin / cos in double on those fp32 values, rounded fp32 -> fp16 */
 int tm_rope_table_ex(void* host_out, int max_pos, const tm_rope_param* p);
+/* the recipe's per-pair inverse frequencies themselves (host): inv_freq fp32 [dim / 2], *attention_factor (may be NULL) the factor
+ * the table scales cos / sin by */
+int tm_rope_inv_freq(float* inv_freq, float* attention_factor, const tm_rope_param* p);
 /* the same table built on the DEVICE (asynchronous on `st`; inverse frequencies from the host recipe, angles / cos / sin per entry
  * as on the host) */
 int tm_rope_table_device(void* dev_out, int max_pos, const tm_rope_param* p, tm_stream_t st);
@@ -514,6 +528,14 @@ typedef struct tm_model_config {
      * An engine with a windowed layer or sinks decodes like head_dim 64: tm_kv_rope_store + the VALU attention kernel, no fused
      * prologue, no folded norm.  KV blocks older than the window stay allocated. */
     int   attn_window, attn_sinks;
+    /* gpt-oss (all three: tp == 1, no folded norm).
+     * attn_out_bias != 0 -> slot "layers.{i}.attention.wo.bias" fp16 [hidden], added behind the o projection in the order of the
+     * reference's invokeResidualBiasRMSNorm: r = h(h(r + wo_out) + bias), in every layer.
+     * hidden_valid (0 = hidden): the model's true hidden size when `hidden` (and `inter`) are the zero-padded sizes the engine runs at
+     * -- the loader pads every tensor with +0 (MXFP4: code 0) up to the next multiple of 128 -- so that the RMSNorms divide by it and
+     * keep the pad columns of the residual stream at +0 (tm_rmsnorm_valid).
+     * rope_yarn_truncate: tm_rope_param::yarn_truncate (1 = the reference's rounded correction range, 0 = fractional). */
+    int   attn_out_bias, hidden_valid, rope_yarn_truncate;
     /* Qwen attention prologue (0 = off): attn_bias -> slot "layers.{i}.attention.w_qkv.bias" fp16 [local qkv columns] added to
      * q / k / v (Qwen2); qk_norm -> slots "layers.{i}.attention.{q,k}_norm.weight" fp16 [head_dim], per-head RMSNorm of q / k with
      * rms_eps (Qwen3).  Order: norm -> bias -> RoPE. */

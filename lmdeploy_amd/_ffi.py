@@ -53,7 +53,14 @@ class RopeParam(C.Structure):
     """struct tm_rope_param"""
     _fields_ = [('dim', c_int), ('base', c_float), ('type', c_int), ('factor', c_float), ('low_freq_factor', c_float),
                 ('high_freq_factor', c_float), ('original_max_position', c_int), ('max_position_embeddings', c_int),
-                ('yarn_beta_fast', c_float), ('yarn_beta_slow', c_float), ('yarn_attention_factor', c_float)]
+                ('yarn_beta_fast', c_float), ('yarn_beta_slow', c_float), ('yarn_attention_factor', c_float),
+                ('yarn_truncate', c_int)]
+
+    def __init__(self, *args, **kw):
+        """yarn_truncate defaults to 1 (the rounded correction range); ctypes alone would leave it 0"""
+        if len(args) < len(self._fields_):
+            kw.setdefault('yarn_truncate', 1)
+        super().__init__(*args, **kw)
 
 
 class ModelConfig(C.Structure):
@@ -67,7 +74,14 @@ class ModelConfig(C.Structure):
                 ('weight_type', c_int), ('moe_experts', c_int), ('moe_top_k', c_int), ('moe_norm_topk', c_int),
                 ('moe_routed_scale', c_float), ('moe_expert_format', c_int), ('moe_act', c_int), ('moe_bias', c_int),
                 ('moe_shared_inter', c_int), ('attn_window', c_int), ('attn_sinks', c_int),
+                ('attn_out_bias', c_int), ('hidden_valid', c_int), ('rope_yarn_truncate', c_int),
                 ('attn_bias', c_int), ('qk_norm', c_int)]
+
+    def __init__(self, *args, **kw):
+        """rope_yarn_truncate defaults to 1 (the rounded YaRN correction range); ctypes alone would leave it 0"""
+        if len(args) <= [f[0] for f in self._fields_].index('rope_yarn_truncate'):
+            kw.setdefault('rope_yarn_truncate', 1)
+        super().__init__(*args, **kw)
 
 
 class EngineConfig(C.Structure):
@@ -87,8 +101,12 @@ _SIGNATURES = {
     'tm_rmsnorm': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p]),
     'tm_residual_rmsnorm': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                     c_int, c_int, c_void_p]),
+    'tm_rmsnorm_valid': (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
+    'tm_residual_rmsnorm_valid': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float,
+                                          c_int, c_int, c_int, c_void_p]),
     'tm_rope_table': (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_float, c_float, c_float, c_int]),
     'tm_rope_table_ex': (c_int, [c_void_p, c_int, POINTER(RopeParam)]),
+    'tm_rope_inv_freq': (c_int, [c_void_p, POINTER(c_float), POINTER(RopeParam)]),
     'tm_rope_table_device': (c_int, [c_void_p, c_int, POINTER(RopeParam), c_void_p]),
     'tm_rope_dynamic_base': (c_float, [c_float, c_float, c_int, c_int, c_int]),
     'tm_kv_rope_store_seq': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

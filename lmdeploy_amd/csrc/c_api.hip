@@ -60,8 +60,9 @@ int rope_inv_freq(RopeInvFreq* out, const tm_rope_param& p)
         const auto corr = [&](float rot) {
             return (dim * std::log((double)p.max_position_embeddings / ((double)rot * 2.0 * M_PI))) / (2.0 * std::log((double)p.base));
         };
-        float low  = (float)std::floor(corr(p.yarn_beta_fast));
-        float high = (float)std::ceil(corr(p.yarn_beta_slow));
+        // yarn_truncate 0 (transformers' `truncate: false`, gpt-oss): the bounds stay fractional
+        float low  = p.yarn_truncate ? (float)std::floor(corr(p.yarn_beta_fast)) : (float)corr(p.yarn_beta_fast);
+        float high = p.yarn_truncate ? (float)std::ceil(corr(p.yarn_beta_slow)) : (float)corr(p.yarn_beta_slow);
         low        = std::max(low, 0.f);
         high       = std::min(high, dim - 1.f);
         if (low == high) {
@@ -123,6 +124,7 @@ int build_rope_table(half_t* out, int max_pos, int dim, float base, int type, fl
     tm_rope_param p{};
     p.dim = dim, p.base = base, p.type = type, p.factor = factor, p.low_freq_factor = low, p.high_freq_factor = high;
     p.original_max_position = orig_max_pos;
+    p.yarn_truncate         = 1;
     return build_rope_table_ex(out, max_pos, p);
 }
 
@@ -175,6 +177,22 @@ int tm_residual_rmsnorm(void* y, void* resid, const void* hidden, const float* p
                                    (const half_t*)bias, (const half_t*)w, eps, M, H, (hipStream_t)st);
 }
 
+int tm_rmsnorm_valid(void* y, const void* x, const void* w, float eps, int M, int H, int Hv, tm_stream_t st)
+{
+    TM_REQUIRE(y && x && w, "null pointer");
+    TM_REQUIRE(Hv > 0, "rmsnorm: the valid width must be a multiple of 8 in (0, H]");
+    return launch_rmsnorm((half_t*)y, (const half_t*)x, (const half_t*)w, eps, M, H, (hipStream_t)st, Hv);
+}
+
+int tm_residual_rmsnorm_valid(void* y, void* resid, const void* hidden, const float* partial, int splits, const void* bias,
+                              const void* w, float eps, int M, int H, int Hv, tm_stream_t st)
+{
+    TM_REQUIRE(y && resid && w, "null pointer");
+    TM_REQUIRE(Hv > 0, "rmsnorm: the valid width must be a multiple of 8 in (0, H]");
+    return launch_residual_rmsnorm((half_t*)y, (half_t*)resid, (const half_t*)hidden, partial, splits,
+                                   (const half_t*)bias, (const half_t*)w, eps, M, H, (hipStream_t)st, Hv);
+}
+
 int tm_rope_table(void* host_out, int max_pos, int rope_dim, float base, int rope_type, float factor,
                   float low_freq_factor, float high_freq_factor, int original_max_position)
 {
@@ -200,6 +218,20 @@ float tm_rope_dynamic_base(float base, float factor, int dim, int max_position_e
         return (float)((double)base * std::pow((double)s, (double)dim / ((double)dim - 2.0)));
     }
     return base;
+}
+
+int tm_rope_inv_freq(float* inv_freq, float* attention_factor, const tm_rope_param* p)
+{
+    TM_REQUIRE(inv_freq && p, "null pointer");
+    RopeInvFreq f;
+    TM_TRY_RC(rope_inv_freq(&f, *p));
+    for (int i = 0; i < p->dim / 2; ++i) {
+        inv_freq[i] = f.inv[i];
+    }
+    if (attention_factor) {
+        *attention_factor = f.attention_factor;
+    }
+    return 0;
 }
 
 int tm_rope_table_device(void* dev_out, int max_pos, const tm_rope_param* p, tm_stream_t st)

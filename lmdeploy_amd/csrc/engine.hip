@@ -103,6 +103,7 @@ static tm_rope_param model_rope_param(const tm_engine* e)
     p.max_position_embeddings = m.rope_max_position_embeddings;
     p.yarn_beta_fast = m.rope_yarn_beta_fast, p.yarn_beta_slow = m.rope_yarn_beta_slow;
     p.yarn_attention_factor = m.rope_yarn_attention_factor;
+    p.yarn_truncate         = m.rope_yarn_truncate;
     return p;
 }
 
@@ -319,12 +320,20 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE((m.moe_act == 0 && m.moe_bias == 0) || m.moe_shared_inter == 0, "moe_act / moe_bias with a shared expert is not built");
     TM_REQUIRE((m.moe_expert_format != TM_WEIGHT_MXFP4 && m.moe_bias == 0) || c->tp == 1,
                "MXFP4 experts / expert biases with tp > 1 are not built: the w2 bias would need a per-rank rule (run with tp = 1)");
+    TM_REQUIRE(m.hidden_valid == 0 || (m.hidden_valid > 0 && m.hidden_valid <= m.hidden && m.hidden_valid % 8 == 0),
+               "hidden_valid: 0 or a multiple of 8 in (0, hidden]");
+    TM_REQUIRE(m.hidden_valid == 0 || m.hidden_valid == m.hidden || c->tp == 1,
+               "hidden_valid != hidden (a zero-padded model) with tp > 1 is not built: the fused all-reduce + norm has no valid-width variant "
+               "(run with tp = 1)");
+    TM_REQUIRE(m.attn_out_bias == 0 || c->tp == 1,
+               "attn_out_bias with tp > 1 is not built: the o_proj bias would have to be added on one rank only (run with tp = 1)");
     TM_TRY(check_linear_images(m, c->tp));
     TM_HIP_CHECK(hipSetDevice(c->device));
 
     auto* e        = new tm_engine();
     e->cfg         = *c;
     e->hidden      = m.hidden;
+    e->hidden_valid = m.hidden_valid ? m.hidden_valid : m.hidden;
     e->q_heads     = m.q_heads / c->tp;
     e->kv_heads    = std::max(1, m.kv_heads / c->tp);
     e->inter       = m.inter / c->tp;
@@ -394,6 +403,9 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
         }
         if (m.attn_sinks) {  // this rank's q heads
             e->slots[p + ".attention.sinks"].bytes = (int64_t)e->q_heads * 2;
+        }
+        if (m.attn_out_bias) {  // tp == 1
+            e->slots[p + ".attention.wo.bias"].bytes = (int64_t)m.hidden * 2;
         }
         if (m.qk_norm) {  // one head, permuted like one head of q / k; replicated over the ranks
             e->slots[p + ".attention.q_norm.weight"].bytes = (int64_t)e->D * 2;
@@ -566,6 +578,9 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
         if (m.attn_sinks) {
             TM_TRY(vec(p + ".attention.sinks", e->q_heads, 0.f, 1.f));
         }
+        if (m.attn_out_bias) {
+            TM_TRY(vec(p + ".attention.wo.bias", m.hidden, 0.f, 0.02f));
+        }
         if (m.qk_norm) {
             TM_TRY(vec(p + ".attention.q_norm.weight", e->D, 1.f, 0.05f));
             TM_TRY(vec(p + ".attention.k_norm.weight", e->D, 1.f, 0.05f));
@@ -678,6 +693,9 @@ int tm_engine_process_weights(tm_engine* e)
         if (m.attn_sinks) {
             TM_TRY(norm(p + ".attention.sinks", &L.sinks));
         }
+        if (m.attn_out_bias) {
+            TM_TRY(norm(p + ".attention.wo.bias", &L.wo_bias));
+        }
         if (m.qk_norm) {
             TM_TRY(norm(p + ".attention.q_norm.weight", &L.q_norm));
             TM_TRY(norm(p + ".attention.k_norm.weight", &L.k_norm));
@@ -753,7 +771,8 @@ int tm_engine_start(tm_engine* e)
             e->layers[i].window = w >= c.session_len ? 0 : w;
             e->windowed |= e->layers[i].window > 0;
         }
-        if (e->windowed) {
+        // the folded norm divides by hidden and has no bias term: a zero-padded model or an o_proj bias runs the norm launches
+        if (e->windowed || e->hidden_valid != e->hidden || m.attn_out_bias) {
             e->fold_norm = 0;
         }
         // block ring: only when EVERY layer is windowed (one KV block holds all layers, so one full-attention layer keeps every

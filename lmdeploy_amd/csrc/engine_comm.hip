@@ -145,8 +145,9 @@ static int p2p_oneshot(tm_engine* e, const half_t* partial, half_t* y, half_t* r
 
 // d_x = RMSNorm(d_resid += sum over ranks of d_tmp): one fused P2P launch per <= p2p_rows rows on the native communicator
 // (any M when there is no RCCL communicator to fall back to), else RCCL all-reduce + the residual-norm kernel
-int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w)
+int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w, const half_t* bias)
 {
+    TM_REQUIRE(!e->use_comm || (!bias && e->hidden_valid == e->hidden), "internal: o_proj bias / zero-padded rows on a communicator");
     if (e->p2p_ready && (M <= e->p2p_rows || !e->comm)) {
         half_t*   data[8];
         uint32_t* flags[8];
@@ -172,8 +173,8 @@ int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w)
         return 0;
     }
     TM_PROF(P_ALLREDUCE, TM_TRY(allreduce_hidden(e, e->d_tmp, M)));
-    TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, e->d_tmp, nullptr, 0, nullptr, norm_w,
-                                                       e->cfg.model.rms_eps, M, e->hidden, e->stream)));
+    TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, e->d_tmp, nullptr, 0, bias, norm_w,
+                                                       e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
     return 0;
 }
 

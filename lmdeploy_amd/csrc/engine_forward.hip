@@ -115,8 +115,9 @@ static GemmConfig pick_config(tm_engine*, const LinearWeight& w, int M, bool)
 }
 
 // row-parallel linear followed by (all-reduce +) residual + RMSNorm
+// (bias: the o_proj bias, r = h(h(r + out) + bias) -- the HAS_BIAS arm of the norm kernel; nullptr for every other linear)
 static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, int M, const half_t* norm_w,
-                                int gemm_cat)
+                                int gemm_cat, const half_t* bias = nullptr)
 {
     GemmConfig cfg = pick_config(e, l.w, M, false);
     const bool can_defer = !e->use_comm && cfg.splits > 1
@@ -128,12 +129,12 @@ static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, i
     TM_PROF(gemm_cat, TM_TRY(launch_linear(l.w, x, ldx, e->d_tmp, e->hidden, M, false, cfg, e->d_gemm_ws, can_defer, &slabs,
                                            e->stream)));
     if (can_defer && slabs > 1) {
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, nullptr, norm_w,
-                                                           e->cfg.model.rms_eps, M, e->hidden, e->stream)));
+        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
+                                                           e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
         return 0;
     }
     TM_REQUIRE(!can_defer || slabs == 1, "internal: deferred reduce without slabs");
-    return reduce_residual_norm(e, M, norm_w);
+    return reduce_residual_norm(e, M, norm_w, bias);
 }
 
 static int linear_plain(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated)
@@ -170,8 +171,8 @@ static int forward_tail_two_halves(tm_engine* e, Layer& L, int M, int Ma, const 
     for (int h = 0; h < 2; ++h) {
         const size_t off = (size_t)r0[h] * H;
         TM_TRY(pipe_wait(e, done[h]));
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, L.ffn_norm, eps,
-                                                           nr[h], H, st)));
+        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, L.wo_bias, L.ffn_norm, eps,
+                                                           nr[h], H, st, e->hidden_valid)));
         TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x + off, H, e->d_act + (size_t)r0[h] * e->inter, e->inter, nr[h], true)));
         TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act + (size_t)r0[h] * e->inter, e->inter, e->d_tmp + off, H, nr[h], false)));
         TM_TRY(allreduce_rows_side(e, r0[h], nr[h], &done[h]));
@@ -180,7 +181,7 @@ static int forward_tail_two_halves(tm_engine* e, Layer& L, int M, int Ma, const 
         const size_t off = (size_t)r0[h] * H;
         TM_TRY(pipe_wait(e, done[h]));
         TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, next_norm, eps,
-                                                           nr[h], H, st)));
+                                                           nr[h], H, st, e->hidden_valid)));
         if (next) {
             TM_PROF(P_GEMM_QKV, TM_TRY(linear_plain(e, next->qkv, e->d_x + off, H, e->d_qkv + (size_t)r0[h] * e->qkv_n, e->qkv_n, nr[h], false)));
         }
@@ -221,7 +222,7 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             if (li > 0) {  // this micro-batch's w2 partial sums of the previous layer are summed by now (or the stream waits here)
                 TM_TRY(pipe_wait(e, done[h]));
                 TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, L.attn_norm,
-                                                                   eps, P.rows, H, st)));
+                                                                   eps, P.rows, H, st, e->hidden_valid)));
             }
             half_t* const qkv = e->d_qkv + (size_t)P.r0 * e->qkv_n;
             TM_PROF(P_GEMM_QKV, TM_TRY(linear_plain(e, L.qkv, e->d_x + off, H, qkv, e->qkv_n, P.rows, false)));
@@ -257,8 +258,8 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
             const Part&  P   = part[h];
             const size_t off = (size_t)P.r0 * H;
             TM_TRY(pipe_wait(e, done[h]));
-            TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, L.ffn_norm, eps,
-                                                               P.rows, H, st)));
+            TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, L.wo_bias, L.ffn_norm, eps,
+                                                               P.rows, H, st, e->hidden_valid)));
             TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x + off, H, e->d_act + (size_t)P.r0 * e->inter, e->inter, P.rows, true)));
             TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act + (size_t)P.r0 * e->inter, e->inter, e->d_tmp + off, H, P.rows, false)));
             TM_TRY(allreduce_rows_side(e, P.r0, P.rows, &done[h]));
@@ -268,7 +269,7 @@ static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int ma
         const size_t off = (size_t)part[h].r0 * H;
         TM_TRY(pipe_wait(e, done[h]));
         TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, e->final_norm, eps,
-                                                           part[h].rows, H, st)));
+                                                           part[h].rows, H, st, e->hidden_valid)));
     }
     return 0;
 }
@@ -364,7 +365,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     half_t* const qkv_p  = e->d_qkv + (size_t)nd * e->qkv_n;            // first prefill row
     half_t* const attn_p = e->d_attn + (size_t)nd * e->q_heads * e->D;
     TM_PROF(P_EMBED, TM_TRY(launch_embedding(e->d_resid, e->tok_embeddings, d_ids, M, e->hidden, m.vocab, st)));
-    TM_PROF(P_RES_NORM, TM_TRY(launch_rmsnorm(e->d_x, e->d_resid, e->layers[0].attn_norm, m.rms_eps, M, e->hidden, st)));
+    TM_PROF(P_RES_NORM, TM_TRY(launch_rmsnorm(e->d_x, e->d_resid, e->layers[0].attn_norm, m.rms_eps, M, e->hidden, st, e->hidden_valid)));
     const float scale_log2 = (1.0f / std::sqrt((float)e->D)) * 1.4426950408889634f;
     // tp > 1 prefill through RCCL: the row-wise part of every dense layer as two row halves, all-reduces on the side stream
     e->pipe_events_used = 0;
@@ -531,7 +532,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
                 TM_PROF(P_GEMM_O, TM_TRY(linear_fold_produce(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, &ss_tiles)));
             }
             else {
-                TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O));
+                TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
             }
             TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_fold_consume(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true, ss_tiles, false, nullptr)));
             ss_tiles = 0;
@@ -543,7 +544,7 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
             }
             continue;
         }
-        TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O));
+        TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
         if (L.is_moe) {
             // router + grouped expert FFNs + combine -> d_tmp, then (all-reduce +) residual + RMSNorm as for the dense FFN
             const half_t* shared = nullptr;

@@ -63,6 +63,7 @@ struct Layer {
     half_t*     ffn_norm  = nullptr;
     // Qwen attention prologue (tm_model_config.attn_bias / qk_norm; nullptr when off): [qkv_n] bias, [D] per-head norm weights
     half_t*     qkv_bias  = nullptr;
+    half_t*     wo_bias   = nullptr;  // tm_model_config.attn_out_bias: [hidden], added behind wo by the residual-norm launch
     half_t*     q_norm    = nullptr;
     half_t*     k_norm    = nullptr;
     // sliding window of this layer after clamping (0: full attention) and its sink logits [q_heads] (nullptr: none); tm_engine_start
@@ -84,6 +85,7 @@ struct tm_engine {
     tm_engine_config cfg{};
     // local (per-rank) dims
     int q_heads = 0, kv_heads = 0, inter = 0, vocab_local = 0, hidden = 0, D = 128;
+    int hidden_valid = 0;  // the rows' valid width (tm_model_config.hidden_valid; == hidden unless the model is served zero-padded)
     int shared_inter = 0;  // Qwen2-MoE: this rank's width of the shared expert (0: none)
     int ffn_inter() const { return shared_inter > 0 ? shared_inter : inter; }  // width of the DENSE w1w3 / w2 slots of a layer
     int qkv_n = 0;
@@ -382,7 +384,7 @@ int rope_admit(tm_engine* e, int slot, int prompt_len);
 int rope_reset(tm_engine* e, int slot0, int n);
 size_t prof_event(tm_engine* e);
 void p2p_tables(tm_engine* e, half_t** data, uint32_t** flags);
-int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w);
+int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w, const half_t* bias = nullptr);
 bool prefill_pipe_ok(const tm_engine* e, int M);
 int allreduce_rows_side(tm_engine* e, int r0, int rows, hipEvent_t* done);
 int pipe_wait(tm_engine* e, hipEvent_t done);

@@ -145,7 +145,7 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
                     TM_TRY(launch_linear(*w, r.x, r.ldx, r.y, r.ldy, M, r.gated, cfg, e->d_gemm_ws, norm_consumer && cfg.splits > 1, &slabs, st));
                     if (norm_consumer) {
                         TM_TRY(launch_residual_rmsnorm(norm_out, e->d_resid, slabs > 1 ? nullptr : e->d_tmp, slabs > 1 ? e->d_gemm_ws : nullptr,
-                                                       slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st));
+                                                       slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st, e->hidden_valid));
                     }
                     else if (r.which == 3 && shared_ffn) {  // the shared expert's consumer: the combine launch
                         TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st,
@@ -378,7 +378,7 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
                     TM_TRY(launch_linear(*w, r.x, r.ldx, r.y, r.ldy, M, r.gated, cfg, e->d_gemm_ws, norm_consumer && cfg.splits > 1, &slabs, st));
                     if (norm_consumer) {
                         TM_TRY(launch_residual_rmsnorm(norm_out, e->d_resid, slabs > 1 ? nullptr : e->d_tmp, slabs > 1 ? e->d_gemm_ws : nullptr,
-                                                       slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st));
+                                                       slabs, nullptr, e->final_norm, e->cfg.model.rms_eps, M, e->hidden, st, e->hidden_valid));
                     }
                     else if (r.which == 3 && shared_ffn) {  // the shared expert's consumer: the combine launch
                         TM_TRY(moe_forward(e->layers[0].moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, st,

@@ -38,14 +38,45 @@ __global__ __launch_bounds__(kNormMaxThreads) void rmsnorm_kernel(half_t* __rest
     }
 }
 
-int launch_rmsnorm(half_t* y, const half_t* x, const half_t* w, float eps, int M, int H, hipStream_t st)
+// The same kernel over rows whose columns [Hv, H) are padding (norm_row.h, VALID): a zero-padded model's norms.  Launched only when
+// Hv != H; the workgroup geometry is that of H.
+template<int MODE, bool HAS_BIAS, int NV>
+__global__ __launch_bounds__(kNormMaxThreads) void rmsnorm_valid_kernel(half_t* __restrict__ y,
+                                                                        half_t* __restrict__ resid,
+                                                                        const half_t* __restrict__ hidden,
+                                                                        const float* __restrict__ partial,
+                                                                        int           splits,
+                                                                        const half_t* __restrict__ bias,
+                                                                        const half_t* __restrict__ weight,
+                                                                        float eps,
+                                                                        int   M,
+                                                                        int   H,
+                                                                        int   Hv)
+{
+    __shared__ float red[8];
+    norm_row<MODE, HAS_BIAS, NV, true>(y, resid, hidden, partial, splits, bias, weight, eps, M, H, blockIdx.x, threadIdx.x, blockDim.x, red, Hv);
+}
+
+int launch_rmsnorm(half_t* y, const half_t* x, const half_t* w, float eps, int M, int H, hipStream_t st, int Hv)
 {
     TM_REQUIRE(H % 8 == 0 && H <= kNormMaxThreads * kNormMaxVec * 8, "rmsnorm: H must be a multiple of 8 and <= 8192");
+    Hv = Hv ? Hv : H;
+    TM_REQUIRE(Hv > 0 && Hv <= H && Hv % 8 == 0, "rmsnorm: the valid width must be a multiple of 8 in (0, H]");
     if (M == 0) {
         return 0;
     }
     int threads, nv;
     norm_geometry(H, &threads, &nv);
+    if (Hv != H) {
+        if (nv == 1) {
+            rmsnorm_valid_kernel<0, false, 1><<<M, threads, 0, st>>>(y, nullptr, x, nullptr, 0, nullptr, w, eps, M, H, Hv);
+        }
+        else {
+            rmsnorm_valid_kernel<0, false, 2><<<M, threads, 0, st>>>(y, nullptr, x, nullptr, 0, nullptr, w, eps, M, H, Hv);
+        }
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     uint64_t* const dbg = gemm_trace_for((size_t)M, "norm", M, 1, 1);
     if (nv == 1) {
         rmsnorm_kernel<0, false, 1><<<M, threads, 0, st>>>(y, nullptr, x, nullptr, 0, nullptr, w, eps, M, H, dbg);
@@ -67,16 +98,47 @@ int launch_residual_rmsnorm(half_t*       y,
                             float         eps,
                             int           M,
                             int           H,
-                            hipStream_t   st)
+                            hipStream_t   st,
+                            int           Hv)
 {
     TM_REQUIRE(H % 8 == 0 && H <= kNormMaxThreads * kNormMaxVec * 8, "rmsnorm: H must be a multiple of 8 and <= 8192");
     TM_REQUIRE((hidden != nullptr) != (partial != nullptr), "exactly one of hidden / partial");
     TM_REQUIRE(!partial || splits >= 1, "splits >= 1");
+    Hv = Hv ? Hv : H;
+    TM_REQUIRE(Hv > 0 && Hv <= H && Hv % 8 == 0, "rmsnorm: the valid width must be a multiple of 8 in (0, H]");
     if (M == 0) {
         return 0;
     }
     int threads, nv;
     norm_geometry(H, &threads, &nv);
+    if (Hv != H) {
+#define TM_NORM_LAUNCH_VALID(MODE, BIAS)                                                                                        \
+    if (nv == 1) {                                                                                                              \
+        rmsnorm_valid_kernel<MODE, BIAS, 1><<<M, threads, 0, st>>>(y, resid, hidden, partial, splits, bias, w, eps, M, H, Hv);  \
+    }                                                                                                                           \
+    else {                                                                                                                      \
+        rmsnorm_valid_kernel<MODE, BIAS, 2><<<M, threads, 0, st>>>(y, resid, hidden, partial, splits, bias, w, eps, M, H, Hv);  \
+    }
+        if (partial) {
+            if (bias) {
+                TM_NORM_LAUNCH_VALID(2, true)
+            }
+            else {
+                TM_NORM_LAUNCH_VALID(2, false)
+            }
+        }
+        else {
+            if (bias) {
+                TM_NORM_LAUNCH_VALID(1, true)
+            }
+            else {
+                TM_NORM_LAUNCH_VALID(1, false)
+            }
+        }
+#undef TM_NORM_LAUNCH_VALID
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     uint64_t* const dbg = gemm_trace_for((size_t)M, partial ? "reduce_norm" : "resid_norm", M, 1, 1);
 #define TM_NORM_LAUNCH(MODE, BIAS)                                                                                    \
     if (nv == 1) {                                                                                                    \

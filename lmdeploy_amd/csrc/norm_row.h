@@ -45,24 +45,33 @@ __device__ __forceinline__ float norm_block_sum(float v, float* smem, int tid, i
 // issued before anything is consumed.  Threads past the row end load clamped (valid) addresses and skip the stores.
 // Two halves: norm_row_load (what does not depend on the producing GEMM: residual, norm weight), then norm_row_finish
 // (slabs -> sum -> residual add -> norm -> stores).
+// VALID (compile time; rows of a zero-padded model, Hv < H, both multiples of 8): only the columns [0, Hv) are the row.  The pad
+// columns [Hv, H) of every input are never read (their threads load the clamped address of the last valid vector), add nothing to the
+// sum of squares, the divisor is Hv, and y / resid receive +0 there -- whatever the inputs hold.  VALID = false is the code as it was.
 template<int NV>
 struct NormRowRegs {
     half8_t wv[NV], r[NV], hc[NV], bv[NV];
     size_t  off[NV];
     bool    ok[NV];
+    int     pad[NV];  // VALID only: > 0 for a vector of the pad columns -- its distance in elements from the (clamped) vector that
+                      // `off` addresses and the loads read; its stores go to off + pad and write +0
 };
 
-template<int MODE, bool HAS_BIAS, int NV>
+template<int MODE, bool HAS_BIAS, int NV, bool VALID = false>
 __device__ __forceinline__ void norm_row_load(NormRowRegs<NV>& g, const half_t* __restrict__ resid, const half_t* __restrict__ hidden,
                                               const half_t* __restrict__ bias, const half_t* __restrict__ weight, int H, int row, int tid,
-                                              int nthreads)
+                                              int nthreads, int Hv = 0)
 {
     const int nvec = H / 8;
+    const int nval = VALID ? Hv / 8 : nvec;  // vectors that may be read
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int vi = tid + i * nthreads;
         g.ok[i]      = tid < nthreads && vi < nvec;
-        const int vc = g.ok[i] ? vi : nvec - 1;
+        const int vc = (g.ok[i] && vi < nval) ? vi : nval - 1;
+        if constexpr (VALID) {
+            g.pad[i] = g.ok[i] ? (vi - vc) * 8 : 0;
+        }
         g.off[i]     = (size_t)row * H + (size_t)vc * 8;
         g.wv[i]      = *(const half8_t*)(weight + (size_t)vc * 8);
         g.r[i]       = *(const half8_t*)((MODE == 0 ? hidden : resid) + g.off[i]);
@@ -75,10 +84,10 @@ __device__ __forceinline__ void norm_row_load(NormRowRegs<NV>& g, const half_t* 
     }
 }
 
-template<int MODE, bool HAS_BIAS, int NV>
+template<int MODE, bool HAS_BIAS, int NV, bool VALID = false>
 __device__ __forceinline__ void norm_row_finish(NormRowRegs<NV>& g, half_t* __restrict__ y, half_t* __restrict__ resid,
                                                 const float* __restrict__ partial, int splits, float eps, int M, int H, int tid,
-                                                int nthreads, float* red)
+                                                int nthreads, float* red, int Hv = 0)
 {
     const size_t slab = (size_t)M * H;
     floatx4      a[NV][4][2];
@@ -132,9 +141,14 @@ __device__ __forceinline__ void norm_row_finish(NormRowRegs<NV>& g, half_t* __re
         if constexpr (HAS_BIAS) {
             g.r[i] = g.r[i] + g.bv[i];
         }
+        if constexpr (VALID) {
+            if (g.pad[i]) {  // a select, not a product: what the clamped loads brought (NaN included) does not survive
+                g.r[i] = half8_t{};
+            }
+        }
         if (g.ok[i]) {
             if constexpr (MODE != 0) {
-                *(half8_t*)(resid + g.off[i]) = g.r[i];
+                *(half8_t*)(resid + g.off[i] + (VALID ? g.pad[i] : 0)) = g.r[i];
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -145,7 +159,7 @@ __device__ __forceinline__ void norm_row_finish(NormRowRegs<NV>& g, half_t* __re
     }
 
     ss              = norm_block_sum(ss, red, tid, nthreads);
-    const float inv = 1.0f / __builtin_sqrtf(ss / (float)H + eps);
+    const float inv = 1.0f / __builtin_sqrtf(ss / (float)(VALID ? Hv : H) + eps);
 
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -156,20 +170,25 @@ __device__ __forceinline__ void norm_row_finish(NormRowRegs<NV>& g, half_t* __re
                 const half_t n = (half_t)((float)g.r[i][e] * inv);  // cast to T first ...
                 o[e]           = n * g.wv[i][e];                    // ... then multiply by w in T
             }
-            *(half8_t*)(y + g.off[i]) = o;
+            if constexpr (VALID) {
+                if (g.pad[i]) {  // +0, not 0 * w (-0 under a negative weight)
+                    o = half8_t{};
+                }
+            }
+            *(half8_t*)(y + g.off[i] + (VALID ? g.pad[i] : 0)) = o;
         }
     }
 }
 
-template<int MODE, bool HAS_BIAS, int NV>
+template<int MODE, bool HAS_BIAS, int NV, bool VALID = false>
 __device__ __forceinline__ void norm_row(half_t* __restrict__ y, half_t* __restrict__ resid, const half_t* __restrict__ hidden,
                                          const float* __restrict__ partial, int splits, const half_t* __restrict__ bias,
                                          const half_t* __restrict__ weight, float eps, int M, int H, int row, int tid, int nthreads,
-                                         float* red)
+                                         float* red, int Hv = 0)
 {
     NormRowRegs<NV> g;
-    norm_row_load<MODE, HAS_BIAS, NV>(g, resid, hidden, bias, weight, H, row, tid, nthreads);
-    norm_row_finish<MODE, HAS_BIAS, NV>(g, y, resid, partial, splits, eps, M, H, tid, nthreads, red);
+    norm_row_load<MODE, HAS_BIAS, NV, VALID>(g, resid, hidden, bias, weight, H, row, tid, nthreads, Hv);
+    norm_row_finish<MODE, HAS_BIAS, NV, VALID>(g, y, resid, partial, splits, eps, M, H, tid, nthreads, red, Hv);
 }
 
 }  // namespace tmk

@@ -41,9 +41,11 @@ struct KvCacheView {
 };
 
 // ---- norm.hip ---------------------------------------------------------------------------
-int launch_rmsnorm(half_t* y, const half_t* x, const half_t* w, float eps, int M, int H, hipStream_t st);
+// Hv (0 = H): the row's valid width; Hv != H runs the variant for zero-padded rows (norm_row.h, VALID): sum over [0, Hv), divisor Hv,
+// columns [Hv, H) of the inputs never read and written as +0
+int launch_rmsnorm(half_t* y, const half_t* x, const half_t* w, float eps, int M, int H, hipStream_t st, int Hv = 0);
 int launch_residual_rmsnorm(half_t* y, half_t* resid, const half_t* hidden, const float* partial, int splits,
-                            const half_t* bias, const half_t* w, float eps, int M, int H, hipStream_t st);
+                            const half_t* bias, const half_t* w, float eps, int M, int H, hipStream_t st, int Hv = 0);
 
 // ---- kv_cache.hip -----------------------------------------------------------------------
 // RoPE(q,k) in fp16 from a (cos,sin) table, quantise K/V of the new tokens and scatter them into the

@@ -186,7 +186,10 @@ class TurbomindEngineConfig:
     TM_KV_RING=0 at engine creation switches the ring off.
     The gpt-oss MoE block -- MXFP4 experts (e2m1 codes, one ue8m0 scale byte per 32 weights), router and per-expert biases, the clamped
     gate * sigmoid(1.702 gate) * (1 + up) activation -- is served with tp = 1 (`synthetic:tiny_gptoss_moe` with model_format='hf' runs
-    it); a published gpt-oss checkpoint is not loadable yet (hidden 2880 is no multiple of 128, no o_proj bias)."""
+    it).  A published gpt-oss checkpoint (GptOssForCausalLM: MXFP4 experts, or the unquantised form save_pretrained writes) loads with
+    tp = 1 and runs in fp16: hidden / expert width 2880 are served zero-padded to 2944, the o_proj bias, the sinks, the per-layer windows of
+    `layer_types` and YaRN with `truncate: false` are read from the checkpoint; tp > 1 is refused, the chat template is not applied
+    (`synthetic:gpt_oss_20b` with model_format='hf' is the 20b geometry for timing)."""
     dtype: str = 'auto'
     model_format: str | None = None
     tp: int = 1

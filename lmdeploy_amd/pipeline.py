@@ -8,6 +8,7 @@ poll: requests leave the batch when they stop, waiting ones take their slots).
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Sequence
 
@@ -44,6 +45,13 @@ SYNTHETIC = {
     'tiny_gptoss_moe': dict(hidden=256, layers=2, q_heads=4, kv_heads=2, head_dim=128, inter=128, vocab=1024,
                             rope=checkpoint.RopeConfig(128, 10000.0), moe_experts=8, moe_top_k=2, moe_expert_format=3, moe_act=1,
                             moe_bias=1),
+    # the published gpt-oss-20b geometry, for timing (model_format='hf': fp16 attention next to the MXFP4 experts): hidden and expert
+    # width 2880 run zero-padded at 2944; the pad channels hold synthetic values like every other weight
+    'gpt_oss_20b': dict(hidden=2880, layers=24, q_heads=64, kv_heads=8, head_dim=64, inter=2880, vocab=201088,
+                        rope=checkpoint.RopeConfig(64, 150000.0, 'yarn', 32.0, max_position_embeddings=4096,
+                                                   attention_factor=0.1 * math.log(32.0) + 1.0, truncate=False),
+                        moe_experts=32, moe_top_k=4, moe_expert_format=3, moe_act=1, moe_bias=1, attn_bias=1, attn_out_bias=1,
+                        attn_sinks=1, layer_windows=[128, 0] * 12, max_position_embeddings=131072),
 }
 
 
@@ -79,7 +87,7 @@ class Pipeline:
                                                     quantized=cfg.model_format != 'hf',
                                                     weight_format={'hf': 'f16', 'fp8': 'fp8'}.get(cfg.model_format, 'u4'))
         else:
-            self.model_cfg = checkpoint.read_config(model_path)
+            self.model_cfg = checkpoint.read_config(model_path, cfg.tp)
             have = self.model_cfg.weight_format if self.model_cfg.quantized else 'f16'
             if cfg.model_format in ('awq', 'fp8') and {'awq': 'u4', 'fp8': 'fp8'}[cfg.model_format] != have:
                 raise ValueError(f'model_format="{cfg.model_format}" but the checkpoint\'s quantization_config says {have} '

@@ -1,7 +1,8 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
 Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
-FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (dense linears and MoE experts alike):
+FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (dense linears and MoE experts alike), and for gpt-oss
+(GptOssForCausalLM: MXFP4 experts as published, or the bf16 experts transformers' save_pretrained writes; served zero-padded):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
                                      qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head;
                                      Qwen3-MoE: mlp.gate router + mlp.experts.X.{gate,up,down}_proj, qwen3.py:110-121;
@@ -23,7 +24,7 @@ from glob import glob
 
 import numpy as np
 
-from .loader import interleave_gate_up, permute_qk_for_interleaved_rope, unpack_awq_gemm
+from .loader import interleave_gate_up, pad_model_weights, permute_qk_for_interleaved_rope, unpack_awq_gemm
 
 
 @dataclass
@@ -42,6 +43,9 @@ class RopeConfig:
     beta_fast: float = 32.0
     beta_slow: float = 1.0
     attention_factor: float = 1.0
+    # yarn: True = the correction range is rounded outwards (the reference; transformers' default), False = it stays fractional
+    # (transformers' `truncate: false`: gpt-oss)
+    truncate: bool = True
 
 
 @dataclass
@@ -73,6 +77,9 @@ class ModelConfig:
     moe_expert_format: int = 0         # 0: the experts follow weight_format; 3: MXFP4 experts (gpt-oss) next to fp16 / u4 attention
     moe_act: int = 0                   # 0: silu(gate) * up; 1: gpt-oss, clamped gate * sigmoid(1.702 gate) * (1 + up)
     moe_bias: int = 0                  # gpt-oss: router bias [E] and per-expert biases on w1w3 / w2
+    attn_out_bias: int = 0             # gpt-oss: the o projection carries a bias
+    attn_sinks: int = 0                # gpt-oss: one sink logit per q head joins every softmax
+    layer_windows: list | None = None  # gpt-oss: one sliding window per layer (0 = full attention), from `layer_types`
 
 
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
@@ -134,16 +141,97 @@ def _scaled_rope(t: str, rs: dict, D: int, base: float, max_pos: int) -> RopeCon
                       beta_slow=float(rs.get('beta_slow', 1.0)), attention_factor=float(af))
 
 
-def read_config(model_path: str) -> ModelConfig:
+def _merged_eos(c: dict, model_path: str):
+    """eos ids: config.json + generation_config.json (GenerationConfig.update_from_hf_gen_cfg, lmdeploy/messages.py:176-199)"""
+    eos = c.get('eos_token_id')
+    gpath = os.path.join(model_path, 'generation_config.json')
+    if os.path.exists(gpath):
+        with open(gpath) as f:
+            ge = json.load(f).get('eos_token_id')
+        if ge is not None:
+            merged = list(eos if isinstance(eos, (list, tuple)) else ([] if eos is None else [eos]))
+            merged += [t for t in (ge if isinstance(ge, (list, tuple)) else [ge]) if t not in merged]
+            eos = merged if len(merged) > 1 else merged[0]
+    return eos
+
+
+def _read_gpt_oss(arch: str, c: dict, model_path: str, tp: int) -> ModelConfig:
+    """GptOssForCausalLM (transformers/models/gpt_oss): head_dim 64 attention with q / k / v / o biases and sinks, sliding and full
+    layers alternating as `layer_types` says, YaRN with a fractional correction range, an MoE block with MXFP4 (published) or bf16
+    (save_pretrained) experts, router and expert biases and the clamped activation.  hidden_size / intermediate_size that are no
+    multiple of 128 (2880) stay as published here: the loader pads the tensors and make_model_config hands the engine the padded
+    sizes."""
+    H = c.get('hidden_size')
+    rs = c.get('rope_parameters') or c.get('rope_scaling')
+    have = dict(c, rope_settings=rs if rs and (c.get('rope_parameters') or c.get('rope_theta') is not None) else None)
+    missing = [k for k in ('layer_types', 'sliding_window', 'rope_settings') if have.get(k) is None]
+    if missing:
+        names = ', '.join('rope_scaling + rope_theta (or rope_parameters)' if k == 'rope_settings' else k for k in missing)
+        raise NotImplementedError(f'{arch}: config.json lacks {names} -- which layers slide, over how many tokens and under which RoPE '
+                                  f'cannot be known without them (a library default would describe some other checkpoint).  '
+                                  f'hidden_size {H} (% 128 != 0 for gpt-oss: 2880 = 22.5 x 128) is served zero-padded to the next '
+                                  f'multiple of 128 and the o_proj bias is loaded, for a complete config only')
+    if tp > 1:
+        raise NotImplementedError(f'{arch} with tp = {tp}: the zero-padded norm, the o_proj bias and the MXFP4 experts are built for '
+                                  f'tp = 1 only')
+    q = c.get('quantization_config')
+    if q is not None and q.get('quant_method') != 'mxfp4':
+        raise NotImplementedError(f'{arch} with quantization_config {q}: the experts are served as MXFP4 (quant_method "mxfp4", the '
+                                  f'published form) or unquantised (no quantization_config)')
+    if float(c.get('swiglu_limit', 7.0)) != 7.0:
+        raise NotImplementedError(f'{arch} with swiglu_limit {c["swiglu_limit"]}: the expert activation clamps at 7')
+    if q is None:
+        dt = str(c.get('torch_dtype', c.get('dtype'))).replace('torch.', '')
+        if dt not in ('float16', 'bfloat16'):
+            raise NotImplementedError(f'{arch} without a quantization_config and with torch_dtype {dt}: unquantised experts are served '
+                                      f'from float16 / bfloat16 checkpoints (config.json must say so)')
+    if not c.get('attention_bias', True):
+        raise NotImplementedError(f'{arch} with attention_bias false: the reader loads the q / k / v / o biases of every layer')
+    heads, layers = c['num_attention_heads'], c['num_hidden_layers']
+    D = c.get('head_dim') or H // heads
+    if D not in (64, 128) or heads * D % 128:
+        raise NotImplementedError(f'{arch} with {heads} attention heads of head_dim {D}: head_dim must be 64 or 128 and '
+                                  f'num_attention_heads * head_dim a multiple of 128')
+    E, k = int(c.get('num_local_experts') or 0), int(c.get('num_experts_per_tok') or 0)
+    if not 1 <= E <= 256 or not 1 <= k <= 8 or k > E:
+        raise NotImplementedError(f'{arch} with num_local_experts {E}, num_experts_per_tok {k}: the router serves up to 256 experts, top-8')
+    types, sw = list(c['layer_types']), c['sliding_window']
+    if len(types) != layers or any(t not in ('sliding_attention', 'full_attention') for t in types):
+        raise NotImplementedError(f'{arch}: layer_types {types} must name sliding_attention or full_attention for each of the {layers} layers')
+    if isinstance(sw, bool) or not isinstance(sw, int) or sw <= 0:
+        raise ValueError(f'{arch}: sliding_window {sw!r} must be a positive integer')
+    base = rs.get('rope_theta', c.get('rope_theta'))
+    if base is None:
+        raise NotImplementedError(f'{arch}: config.json lacks rope_theta')
+    max_pos = int(c.get('max_position_embeddings', 0))
+    t = rs.get('rope_type', rs.get('type'))
+    if t == 'yarn':
+        if 'original_max_position_embeddings' not in rs or max_pos <= 0:
+            raise NotImplementedError(f'{arch}: YaRN needs original_max_position_embeddings and max_position_embeddings')
+        # factor and attention factor as for Llama / InternLM; the correction range is taken over the ORIGINAL length and left
+        # fractional under `truncate: false`, as transformers computes it (DESIGN 7.6: the reference's parse does neither)
+        rope = _scaled_rope('yarn', rs, D, float(base), max_pos)
+        rope.max_position_embeddings = int(rs['original_max_position_embeddings'])
+        rope.truncate = bool(rs.get('truncate', True))
+    elif t in (None, 'default'):
+        rope = RopeConfig(dim=D, base=float(base))
+    else:
+        raise NotImplementedError(f'{arch}: rope type {t}')
+    return ModelConfig(hidden=H, layers=layers, q_heads=heads, kv_heads=c.get('num_key_value_heads', heads), head_dim=D,
+                       inter=c['intermediate_size'], vocab=c['vocab_size'], rms_eps=float(c.get('rms_norm_eps', 1e-5)), rope=rope,
+                       arch='gpt_oss', quantized=False, weight_format='f16', moe_experts=E, moe_top_k=k, moe_norm_topk=True,
+                       eos_token_id=_merged_eos(c, model_path), max_position_embeddings=max_pos or 8192, attn_bias=1, attn_out_bias=1,
+                       attn_sinks=1, layer_windows=[int(sw) if t_ == 'sliding_attention' else 0 for t_ in types],
+                       moe_expert_format=3 if q is not None else 0, moe_act=1, moe_bias=1,
+                       tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
+
+
+def read_config(model_path: str, tp: int = 1) -> ModelConfig:
     with open(os.path.join(model_path, 'config.json')) as f:
         c = json.load(f)
     arch = (c.get('architectures') or ['LlamaForCausalLM'])[0]
     if arch == 'GptOssForCausalLM':
-        # the MoE block is served (MXFP4 experts, router / expert biases, the clamped activation: gpt_oss_expert_slots maps the
-        # published tensors), as are sliding windows, sinks and YaRN.  What a published checkpoint still needs:
-        raise NotImplementedError(f'{arch}: not loadable yet -- hidden_size {c.get("hidden_size")} % 128 != 0 is not served (every '
-                                  f'GEMM, norm and router takes K % 128 == 0; gpt-oss has 2880 = 22.5 x 128) and the o_proj bias is '
-                                  f'not implemented')
+        return _read_gpt_oss(arch, c, model_path, tp)
     kind = 'internlm2' if 'InternLM2' in arch else 'llama'
     qwen = arch in QWEN_ARCHS
     internlm3 = arch == 'InternLM3ForCausalLM'      # a plain Llama (the reference: supported_models.py) -- without projection biases
@@ -207,16 +295,7 @@ def read_config(model_path: str) -> ModelConfig:
             rope = _scaled_rope(t, rs, D, rope.base, int(c.get('max_position_embeddings', 0)))
         elif t not in (None, 'default'):
             raise NotImplementedError(f'rope_scaling type {t}')
-    # eos ids: config.json + generation_config.json (GenerationConfig.update_from_hf_gen_cfg, lmdeploy/messages.py:176-199)
-    eos = c.get('eos_token_id')
-    gpath = os.path.join(model_path, 'generation_config.json')
-    if os.path.exists(gpath):
-        with open(gpath) as f:
-            ge = json.load(f).get('eos_token_id')
-        if ge is not None:
-            merged = list(eos if isinstance(eos, (list, tuple)) else ([] if eos is None else [eos]))
-            merged += [t for t in (ge if isinstance(ge, (list, tuple)) else [ge]) if t not in merged]
-            eos = merged if len(merged) > 1 else merged[0]
+    eos = _merged_eos(c, model_path)
     c = dict(c, eos_token_id=eos)
     if arch == 'Qwen3MoeForCausalLM':
         moe = _qwen3_moe_fields(arch, c, q is not None)
@@ -265,6 +344,74 @@ def gpt_oss_expert_slots(tensors: dict, layer: int) -> dict:
         slots[q + '.w2.scales'] = np.ascontiguousarray(dn_s[x])
         slots[q + '.w2.bias'] = np.ascontiguousarray(dn_bias[x], dtype=np.float16)
     return slots
+
+
+def gpt_oss_expert_slots_f16(tensors: dict, layer: int) -> dict:
+    """gpt_oss_expert_slots for the unquantised form (what transformers' save_pretrained writes, bf16 or fp16):
+      model.layers.{i}.mlp.experts.gate_up_proj [E, H, 2I]   input-major, columns (gate_j, up_j)-interleaved: w1w3 [K][N] as stored
+      ...gate_up_proj_bias [E, 2I]     ...down_proj [E, I, H]     ...down_proj_bias [E, H]     router as published
+    -> fp16 "...w1w3.weight" [H][2I] / "...w2.weight" [I][H] slots next to the same bias and router slots."""
+    m = f'model.layers.{layer}.mlp'
+    gu, gu_bias = np.asarray(tensors[f'{m}.experts.gate_up_proj']), np.asarray(tensors[f'{m}.experts.gate_up_proj_bias'])
+    dn, dn_bias = np.asarray(tensors[f'{m}.experts.down_proj']), np.asarray(tensors[f'{m}.experts.down_proj_bias'])
+    rw, rb = np.asarray(tensors[f'{m}.router.weight']), np.asarray(tensors[f'{m}.router.bias'])
+    E, H, N13 = gu.shape
+    I = N13 // 2
+    if N13 % 2 or gu_bias.shape != (E, N13) or dn.shape != (E, I, H) or dn_bias.shape != (E, H) or rw.shape != (E, H) or rb.shape != (E,):
+        raise ValueError(f'{m}: tensor shapes do not describe {E} experts of hidden {H}, width {I}')
+    p = f'layers.{layer}.moe_ffn'
+    slots = {p + '.gate.weight': np.ascontiguousarray(rw.astype(np.float16).T),
+             p + '.gate.bias': np.ascontiguousarray(rb, dtype=np.float32)}
+    for x in range(E):
+        q = f'{p}.experts.{x}'
+        slots[q + '.w1w3.weight'] = np.ascontiguousarray(gu[x], dtype=np.float16)
+        slots[q + '.w1w3.bias'] = np.ascontiguousarray(gu_bias[x], dtype=np.float16)
+        slots[q + '.w2.weight'] = np.ascontiguousarray(dn[x], dtype=np.float16)
+        slots[q + '.w2.bias'] = np.ascontiguousarray(dn_bias[x], dtype=np.float16)
+    return slots
+
+
+def _load_gpt_oss(t: '_Tensors', cfg: ModelConfig) -> dict:
+    """GptOssForCausalLM -> the weights of export_weights, zero-padded to multiples of 128 (loader.pad_model_weights)"""
+    D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
+    layers = []
+    for i in range(cfg.layers):
+        p = f'model.layers.{i}'
+        a = p + '.self_attn.'
+        q, k, v, wo = (_linear(t, a + n, False) for n in ('q_proj', 'k_proj', 'v_proj', 'o_proj'))
+        q = _map(q, lambda w: permute_qk_for_interleaved_rope(w, Hq, D))
+        k = _map(k, lambda w: permute_qk_for_interleaved_rope(w, Hkv, D))
+        qkv_bias = np.concatenate([permute_qk_for_interleaved_rope(t.get(a + 'q_proj.bias').astype(np.float16), Hq, D),
+                                   permute_qk_for_interleaved_rope(t.get(a + 'k_proj.bias').astype(np.float16), Hkv, D),
+                                   t.get(a + 'v_proj.bias').astype(np.float16)])
+        m = p + '.mlp'
+        mx = cfg.moe_expert_format == 3
+        names = [f'{m}.router.weight', f'{m}.router.bias'] + [
+            f'{m}.experts.{w}{sfx}' for w in ('gate_up_proj', 'down_proj') for sfx in (('_blocks', '_scales', '_bias') if mx else ('', '_bias'))]
+        missing = [n for n in names if n not in t]
+        if missing:
+            raise FileNotFoundError(f'gpt-oss checkpoint ({"MXFP4" if mx else "unquantised"} experts per config.json) lacks {missing[0]}')
+        slots = (gpt_oss_expert_slots if mx else gpt_oss_expert_slots_f16)({n: t.get(n) for n in names}, i)
+        s = f'layers.{i}.moe_ffn'
+        if slots[s + '.gate.weight'].shape != (cfg.hidden, cfg.moe_experts):
+            raise ValueError(f'{m}: the tensors describe a router of {slots[s + ".gate.weight"].shape}, config.json says '
+                             f'({cfg.hidden}, {cfg.moe_experts})')
+        experts = []
+        for x in range(cfg.moe_experts):
+            e = f'{s}.experts.{x}'
+            lin = (lambda w: dict(blocks=slots[f'{e}.{w}.blocks'], scales=slots[f'{e}.{w}.scales'])) if mx else \
+                (lambda w: dict(w=slots[f'{e}.{w}.weight']))
+            experts.append(dict(w1w3=lin('w1w3'), w2=lin('w2'), w1w3_bias=slots[e + '.w1w3.bias'], w2_bias=slots[e + '.w2.bias']))
+        layers.append(dict(attn_norm=t.get(p + '.input_layernorm.weight').astype(np.float16),
+                           ffn_norm=t.get(p + '.post_attention_layernorm.weight').astype(np.float16), w_qkv=_cat([q, k, v]), wo=wo,
+                           qkv_bias=qkv_bias, wo_bias=t.get(a + 'o_proj.bias').astype(np.float16),
+                           sinks=t.get(a + 'sinks').astype(np.float16), moe_gate=slots[s + '.gate.weight'],
+                           moe_gate_bias=slots[s + '.gate.bias'], experts=experts))
+    emb = t.get('model.embed_tokens.weight')
+    head = emb if (cfg.tie_word_embeddings or 'lm_head.weight' not in t) else t.get('lm_head.weight')
+    w = dict(tok_embeddings=emb.astype(np.float16), layers=layers, norm=t.get('model.norm.weight').astype(np.float16),
+             output=np.ascontiguousarray(head.astype(np.float16).T))
+    return pad_model_weights(w, cfg.hidden, cfg.inter)
 
 
 class _Tensors:
@@ -330,6 +477,8 @@ def _fuse_w1w3(w1: dict, w3: dict) -> dict:
 
 def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
     t = _Tensors(model_path)
+    if cfg.arch == 'gpt_oss':
+        return _load_gpt_oss(t, cfg)
     D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
     layers = []
     llama_names = cfg.arch != 'internlm2'        # Llama / Mixtral / Qwen2 / Qwen3

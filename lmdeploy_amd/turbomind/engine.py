@@ -22,9 +22,12 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     .factor,.low_freq_factor,.high_freq_factor,.original_max_position_embeddings; optional .max_position_embeddings, .beta_fast,
     .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert;
     moe_expert_format 3 = MXFP4 experts, moe_act 1 = the gpt-oss activation, moe_bias = router and expert biases), attn_bias,
-    qk_norm, window (sliding window of every layer, 0 = none), attn_sinks."""
+    qk_norm, window (sliding window of every layer, 0 = none), attn_sinks, attn_out_bias (o_proj bias), rope.truncate (YaRN: False =
+    fractional correction range).  hidden / inter that are no multiple of 128 (gpt-oss: 2880) are handed over as the next multiple,
+    the width the loader pads every tensor to (loader.pad_model_weights), with hidden_valid = the model's own hidden size."""
     r = cfg.rope
-    return _ffi.ModelConfig(cfg.hidden, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, cfg.inter, cfg.vocab,
+    Hp, Ip = -(-cfg.hidden // 128) * 128, -(-cfg.inter // 128) * 128
+    return _ffi.ModelConfig(Hp, cfg.layers, cfg.q_heads, cfg.kv_heads, cfg.head_dim, Ip, cfg.vocab,
                             cfg.rms_eps, r.base, _ROPE_TYPES[r.type], r.factor, r.low_freq_factor, r.high_freq_factor,
                             r.original_max_position_embeddings, int(getattr(r, 'max_position_embeddings', 0) or 0),
                             float(getattr(r, 'beta_fast', 32.0)), float(getattr(r, 'beta_slow', 1.0)),
@@ -35,6 +38,8 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
                             int(bool(getattr(cfg, 'moe_bias', 0))),
                             int(getattr(cfg, 'moe_shared_inter', 0) or 0),
                             int(getattr(cfg, 'window', 0) or 0), int(bool(getattr(cfg, 'attn_sinks', 0))),
+                            int(bool(getattr(cfg, 'attn_out_bias', 0))), cfg.hidden if Hp != cfg.hidden else 0,
+                            int(bool(getattr(r, 'truncate', True))),
                             int(bool(getattr(cfg, 'attn_bias', 0))), int(bool(getattr(cfg, 'qk_norm', 0))))
 
 

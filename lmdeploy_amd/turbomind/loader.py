@@ -46,6 +46,81 @@ def interleave_gate_up(w1: np.ndarray, w3: np.ndarray) -> np.ndarray:
     return out
 
 
+def roundup128(n: int) -> int:
+    return -(-int(n) // 128) * 128
+
+
+def pad_f16(a: np.ndarray, shape: tuple) -> np.ndarray:
+    """a in the leading corner of a +0 array of `shape` (same dtype)"""
+    a = np.asarray(a)
+    assert a.ndim == len(shape) and all(n <= m for n, m in zip(a.shape, shape)), f'cannot pad {a.shape} to {shape}'
+    if a.shape == tuple(shape):
+        return a
+    out = np.zeros(shape, a.dtype)
+    out[tuple(slice(0, n) for n in a.shape)] = a
+    return out
+
+
+def pad_mxfp4(lin: dict, N: int, K: int) -> dict:
+    """MXFP4 linear {'blocks' uint8 [n, k / 2], 'scales' uint8 [n, k / 32]} -> [N, K / 2], [N, K / 32]: the pad codes are 0x00 (two e2m1
+    +0) and the pad scale bytes 127 (2^0), along K and along N alike -- every pad weight dequantises to +0."""
+    blocks, scales = np.asarray(lin['blocks']), np.asarray(lin['scales'])
+    n, k2 = blocks.shape
+    assert blocks.dtype == np.uint8 and scales.dtype == np.uint8 and scales.shape == (n, k2 // 16) and K % 32 == 0
+    sc = np.full((N, K // 32), 127, np.uint8)
+    sc[:n, :k2 // 16] = scales
+    return dict(blocks=pad_f16(blocks, (N, K // 2)), scales=sc)
+
+
+def _pad_linear(lin: dict, K: int, N: int, what: str) -> dict:
+    """an fp16 linear {'w' [k, n]} or an MXFP4 one (output-major) to K x N"""
+    if 'blocks' in lin:
+        return pad_mxfp4(lin, N, K)
+    if 'w' not in lin:
+        raise NotImplementedError(f'{what}: only fp16 and MXFP4 linears are served zero-padded (AWQ / FP8 groups would straddle the pad)')
+    return dict(w=pad_f16(lin['w'], (K, N)))
+
+
+def pad_model_weights(weights: dict, H: int, inter: int) -> dict:
+    """The weights of export_weights with every hidden axis padded from H to roundup128(H) and every FFN-width axis from `inter` to
+    roundup128(inter), so that a model whose sizes are no multiple of 128 (gpt-oss: 2880 -> 2944) runs on the engine's GEMMs as they are.
+    All pads are +0 (MXFP4: code 0x00 under scale byte 127): embedding columns, lm_head K rows, norm weights, w_qkv K rows, wo N columns
+    and bias, router rows, expert w1w3 K rows and extra (gate, up) column pairs with +0 biases, w2 K rows, N columns and bias.  A padded
+    (gate, up) pair gives act(0, 0) = 0 -- silu(0) * 0, and 0 * sigmoid(0) * (1 + 0) for gpt-oss -- so w2's pad rows see only zeros; the
+    norms write +0 into the pad columns of the residual stream (tm_model_config.hidden_valid).  Sizes that are multiples of 128 already:
+    the same arrays."""
+    Hp, Ip = roundup128(H), roundup128(inter)
+    if (Hp, Ip) == (H, inter):
+        return weights
+
+    def ffn(d: dict, what: str) -> dict:
+        out = dict(d, w1w3=_pad_linear(d['w1w3'], Hp, 2 * Ip, what + '.w1w3'), w2=_pad_linear(d['w2'], Ip, Hp, what + '.w2'))
+        if 'w1w3_bias' in d:
+            out.update(w1w3_bias=pad_f16(d['w1w3_bias'], (2 * Ip,)), w2_bias=pad_f16(d['w2_bias'], (Hp,)))
+        return out
+
+    layers = []
+    for li, L in enumerate(weights['layers']):
+        if 'shared_gate' in L:
+            raise NotImplementedError('a shared expert is not served zero-padded')
+        if 'w' not in L['w_qkv'] or 'w' not in L['wo']:
+            raise NotImplementedError(f'layers.{li}.attention: only fp16 attention linears are served zero-padded')
+        P = dict(L, attn_norm=pad_f16(L['attn_norm'], (Hp,)), ffn_norm=pad_f16(L['ffn_norm'], (Hp,)),
+                 w_qkv=_pad_linear(L['w_qkv'], Hp, L['w_qkv']['w'].shape[1], f'layers.{li}.w_qkv'),
+                 wo=_pad_linear(L['wo'], L['wo']['w'].shape[0], Hp, f'layers.{li}.wo'))
+        if 'wo_bias' in L:
+            P['wo_bias'] = pad_f16(L['wo_bias'], (Hp,))
+        if 'experts' in L:
+            P['moe_gate'] = pad_f16(L['moe_gate'], (Hp, np.asarray(L['moe_gate']).shape[1]))
+            P['experts'] = [ffn(E_, f'layers.{li}.experts.{x}') for x, E_ in enumerate(L['experts'])]
+        else:
+            P.update(ffn(L, f'layers.{li}.feed_forward'))
+        layers.append(P)
+    V = np.asarray(weights['tok_embeddings']).shape[0]
+    return dict(weights, tok_embeddings=pad_f16(weights['tok_embeddings'], (V, Hp)), norm=pad_f16(weights['norm'], (Hp,)),
+                output=pad_f16(weights['output'], (Hp, np.asarray(weights['output']).shape[1])), layers=layers)
+
+
 def _cols(t: np.ndarray, lo: int, hi: int) -> np.ndarray:
     return t[..., lo:hi]
 
@@ -105,14 +180,14 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
     """weights (unsharded, TM layout): {'tok_embeddings' [V,H], 'norm' [H], 'output' [H,V],
     'layers': [{'attn_norm','ffn_norm', 'w_qkv','wo','w1w3','w2': linear dicts}]} with w_qkv = [Q|K|V] along N and
     w1w3 already (gate_j, up_j)-interleaved; Qwen layers add 'qkv_bias' [Hq*D + 2*Hkv*D] (q / k permuted like w_qkv) and /
-    or 'q_norm', 'k_norm' [D]; layers with attention sinks add 'sinks' [Hq]; MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
+    or 'q_norm', 'k_norm' [D]; layers with attention sinks add 'sinks' [Hq], layers with an o_proj bias 'wo_bias' [H] (tp = 1); MoE layers carry 'moe_gate' [H,E] and 'experts' [{'w1w3','w2'}] instead of w1w3 / w2, Qwen2-MoE layers
     all of them: w1w3 / w2 are then the shared expert (width cfg.moe_shared_inter) next to its 'shared_gate' [H].
     gpt-oss blocks: an MXFP4 expert linear is {'blocks' uint8 [N, K/2], 'scales' uint8 [N, K/32]} (output-major, the checkpoint
     layout; w1w3's N rows (gate_j, up_j)-interleaved); with cfg.moe_bias every expert carries 'w1w3_bias' [2I] and 'w2_bias' [H] and the
     layer 'moe_gate_bias' [E] (fp32).  Neither shards: tp must be 1.
     Returns {slot name: contiguous numpy array} for this rank."""
     D = cfg.head_dim
-    Hq, Hkv, I, G = cfg.q_heads, cfg.kv_heads, cfg.inter, cfg.group
+    Hq, Hkv, I, G = cfg.q_heads, cfg.kv_heads, roundup128(cfg.inter), cfg.group
     assert Hq % tp == 0 and I % tp == 0 and cfg.vocab % tp == 0
     hq_l = Hq // tp
     if Hkv >= tp:
@@ -171,6 +246,10 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
         if 'qkv_bias' in L:    # the same column slices as w_qkv (replicated kv heads included)
             slots[p + '.attention.w_qkv.bias'] = np.ascontiguousarray(
                 np.concatenate([L['qkv_bias'][lo:hi] for lo, hi in qkv_slices]), dtype=np.float16)
+        if 'wo_bias' in L:     # added behind the all-reduce on every rank alike, which the engine does not build: tp == 1
+            if tp > 1:
+                raise ValueError(f'an o_proj bias does not shard over tp = {tp}')
+            slots[p + '.attention.wo.bias'] = np.ascontiguousarray(L['wo_bias'], dtype=np.float16)
         if 'sinks' in L:       # one logit per q head: this rank's heads (the reference: 'sinks': SplitSide.OUTPUT)
             hq_l = Hq // tp
             slots[p + '.attention.sinks'] = np.ascontiguousarray(L['sinks'][rank * hq_l:(rank + 1) * hq_l], dtype=np.float16)

@@ -3,7 +3,8 @@
 contents.  python tools/bench_attention.py [--ctx 1536] [--bits 8] [--splits 1,2,4] [--head-dim 128]
 --head-dim 64 times the head_dim 64 kernel (VALU, every KV width); set TM_ATTN_VALU=1 to time the same kernel family at head_dim 128.
 --window W times tm_decode_attention_window (the VALU kernel's sliding-window variant, both head dims): the bytes per launch are those
-of the last min(ctx, W) tokens.
+of the last min(ctx, W) tokens; --sinks adds one sink logit per head to it.
+--rounds N repeats every measurement (a median of --iters launches each) N times in this one process.
 --engine-decode times whole decode steps of a SYNTHETIC Llama-3.2-1B geometry instead (tm_engine_init_synthetic weights, int8 KV)."""
 import argparse
 import os
@@ -27,6 +28,8 @@ def main():
     ap.add_argument('--engine-decode', action='store_true',
                     help='decode tok/s of a synthetic Llama-3.2-1B geometry (2048 / 16 layers / 32 x 8 heads of 64 / 8192 / 128256)')
     ap.add_argument('--window', type=int, default=0, help='sliding window (0 = none): tm_decode_attention_window')
+    ap.add_argument('--sinks', action='store_true', help='with --window: attention sinks (one logit per head)')
+    ap.add_argument('--rounds', type=int, default=1)
     ap.add_argument('--splits', default='1,2,4')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--trace', action='store_true')
@@ -65,10 +68,12 @@ def main():
     seen = min(ctx, a.window) if a.window > 0 else ctx
     bytes_per_launch = B * seen * 2 * Hkv * (D * bits // 8 + (4 if bits < 16 else 0))
 
+    sinks = torch.empty(Hq, device='cuda').uniform_(-2.0, 4.0).half() if a.sinks else None
+
     def attend(splits, ws, view):
         if a.window > 0:
             return tm.tm_decode_attention_window(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits, ws.data_ptr(),
-                                                 view, a.window, None, st)
+                                                 view, a.window, sinks.data_ptr() if a.sinks else None, st)
         return tm.tm_decode_attention(out.data_ptr(), q.data_ptr(), Hq * D, klen.data_ptr(), B, Hq, 0.0, splits, ws.data_ptr(), view, st)
     if a.trace:
         # in-kernel phase stamps (100 MHz): start / prologue done (q ready, first block issued) / wave 0 done /
@@ -114,22 +119,24 @@ def main():
         return
     for splits in [int(s) for s in a.splits.split(',')]:
         ws = torch.empty(max(1, tm.tm_decode_attention_workspace(B, Hq, splits)), dtype=torch.uint8, device='cuda')
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
-        for i in range(4):   # warm-up: code-object load and clocks, outside the timed launches
-            view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
-            _ffi.check(attend(splits, ws, view))
-        torch.cuda.synchronize()
-        for i, (e0, e1) in enumerate(ev):
-            view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
-            e0.record()
-            _ffi.check(attend(splits, ws, view))
-            e1.record()
-        torch.cuda.synchronize()
-        ts = sorted(x.elapsed_time(y) for x, y in ev)
-        med = ts[len(ts) // 2]
-        gbs = bytes_per_launch / (med * 1e-3) / 1e9
-        print(f'head_dim={D} ctx={ctx} window={a.window} bits={bits} splits={splits}: {med*1e3:8.1f} us  {gbs:7.0f} GB/s = {gbs / 8000:.3f} of 8 TB/s '
-              f'({bytes_per_launch/1e6:.1f} MB/launch)  layout={a.layout} layers={layers}', flush=True)
+        for rnd in range(a.rounds):
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+            for i in range(4):   # warm-up: code-object load and clocks, outside the timed launches
+                view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
+                _ffi.check(attend(splits, ws, view))
+            torch.cuda.synchronize()
+            for i, (e0, e1) in enumerate(ev):
+                view = _ffi.KvCache(tables[i % layers].data_ptr(), cu.data_ptr(), off_of(i % layers), Hkv, D, 64, bits)
+                e0.record()
+                _ffi.check(attend(splits, ws, view))
+                e1.record()
+            torch.cuda.synchronize()
+            ts = sorted(x.elapsed_time(y) for x, y in ev)
+            med = ts[len(ts) // 2]
+            gbs = bytes_per_launch / (med * 1e-3) / 1e9
+            tag = f' round={rnd}' if a.rounds > 1 else ''
+            print(f'head_dim={D} ctx={ctx} window={a.window} bits={bits} splits={splits}{tag}: {med*1e3:8.1f} us  {gbs:7.0f} GB/s = '
+                  f'{gbs / 8000:.3f} of 8 TB/s ({bytes_per_launch/1e6:.1f} MB/launch)  layout={a.layout} layers={layers}', flush=True)
 
 
 def engine_decode(batch, ctx, bits, warmup=8, steps=64, rounds=3):
