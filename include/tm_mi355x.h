@@ -318,6 +318,24 @@ int    tm_linear_fold_consume(const tm_linear* w, const void* xg, int ldx, void*
 /* the fused w1w3 linear of an fp8 checkpoint: (gate_j, up_j)-interleaved e4m3 columns whose block-scale row is
  * [w1's inter/128 blocks | w3's inter/128 blocks] (w1 / w3 are quantised separately; lmdeploy/turbomind/builders/ffn.py:31-34) */
 int    tm_linear_prepare_fp8_gated(tm_linear* w, const void* weight, const void* scales, tm_stream_t st);
+/* Channel-scaled e4m3 weights (per-tensor and per-channel FP8 checkpoints): codes [K][N] with ONE fp32 scale per output column,
+ * scales = device fp32 [N] (a per-tensor scale is that scalar repeated; fused linears concatenate / interleave their parts' scales
+ * like their columns); N % 32 == 0.  Activations are quantised per token over the whole row (tm_quant_fp8_token: codes [M][K],
+ * sx fp32 [M]; absmax clamped to 1e-8, sx = absmax / 448, q = e4m3_rne_sat(x * (448 / absmax)); K % 128 == 0, K <= 32768), and
+ *   y[m, n] = h( (sx[m] * sw[n]) * sum_k xq[m, k] * wq[k, n] )
+ * with the sum chained in fp32 on the matrix core over all of K and the scale product applied once, in the epilogue (split-K slabs
+ * are written scaled).  tm_linear_forward_fp8 / tm_linear_fp8_workspace serve a weight prepared this way; tm_linear_forward does not
+ * (there is no weight-only image: its fp16 (s, 0) scales would push small per-tensor scales into fp16 subnormals), and
+ * TM_FP8_MFMA=0 makes the preparation return TM_INVALID. */
+int    tm_linear_prepare_fp8_channel(tm_linear* w, const void* weight, const void* scales_f32_N, tm_stream_t st);
+int    tm_quant_fp8_token(void* xq, float* sx, const void* x, int ldx, int M, int K, tm_stream_t st);
+/* The grouped (mixture-of-experts) form of tm_linear_forward_fp8 on its own: `experts` = host array of E handles of one shape and
+ * one scale mode; flat output rows seg[e] .. seg[e + 1] (device int32 [E + 1]) belong to expert e and read row row_idx[f] of x
+ * (device int32, NULL: f itself); x fp16 [x_rows][K] is quantised first (per token for channel-scaled experts); m_cap = upper bound
+ * of an expert's rows.  workspace >= tm_linear_fp8_grouped_workspace(E, x_rows, K) bytes.  Synchronises the stream once. */
+size_t tm_linear_fp8_grouped_workspace(int experts, int x_rows, int K);
+int    tm_linear_forward_fp8_grouped(const tm_linear* const* experts, int E, const void* x, int ldx, int x_rows, void* y, int ldy,
+                                     int m_cap, int gated_silu, const int* seg, const int* row_idx, void* workspace, tm_stream_t st);
 size_t tm_linear_fp8_workspace(const tm_linear* w, int M);
 int    tm_quant_fp8_rows(void* xq, float* sx, const void* x, int ldx, int M, int K, int ldsx, tm_stream_t st);
 int    tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
@@ -372,6 +390,10 @@ int    tm_moe_set_shared_gate(tm_moe* m, const void* gate_fp16_hidden, tm_stream
 int    tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void* w13_scales, const void* w13_zeros,
                          const void* w2_weight, const void* w2_scales, const void* w2_zeros, tm_stream_t st);
 int    tm_moe_set_activation(tm_moe* m, int kind);
+/* fp8 experts: 0 = 128 x 128 block scales (default), 1 = channel (tm_linear_prepare_fp8_channel's form).  One call per block, before
+ * the first tm_moe_set_expert, whose scales arguments are then fp32 [2 * inter] ((gate_j, up_j)-interleaved like the columns) and
+ * [hidden]; x is quantised per token and the gated-SiLU output per (token, expert) row. */
+int    tm_moe_set_fp8_scale_mode(tm_moe* m, int mode);
 int    tm_moe_set_gate_bias(tm_moe* m, const void* bias_fp32_experts, tm_stream_t st);
 int    tm_moe_set_expert_bias(tm_moe* m, int expert, const void* b13_fp16, const void* b2_fp16, tm_stream_t st);
 int    tm_mxfp4_dequant_f16(void* out_kn, const void* blocks, const void* scales, int K, int N, tm_stream_t st);
@@ -536,6 +558,13 @@ typedef struct tm_model_config {
      * keep the pad columns of the residual stream at +0 (tm_rmsnorm_valid).
      * rope_yarn_truncate: tm_rope_param::yarn_truncate (1 = the reference's rounded correction range, 0 = fractional). */
     int   attn_out_bias, hidden_valid, rope_yarn_truncate;
+    /* weight_type TM_WEIGHT_FP8 only (0 = the engine as before): 0 = 128 x 128 block scales, slots "*.scales" fp32
+     * [K / 128][ceil(N / 128)]; 1 = channel (per-tensor and per-channel FP8 checkpoints): slots "*.scales" fp32 [N], one scale per output
+     * column -- a per-tensor scale repeated over its columns, the scales of fused linears (q | k | v, (gate_j, up_j)-interleaved w1w3,
+     * experts alike) concatenated / interleaved like their columns.  Every dense decoder linear and every expert then runs
+     * tm_quant_fp8_token + the channel-scaled fp8 x fp8 GEMM (tm_linear_prepare_fp8_channel) for every M; lm_head and embeddings stay
+     * fp16; the folded norm and the dense GEMM tuner pass these linears by; TM_FP8_MFMA=0 is refused when the weights are prepared. */
+    int   fp8_scale_mode;
     /* Qwen attention prologue (0 = off): attn_bias -> slot "layers.{i}.attention.w_qkv.bias" fp16 [local qkv columns] added to
      * q / k / v (Qwen2); qk_norm -> slots "layers.{i}.attention.{q,k}_norm.weight" fp16 [head_dim], per-head RMSNorm of q / k with
      * rms_eps (Qwen3).  Order: norm -> bias -> RoPE. */

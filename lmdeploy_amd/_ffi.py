@@ -75,7 +75,7 @@ class ModelConfig(C.Structure):
                 ('moe_routed_scale', c_float), ('moe_expert_format', c_int), ('moe_act', c_int), ('moe_bias', c_int),
                 ('moe_shared_inter', c_int), ('attn_window', c_int), ('attn_sinks', c_int),
                 ('attn_out_bias', c_int), ('hidden_valid', c_int), ('rope_yarn_truncate', c_int),
-                ('attn_bias', c_int), ('qk_norm', c_int)]
+                ('fp8_scale_mode', c_int), ('attn_bias', c_int), ('qk_norm', c_int)]
 
     def __init__(self, *args, **kw):
         """rope_yarn_truncate defaults to 1 (the rounded YaRN correction range); ctypes alone would leave it 0"""
@@ -179,6 +179,12 @@ _SIGNATURES = {
                                        c_int, c_void_p, c_void_p]),
     'tm_linear_destroy': (c_int, [c_void_p]),
     'tm_linear_prepare_fp8_gated': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_linear_prepare_fp8_channel': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_quant_fp8_token': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tm_linear_fp8_grouped_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'tm_linear_forward_fp8_grouped': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    'tm_moe_set_fp8_scale_mode': (c_int, [c_void_p, c_int]),
     'tm_linear_fp8_workspace': (c_size_t, [c_void_p, c_int]),
     'tm_quant_fp8_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'tm_linear_forward_fp8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -484,6 +484,7 @@ int tm_linear_forward(const tm_linear* w, const void* x, int ldx, void* y, int l
                       int splits, int waves, void* workspace, tm_stream_t st)
 {
     TM_REQUIRE(w && x && y, "null pointer");
+    TM_REQUIRE(!w->w.cscale, "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
     GemmConfig cfg = gemm_pick_config(w->w, M);  // (workspace: tm_linear_workspace(w, M) bytes)
     if (nt > 0) {
         cfg.nt = nt;
@@ -631,6 +632,19 @@ int tm_linear_fold_consume(const tm_linear* w, const void* xg, int ldx, void* y,
     return 0;
 }
 
+int tm_linear_prepare_fp8_channel(tm_linear* w, const void* weight, const void* scales, tm_stream_t st)
+{
+    TM_REQUIRE(w && weight && scales, "null pointer");
+    TM_REQUIRE(w->w.type == TM_WEIGHT_FP8, "tm_linear_prepare_fp8_channel: fp8 weights only");
+    return linear_weight_prepare_fp8_channel(w->w, (const uint8_t*)weight, (const float*)scales, (hipStream_t)st);
+}
+
+int tm_quant_fp8_token(void* xq, float* sx, const void* x, int ldx, int M, int K, tm_stream_t st)
+{
+    TM_REQUIRE(xq && sx && x, "null pointer");
+    return launch_quant_fp8_token((uint8_t*)xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st);
+}
+
 int tm_linear_prepare_fp8_gated(tm_linear* w, const void* weight, const void* scales, tm_stream_t st)
 {
     TM_REQUIRE(w && weight && scales, "null pointer");
@@ -663,7 +677,8 @@ int tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, i
     const int ldsx = (M + 3) / 4 * 4;
     float*    sx   = (float*)(xq + (size_t)M * K);
     float*    slab = (float*)((char*)workspace + (fp8_act_workspace_bytes(M, K) + 255) / 256 * 256);
-    int       rc   = launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, M, K, ldsx, (hipStream_t)st);
+    int       rc   = w->w.cscale ? launch_quant_fp8_token(xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st)
+                                 : launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, M, K, ldsx, (hipStream_t)st);
     if (rc) {
         return rc;
     }
@@ -676,6 +691,37 @@ int tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, i
         return launch_splitk_reduce((half_t*)y, ldy, slab, nslab, M, w->w.N, gated_silu != 0, (hipStream_t)st);
     }
     return 0;
+}
+
+size_t tm_linear_fp8_grouped_workspace(int experts, int x_rows, int K)
+{
+    return (size_t)(experts + 31) / 32 * 256 + (fp8_act_workspace_bytes(x_rows, K) + 255) / 256 * 256;
+}
+
+int tm_linear_forward_fp8_grouped(const tm_linear* const* experts, int E, const void* x, int ldx, int x_rows, void* y, int ldy, int m_cap,
+                                  int gated_silu, const int* seg, const int* row_idx, void* workspace, tm_stream_t st)
+{
+    TM_REQUIRE(experts && E >= 1 && x && y && seg && workspace, "null pointer");
+    std::vector<const void*> h(E);
+    for (int e = 0; e < E; ++e) {
+        TM_REQUIRE(experts[e] && fp8_mfma_supported(experts[e]->w), "grouped fp8 linear: e4m3 experts with their P8 image (TM_FP8_MFMA=0 disables the path)");
+        TM_REQUIRE(experts[e]->w.K == experts[0]->w.K && experts[e]->w.N == experts[0]->w.N
+                       && (experts[e]->w.cscale != nullptr) == (experts[0]->w.cscale != nullptr),
+                   "grouped fp8 linear: experts of one shape and one scale mode");
+        h[e] = experts[e]->w.packed8;
+    }
+    const LinearWeight& proto = experts[0]->w;
+    TM_REQUIRE(ldx == proto.K, "grouped fp8 linear: x must be row-contiguous");
+    char*     ws   = (char*)workspace;
+    uint8_t*  xq   = (uint8_t*)(ws + (size_t)(E + 31) / 32 * 256);
+    const int ldsx = (x_rows + 3) / 4 * 4;
+    float*    sx   = (float*)(xq + (size_t)x_rows * proto.K);
+    TM_HIP_CHECK(hipMemcpyAsync(ws, h.data(), sizeof(void*) * E, hipMemcpyHostToDevice, (hipStream_t)st));
+    TM_HIP_CHECK(hipStreamSynchronize((hipStream_t)st));  // `h` is a host temporary
+    TM_TRY_RC(proto.cscale ? launch_quant_fp8_token(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, (hipStream_t)st)
+                           : launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, ldsx, (hipStream_t)st));
+    return launch_linear_fp8_grouped(proto, ws, E, xq, sx, ldsx, x_rows, (half_t*)y, ldy, m_cap, m_cap, gated_silu != 0, seg, row_idx,
+                                     (hipStream_t)st);
 }
 
 int tm_linear_destroy(tm_linear* w)
@@ -736,6 +782,7 @@ struct tm_moe {
     tmk::MoeBlock m;
     int           type = 0;
     bool          prepared = false;
+    bool          fp8_channel = false;  // tm_moe_set_fp8_scale_mode(1)
 };
 
 int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk, float routed_scale)
@@ -807,8 +854,24 @@ int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void*
         return linear_weight_prepare_u4(m->m.w2[expert], (const int32_t*)w2_weight, (const half_t*)w2_scales,
                                         (const half_t*)w2_zeros, (hipStream_t)st);
     }
+    if (m->fp8_channel) {  // fp32 column scales [2 * inter] ((gate_j, up_j)-interleaved like the columns) and [hidden]
+        TM_TRY_RC(linear_weight_prepare_fp8_channel(m->m.w13[expert], (const uint8_t*)w13_weight, (const float*)w13_scales, (hipStream_t)st));
+        return linear_weight_prepare_fp8_channel(m->m.w2[expert], (const uint8_t*)w2_weight, (const float*)w2_scales, (hipStream_t)st);
+    }
     TM_TRY_RC(linear_weight_prepare_fp8(m->m.w13[expert], (const uint8_t*)w13_weight, (const float*)w13_scales, true, (hipStream_t)st));
     return linear_weight_prepare_fp8(m->m.w2[expert], (const uint8_t*)w2_weight, (const float*)w2_scales, false, (hipStream_t)st);
+}
+
+int tm_moe_set_fp8_scale_mode(tm_moe* m, int mode)
+{
+    TM_REQUIRE(m, "null pointer");
+    TM_REQUIRE(mode == 0 || mode == 1, "moe fp8 scale mode: 0 (128 x 128 blocks) or 1 (channel)");
+    TM_REQUIRE(m->type == TM_WEIGHT_FP8 || mode == 0, "moe fp8 scale mode: fp8 experts only");
+    for (int e = 0; e < m->m.experts; ++e) {
+        TM_REQUIRE(!m->m.w13[e].packed8 && !m->m.w13[e].packed, "moe fp8 scale mode: set it before the first tm_moe_set_expert");
+    }
+    m->fp8_channel = mode == 1;
+    return 0;
 }
 
 int tm_moe_set_activation(tm_moe* m, int kind)

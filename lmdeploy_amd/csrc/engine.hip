@@ -153,7 +153,9 @@ static int64_t slot_bytes_linear(const tm_engine* e, int K, int N, const char* p
     if (!strcmp(part, "scales") || !strcmp(part, "zeros")) return (int64_t)(K / e->cfg.model.group_size) * N * 2;
     if (!strcmp(part, "weight")) return (int64_t)K * N * 2;
     if (!strcmp(part, "weight_fp8")) return (int64_t)K * N;
-    if (!strcmp(part, "scales_fp8")) return (int64_t)(K / 128) * ((N + 127) / 128) * 4;
+    if (!strcmp(part, "scales_fp8")) {  // 128 x 128 block scales, or (fp8_scale_mode 1) one fp32 scale per output column
+        return e->cfg.model.fp8_scale_mode == 1 ? (int64_t)N * 4 : (int64_t)(K / 128) * ((N + 127) / 128) * 4;
+    }
     return 0;
 }
 
@@ -267,7 +269,12 @@ static int prepare_linear(tm_engine* e, LinearSlots& l)
         Slot &w = e->slots[l.prefix + ".weight"], &s = e->slots[l.prefix + ".scales"];
         TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
         const bool gated = l.prefix.size() >= 5 && l.prefix.compare(l.prefix.size() - 5, 5, ".w1w3") == 0;
-        TM_TRY(linear_weight_prepare_fp8(l.w, (const uint8_t*)w.dev, (const float*)s.dev, gated, e->stream));
+        if (e->cfg.model.fp8_scale_mode == 1) {  // channel: the scales of a fused linear are concatenated / interleaved like its columns
+            TM_TRY(linear_weight_prepare_fp8_channel(l.w, (const uint8_t*)w.dev, (const float*)s.dev, e->stream));
+        }
+        else {
+            TM_TRY(linear_weight_prepare_fp8(l.w, (const uint8_t*)w.dev, (const float*)s.dev, gated, e->stream));
+        }
         TM_HIP_CHECK(hipStreamSynchronize(e->stream));
         for (Slot* p : {&w, &s}) {
             TM_HIP_CHECK(hipFree(p->dev));
@@ -305,6 +312,10 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
                "quant_policy in {0,4,8} (lmdeploy/messages.py:351-358)");
     TM_REQUIRE(c->cache_block_seq_len == 64, "cache_block_seq_len must be 64");
     TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8, "weight_type");
+    TM_REQUIRE(m.fp8_scale_mode == 0 || (m.fp8_scale_mode == 1 && m.weight_type == TM_WEIGHT_FP8),
+               "fp8_scale_mode: 0 (128 x 128 blocks) or, with weight_type fp8, 1 (one scale per output channel)");
+    TM_REQUIRE(m.fp8_scale_mode == 0 || std::max(m.hidden, std::max(m.inter, m.moe_shared_inter)) <= kFp8TokenMaxK,
+               "fp8_scale_mode 1: the per-token quantiser serves rows of up to 32768 channels");
     TM_REQUIRE(c->max_batch_size >= 1 && c->max_batch_size <= 1024 && c->session_len >= 1,
                "1 <= max_batch_size <= 1024, session_len >= 1");
     TM_REQUIRE(m.moe_shared_inter >= 0 && (m.moe_shared_inter == 0 || m.moe_experts > 0), "moe_shared_inter needs moe_experts > 0");
@@ -614,7 +625,7 @@ int tm_engine_process_weights(tm_engine* e)
         const std::string p = "layers." + std::to_string(i);
         Layer&            L = e->layers[i];
         for (LinearSlots* l : {&L.qkv, &L.wo}) {
-            if (!l->w.packed && !l->w.packed32) {
+            if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
                 TM_TRY(prepare_linear(e, *l));
             }
         }
@@ -629,14 +640,14 @@ int tm_engine_process_weights(tm_engine* e)
             L.moe.w2.resize(m.moe_experts);
             for (int x = 0; x < m.moe_experts; ++x) {
                 for (LinearSlots* l : {&L.ex13[x], &L.ex2[x]}) {
-                    if (!l->w.packed && !l->w.packed32) {
+                    if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
                         TM_TRY(prepare_linear(e, *l));
                     }
                 }
                 L.moe.w13[x] = L.ex13[x].w;  // the MoE block owns the packed weights from here on
                 L.moe.w2[x]  = L.ex2[x].w;
-                L.ex13[x].w.packed = nullptr, L.ex13[x].w.sz = nullptr, L.ex13[x].w.packed32 = nullptr, L.ex13[x].w.packed8 = nullptr;
-                L.ex2[x].w.packed = nullptr, L.ex2[x].w.sz = nullptr, L.ex2[x].w.packed32 = nullptr, L.ex2[x].w.packed8 = nullptr;
+                L.ex13[x].w.packed = nullptr, L.ex13[x].w.sz = nullptr, L.ex13[x].w.packed32 = nullptr, L.ex13[x].w.packed8 = nullptr, L.ex13[x].w.cscale = nullptr;
+                L.ex2[x].w.packed = nullptr, L.ex2[x].w.sz = nullptr, L.ex2[x].w.packed32 = nullptr, L.ex2[x].w.packed8 = nullptr, L.ex2[x].w.cscale = nullptr;
             }
             L.moe.act = m.moe_act;
             if (m.moe_bias) {  // the experts' biases side by side ([E][2I], [E][H]: what the grouped GEMM and the combine index)
@@ -667,7 +678,7 @@ int tm_engine_process_weights(tm_engine* e)
             g.dev      = nullptr;
             if (L.has_shared) {
                 for (LinearSlots* l : {&L.w13, &L.w2}) {
-                    if (!l->w.packed && !l->w.packed32) {
+                    if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
                         TM_TRY(prepare_linear(e, *l));
                     }
                 }
@@ -680,7 +691,7 @@ int tm_engine_process_weights(tm_engine* e)
         }
         else {
             for (LinearSlots* l : {&L.w13, &L.w2}) {
-                if (!l->w.packed && !l->w.packed32) {
+                if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
                     TM_TRY(prepare_linear(e, *l));
                 }
             }
@@ -743,6 +754,13 @@ int tm_engine_start(tm_engine* e)
     const int wide_n = std::max(std::max(e->qkv_n, 2 * std::max(e->inter, e->shared_inter)), e->hidden);  // widest linear output
     e->gemm_ws_bytes = (size_t)16 * 64 * wide_n * sizeof(float);
     TM_HIP_CHECK(hipMalloc((void**)&e->d_gemm_ws, e->gemm_ws_bytes));
+    if (m.weight_type == TM_WEIGHT_FP8 && m.fp8_scale_mode == 1) {
+        // channel-scaled fp8: codes and per-token scales of ONE GEMM input (the widest K of a dense linear), written by the quantiser
+        // in front of every dense GEMM -- sized here, nothing is allocated in a forward
+        const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), std::max(e->inter, e->shared_inter));
+        TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_xq, T * wide_k));
+        TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_sx, T * sizeof(float)));
+    }
     {
         const size_t tiles = (size_t)(e->hidden + 63) / 64;
         TM_TRY(dmalloc(&e->d_ss, tiles * kFoldMaxRows));
@@ -1082,7 +1100,7 @@ int tm_engine_destroy(tm_engine* e)
         }
     }
     void* bufs[] = {e->pool, e->d_block_ptrs, e->d_cu_block_nums, e->d_resid, e->d_x, e->d_qkv, e->d_attn, e->d_act,
-                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
+                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_f8_xq, e->d_f8_sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
                     e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
                     e->d_rope_row0};

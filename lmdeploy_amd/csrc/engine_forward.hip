@@ -114,11 +114,42 @@ static GemmConfig pick_config(tm_engine*, const LinearWeight& w, int M, bool)
     return gemm_pick_config(w, M);
 }
 
+// Channel-scaled fp8 linear (fp8_scale_mode 1; LinearWeight::cscale): the GEMM input is quantised per token into the engine's code /
+// scale buffers, then the fp8 x fp8 kernel runs, for every M -- one tile choice per M class, nothing to pick from a table.  Split-K
+// slabs are written scaled; `defer` leaves them in d_gemm_ws for the consumer (*slabs > 1), else they are reduced into y here.
+static int linear_fp8_channel(tm_engine* e, const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
+                              int* slabs)
+{
+    TM_REQUIRE(e->d_f8_xq && e->d_f8_sx && M <= e->max_tokens, "internal: channel-scaled fp8 linear without its activation buffers");
+    TM_TRY(launch_quant_fp8_token(e->d_f8_xq, e->d_f8_sx, x, ldx, M, w.K, e->stream));
+    float* const ws    = gemm_workspace_bytes(M, w.N, 16) <= e->gemm_ws_bytes ? e->d_gemm_ws : nullptr;  // nullptr: one slice
+    int          nslab = 1;
+    TM_TRY(launch_linear_fp8(w, e->d_f8_xq, e->d_f8_sx, 0, y, ldy, M, gated, 0, ws, &nslab, e->stream));
+    if (nslab > 1 && !defer) {
+        TM_TRY(launch_splitk_reduce(y, ldy, ws, nslab, M, w.N, gated, e->stream));
+        nslab = 1;
+    }
+    if (slabs) {
+        *slabs = nslab;
+    }
+    return 0;
+}
+
 // row-parallel linear followed by (all-reduce +) residual + RMSNorm
 // (bias: the o_proj bias, r = h(h(r + out) + bias) -- the HAS_BIAS arm of the norm kernel; nullptr for every other linear)
 static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, int M, const half_t* norm_w,
                                 int gemm_cat, const half_t* bias = nullptr)
 {
+    if (l.w.cscale) {  // the slabs feed the residual-norm launch as the u4 path's do
+        int slabs = 1;
+        TM_PROF(gemm_cat, TM_TRY(linear_fp8_channel(e, l.w, x, ldx, e->d_tmp, e->hidden, M, false, !e->use_comm, &slabs)));
+        if (slabs > 1) {
+            TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
+                                                               e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
+            return 0;
+        }
+        return reduce_residual_norm(e, M, norm_w, bias);
+    }
     GemmConfig cfg = pick_config(e, l.w, M, false);
     const bool can_defer = !e->use_comm && cfg.splits > 1
                            && gemm_workspace_bytes(M, l.w.N, cfg.splits) <= e->gemm_ws_bytes;
@@ -139,6 +170,9 @@ static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, i
 
 static int linear_plain(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated)
 {
+    if (l.w.cscale) {
+        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, false, nullptr);
+    }
     GemmConfig cfg = pick_config(e, l.w, M, gated);
     if (gemm_workspace_bytes(M, l.w.N, cfg.splits) > e->gemm_ws_bytes) {
         cfg.splits = 1;
@@ -398,6 +432,9 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
                 TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
                                                                e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps, rope_row0)));
             }
+        }
+        else if (fuse_qkv && L.qkv.w.cscale) {
+            TM_PROF(P_GEMM_QKV, TM_TRY(linear_fp8_channel(e, L.qkv.w, e->d_x, e->hidden, e->d_qkv, e->qkv_n, M, false, true, &qkv_slabs)));
         }
         else if (fuse_qkv) {
             GemmConfig cfg = gemm_pick_config(L.qkv.w, M);

@@ -87,6 +87,75 @@ int launch_quant_fp8_rows(uint8_t* xq, float* sx, const half_t* x, int ldx, int 
     return 0;
 }
 
+// ---- per-token activation quantiser (channel-scaled weights) --------------------------------------------------------
+// One workgroup = one row: the whole row lives in registers (NV 16-byte vectors per lane), absmax by DPP inside a wave and
+// through LDS across the four waves, then the codes -- one pass over HBM.  Same arithmetic as above with group = K.
+template<int NV>
+__global__ __launch_bounds__(256) void quant_fp8_token_kernel(uint8_t* __restrict__ xq, float* __restrict__ sx, const half_t* __restrict__ x,
+                                                              int ldx, int K)
+{
+    __shared__ float wmax[4];
+    const int     m  = blockIdx.x;
+    const int     nv = K / 8;
+    const half_t* xr = x + (size_t)m * ldx;
+    half8_t       v[NV];
+    float         amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + threadIdx.x;
+        if (c < nv) {
+            v[i] = *(const half8_t*)(xr + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                amax = fmaxf(amax, fabsf((float)v[i][e]));
+            }
+        }
+    }
+    amax = group_max<64>(amax);
+    if ((threadIdx.x & 63) == 0) {
+        wmax[threadIdx.x >> 6] = amax;
+    }
+    __syncthreads();
+    amax            = fmaxf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), 1e-8f);
+    const float inv = 448.0f / amax;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + threadIdx.x;
+        if (c < nv) {
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                f[e] = fminf(fmaxf((float)v[i][e] * inv, -448.0f), 448.0f);
+            }
+            int w0 = 0, w1 = 0;
+            w0     = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
+            w0     = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+            w1     = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
+            w1     = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
+            *(u32x2*)(xq + (size_t)m * K + c * 8) = u32x2{(uint32_t)w0, (uint32_t)w1};
+        }
+    }
+    if (threadIdx.x == 0) {
+        sx[m] = amax / 448.0f;
+    }
+}
+
+int launch_quant_fp8_token(uint8_t* xq, float* sx, const half_t* x, int ldx, int M, int K, hipStream_t st)
+{
+    TM_REQUIRE(K % 128 == 0 && ldx % 8 == 0 && K <= kFp8TokenMaxK, "fp8 per-token quantiser: K % 128 == 0, K <= 32768, 16-byte aligned rows");
+    if (M == 0) {
+        return 0;
+    }
+    if (K <= 4 * 2048) {
+        quant_fp8_token_kernel<4><<<M, 256, 0, st>>>(xq, sx, x, ldx, K);
+    }
+    else {
+        quant_fp8_token_kernel<16><<<M, 256, 0, st>>>(xq, sx, x, ldx, K);
+    }
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // ---- load-time repack ---------------------------------------------------------------------------------------------
 __global__ void repack_p8_kernel(uint32_t* __restrict__ out, const uint8_t* __restrict__ w, const float* __restrict__ block_scales, int K,
                                  int N, int gated)
@@ -107,7 +176,7 @@ __global__ void repack_p8_kernel(uint32_t* __restrict__ out, const uint8_t* __re
         if (d - 1024 < 2) {
             const int n = cg * 32 + (d - 1024);
             const int b = gated ? (n & 1) * (nb / 2) + (n >> 1) / 128 : n / 128;
-            s           = block_scales[(size_t)kb * nb + b];
+            s           = block_scales ? block_scales[(size_t)kb * nb + b] : 1.0f;  // channel mode: the words are unused
         }
         out[idx] = bit_cast<uint32_t>(s);
         return;
@@ -132,6 +201,27 @@ size_t p8_bytes(int K, int N)
     return (size_t)(K / 128) * (N / 32) * kP8Unit;
 }
 
+// Channel-scaled e4m3 weights: the P8 image (unit scale words = 1.0f, unused) followed by the N fp32 column scales -- one
+// allocation, so a grouped launch finds an expert's scales behind its units.  No weight-only image: see the message.
+int linear_weight_prepare_fp8_channel(LinearWeight& w, const uint8_t* weight, const float* scales, hipStream_t st)
+{
+    TM_REQUIRE(w.K % 128 == 0 && w.N % 32 == 0, "channel-scaled fp8: K % 128 == 0 and N % 32 == 0");
+    const char* ev = getenv("TM_FP8_MFMA");
+    TM_REQUIRE(!ev || atoi(ev) != 0,
+               "channel-scaled fp8 weights run on the fp8 matrix cores only: TM_FP8_MFMA=0 (the weight-only kernel) is not offered, its "
+               "fp16 (s, 0) scale image would push small per-tensor scales into fp16 subnormals");
+    TM_REQUIRE(!w.packed, "channel-scaled fp8: the handle already holds a block-scaled weight");
+    w.type          = 2;
+    w.group         = 128;
+    w.packed8_bytes = p8_bytes(w.K, w.N) + (size_t)w.N * sizeof(float);
+    if (!w.packed8) {
+        TM_HIP_CHECK(hipMalloc(&w.packed8, w.packed8_bytes));
+    }
+    w.cscale = (float*)((char*)w.packed8 + p8_bytes(w.K, w.N));
+    TM_HIP_CHECK(hipMemcpyAsync(w.cscale, scales, (size_t)w.N * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return launch_repack_p8(w.packed8, weight, nullptr, w.K, w.N, false, st);
+}
+
 int launch_repack_p8(void* out, const uint8_t* weight, const float* block_scales, int K, int N, bool gated, hipStream_t st)
 {
     const size_t total = p8_bytes(K, N) / 4;
@@ -143,7 +233,7 @@ int launch_repack_p8(void* out, const uint8_t* weight, const float* block_scales
 // ---- GEMM -----------------------------------------------------------------------------------------------------------
 struct Fp8Params {
     const uint8_t* xq;   // [rows][K] e4m3 codes
-    const float*   sx;   // [K/128][ldsx] activation scales
+    const float*   sx;   // [K/128][ldsx] activation scales (channel mode: [rows], one per token)
     int            ldsx;
     const void*    wp;   // P8 units (plain) ...
     const void* const* groups;  // ... or device [experts] unit pointers (grouped)
@@ -168,7 +258,10 @@ __device__ __forceinline__ void static_for8(F&& f)
     }
 }
 
-template<int MH, int CG, int WK, int S, bool GRP>
+// CH (channel-scaled weights, per-token activations): the MFMA accumulator is chained over every k-block of the slice -- no
+// scale loads in the ring, no per-group fma --, and the store loop multiplies by sx[row] * sw[column]; sw = the N floats
+// behind the last P8 unit of the (expert's) image.
+template<int MH, int CG, int WK, int S, bool GRP, bool CH>
 __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
 {
     constexpr int WAVES = CG * WK;
@@ -214,7 +307,8 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
 
     const auto rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)wbase, 0, (int)((size_t)p.KB * p.ncg * kP8Unit), 0x00020000);
     const auto rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.xq, 0, (int)((size_t)p.x_rows * p.K), 0x00020000);
-    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)p.sx, 0, (int)((size_t)p.KB * p.ldsx * 4), 0x00020000);
+    const auto rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)p.sx, 0, CH ? p.x_rows * 4 : (int)((size_t)p.KB * p.ldsx * 4), 0x00020000);
+    const auto rs_c = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)wbase + (size_t)p.KB * p.ncg * kP8Unit), 0, CH ? p.N * 4 : 0, 0x00020000);
 
     // x / sx row of local row m (clamped duplicates past Mloc only feed rows that are never stored)
     auto xrow = [&](int m) {
@@ -233,7 +327,7 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
     int sxoff[MH];  // byte offset of this lane's row in one k-group row of sx
 #pragma unroll
     for (int h = 0; h < MH; ++h) {
-        sxoff[h] = xrow(32 * h + l31) * 4;
+        sxoff[h] = CH ? 0 : xrow(32 * h + l31) * 4;
     }
     // B fragment of 16-k step j: row (l & 31) [+ 32h], 16-byte unit j XOR-swizzled by (row >> 1) & 7, 8-byte half (l >> 5)
     int coff[8];
@@ -281,13 +375,15 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
         {                                                                                                         \
             ring[slot][v] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, vw + v * 1024, uo_, /*nt*/ 2);            \
         }                                                                                                         \
-        swr[slot] = __builtin_amdgcn_raw_buffer_load_b64(rs_w, 4096, uo_, 0);                                     \
-        _Pragma("unroll") for (int h = 0; h < MH; ++h)                                                            \
-        {                                                                                                         \
-            sxr[slot][h] = bit_cast<float>(__builtin_amdgcn_raw_buffer_load_b32(rs_s, sxoff[h], kbx_ * p.ldsx * 4, 0)); \
+        if constexpr (!CH) {                                                                                      \
+            swr[slot] = __builtin_amdgcn_raw_buffer_load_b64(rs_w, 4096, uo_, 0);                                 \
+            _Pragma("unroll") for (int h = 0; h < MH; ++h)                                                        \
+            {                                                                                                     \
+                sxr[slot][h] = bit_cast<float>(__builtin_amdgcn_raw_buffer_load_b32(rs_s, sxoff[h], kbx_ * p.ldsx * 4, 0)); \
+            }                                                                                                     \
         }                                                                                                         \
     }
-    constexpr int LPB = 4 + 1 + MH;  // loads per ring slot
+    constexpr int LPB = CH ? 4 : 4 + 1 + MH;  // loads per ring slot (the vmcnt arithmetic below counts them)
 
     if (nst > 0) {
         F8_DMA_X(0, 0);
@@ -305,7 +401,12 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
             // make hipcc wait for this stage's ring slots HERE, then start the (invisible to its waitcnt pass) DMA of x(t+1)
 #pragma unroll
             for (int i = 0; i < BPS; ++i) {
-                asm volatile("" ::"v"(ring[u * BPS + i][0]), "v"(ring[u * BPS + i][3]), "v"(swr[u * BPS + i]), "v"(sxr[u * BPS + i][MH - 1]));
+                if constexpr (CH) {
+                    asm volatile("" ::"v"(ring[u * BPS + i][0]), "v"(ring[u * BPS + i][3]));
+                }
+                else {
+                    asm volatile("" ::"v"(ring[u * BPS + i][0]), "v"(ring[u * BPS + i][3]), "v"(swr[u * BPS + i]), "v"(sxr[u * BPS + i][MH - 1]));
+                }
             }
             if (t + 1 < nst) {  // uniform; see gemm_dec32_kernel: a DMA behind the last stage could land on the reduction image
                 F8_DMA_X(t + 1, buf ^ 1);
@@ -316,6 +417,21 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
                 const int  kbi  = wk + i * WK;
                 const bool live = t * S + kbi < nkb;
                 const char* xb  = smem + buf * STG + kbi * KBB;
+                if constexpr (CH) {
+                    if (live) {  // wave-uniform
+                        static_for8<8>([&](auto J) {
+                            constexpr int j  = decltype(J)::value;
+                            const u32x4   wv = ring[slot][j >> 1];
+                            const long    a  = bit_cast<long>(u32x2{wv[(j & 1) * 2], wv[(j & 1) * 2 + 1]});
+#pragma unroll
+                            for (int h = 0; h < MH; ++h) {
+                                const long b = *(const long*)(xb + h * 4096 + coff[j]);
+                                acc[h]       = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, acc[h], 0, 0, 0);
+                            }
+                        });
+                    }
+                    continue;
+                }
                 floatx16    tt[MH];
                 static_for8<8>([&](auto J) {
                     constexpr int j  = decltype(J)::value;
@@ -398,6 +514,14 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
                 continue;
             }
             const size_t mg = (size_t)row0 + m0 + m;  // (flat) output row
+            if constexpr (CH) {  // the one scaling of the channel mode: (sx[row] * sw[column]) * sum, fp32
+                const float rsx = bit_cast<float>(__builtin_amdgcn_raw_buffer_load_b32(rs_s, xrow(m) * 4, 0, 0));
+                const u32x4 cs  = __builtin_amdgcn_raw_buffer_load_b128(rs_c, n * 4, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a[i] *= rsx * bit_cast<float>(cs[i]);
+                }
+            }
             if (p.epilogue == 2) {
                 *(floatx4*)(p.partial + ((size_t)blockIdx.y * p.M + mg) * p.N + n) = a;
             }
@@ -415,17 +539,17 @@ __global__ __launch_bounds__(CG* WK * 64) void gemm_fp8_kernel(Fp8Params p)
     }
 }
 
-template<int MH, int CG, int WK, bool GRP>
+template<int MH, int CG, int WK, bool GRP, bool CH>
 static int launch_fp8_one(const Fp8Params& p, dim3 grid, hipStream_t st)
 {
     constexpr int S     = 4;
     constexpr int stage = 2 * S * 32 * MH * 128;
     constexpr int red   = WK * 32 * MH * CG * 128;
     constexpr int lds   = stage > red ? stage : red;
-    if (const int rc = ensure_dynamic_lds((const void*)gemm_fp8_kernel<MH, CG, WK, S, GRP>, lds)) {
+    if (const int rc = ensure_dynamic_lds((const void*)gemm_fp8_kernel<MH, CG, WK, S, GRP, CH>, lds)) {
         return rc;
     }
-    gemm_fp8_kernel<MH, CG, WK, S, GRP><<<grid, CG * WK * 64, lds, st>>>(p);
+    gemm_fp8_kernel<MH, CG, WK, S, GRP, CH><<<grid, CG * WK * 64, lds, st>>>(p);
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -459,7 +583,8 @@ static int fp8_splits(int col_wgs, int KB, int want)
     return splits;
 }
 
-// y = fp8 x fp8 linear of PRE-QUANTISED activations (xq, sx from launch_quant_fp8_rows).  splits = 0: heuristic.
+// y = fp8 x fp8 linear of PRE-QUANTISED activations (xq, sx from launch_quant_fp8_rows; channel-scaled weights: from
+// launch_quant_fp8_token, ldsx unused).  splits = 0: heuristic.
 int launch_linear_fp8(const LinearWeight& w, const uint8_t* xq, const float* sx, int ldsx, half_t* y, int ldy, int M, bool gated_silu,
                       int splits, float* workspace, int* slabs_out, hipStream_t st)
 {
@@ -484,7 +609,13 @@ int launch_linear_fp8(const LinearWeight& w, const uint8_t* xq, const float* sx,
     p.kb_per_split     = per;
     p.epilogue         = sp > 1 ? 2 : (gated_silu ? 1 : 0);
     dim3 grid((p.ncg + 3) / 4, sp, zb);
-    const int rc = M <= 32 ? launch_fp8_one<1, 4, 4, false>(p, grid, st) : launch_fp8_one<2, 4, 2, false>(p, grid, st);
+    int rc;
+    if (w.cscale) {  // channel-scaled weights: sx = one scale per row (launch_quant_fp8_token)
+        rc = M <= 32 ? launch_fp8_one<1, 4, 4, false, true>(p, grid, st) : launch_fp8_one<2, 4, 2, false, true>(p, grid, st);
+    }
+    else {
+        rc = M <= 32 ? launch_fp8_one<1, 4, 4, false, false>(p, grid, st) : launch_fp8_one<2, 4, 2, false, false>(p, grid, st);
+    }
     if (rc) {
         return rc;
     }
@@ -495,7 +626,7 @@ int launch_linear_fp8(const LinearWeight& w, const uint8_t* xq, const float* sx,
 }
 
 // grouped: flat rows seg[e] .. seg[e+1] of expert e, x / sx row of flat row f = row_idx ? row_idx[f] : f; m_hint = expected rows
-// per expert (tile height), m_cap = upper bound
+// per expert (tile height), m_cap = upper bound.  proto.cscale != nullptr: every expert is channel-scaled (sx = [x_rows])
 int launch_linear_fp8_grouped(const LinearWeight& proto, const void* d_groups, int E, const uint8_t* xq, const float* sx, int ldsx,
                               int x_rows, half_t* y, int ldy, int m_cap, int m_hint, bool gated_silu, const int* seg,
                               const int* row_idx, hipStream_t st)
@@ -524,11 +655,11 @@ int launch_linear_fp8_grouped(const LinearWeight& proto, const void* d_groups, i
     if (rows == 32) {
         p.zper = (m_cap + 31) / 32;
         dim3 grid((p.ncg + 3) / 4, 1, E * p.zper);
-        return launch_fp8_one<1, 4, 4, true>(p, grid, st);
+        return proto.cscale ? launch_fp8_one<1, 4, 4, true, true>(p, grid, st) : launch_fp8_one<1, 4, 4, true, false>(p, grid, st);
     }
     p.zper = (m_cap + 63) / 64;
     dim3 grid((p.ncg + 3) / 4, 1, E * p.zper);
-    return launch_fp8_one<2, 4, 2, true>(p, grid, st);
+    return proto.cscale ? launch_fp8_one<2, 4, 2, true, true>(p, grid, st) : launch_fp8_one<2, 4, 2, true, false>(p, grid, st);
 }
 
 }  // namespace tmk

@@ -183,6 +183,7 @@ void linear_weight_free(LinearWeight& w)
     }
     w.image16 = nullptr;
     w.packed8 = nullptr;
+    w.cscale  = nullptr;
     w.packed   = nullptr;
     w.sz       = nullptr;
     w.packed32 = nullptr;
@@ -232,6 +233,7 @@ int linear_weight_prepare_fp8(LinearWeight& w, const uint8_t* weight, const floa
 {
     TM_REQUIRE(w.K % 128 == 0 && w.N % 16 == 0, "K % 128 == 0 and N % 16 == 0");
     TM_REQUIRE(!gated_scales || w.N % 256 == 0, "fp8 w1w3: inter must be a multiple of the 128-column scale block");
+    TM_REQUIRE(!w.cscale, "fp8: the handle already holds a channel-scaled weight");
     w.type         = 2;
     w.group        = 128;
     w.packed_bytes = (size_t)w.K * w.N;
@@ -1336,7 +1338,8 @@ int moe_build_groups(void** d_groups, const LinearWeight* experts, int E, hipStr
 {
     std::vector<GemmGroup> h(E);
     for (int e = 0; e < E; ++e) {
-        TM_REQUIRE(experts[e].packed != nullptr, "expert weight not prepared");
+        // (channel-scaled fp8 experts have no weight-only image: their table stays unused, the P8 table of moe_prepare serves them)
+        TM_REQUIRE(experts[e].packed != nullptr || experts[e].cscale != nullptr, "expert weight not prepared");
         h[e] = GemmGroup{experts[e].packed, experts[e].sz};
     }
     if (!*d_groups) {

@@ -670,12 +670,16 @@ int moe_prepare(MoeBlock& m, hipStream_t st)
     TM_REQUIRE((m.b13 != nullptr) == (m.b2 != nullptr), "moe: expert biases come for both linears (w1w3 and w2)");
     TM_REQUIRE(!m.b13 || m.act == 1, "moe: expert biases are built with the gpt-oss activation only");
     TM_REQUIRE(!m.shared_gate || (!m.b2 && m.act == 0), "moe: a shared expert with the gpt-oss activation or expert biases is not built");
+    TM_REQUIRE(!m.w13[0].cscale || (fp8_mfma_supported(m.w13[0]) && fp8_mfma_supported(m.w2[0])),
+               "moe: channel-scaled fp8 experts run on the fp8 matrix cores only (TM_FP8_MFMA=0 is not offered for them)");
     TM_TRY_RC(moe_build_groups(&m.groups13, m.w13.data(), m.experts, st));
     TM_TRY_RC(moe_build_groups(&m.groups2, m.w2.data(), m.experts, st));
     if (fp8_mfma_supported(m.w13[0]) && fp8_mfma_supported(m.w2[0])) {  // device tables of the experts' P8 unit pointers
         std::vector<const void*> h13(m.experts), h2(m.experts);
         for (int e = 0; e < m.experts; ++e) {
             TM_REQUIRE(m.w13[e].packed8 && m.w2[e].packed8, "moe: fp8 expert without its P8 image");
+            TM_REQUIRE((m.w13[e].cscale != nullptr) == (m.w13[0].cscale != nullptr) && (m.w2[e].cscale != nullptr) == (m.w13[0].cscale != nullptr),
+                       "moe: fp8 experts of one block share one scale mode (block 128 or channel)");
             h13[e] = m.w13[e].packed8;
             h2[e]  = m.w2[e].packed8;
         }
@@ -736,13 +740,16 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
         const int    ldsx2 = ((int)pairs + 3) / 4 * 4;
         float*       sx2   = (float*)(aq + pairs * m.inter);
         TM_REQUIRE(ldx == m.hidden || tokens == 1, "moe fp8: x must be row-contiguous");
+        const bool chan = m.w13[0].cscale != nullptr;  // channel-scaled experts: one activation scale per row, over all of K
         if (stages & kMoeW13) {
-            TM_TRY_RC(launch_quant_fp8_rows(xq, sx1, x, ldx, tokens, m.hidden, ldsx1, st));
+            TM_TRY_RC(chan ? launch_quant_fp8_token(xq, sx1, x, ldx, tokens, m.hidden, st)
+                           : launch_quant_fp8_rows(xq, sx1, x, ldx, tokens, m.hidden, ldsx1, st));
             TM_TRY_RC(launch_linear_fp8_grouped(m.w13[0], m.groups13_p8, m.experts, xq, sx1, ldsx1, tokens, act, m.inter, tokens, hint, true,
                                                 offs, f2n, st));
         }
         if (stages & kMoeW2) {
-            TM_TRY_RC(launch_quant_fp8_rows(aq, sx2, act, m.inter, (int)pairs, m.inter, ldsx2, st));
+            TM_TRY_RC(chan ? launch_quant_fp8_token(aq, sx2, act, m.inter, (int)pairs, m.inter, st)
+                           : launch_quant_fp8_rows(aq, sx2, act, m.inter, (int)pairs, m.inter, ldsx2, st));
             TM_TRY_RC(launch_linear_fp8_grouped(m.w2[0], m.groups2_p8, m.experts, aq, sx2, ldsx2, (int)pairs, y2, m.hidden, tokens, hint, false,
                                                 offs, nullptr, st));
         }

@@ -157,6 +157,9 @@ struct LinearWeight {
     // their even / odd column block scales)
     void*     packed8 = nullptr;
     size_t    packed8_bytes = 0;
+    // fp8 only, channel-scaled weights (linear_weight_prepare_fp8_channel): the N fp32 column scales, stored behind the last
+    // P8 unit of `packed8` (not owned).  Such a weight has no `packed` / `sz` image: it runs on the fp8 matrix cores only.
+    float*    cscale = nullptr;
     // u4 only, optional (linear_weight_build_f16_image; the engine builds it for dense linears unless TM_PREFILL_F16_IMAGE=0): the fp16
     // [N][K] image of the dequantised weights -- bit for bit the operand the fused tiles build on chip -- that prefill-sized forwards
     // contract on the matrix pipe without any dequantisation work in the loop (gemm_prefill_f16.hip, shape kShapeF16).  2 bytes per
@@ -275,6 +278,11 @@ size_t p8_bytes(int K, int N);
 int    launch_repack_p8(void* out, const uint8_t* weight, const float* block_scales, int K, int N, bool gated, hipStream_t st);
 bool   fp8_mfma_supported(const LinearWeight& w);
 size_t fp8_act_workspace_bytes(int rows, int K);
+constexpr int kFp8TokenMaxK = 32768;
+int    linear_weight_prepare_fp8_channel(LinearWeight& w, const uint8_t* weight /*[K][N] e4m3*/, const float* scales /*[N] fp32, device*/,
+                                         hipStream_t st);
+// per-token form (channel-scaled weights): one scale per row over all of K, sx[M]; K % 128 == 0, K <= kFp8TokenMaxK
+int    launch_quant_fp8_token(uint8_t* xq, float* sx, const half_t* x, int ldx, int M, int K, hipStream_t st);
 int    launch_quant_fp8_rows(uint8_t* xq, float* sx, const half_t* x, int ldx, int M, int K, int ldsx, hipStream_t st);
 int    launch_linear_fp8(const LinearWeight& w, const uint8_t* xq, const float* sx, int ldsx, half_t* y, int ldy, int M, bool gated_silu,
                          int splits, float* workspace, int* slabs_out, hipStream_t st);

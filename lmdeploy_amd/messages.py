@@ -177,7 +177,14 @@ class TurbomindEngineConfig:
     """TurboMind Engine config -- same field names and defaults as the reference (lmdeploy/messages.py:302-343).
 
     Models: the attention path serves head_dim 128 and, through the Llama reader (Llama-3.2-1B, TinyLlama, SmolLM2: fp16 / bf16 or
-    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' needs head_dim 128.  Mistral / Mixtral
+    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' with 128x128 block scales needs head_dim
+    128.  FP8 checkpoints with one scale per tensor (`quant_method: "fp8"` without weight_block_size: AutoFP8 / `*-FP8`) or per output
+    channel (`quant_method: "compressed-tensors"`, `format: "float-quantized"`: llm-compressor `*-FP8-dynamic`) load as they are, dense
+    and Mixtral alike, head_dim 64 included: every decoder linear and expert runs on the fp8 matrix cores with its activations quantised
+    per token (never coarser than a per-tensor static scale: `input_scale` / `activation_scheme: "static"` and `k_scale` / `v_scale` /
+    `kv_cache_scheme` in such a checkpoint are read past; the KV cache follows quant_policy, and quant_policy=16 stays refused);
+    lm_head and router gates stay fp16; TM_FP8_MFMA=0 is refused for them.  model_format='fp8_channel' asks for that form (a
+    `synthetic:` model is built in it).  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
     on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
     R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
@@ -253,9 +260,9 @@ class TurbomindEngineConfig:
             raise NotImplementedError('quant_policy=TURBO_QUANT')
         if self.dtype == 'bfloat16':
             raise NotImplementedError('dtype=bfloat16: the AWQ path is fp16 (lmdeploy/turbomind/converter.py:40-48)')
-        if self.model_format not in (None, 'awq', 'hf', 'fp8'):
+        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel'):
             raise NotImplementedError(f'model_format={self.model_format!r}: only "awq" (W4A16 g128), "fp8" (e4m3, 128x128 '
-                                      f'block scales) and "hf" (fp16)')
+                                      f'block scales), "fp8_channel" (e4m3, one scale per tensor / output channel) and "hf" (fp16)')
         if self.cache_block_seq_len != 64:
             raise NotImplementedError('cache_block_seq_len must be 64')
         unsupported = {'dp': 1, 'cp': 1, 'ep': 1, 'attn_tp_size': None, 'attn_cp_size': None, 'attn_dp_size': None,

@@ -85,11 +85,15 @@ class Pipeline:
         if synthetic:
             self.model_cfg = checkpoint.ModelConfig(**SYNTHETIC[model_path.split(':', 1)[1]],
                                                     quantized=cfg.model_format != 'hf',
-                                                    weight_format={'hf': 'f16', 'fp8': 'fp8'}.get(cfg.model_format, 'u4'))
+                                                    weight_format={'hf': 'f16', 'fp8': 'fp8', 'fp8_channel': 'fp8'}.get(cfg.model_format, 'u4'),
+                                                    fp8_scale_mode=int(cfg.model_format == 'fp8_channel'))
         else:
             self.model_cfg = checkpoint.read_config(model_path, cfg.tp)
             have = self.model_cfg.weight_format if self.model_cfg.quantized else 'f16'
-            if cfg.model_format in ('awq', 'fp8') and {'awq': 'u4', 'fp8': 'fp8'}[cfg.model_format] != have:
+            have += '_channel' if have == 'fp8' and self.model_cfg.fp8_scale_mode == 1 else ''
+            # ('fp8' takes either scale form of an e4m3 checkpoint, 'fp8_channel' only the per-tensor / per-channel one)
+            if cfg.model_format in ('awq', 'fp8', 'fp8_channel') and have not in {'awq': ('u4',), 'fp8': ('fp8', 'fp8_channel'),
+                                                                                  'fp8_channel': ('fp8_channel',)}[cfg.model_format]:
                 raise ValueError(f'model_format="{cfg.model_format}" but the checkpoint\'s quantization_config says {have} '
                                  f'(lmdeploy/turbomind/converter.py:174-176)')
         session_len = cfg.session_len or self.model_cfg.max_position_embeddings

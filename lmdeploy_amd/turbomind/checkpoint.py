@@ -1,7 +1,10 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
 Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
-FP8 (e4m3, 128x128 block scales, `.weight_scale_inv`) or fp16 / bf16 weights (dense linears and MoE experts alike), and for gpt-oss
+FP8 (e4m3: 128x128 block scales, `.weight_scale_inv`; or one scale per tensor / per output channel, `.weight_scale` -- AutoFP8
+`quant_method: "fp8"` without weight_block_size and compressed-tensors `float-quantized`; their static `input_scale` / `k_scale` /
+`v_scale` tensors are read past: activations are quantised per token, the KV cache follows quant_policy) or fp16 / bf16 weights
+(dense linears and MoE experts alike), and for gpt-oss
 (GptOssForCausalLM: MXFP4 experts as published, or the bf16 experts transformers' save_pretrained writes; served zero-padded):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
                                      qwen2.py, qwen3.py (q/k/v bias; per-head q/k norm, reordered like one head;
@@ -62,7 +65,8 @@ class ModelConfig:
     group: int = 128
     arch: str = 'llama'
     quantized: bool = True
-    weight_format: str = 'u4'          # 'u4' (AWQ) | 'fp8' (block 128x128) | 'f16'
+    weight_format: str = 'u4'          # 'u4' (AWQ) | 'fp8' (block 128x128, or one scale per channel: fp8_scale_mode) | 'f16'
+    fp8_scale_mode: int = 0            # weight_format 'fp8': 0 = 128x128 block scales, 1 = channel (per-tensor / per-channel checkpoints)
     moe_experts: int = 0               # Mixtral: num_local_experts
     moe_top_k: int = 0                 # num_experts_per_tok
     moe_norm_topk: bool = True
@@ -226,6 +230,36 @@ def _read_gpt_oss(arch: str, c: dict, model_path: str, tp: int) -> ModelConfig:
                        tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
+# router gates a compressed-tensors `ignore` list may name next to lm_head (they are read as fp16 anyway)
+_CT_IGNORE_OK = ('lm_head', 're:.*lm_head', 're:.*block_sparse_moe.gate', 're:.*mlp.gate$', 're:.*mlp.shared_expert_gate$')
+
+
+def _check_compressed_tensors(q: dict):
+    """quantization_config of llm-compressor's FP8 exports (`format: float-quantized`): ONE config group, 8-bit float symmetric
+    weights with a per-tensor or per-channel scale, input activations absent or 8-bit float per token / per tensor.  Anything else
+    is refused with the offending key."""
+    def no(key, val, want):
+        return NotImplementedError(f'compressed-tensors quantization_config: {key} = {val!r} is not served ({want})')
+    if q.get('format') != 'float-quantized':
+        raise no('format', q.get('format'), 'only "float-quantized": e4m3 weights with .weight_scale')
+    groups = q.get('config_groups') or {}
+    if len(groups) != 1:
+        raise no('config_groups', sorted(groups), 'exactly one config group')
+    (gname, g), = groups.items()
+    w = g.get('weights') or {}
+    for key, ok in (('num_bits', (8,)), ('type', ('float',)), ('symmetric', (True,)), ('strategy', ('tensor', 'channel'))):
+        if w.get(key) not in ok:
+            raise no(f'config_groups.{gname}.weights.{key}', w.get(key), ' | '.join(map(repr, ok)))
+    a = g.get('input_activations')
+    if a is not None:
+        for key, ok in (('num_bits', (8,)), ('type', ('float',)), ('strategy', ('token', 'tensor'))):
+            if a.get(key) not in ok:
+                raise no(f'config_groups.{gname}.input_activations.{key}', a.get(key), ' | '.join(map(repr, ok)))
+    for name in q.get('ignore') or []:
+        if name not in _CT_IGNORE_OK and not name.endswith('lm_head'):
+            raise no('ignore', name, 'only lm_head and router gates may stay unquantised: every decoder linear is e4m3')
+
+
 def read_config(model_path: str, tp: int = 1) -> ModelConfig:
     with open(os.path.join(model_path, 'config.json')) as f:
         c = json.load(f)
@@ -268,18 +302,29 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                 raise ValueError(f'{arch}: sliding_window {sw!r} must be a non-negative integer or null')
             window = sw
     q = c.get('quantization_config')
-    wfmt = 'f16'
+    wfmt, fp8_mode = 'f16', 0
     if q is not None:
-        if q.get('quant_method') == 'fp8':       # converter.py:186-187; block size fixed at 128 (converter.py:82,90)
-            if list(q.get('weight_block_size') or [128, 128]) != [128, 128]:
-                raise NotImplementedError(f'quantization_config {q}: fp8 needs 128x128 weight blocks')
+        if q.get('quant_method') == 'compressed-tensors':
+            _check_compressed_tensors(q)
+            wfmt, fp8_mode = 'fp8', 1
+        elif q.get('quant_method') == 'fp8' and q.get('weight_block_size') is None:
+            # AutoFP8 / neuralmagic *-FP8: one scale per tensor (`.weight_scale`).  head_dim 64 is fine: no scale block straddles a head
+            for name in q.get('ignored_layers') or []:
+                if not name.endswith(('lm_head', '.gate')):
+                    raise NotImplementedError(f'fp8 quantization_config: ignored_layers = {name!r} is not served (only lm_head and '
+                                              f'router gates may stay unquantised: every decoder linear is e4m3)')
+            wfmt, fp8_mode = 'fp8', 1
+        elif q.get('quant_method') == 'fp8':     # converter.py:186-187; block size fixed at 128 (converter.py:82,90)
+            if list(q.get('weight_block_size')) != [128, 128]:
+                raise NotImplementedError(f'quantization_config {q}: fp8 needs 128x128 weight blocks (weight_block_size), or none at '
+                                          f'all (one scale per tensor)')
             if D == 64:
                 raise NotImplementedError(f'{arch} with fp8 weights and head_dim 64: the 128-column scale blocks of the q / k / v '
                                           f'projections straddle heads; fp8 needs head_dim 128')
             wfmt = 'fp8'
         elif q.get('quant_method') != 'awq' or q.get('bits', 4) != 4 or q.get('group_size', 128) != 128:
-            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128 or block-128 FP8 '
-                                      f'(lmdeploy/turbomind/converter.py:82-92)')
+            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, block-128 FP8, per-tensor FP8 or '
+                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92)')
         else:
             wfmt = 'u4'
     rope = RopeConfig(dim=D, base=float(c.get('rope_theta', 10000.0)))
@@ -308,7 +353,8 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                        kv_heads=c.get('num_key_value_heads', heads), head_dim=D,
                        vocab=c['vocab_size'], rms_eps=float(c.get('rms_norm_eps', 1e-5)), rope=rope, arch=kind,
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
-                       max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, **moe,
+                       max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, fp8_scale_mode=fp8_mode,
+                       **moe,
                        attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
@@ -445,7 +491,18 @@ class _Tensors:
 
 def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
     """-> {'q','s','z'} (uint8 [K,N], fp16 [K/g,N] x2), {'f8','bs'} (e4m3 codes [K,N], fp32 block scales
-    [K/128, ceil(N/128)]) or {'w'} fp16 [K,N]."""
+    [K/128, ceil(N/128)]), {'f8','cs'} (e4m3 codes [K,N], one fp32 scale per output channel [N]) or {'w'} fp16 [K,N]."""
+    if quantized and (prefix + '.weight_scale') in t:           # per-tensor ([] / [1]) or per-channel ([N] / [N, 1]) scale
+        w = t.get(prefix + '.weight')
+        if w.dtype != np.uint8:
+            raise ValueError(f'{prefix}.weight: expected float8_e4m3fn codes next to .weight_scale, got {w.dtype}')
+        N = w.shape[0]
+        s = t.get(prefix + '.weight_scale').astype(np.float32)
+        if s.shape not in ((), (1,), (N,), (N, 1)):
+            raise ValueError(f'{prefix}.weight_scale: shape {tuple(s.shape)} is neither a per-tensor ([] / [1]) nor a per-channel '
+                             f'([{N}] / [{N}, 1]) scale')
+        # (.input_scale / .k_scale / .v_scale of static checkpoints are not read)
+        return dict(f8=np.ascontiguousarray(w.T), cs=np.ascontiguousarray(np.broadcast_to(s.reshape(-1), (N,))))
     if quantized and (prefix + '.weight_scale_inv') in t:       # FP8Format.normalize: transpose weight and scales
         w = t.get(prefix + '.weight')
         assert w.dtype == np.uint8, f'{prefix}.weight: expected float8_e4m3fn / uint8 codes, got {w.dtype}'
@@ -462,13 +519,16 @@ def _cat(parts: list) -> dict:
 
 
 def _map(lin: dict, fn) -> dict:
-    """apply a per-output-channel permutation; fp8 block scales cover whole heads (128 channels) and stay put"""
+    """apply a per-output-channel permutation; fp8 block scales cover whole heads (128 channels) and stay put (channel scales
+    'cs' move with their columns)"""
     return {k: (v if k == 'bs' else fn(v)) for k, v in lin.items()}
 
 
 def _fuse_w1w3(w1: dict, w3: dict) -> dict:
     """(gate_j, up_j) column interleave (builders/ffn.py:31-34).  fp8: codes interleaved, the scale row becomes
     [w1 blocks | w3 blocks] -- the engine's layout for *.w1w3.scales (include/tm_mi355x.h, tm_moe_set_expert)."""
+    if 'cs' in w1:
+        return dict(f8=interleave_gate_up(w1['f8'], w3['f8']), cs=interleave_gate_up(w1['cs'], w3['cs']))
     if 'f8' in w1:
         assert w1['f8'].shape[1] % 128 == 0, 'fp8 w1/w3: intermediate size must be a multiple of the 128-column block'
         return dict(f8=interleave_gate_up(w1['f8'], w3['f8']), bs=np.concatenate([w1['bs'], w3['bs']], axis=1), gated=True)

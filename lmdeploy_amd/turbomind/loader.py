@@ -129,6 +129,16 @@ def _shard_linear(lin: dict, kind: str, tp: int, rank: int, group: int, col_slic
     """lin: {'q','s','z'} (u4 as uint8 [K,N], fp16 [K/g,N]) or {'w'} fp16 [K,N].
     kind 'col': take `col_slices` (list of (lo,hi)) of the output dim; 'row': split the input dim evenly."""
     out = {}
+    if 'cs' in lin:
+        # e4m3 codes [K,N] + one fp32 scale per output channel [N]: column shards slice the scales with their columns (whole
+        # (gate, up) pairs for w1w3: its slice bounds are even), row shards keep them whole
+        f8, cs = lin['f8'], lin['cs']
+        if kind == 'col':
+            return {'f8': np.concatenate([f8[:, lo:hi] for lo, hi in col_slices], axis=1),
+                    'cs': np.concatenate([cs[lo:hi] for lo, hi in col_slices])}
+        K = f8.shape[0]
+        assert K % tp == 0 and (K // tp) % 128 == 0, 'fp8 row-parallel shards must keep whole 128-row k-blocks'
+        return {'f8': f8[rank * (K // tp):(rank + 1) * (K // tp)], 'cs': cs}
     if 'f8' in lin:
         # e4m3 codes [K,N] + fp32 scales of 128x128 blocks [K/128, ceil(N/128)]: a shard must keep whole blocks
         f8, bs = lin['f8'], lin['bs']
@@ -169,9 +179,9 @@ def _emit(slots: dict, prefix: str, lin: dict):
         slots[prefix + '.qweight'] = np.ascontiguousarray(pack_u4_row(lin['q']))
         slots[prefix + '.scales'] = np.ascontiguousarray(lin['s'], dtype=np.float16)
         slots[prefix + '.zeros'] = np.ascontiguousarray(lin['z'], dtype=np.float16)
-    elif 'f8' in lin:        # e4m3 codes [K,N] + fp32 128x128 block scales (lmdeploy/turbomind/weight_format.py:349-393)
+    elif 'f8' in lin:        # e4m3 codes [K,N] + fp32 128x128 block scales (lmdeploy/turbomind/weight_format.py:349-393) or [N] channel scales
         slots[prefix + '.weight'] = np.ascontiguousarray(lin['f8'], dtype=np.uint8)
-        slots[prefix + '.scales'] = np.ascontiguousarray(lin['bs'], dtype=np.float32)
+        slots[prefix + '.scales'] = np.ascontiguousarray(lin['cs'] if 'cs' in lin else lin['bs'], dtype=np.float32)
     else:
         slots[prefix + '.weight'] = np.ascontiguousarray(lin['w'], dtype=np.float16)
 
@@ -209,7 +219,8 @@ def export_weights(cfg, weights: dict, tp: int = 1, rank: int = 0) -> dict:
         _emit(slots, p + '.attention.w_qkv', _shard_linear(L['w_qkv'], 'col', tp, rank, G, qkv_slices))
         _emit(slots, p + '.attention.wo', _shard_linear(L['wo'], 'row', tp, rank, G))
         if 'experts' in L:     # mixture of experts: replicated router, every expert sharded like the dense FFN
-            if tp > 1 and i_l % 128:
+            fp8_channel = any('cs' in E_['w1w3'] for E_ in L['experts'])
+            if tp > 1 and i_l % 128 and not fp8_channel:
                 # the rank's half of a *.w1w3.scales row is i_l / 128 blocks, and the fp8 gated linear needs N = 2 * i_l % 256 == 0
                 raise ValueError(f'moe experts of width {I} do not shard over tp = {tp}: {I} / {tp} = {I / tp:g} is not a multiple '
                                  f'of 128')
