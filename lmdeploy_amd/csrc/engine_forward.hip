@@ -86,13 +86,22 @@ __global__ void pack_candidates_kernel(float* cand, const int* ids, const half_t
     }
 }
 
-static KvCacheView cache_view(const tm_engine* e, int layer)
+// A range of a forward's rows and the sequences that own them: the whole forward, the prefill rows or the decode rows of a mixed
+// forward, a micro-batch.  A row half has rows only (the row-wise operators read r0 / rows and nothing else).
+struct Rows {
+    int        r0, rows;  // first row, row count
+    int        s0, nseq;  // first sequence in the forward's per-sequence arrays (block table, d_cu_koff, rope_row0), sequence count
+    const int* cu_q;      // [nseq + 1], counted from the range's first row
+    const int* k_len;     // [nseq] context lengths
+};
+
+static KvCacheView cache_view(const tm_engine* e, int layer, int s0 = 0)
 {
     KvCacheView v{};
-    v.block_ptrs    = e->d_block_ptrs;
+    v.block_ptrs    = e->d_block_ptrs + (size_t)s0 * e->max_blocks_per_seq;  // cu_block_nums[b] = b * max_blocks_per_seq (create())
     v.cu_block_nums = e->d_cu_block_nums;
     static const bool rect = !getenv("TM_ATTN_RECT") || atoi(getenv("TM_ATTN_RECT")) != 0;  // A/B switch
-    v.block_stride  = rect ? e->max_blocks_per_seq : 0;  // cu_block_nums[b] = b * max_blocks_per_seq (create())
+    v.block_stride  = rect ? e->max_blocks_per_seq : 0;
     v.layer_offset  = (int64_t)layer * e->layout.layer_size();
     v.layout        = e->layout;
     return v;
@@ -109,11 +118,6 @@ size_t prof_event(tm_engine* e)
     return e->prof_used++;
 }
 
-static GemmConfig pick_config(tm_engine*, const LinearWeight& w, int M, bool)
-{
-    return gemm_pick_config(w, M);
-}
-
 // Channel-scaled fp8 linear (fp8_scale_mode 1; LinearWeight::cscale): the GEMM input is quantised per token into the engine's code /
 // scale buffers, then the fp8 x fp8 kernel runs, for every M -- one tile choice per M class, nothing to pick from a table.  Split-K
 // slabs are written scaled; `defer` leaves them in d_gemm_ws for the consumer (*slabs > 1), else they are reduced into y here.
@@ -122,190 +126,58 @@ static int linear_fp8_channel(tm_engine* e, const LinearWeight& w, const half_t*
 {
     TM_REQUIRE(e->d_f8_xq && e->d_f8_sx && M <= e->max_tokens, "internal: channel-scaled fp8 linear without its activation buffers");
     TM_TRY(launch_quant_fp8_token(e->d_f8_xq, e->d_f8_sx, x, ldx, M, w.K, e->stream));
-    float* const ws    = gemm_workspace_bytes(M, w.N, 16) <= e->gemm_ws_bytes ? e->d_gemm_ws : nullptr;  // nullptr: one slice
+    float* const ws    = fit_splits(e, M, w.N, 16) == 16 ? e->d_gemm_ws : nullptr;  // room for the launcher's 16 slabs, or one slice
     int          nslab = 1;
     TM_TRY(launch_linear_fp8(w, e->d_f8_xq, e->d_f8_sx, 0, y, ldy, M, gated, 0, ws, &nslab, e->stream));
     if (nslab > 1 && !defer) {
         TM_TRY(launch_splitk_reduce(y, ldy, ws, nslab, M, w.N, gated, e->stream));
         nslab = 1;
     }
-    if (slabs) {
-        *slabs = nslab;
-    }
+    *slabs = nslab;
     return 0;
-}
-
-// row-parallel linear followed by (all-reduce +) residual + RMSNorm
-// (bias: the o_proj bias, r = h(h(r + out) + bias) -- the HAS_BIAS arm of the norm kernel; nullptr for every other linear)
-static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, int M, const half_t* norm_w,
-                                int gemm_cat, const half_t* bias = nullptr)
-{
-    if (l.w.cscale) {  // the slabs feed the residual-norm launch as the u4 path's do
-        int slabs = 1;
-        TM_PROF(gemm_cat, TM_TRY(linear_fp8_channel(e, l.w, x, ldx, e->d_tmp, e->hidden, M, false, !e->use_comm, &slabs)));
-        if (slabs > 1) {
-            TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
-                                                               e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
-            return 0;
-        }
-        return reduce_residual_norm(e, M, norm_w, bias);
-    }
-    GemmConfig cfg = pick_config(e, l.w, M, false);
-    const bool can_defer = !e->use_comm && cfg.splits > 1
-                           && gemm_workspace_bytes(M, l.w.N, cfg.splits) <= e->gemm_ws_bytes;
-    if (gemm_workspace_bytes(M, l.w.N, cfg.splits) > e->gemm_ws_bytes) {
-        cfg.splits = 1;
-    }
-    int slabs = 1;
-    TM_PROF(gemm_cat, TM_TRY(launch_linear(l.w, x, ldx, e->d_tmp, e->hidden, M, false, cfg, e->d_gemm_ws, can_defer, &slabs,
-                                           e->stream)));
-    if (can_defer && slabs > 1) {
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
-                                                           e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
-        return 0;
-    }
-    TM_REQUIRE(!can_defer || slabs == 1, "internal: deferred reduce without slabs");
-    return reduce_residual_norm(e, M, norm_w, bias);
 }
 
 static int linear_plain(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated)
 {
     if (l.w.cscale) {
-        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, false, nullptr);
+        int one;  // the slab count behind a launch that defers nothing
+        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, false, &one);
     }
-    GemmConfig cfg = pick_config(e, l.w, M, gated);
-    if (gemm_workspace_bytes(M, l.w.N, cfg.splits) > e->gemm_ws_bytes) {
-        cfg.splits = 1;
-    }
-    cfg.tickets = e->d_tickets;
+    GemmConfig cfg = gemm_pick_config(l.w, M);
+    cfg.splits     = fit_splits(e, M, l.w.N, cfg.splits);
+    cfg.tickets    = e->d_tickets;
     return launch_linear(l.w, x, ldx, y, ldy, M, gated, cfg, e->d_gemm_ws, false, nullptr, e->stream);
 }
 
-// Tensor-parallel prefill forward, dense layer, from the attention output to the next layer's QKV projection, as two row halves
-// A = [0, Ma), B = [Ma, M): every operator here is row-wise, so a half's all-reduce (RCCL on the side stream, engine_comm.hip) runs
-// under the other half's GEMMs on the engine stream --
-//   engine stream:  wo A | wo B | norm A  w1w3 A  w2 A | norm B  w1w3 B  w2 B | norm A  qkv' A | norm B  qkv' B
-//   side stream:         | AR A        | AR B                 | AR A                   | AR B
-// (qkv' = the NEXT layer's w_qkv: it hides the last exchange; absent behind the last layer).  Same kernels, same per-row arithmetic
-// as the unsplit sequence (reduce_residual_norm's RCCL branch): a row's result does not depend on which rows share its launch, as
-// long as both forms pick the same tiling -- they pick per launch size, so equality with the unsplit forward is to rounding, and the
-// parity gate is the engine's usual one against the oracle.  Reference role: the overlap the reference gets from its fused
-// all-reduce + norm kernel (unified_decoder.cc:278,328; comm/cuda_ipc/fused_allreduce.cu:406-500).
-static int forward_tail_two_halves(tm_engine* e, Layer& L, int M, int Ma, const half_t* next_norm, Layer* next)
+// A linear whose consumer can sum the split-K slices itself (the residual-norm launch, the decode attention's fused prologue):
+// `defer` and a split launch leave the fp32 slabs in d_gemm_ws, *slabs > 1; otherwise y holds the result and *slabs = 1.
+// (No arrival counters here, unlike linear_plain: launch_linear then runs a merge shape as the plain form of the same tile.)
+static int linear_deferrable(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
+                             int* slabs)
 {
-    const int    r0[2] = {0, Ma}, nr[2] = {Ma, M - Ma};
-    const int    kq = e->q_heads * e->D, H = e->hidden;
-    const float  eps = e->cfg.model.rms_eps;
-    hipStream_t  st = e->stream;
-    hipEvent_t   done[2];
-    for (int h = 0; h < 2; ++h) {
-        TM_PROF(P_GEMM_O, TM_TRY(linear_plain(e, L.wo, e->d_attn + (size_t)r0[h] * kq, kq, e->d_tmp + (size_t)r0[h] * H, H, nr[h], false)));
-        TM_TRY(allreduce_rows_side(e, r0[h], nr[h], &done[h]));
+    if (l.w.cscale) {
+        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, defer, slabs);
     }
-    for (int h = 0; h < 2; ++h) {
-        const size_t off = (size_t)r0[h] * H;
-        TM_TRY(pipe_wait(e, done[h]));
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, L.wo_bias, L.ffn_norm, eps,
-                                                           nr[h], H, st, e->hidden_valid)));
-        TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x + off, H, e->d_act + (size_t)r0[h] * e->inter, e->inter, nr[h], true)));
-        TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act + (size_t)r0[h] * e->inter, e->inter, e->d_tmp + off, H, nr[h], false)));
-        TM_TRY(allreduce_rows_side(e, r0[h], nr[h], &done[h]));
-    }
-    for (int h = 0; h < 2; ++h) {
-        const size_t off = (size_t)r0[h] * H;
-        TM_TRY(pipe_wait(e, done[h]));
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, next_norm, eps,
-                                                           nr[h], H, st, e->hidden_valid)));
-        if (next) {
-            TM_PROF(P_GEMM_QKV, TM_TRY(linear_plain(e, next->qkv, e->d_x + off, H, e->d_qkv + (size_t)r0[h] * e->qkv_n, e->qkv_n, nr[h], false)));
-        }
-    }
-    return 0;
+    GemmConfig cfg = gemm_pick_config(l.w, M);
+    cfg.splits     = fit_splits(e, M, l.w.N, cfg.splits);
+    defer          = defer && cfg.splits > 1;
+    *slabs         = 1;  // (not deferred: launch_linear would report the slabs it reduced itself)
+    return launch_linear(l.w, x, ldx, y, ldy, M, gated, cfg, e->d_gemm_ws, defer, defer ? slabs : nullptr, e->stream);
 }
 
-// Tensor-parallel prefill forward whose sequences split into two micro-batches A = sequences [0, seqs_a) = rows [0, rows_a) and B = the
-// rest (prefill_slots decides; e->mb): between the embedding and the lm_head the two share nothing -- not even the attention -- so they
-// leapfrog through ALL layers, every all-reduce of one running on the side stream under a whole block of the other:
-//   engine stream:  attn-block A | attn-block B | ffn A | ffn B | attn-block' A | attn-block' B | ...
-//   side stream:                 | AR(wo A)     | AR(wo B)  | AR(w2 A) | AR(w2 B)       | ...
-// attn-block = (residual + RMSNorm of the previous layer's w2 sum,) w_qkv, RoPE + K/V quantise-store, flatten, attention, wo;
-// ffn = residual + RMSNorm of the wo sum, w1w3 + gated SiLU, w2.  The row-half schedule inside a layer (forward_tail_two_halves) can
-// hide AR(wo A) only under wo B and AR(w2 B) only under the next w_qkv A; here every exchange has a third to a half of the other
-// micro-batch's layer to hide under (measured with the 1-rank exchange stand-in: profiles/r05_prefill_overlap_emulated_exchange.txt).
-// Same kernels and per-row arithmetic as the unsplit forward; dense layers only.
-static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int max_q_len, int max_k_len, int kflat_stride, float scale_log2,
-                                           const int* rope_row0)
+// row-parallel linear followed by (all-reduce +) residual + RMSNorm; without a communicator the norm launch sums the slabs
+// (bias: the o_proj bias, r = h(h(r + out) + bias) -- the HAS_BIAS arm of the norm kernel; nullptr for every other linear)
+static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, int M, const half_t* norm_w,
+                                int gemm_cat, const half_t* bias = nullptr)
 {
-    const tm_model_config& m  = e->cfg.model;
-    hipStream_t            st = e->stream;
-    struct Part {
-        int        r0, rows, s0, nseq;
-        const int* cu_q;  // counted from the part's first row
-    };
-    const Part   part[2] = {{0, e->mb.rows_a, 0, e->mb.seqs_a, e->d_cu_q},
-                            {e->mb.rows_a, M - e->mb.rows_a, e->mb.seqs_a, nseq - e->mb.seqs_a, e->d_cu_q_b}};
-    const int    H = e->hidden, kq = e->q_heads * e->D;
-    const float  eps = m.rms_eps;
-    hipEvent_t   done[2] = {nullptr, nullptr};
-    for (int li = 0; li < m.layers; ++li) {
-        Layer& L = e->layers[li];
-        TM_REQUIRE(!L.is_moe, "internal: micro-batch schedule on a MoE layer");
-        for (int h = 0; h < 2; ++h) {
-            const Part&  P   = part[h];
-            const size_t off = (size_t)P.r0 * H;
-            if (li > 0) {  // this micro-batch's w2 partial sums of the previous layer are summed by now (or the stream waits here)
-                TM_TRY(pipe_wait(e, done[h]));
-                TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, L.attn_norm,
-                                                                   eps, P.rows, H, st, e->hidden_valid)));
-            }
-            half_t* const qkv = e->d_qkv + (size_t)P.r0 * e->qkv_n;
-            TM_PROF(P_GEMM_QKV, TM_TRY(linear_plain(e, L.qkv, e->d_x + off, H, qkv, e->qkv_n, P.rows, false)));
-            KvCacheView cv = cache_view(e, li);
-            cv.block_ptrs += (size_t)P.s0 * e->max_blocks_per_seq;  // cu_block_nums[b] = b * max_blocks_per_seq: the part's sequence 0
-            TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv, e->q_heads, P.cu_q, e->d_k_len + P.s0, P.nseq, P.rows, e->d_rope, e->rope_max_pos,
-                                                           cv, st, L.qkv_bias, L.q_norm, L.k_norm, eps, rope_row0 ? rope_row0 + P.s0 : nullptr)));
-            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + P.s0, e->d_k_len + P.s0, P.cu_q, L.window,
-                                                               P.nseq, max_k_len, kflat_stride, cv, st)));
-            PrefillAttnParams p{};
-            p.q          = qkv;
-            p.q_stride   = e->qkv_n;
-            p.out        = e->d_attn + (size_t)P.r0 * kq;
-            p.k          = e->d_kflat;
-            p.vt         = e->d_vflat;
-            p.k_stride   = kflat_stride;
-            p.cu_q_len   = P.cu_q;
-            p.cu_k_off   = e->d_cu_koff + P.s0;   // offsets into the flat K / V^T scratch of the WHOLE forward
-            p.k_len      = e->d_k_len + P.s0;
-            p.batch      = P.nseq;
-            p.max_q_len  = max_q_len;
-            p.q_heads    = e->q_heads;
-            p.kv_heads   = e->kv_heads;
-            p.scale_log2 = scale_log2;
-            p.head_dim   = e->D;
-            p.window     = L.window;
-            p.sinks      = L.sinks;
-            TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
-            TM_PROF(P_GEMM_O, TM_TRY(linear_plain(e, L.wo, e->d_attn + (size_t)P.r0 * kq, kq, e->d_tmp + off, H, P.rows, false)));
-            TM_TRY(allreduce_rows_side(e, P.r0, P.rows, &done[h]));
-        }
-        for (int h = 0; h < 2; ++h) {
-            const Part&  P   = part[h];
-            const size_t off = (size_t)P.r0 * H;
-            TM_TRY(pipe_wait(e, done[h]));
-            TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, L.wo_bias, L.ffn_norm, eps,
-                                                               P.rows, H, st, e->hidden_valid)));
-            TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x + off, H, e->d_act + (size_t)P.r0 * e->inter, e->inter, P.rows, true)));
-            TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act + (size_t)P.r0 * e->inter, e->inter, e->d_tmp + off, H, P.rows, false)));
-            TM_TRY(allreduce_rows_side(e, P.r0, P.rows, &done[h]));
-        }
+    int slabs = 1;
+    TM_PROF(gemm_cat, TM_TRY(linear_deferrable(e, l, x, ldx, e->d_tmp, e->hidden, M, false, !e->use_comm, &slabs)));
+    if (slabs > 1) {
+        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
+                                                           e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
+        return 0;
     }
-    for (int h = 0; h < 2; ++h) {
-        const size_t off = (size_t)part[h].r0 * H;
-        TM_TRY(pipe_wait(e, done[h]));
-        TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, nullptr, e->final_norm, eps,
-                                                           part[h].rows, H, st, e->hidden_valid)));
-    }
-    return 0;
+    return reduce_residual_norm(e, M, norm_w, bias);
 }
 
 // ---- RMSNorm folded into the decode GEMMs (tp = 1, dense u4 layers, M <= 64; NormFold in tm_kernels.h) ----------------------------
@@ -322,9 +194,7 @@ static void fold_tiling(tm_engine* e, const LinearWeight& w, int M, int* shape, 
         *shape  = M <= 64 ? 0 : (producer ? 7 : 4);
         *splits = 1;
     }
-    if (gemm_workspace_bytes(M, w.N, *splits) > e->gemm_ws_bytes) {
-        *splits = 1;
-    }
+    *splits = fit_splits(e, M, w.N, *splits);
 }
 
 static bool fold_ok(const tm_engine* e, const Layer& L, int M)
@@ -380,6 +250,356 @@ static int linear_fold_produce(tm_engine* e, LinearSlots& l, const half_t* x, in
     return 0;
 }
 
+// ---- layer blocks: written once for every schedule; the only places where a Layer's attention features reach a kernel --------------
+// w_qkv over R's rows of d_x -> d_qkv.  fold: the consumer of a folded norm (ss_tiles).  fused (decode + int8 KV): the attention kernel
+// consumes the GEMM's raw output (fp32 split-K slabs, *slabs > 1, or fp16), applies RoPE and quantises / stores the new K/V itself -> no
+// splitk_reduce, no kv_rope_store launch; it defers whenever the launch splits, communicator or not
+static int qkv_project(tm_engine* e, Layer& L, const Rows& R, bool fold, bool fused, int ss_tiles, int* slabs)
+{
+    const half_t* const x = e->d_x + (size_t)R.r0 * e->hidden;
+    half_t* const       y = e->d_qkv + (size_t)R.r0 * e->qkv_n;
+    TM_PROF(P_GEMM_QKV, TM_TRY(fold  ? linear_fold_consume(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false, ss_tiles, fused, slabs) :
+                               fused ? linear_deferrable(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false, true, slabs) :
+                                       linear_plain(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false)));
+    return 0;
+}
+
+// RoPE + K/V quantise-store of R's rows of d_qkv (rope_row0: the forward's per-sequence table rows, nullptr: one table)
+static int kv_store(tm_engine* e, const Layer& L, const KvCacheView& cv, const Rows& R, hipStream_t st, const int* rope_row0)
+{
+    return launch_kv_rope_store(e->d_qkv + (size_t)R.r0 * e->qkv_n, e->q_heads, R.cu_q, R.k_len, R.nseq, R.rows, e->d_rope, e->rope_max_pos, cv,
+                                st, L.qkv_bias, L.q_norm, L.k_norm, e->cfg.model.rms_eps, rope_row0 ? rope_row0 + R.s0 : nullptr);
+}
+
+// prefill attention of R's sequences: their K/V (stored before: kv_store) flattened into the scratch, attention over it
+static int prefill_attention_block(tm_engine* e, const Layer& L, const KvCacheView& cv, const Rows& R, int max_q_len, int max_k_len,
+                                   int kflat_stride, float scale_log2)
+{
+    // (a windowed layer flattens from the first 64-key stage of its window on: launch_flatten_kv_window; window 0 = the whole context)
+    TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + R.s0, R.k_len, R.cu_q, L.window, R.nseq,
+                                                       max_k_len, kflat_stride, cv, e->stream)));
+    PrefillAttnParams p{};
+    p.q          = e->d_qkv + (size_t)R.r0 * e->qkv_n;
+    p.q_stride   = e->qkv_n;
+    p.out        = e->d_attn + (size_t)R.r0 * e->q_heads * e->D;
+    p.k          = e->d_kflat;
+    p.vt         = e->d_vflat;
+    p.k_stride   = kflat_stride;
+    p.cu_q_len   = R.cu_q;
+    p.cu_k_off   = e->d_cu_koff + R.s0;  // offsets into the flat K / V^T scratch of the WHOLE forward
+    p.k_len      = R.k_len;
+    p.batch      = R.nseq;
+    p.max_q_len  = max_q_len;
+    p.q_heads    = e->q_heads;
+    p.kv_heads   = e->kv_heads;
+    p.scale_log2 = scale_log2;
+    p.head_dim   = e->D;
+    p.window     = L.window;
+    p.sinks      = L.sinks;
+    TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, e->stream)));
+    return 0;
+}
+
+// decode attention of R's one-token sequences on stream `st`: a pure decode step, or the leading decode rows of a mixed forward.
+// prologue_slabs >= 1: the kernel's fused prologue (bias, q/k norm, RoPE, K/V quantise-store) reads the raw projection -- 1: the fp16 rows
+// of d_qkv, > 1: that many fp32 split-K slabs in d_gemm_ws; 0 (fp16 KV, head_dim 64, windows, per-sequence RoPE): kv_store first
+static int decode_attention_block(tm_engine* e, const Layer& L, const KvCacheView& cv, const Rows& R, int prologue_slabs, float scale_log2,
+                                  hipStream_t st, const int* rope_row0)
+{
+    DecodeAttnParams p{};
+    if (prologue_slabs == 0) {
+        TM_PROF(P_KV_STORE, TM_TRY(kv_store(e, L, cv, R, st, rope_row0)));
+    }
+    else {
+        p.qkv_slabs  = prologue_slabs > 1 ? e->d_gemm_ws : nullptr;
+        p.qkv_f16    = prologue_slabs > 1 ? nullptr : e->d_qkv;
+        p.qkv_splits = prologue_slabs > 1 ? prologue_slabs : 0;
+        p.qkv_n      = e->qkv_n;
+        p.cos_sin    = e->d_rope;
+        p.max_pos    = e->rope_max_pos;
+        p.qkv_bias   = L.qkv_bias;
+        p.q_norm     = L.q_norm;
+        p.k_norm     = L.k_norm;
+        p.qk_eps     = e->cfg.model.rms_eps;
+    }
+    p.q          = e->d_qkv;
+    p.q_stride   = e->qkv_n;
+    p.out        = e->d_attn;
+    p.k_len      = R.k_len;
+    p.batch      = R.nseq;
+    p.q_heads    = e->q_heads;
+    p.scale_log2 = scale_log2;
+    p.splits     = e->decode_splits;
+    p.partial_o  = e->d_attn_ws;
+    p.partial_ml = e->d_attn_ws + (size_t)R.nseq * e->q_heads * e->decode_splits * e->D;
+    p.cache      = cv;
+    p.window     = L.window;
+    p.sinks      = L.sinks;
+    TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, st)));
+    return 0;
+}
+
+// tp > 1 prefill on the pipe, R's rows: wo -> d_tmp, the exchange of the partial sums started on the side stream (*done)
+static int pipe_wo(tm_engine* e, Layer& L, const Rows& R, hipEvent_t* done)
+{
+    const int kq = e->q_heads * e->D;
+    TM_PROF(P_GEMM_O, TM_TRY(linear_plain(e, L.wo, e->d_attn + (size_t)R.r0 * kq, kq, e->d_tmp + (size_t)R.r0 * e->hidden, e->hidden, R.rows, false)));
+    return allreduce_rows_side(e, R.r0, R.rows, done);
+}
+
+// closes an exchange: R's rows of d_tmp are summed by now (or the stream waits here); residual (+ bias) + RMSNorm of them
+static int pipe_close(tm_engine* e, const Rows& R, hipEvent_t done, const half_t* bias, const half_t* norm_w)
+{
+    const size_t off = (size_t)R.r0 * e->hidden;
+    TM_TRY(pipe_wait(e, done));
+    TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x + off, e->d_resid + off, e->d_tmp + off, nullptr, 0, bias, norm_w,
+                                                       e->cfg.model.rms_eps, R.rows, e->hidden, e->stream, e->hidden_valid)));
+    return 0;
+}
+
+// row-wise dense FFN of R's rows: closes their wo exchange (*done), w1w3 + gated SiLU, w2 -> d_tmp, exchange started (*done)
+static int pipe_ffn(tm_engine* e, Layer& L, const Rows& R, hipEvent_t* done)
+{
+    half_t* const act = e->d_act + (size_t)R.r0 * e->inter;
+    const size_t  off = (size_t)R.r0 * e->hidden;
+    TM_TRY(pipe_close(e, R, *done, L.wo_bias, L.ffn_norm));
+    TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x + off, e->hidden, act, e->inter, R.rows, true)));
+    TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, act, e->inter, e->d_tmp + off, e->hidden, R.rows, false)));
+    return allreduce_rows_side(e, R.r0, R.rows, done);
+}
+
+// -- the unsplit tail of a layer over all M rows: from the attention output to the next layer's normalised input
+static int tail_dense(tm_engine* e, Layer& L, int M, const half_t* next_norm)
+{
+    TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
+    TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true)));
+    return linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN);
+}
+
+// wo's epilogue updates the residual stream and hands r . g + sums of squares to w1w3, whose accumulators take the row factor before
+// the gated SiLU; w2 does the same for the next layer's w_qkv when that layer folds too (next_folds; the last layer's w2 feeds the final
+// norm and the fp16 lm_head: reduce-norm launch as before).  5 launches per layer instead of 7.  *ss_tiles: what w2 leaves for w_qkv.
+static int tail_folded(tm_engine* e, Layer& L, int M, const half_t* next_norm, bool next_folds, int* ss_tiles)
+{
+    if (e->fold_norm & 1) {
+        TM_PROF(P_GEMM_O, TM_TRY(linear_fold_produce(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, ss_tiles)));
+    }
+    else {
+        TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
+    }
+    TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_fold_consume(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true, *ss_tiles, false, nullptr)));
+    *ss_tiles = 0;
+    if ((e->fold_norm & 2) && next_folds) {
+        TM_PROF(P_GEMM_DOWN, TM_TRY(linear_fold_produce(e, L.w2, e->d_act, e->inter, M, next_norm, ss_tiles)));
+        return 0;
+    }
+    return linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN);
+}
+
+// router + grouped expert FFNs + combine -> d_tmp, then (all-reduce +) residual + RMSNorm as for the dense FFN
+static int tail_moe(tm_engine* e, Layer& L, int M, const half_t* next_norm)
+{
+    TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
+    const half_t* shared = nullptr;
+    if (L.has_shared) {
+        // Qwen2-MoE: the shared expert is the layer's dense FFN (unified_decoder.cc:295-318); its output waits in d_shared for
+        // the combine, which scales it by sigmoid(x . shared_gate) and adds the routed experts (moe_combine_shared_kernel)
+        TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->shared_inter, M, true)));
+        TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act, e->shared_inter, e->d_shared, e->hidden, M, false)));
+        shared = e->d_shared;
+    }
+    TM_PROF(P_GEMM_GATE_UP, TM_TRY(moe_forward(L.moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr, nullptr, e->stream,
+                                               kMoeAll, shared)));
+    return reduce_residual_norm(e, M, next_norm);
+}
+
+// Tensor-parallel prefill forward, dense layer, from the attention output to the next layer's QKV projection, as two row halves
+// A = [0, Ma), B = [Ma, M): every operator here is row-wise, so a half's all-reduce (RCCL on the side stream, engine_comm.hip) runs
+// under the other half's GEMMs on the engine stream --
+//   engine stream:  wo A | wo B | norm A  w1w3 A  w2 A | norm B  w1w3 B  w2 B | norm A  qkv' A | norm B  qkv' B
+//   side stream:         | AR A        | AR B                 | AR A                   | AR B
+// (qkv' = the NEXT layer's w_qkv: it hides the last exchange; absent behind the last layer).  Same kernels, same per-row arithmetic
+// as the unsplit sequence (reduce_residual_norm's RCCL branch): a row's result does not depend on which rows share its launch, as
+// long as both forms pick the same tiling -- they pick per launch size, so equality with the unsplit forward is to rounding, and the
+// parity gate is the engine's usual one against the oracle.  Reference role: the overlap the reference gets from its fused
+// all-reduce + norm kernel (unified_decoder.cc:278,328; comm/cuda_ipc/fused_allreduce.cu:406-500).
+static int forward_tail_two_halves(tm_engine* e, Layer& L, int M, int Ma, const half_t* next_norm, Layer* next)
+{
+    const Rows half[2] = {{0, Ma}, {Ma, M - Ma}};
+    hipEvent_t done[2];
+    for (int h = 0; h < 2; ++h) {
+        TM_TRY(pipe_wo(e, L, half[h], &done[h]));
+    }
+    for (int h = 0; h < 2; ++h) {
+        TM_TRY(pipe_ffn(e, L, half[h], &done[h]));
+    }
+    for (int h = 0; h < 2; ++h) {
+        TM_TRY(pipe_close(e, half[h], done[h], nullptr, next_norm));
+        if (next) {
+            TM_TRY(qkv_project(e, *next, half[h], false, false, 0, nullptr));
+        }
+    }
+    return 0;
+}
+
+// Tensor-parallel prefill forward whose sequences split into two micro-batches A = sequences [0, seqs_a) = rows [0, rows_a) and B = the
+// rest (prefill_slots decides; e->mb): between the embedding and the lm_head the two share nothing -- not even the attention -- so they
+// leapfrog through ALL layers, every all-reduce of one running on the side stream under a whole block of the other:
+//   engine stream:  attn-block A | attn-block B | ffn A | ffn B | attn-block' A | attn-block' B | ...
+//   side stream:                 | AR(wo A)     | AR(wo B)  | AR(w2 A) | AR(w2 B)       | ...
+// attn-block = (residual + RMSNorm of the previous layer's w2 sum,) w_qkv, RoPE + K/V quantise-store, flatten, attention, wo;
+// ffn = residual + RMSNorm of the wo sum, w1w3 + gated SiLU, w2.  The row-half schedule inside a layer (forward_tail_two_halves) can
+// hide AR(wo A) only under wo B and AR(w2 B) only under the next w_qkv A; here every exchange has a third to a half of the other
+// micro-batch's layer to hide under (measured with the 1-rank exchange stand-in: profiles/r05_prefill_overlap_emulated_exchange.txt).
+// Same kernels and per-row arithmetic as the unsplit forward; dense layers only.
+static int forward_layers_two_microbatches(tm_engine* e, int M, int nseq, int max_q_len, int max_k_len, int kflat_stride, float scale_log2,
+                                           const int* rope_row0)
+{
+    const tm_model_config& m       = e->cfg.model;
+    const int              sa      = e->mb.seqs_a;
+    const Rows             part[2] = {{0, e->mb.rows_a, 0, sa, e->d_cu_q, e->d_k_len},
+                                      {e->mb.rows_a, M - e->mb.rows_a, sa, nseq - sa, e->d_cu_q_b, e->d_k_len + sa}};
+    hipEvent_t             done[2] = {nullptr, nullptr};
+    for (int li = 0; li < m.layers; ++li) {
+        Layer& L = e->layers[li];
+        TM_REQUIRE(!L.is_moe, "internal: micro-batch schedule on a MoE layer");
+        for (int h = 0; h < 2; ++h) {
+            const Rows&       P  = part[h];
+            const KvCacheView cv = cache_view(e, li, P.s0);
+            if (li > 0) {  // this micro-batch's w2 partial sums of the previous layer
+                TM_TRY(pipe_close(e, P, done[h], nullptr, L.attn_norm));
+            }
+            TM_TRY(qkv_project(e, L, P, false, false, 0, nullptr));
+            TM_PROF(P_KV_STORE, TM_TRY(kv_store(e, L, cv, P, e->stream, rope_row0)));
+            TM_TRY(prefill_attention_block(e, L, cv, P, max_q_len, max_k_len, kflat_stride, scale_log2));
+            TM_TRY(pipe_wo(e, L, P, &done[h]));
+        }
+        for (int h = 0; h < 2; ++h) {
+            TM_TRY(pipe_ffn(e, L, part[h], &done[h]));
+        }
+    }
+    for (int h = 0; h < 2; ++h) {
+        TM_TRY(pipe_close(e, part[h], done[h], nullptr, e->final_norm));
+    }
+    return 0;
+}
+
+// tm_engine_score: every row's final-normed hidden state through the lm_head, then its NLL against the next token (the
+// reference's ComputeAndOutputLogits + ComputeCeLoss, output_processor.cc:236-300); no arg-max, sampling or processors
+static int score_rows(tm_engine* e, int M)
+{
+    for (int r0 = 0; r0 < M; r0 += e->score_rows) {
+        const int n = std::min(e->score_rows, M - r0);
+        TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, e->d_x + (size_t)r0 * e->hidden, e->hidden, e->d_score_logits, e->score_ld,
+                                               n, false)));
+        TM_PROF(P_SAMPLE, TM_TRY(launch_cross_entropy(e->d_score_nll + e->score_base + r0, e->d_score_logits,
+                                                      e->d_score_tgt + e->score_base + r0, n, e->vocab_local, e->score_ld, e->stream)));
+    }
+    return 0;
+}
+
+// tp > 1 sampling: the vocabulary shards of `n` logits rows are all-gathered into full rows, d_logits_full (the reference gathers the
+// logits too, models/language_model.cc:304-333); EVERY rank then draws from the same distribution with the same Philox number -> the
+// same token everywhere, no further exchange
+static int gather_logits_tp(tm_engine* e, const half_t* logits, int n)
+{
+    hipStream_t  st  = e->stream;
+    const size_t cnt = (size_t)n * e->vocab_local;
+    if (!e->comm) {
+        // native communicator alone: the shards travel through the P2P segments, as many whole rows per exchange as
+        // one segment buffer holds; rank q's rows land in its [n][vocab / tp] plane of d_logits_gather
+        half_t*   data[8];
+        uint32_t* flags[8];
+        p2p_tables(e, data, flags);
+        const size_t tile = (size_t)e->p2p_rows * e->hidden;  // fp16 elements of one segment buffer
+        const int    per  = (int)std::min<size_t>(n, tile / e->vocab_local);
+        TM_REQUIRE(per >= 1, "native communicator: one logits row does not fit a segment buffer (export more rows)");
+        for (int r0 = 0; r0 < n; r0 += per) {
+            const int rows = std::min(per, n - r0);
+            TM_TRY(launch_p2p_allgather(data, flags, e->cfg.tp, e->cfg.rank, e->p2p_state, tile, logits + (size_t)r0 * e->vocab_local,
+                                        e->d_logits_gather + (size_t)r0 * e->vocab_local, rows * e->vocab_local / 2, st,
+                                        cnt / 2));
+        }
+    }
+    else {
+        TM_NCCL_CHECK(ncclAllGather(logits, e->d_logits_gather, cnt, ncclHalf, e->comm, st));
+    }
+    gather_vocab_kernel<<<std::min<size_t>(1024, (cnt * e->cfg.tp / 8 + 255) / 256), 256, 0, st>>>(
+        e->d_logits_full, e->d_logits_gather, n, e->vocab_local, e->cfg.tp);
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// tp > 1 greedy: every rank's (best value, global index) per row is exchanged, the best of them picked -> ids
+static int argmax_tp(tm_engine* e, int* ids, const half_t* logits, int n)
+{
+    hipStream_t st = e->stream;
+    TM_TRY(launch_argmax(ids, e->d_argmax_val, logits, n, e->vocab_local, e->vocab_local, e->cfg.rank * e->vocab_local, st));
+    pack_candidates_kernel<<<(n + 63) / 64, 64, 0, st>>>(e->d_cand, ids, e->d_argmax_val, n);
+    TM_HIP_CHECK(hipGetLastError());
+    if (e->p2p_ready) {
+        half_t*   data[8];
+        uint32_t* flags[8];
+        p2p_tables(e, data, flags);
+        TM_TRY(launch_p2p_allgather(data, flags, e->cfg.tp, e->cfg.rank, e->p2p_state, (size_t)e->p2p_rows * e->hidden, e->d_cand,
+                                    e->d_cand_all, n * 2, st));
+    }
+    else {
+        TM_NCCL_CHECK(ncclAllGather(e->d_cand, e->d_cand_all, (size_t)n * 2, ncclFloat, e->comm, st));
+    }
+    pick_kernel<<<(n + 63) / 64, 64, 0, st>>>(ids, e->d_cand_all, e->cfg.tp, n);
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// last-token hidden states -> logits -> next ids, for `n` sequences whose logits / next ids land in the batch slots
+// [slot, slot + n): hx = their hidden rows, ids_in / cu_q (nullptr: one token per sequence) / ntok = the tokens this forward
+// consumed for them, k_len = their context lengths
+static int head(tm_engine* e, const half_t* hx, int n, int slot, const int* ids_in, const int* cu_q, int ntok, const int* k_len,
+                const int* active = nullptr)
+{
+    hipStream_t st     = e->stream;
+    half_t*     logits = e->d_logits + (size_t)slot * e->vocab_local;
+    int*        ids    = e->d_next_ids + slot;
+    TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, hx, e->hidden, logits, e->vocab_local, n, false)));
+    if (e->logits_on) {
+        // the tokens this forward consumed join the slots' seen masks, then penalty / bans on the (local) logits
+        uint32_t* seen = e->d_seen + (size_t)slot * e->seen_words;
+        TM_PROF(P_SAMPLE, TM_TRY(launch_seen_update(seen, e->seen_words, ids_in, cu_q, n, ntok, e->cfg.model.vocab, st, active)));
+        TM_PROF(P_SAMPLE, TM_TRY(launch_logits_process(logits, n, e->vocab_local, e->vocab_local,
+                                                       e->vocab_local < e->cfg.model.vocab ? e->cfg.rank * e->vocab_local : 0, seen,
+                                                       e->seen_words, e->d_lp_rep + slot, e->d_lp_ban + slot * kMaxBadIds,
+                                                       e->d_lp_end + slot * kMaxEndIds, k_len, e->d_lp_minlen + slot, st)));
+    }
+    if (e->sampling_on && (!e->use_comm || ((e->comm || e->p2p_ready) && e->d_logits_full))) {
+        // parameters are indexed by batch slot, the counter (context length) by the row of this forward
+        const half_t* lg = logits;
+        int           V  = e->vocab_local;
+        if (e->use_comm) {
+            TM_TRY(gather_logits_tp(e, logits, n));
+            V  = e->vocab_local * e->cfg.tp;
+            lg = e->d_logits_full;
+        }
+        TM_PROF(P_SAMPLE, TM_TRY(launch_sample_uniform(e->d_u + slot, e->d_seed + slot, k_len, n, st)));
+        // static batch with tm_engine_set_logprobs: the kept candidates' logprobs of this step join the record of (slot, step)
+        // continuous batching with tm_engine_request_logprobs: the record of (slot, this step), handed to the host behind the step
+        const bool           lpr_cb = e->sched && e->cb_logprobs_on;
+        const bool           lpr    = (e->logprobs_on && !e->sched) || lpr_cb;
+        const SampleLogprobs lp = lpr_cb ? SampleLogprobs{e->d_cb_lp_vals, e->d_cb_lp_idx, e->d_cb_lp_num, e->d_cb_lp_sel, kMaxLogProb, nullptr, 0, 1, slot, 1}
+                                         : SampleLogprobs{e->d_lpr_vals, e->d_lpr_idx, e->d_lpr_num, e->d_lpr_sel, e->logprobs_n, e->d_step, 1, e->max_new,
+                                                          slot, e->max_new};
+        TM_PROF(P_SAMPLE, TM_TRY(launch_sample(ids, lpr ? e->d_kept + slot : nullptr, lg, n, V, V, e->d_temp + slot, e->d_topk + slot,
+                                               e->d_topp + slot, e->d_minp + slot, e->d_u + slot, e->d_sample_ws, st, lpr ? &lp : nullptr)));
+    }
+    else if (!e->use_comm) {
+        TM_PROF(P_SAMPLE, TM_TRY(launch_argmax(ids, nullptr, logits, n, e->vocab_local, e->vocab_local, 0, st)));
+    }
+    else {
+        TM_TRY(argmax_tp(e, ids, logits, n));
+    }
+    return 0;
+}
+
 // One forward over M tokens.  decode: one token per sequence (cu_q = 0..B); prefill: nseq sequences.
 // Mixed forward (continuous batching, the reference's unified batch: unified_attention_layer.cc:310-311 puts the decode rows
 // first): `md` != nullptr and !decode -> rows [0, md->rows) are the decode tokens of batch slots 0 .. md->rows-1 (their KV
@@ -396,12 +616,12 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     // per-sequence RoPE tables: the row offsets are indexed by batch slot, this forward's sequence 0 sits in slot0
     const int* const rope_row0 = e->d_rope_row0 ? e->d_rope_row0 + slot0 : nullptr;
     TM_REQUIRE(!rope_row0 || !e->fuse_qkv, "internal: fused decode prologue with per-sequence RoPE tables");
-    half_t* const qkv_p  = e->d_qkv + (size_t)nd * e->qkv_n;            // first prefill row
-    half_t* const attn_p = e->d_attn + (size_t)nd * e->q_heads * e->D;
+    const float scale_log2 = (1.0f / std::sqrt((float)e->D)) * 1.4426950408889634f;
+    const Rows  own{nd, M - nd, 0, nseq, e->d_cu_q, e->d_k_len};  // the forward's own sequences: every row unless it is mixed
+    const Rows  dec{0, nd, 0, nd, md ? md->cu_q : nullptr, md ? md->k_len : nullptr};  // mixed: decode rows = batch slots 0 .. nd-1
     TM_PROF(P_EMBED, TM_TRY(launch_embedding(e->d_resid, e->tok_embeddings, d_ids, M, e->hidden, m.vocab, st)));
     TM_PROF(P_RES_NORM, TM_TRY(launch_rmsnorm(e->d_x, e->d_resid, e->layers[0].attn_norm, m.rms_eps, M, e->hidden, st, e->hidden_valid)));
-    const float scale_log2 = (1.0f / std::sqrt((float)e->D)) * 1.4426950408889634f;
-    // tp > 1 prefill through RCCL: the row-wise part of every dense layer as two row halves, all-reduces on the side stream
+    // tp > 1 prefill through RCCL: whole dense layers as two micro-batches, or their row-wise part as two row halves (side-stream all-reduces)
     e->pipe_events_used = 0;
     const bool  pipe     = !decode && !md && prefill_pipe_ok(e, M);
     const int   Ma       = pipe ? (M / 2 + 63) / 64 * 64 : 0;
@@ -414,297 +634,74 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
         e->pipe_mb_forwards += 1;
         TM_TRY(forward_layers_two_microbatches(e, M, nseq, max_q_len, max_k_len, kflat_stride, scale_log2, rope_row0));
     }
-    bool        qkv_done = false;  // the previous layer's two-halves tail already projected this layer's QKV
-    int         ss_tiles   = 0;  // > 0: d_x holds r . g of a folded producer, d_ss its sums of squares (the next GEMM applies the row factor)
+    const bool aux      = md && e->mixed_two_streams && e->aux_stream;  // mixed: the decode rows' attention beside the prefill rows'
+    const bool fuse_qkv = decode && e->fuse_qkv;
+    bool       qkv_done = false;  // the previous layer's two-halves tail already projected this layer's QKV
+    int        ss_tiles = 0;  // > 0: d_x holds r . g of a folded producer, d_ss its sums of squares (the next GEMM applies the row factor)
     for (int li = 0; li < (two_mb ? 0 : m.layers); ++li) {
-        Layer& L = e->layers[li];
-        KvCacheView cv = cache_view(e, li);
-        const bool fold = decode && fold_ok(e, L, M);
+        Layer&            L    = e->layers[li];
+        Layer* const      nxt  = li + 1 < m.layers ? &e->layers[li + 1] : nullptr;
+        const half_t*     next_norm = nxt ? nxt->attn_norm : e->final_norm;
+        const KvCacheView cv   = cache_view(e, li);
+        const bool        fold = decode && fold_ok(e, L, M);
         TM_REQUIRE(ss_tiles == 0 || fold, "internal: folded norm without a folded consumer");
-        // decode + int8 KV: the attention kernel consumes the qkv GEMM's raw output (fp32 split-K slabs or fp16),
-        // applies RoPE and quantises/stores the new K/V itself -> no splitk_reduce, no kv_rope_store launch
-        const bool fuse_qkv = decode && e->fuse_qkv;
-        int        qkv_slabs = 1;
-        if (fold) {
-            TM_PROF(P_GEMM_QKV, TM_TRY(linear_fold_consume(e, L.qkv, e->d_x, e->hidden, e->d_qkv, e->qkv_n, M, false, ss_tiles, fuse_qkv, &qkv_slabs)));
-            ss_tiles = 0;
-            if (!fuse_qkv) {
-                TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                               e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps, rope_row0)));
-            }
+        int qkv_slabs = 1;
+        if (!qkv_done) {
+            TM_TRY(qkv_project(e, L, Rows{0, M}, fold, fuse_qkv, ss_tiles, &qkv_slabs));
         }
-        else if (fuse_qkv && L.qkv.w.cscale) {
-            TM_PROF(P_GEMM_QKV, TM_TRY(linear_fp8_channel(e, L.qkv.w, e->d_x, e->hidden, e->d_qkv, e->qkv_n, M, false, true, &qkv_slabs)));
-        }
-        else if (fuse_qkv) {
-            GemmConfig cfg = gemm_pick_config(L.qkv.w, M);
-            if (gemm_workspace_bytes(M, L.qkv.w.N, cfg.splits) > e->gemm_ws_bytes) {
-                cfg.splits = 1;
-            }
-            TM_PROF(P_GEMM_QKV, TM_TRY(launch_linear(L.qkv.w, e->d_x, e->hidden, e->d_qkv, e->qkv_n, M, false, cfg,
-                                                     e->d_gemm_ws, cfg.splits > 1, &qkv_slabs, st)));
-        }
-        else {
-            if (!qkv_done) {
-                TM_PROF(P_GEMM_QKV, TM_TRY(linear_plain(e, L.qkv, e->d_x, e->hidden, e->d_qkv, e->qkv_n, M, false)));
-            }
-            qkv_done = false;
-            TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(qkv_p, e->q_heads, e->d_cu_q, e->d_k_len, nseq, M - nd, e->d_rope,
-                                                           e->rope_max_pos, cv, st, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps, rope_row0)));
-        }
-        if (md) {
-            // decode rows: (fused prologue: RoPE + K/V quantise-store) + attention on the fp16 projection rows; they share
-            // nothing with the prefill rows' path below, so they run beside it on the aux stream (fork here, join behind the
-            // prefill attention) -- the reference's decode / prefill split of a unified batch
-            hipStream_t dst = st;
-            if (e->mixed_two_streams && e->aux_stream) {
-                TM_HIP_CHECK(hipEventRecord(e->ev_aux_fork, st));
-                TM_HIP_CHECK(hipStreamWaitEvent(e->aux_stream, e->ev_aux_fork, 0));
-                dst = e->aux_stream;
-            }
-            KvCacheView cvd = cv;
-            cvd.block_ptrs  = md->block_ptrs;
-            DecodeAttnParams p{};
-            if (e->fuse_qkv) {
-                p.qkv_f16 = e->d_qkv;
-                p.qkv_n   = e->qkv_n;
-                p.cos_sin = e->d_rope;
-                p.max_pos = e->rope_max_pos;
-                p.qkv_bias = L.qkv_bias;
-                p.q_norm   = L.q_norm;
-                p.k_norm   = L.k_norm;
-                p.qk_eps   = m.rms_eps;
-            }
-            else {  // fp16 KV (no fused prologue): RoPE + store of the decode rows' K/V first
-                TM_PROF(P_KV_STORE, TM_TRY(launch_kv_rope_store(e->d_qkv, e->q_heads, md->cu_q, md->k_len, nd, nd, e->d_rope,
-                                                               e->rope_max_pos, cvd, dst, L.qkv_bias, L.q_norm, L.k_norm, m.rms_eps,
-                                                               e->d_rope_row0)));  // decode rows = batch slots 0 .. nd-1
-            }
-            p.q              = e->d_qkv;
-            p.q_stride       = e->qkv_n;
-            p.out            = e->d_attn;
-            p.k_len          = md->k_len;
-            p.batch          = nd;
-            p.q_heads        = e->q_heads;
-            p.scale_log2     = scale_log2;
-            p.splits         = e->decode_splits;
-            p.partial_o      = e->d_attn_ws;
-            p.partial_ml     = e->d_attn_ws + (size_t)nd * e->q_heads * e->decode_splits * e->D;
-            p.cache          = cvd;
-            p.window         = L.window;
-            p.sinks          = L.sinks;
-            TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, dst)));
-            if (dst != st) {
-                TM_HIP_CHECK(hipEventRecord(e->ev_aux_join, dst));
-            }
-        }
+        ss_tiles = 0;
+        qkv_done = false;
         if (decode) {
-            DecodeAttnParams p{};
-            if (fuse_qkv) {
-                p.qkv_slabs  = qkv_slabs > 1 ? e->d_gemm_ws : nullptr;
-                p.qkv_f16    = qkv_slabs > 1 ? nullptr : e->d_qkv;
-                p.qkv_splits = qkv_slabs > 1 ? qkv_slabs : 0;
-                p.qkv_n      = e->qkv_n;
-                p.cos_sin    = e->d_rope;
-                p.max_pos    = e->rope_max_pos;
-                p.qkv_bias   = L.qkv_bias;
-                p.q_norm     = L.q_norm;
-                p.k_norm     = L.k_norm;
-                p.qk_eps     = m.rms_eps;
-            }
-            p.q          = e->d_qkv;
-            p.q_stride   = e->qkv_n;
-            p.out        = e->d_attn;
-            p.k_len      = e->d_k_len;
-            p.batch      = nseq;
-            p.q_heads    = e->q_heads;
-            p.scale_log2 = scale_log2;
-            p.splits     = e->decode_splits;
-            p.partial_o  = e->d_attn_ws;
-            p.partial_ml = e->d_attn_ws + (size_t)nseq * e->q_heads * e->decode_splits * e->D;
-            p.cache      = cv;
-            p.window     = L.window;
-            p.sinks      = L.sinks;
-            TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, st)));
+            TM_TRY(decode_attention_block(e, L, cv, own, fuse_qkv ? qkv_slabs : 0, scale_log2, st, rope_row0));
         }
         else {
-            // (a windowed layer flattens from the first 64-key stage of its window on: launch_flatten_kv_window; window 0 = the whole context)
-            TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff, e->d_k_len, e->d_cu_q, L.window, nseq,
-                                                               max_k_len, kflat_stride, cv, st)));
-            PrefillAttnParams p{};
-            p.q          = qkv_p;
-            p.q_stride   = e->qkv_n;
-            p.out        = attn_p;
-            p.k          = e->d_kflat;
-            p.vt         = e->d_vflat;
-            p.k_stride   = kflat_stride;
-            p.cu_q_len   = e->d_cu_q;
-            p.cu_k_off   = e->d_cu_koff;
-            p.k_len      = e->d_k_len;
-            p.batch      = nseq;
-            p.max_q_len  = max_q_len;
-            p.q_heads    = e->q_heads;
-            p.kv_heads   = e->kv_heads;
-            p.scale_log2 = scale_log2;
-            p.head_dim   = e->D;
-            p.window     = L.window;
-            p.sinks      = L.sinks;
-            TM_PROF(P_ATTN, TM_TRY(launch_prefill_attention(p, st)));
-            if (md && e->mixed_two_streams && e->aux_stream) {
+            TM_PROF(P_KV_STORE, TM_TRY(kv_store(e, L, cv, own, st, rope_row0)));
+            if (md) {
+                // decode rows: (fused prologue: RoPE + K/V quantise-store) + attention on the fp16 projection rows; they share
+                // nothing with the prefill rows' path below, so they run beside it on the aux stream (fork here, join behind the
+                // prefill attention) -- the reference's decode / prefill split of a unified batch
+                if (aux) {
+                    TM_HIP_CHECK(hipEventRecord(e->ev_aux_fork, st));
+                    TM_HIP_CHECK(hipStreamWaitEvent(e->aux_stream, e->ev_aux_fork, 0));
+                }
+                KvCacheView cvd = cv;
+                cvd.block_ptrs  = md->block_ptrs;
+                TM_TRY(decode_attention_block(e, L, cvd, dec, e->fuse_qkv ? 1 : 0, scale_log2, aux ? e->aux_stream : st, e->d_rope_row0));
+                if (aux) {
+                    TM_HIP_CHECK(hipEventRecord(e->ev_aux_join, e->aux_stream));
+                }
+            }
+            TM_TRY(prefill_attention_block(e, L, cv, own, max_q_len, max_k_len, kflat_stride, scale_log2));
+            if (aux) {
                 TM_HIP_CHECK(hipStreamWaitEvent(st, e->ev_aux_join, 0));  // join: wo reads the decode rows' attention output too
             }
         }
-        const half_t* next_norm = li + 1 < m.layers ? e->layers[li + 1].attn_norm : e->final_norm;
         if (pipe && !L.is_moe) {
-            Layer* const nxt = li + 1 < m.layers ? &e->layers[li + 1] : nullptr;
             TM_TRY(forward_tail_two_halves(e, L, M, Ma, next_norm, nxt));
             qkv_done = nxt != nullptr;
-            continue;
         }
-        if (fold) {
-            // wo's epilogue updates the residual stream and hands r . g + sums of squares to w1w3, whose accumulators take the row
-            // factor before the gated SiLU; w2 does the same for the next layer's w_qkv (the last layer's w2 feeds the final norm
-            // and the fp16 lm_head: reduce-norm launch as before).  5 launches per layer instead of 7.
-            if (e->fold_norm & 1) {
-                TM_PROF(P_GEMM_O, TM_TRY(linear_fold_produce(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, &ss_tiles)));
-            }
-            else {
-                TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
-            }
-            TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_fold_consume(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true, ss_tiles, false, nullptr)));
-            ss_tiles = 0;
-            if ((e->fold_norm & 2) && li + 1 < m.layers && fold_ok(e, e->layers[li + 1], M)) {
-                TM_PROF(P_GEMM_DOWN, TM_TRY(linear_fold_produce(e, L.w2, e->d_act, e->inter, M, next_norm, &ss_tiles)));
-            }
-            else {
-                TM_TRY(linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN));
-            }
-            continue;
+        else if (fold) {
+            TM_TRY(tail_folded(e, L, M, next_norm, nxt && fold_ok(e, *nxt, M), &ss_tiles));
         }
-        TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
-        if (L.is_moe) {
-            // router + grouped expert FFNs + combine -> d_tmp, then (all-reduce +) residual + RMSNorm as for the dense FFN
-            const half_t* shared = nullptr;
-            if (L.has_shared) {
-                // Qwen2-MoE: the shared expert is the layer's dense FFN (unified_decoder.cc:295-318); its output waits in d_shared for
-                // the combine, which scales it by sigmoid(x . shared_gate) and adds the routed experts (moe_combine_shared_kernel)
-                TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->shared_inter, M, true)));
-                TM_PROF(P_GEMM_DOWN, TM_TRY(linear_plain(e, L.w2, e->d_act, e->shared_inter, e->d_shared, e->hidden, M, false)));
-                shared = e->d_shared;
-            }
-            TM_PROF(P_GEMM_GATE_UP, TM_TRY(moe_forward(L.moe, e->d_tmp, e->hidden, e->d_x, e->hidden, M, e->d_moe_ws, nullptr,
-                                                       nullptr, st, kMoeAll, shared)));
-            TM_TRY(reduce_residual_norm(e, M, next_norm));
-            continue;
-        }
-        TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true)));
-        TM_TRY(linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN));
-    }
-    if (e->scoring) {
-        // tm_engine_score: every row's final-normed hidden state through the lm_head, then its NLL against the next token (the
-        // reference's ComputeAndOutputLogits + ComputeCeLoss, output_processor.cc:236-300); no arg-max, sampling or processors
-        TM_REQUIRE(!decode && !md && !e->use_comm, "internal: scoring forward");
-        for (int r0 = 0; r0 < M; r0 += e->score_rows) {
-            const int n = std::min(e->score_rows, M - r0);
-            TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, e->d_x + (size_t)r0 * e->hidden, e->hidden, e->d_score_logits, e->score_ld,
-                                                   n, false)));
-            TM_PROF(P_SAMPLE, TM_TRY(launch_cross_entropy(e->d_score_nll + e->score_base + r0, e->d_score_logits,
-                                                          e->d_score_tgt + e->score_base + r0, n, e->vocab_local, e->score_ld, st)));
-        }
-        return 0;
-    }
-    // last-token hidden states -> logits -> next ids, for `n` sequences whose logits / next ids land in the batch slots
-    // [slot, slot + n): hx = their hidden rows, ids / cu_q (nullptr: one token per sequence) / ntok = the tokens this forward
-    // consumed for them, k_len = their context lengths
-    auto head = [&](const half_t* hx, int n, int slot, const int* ids_in, const int* cu_q, int ntok, const int* k_len,
-                    const int* active = nullptr) -> int {
-        half_t* logits = e->d_logits + (size_t)slot * e->vocab_local;
-        int*    ids    = e->d_next_ids + slot;
-        TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, hx, e->hidden, logits, e->vocab_local, n, false)));
-        if (e->logits_on) {
-            // the tokens this forward consumed join the slots' seen masks, then penalty / bans on the (local) logits
-            uint32_t* seen = e->d_seen + (size_t)slot * e->seen_words;
-            TM_PROF(P_SAMPLE, TM_TRY(launch_seen_update(seen, e->seen_words, ids_in, cu_q, n, ntok, m.vocab, st, active)));
-            TM_PROF(P_SAMPLE, TM_TRY(launch_logits_process(logits, n, e->vocab_local, e->vocab_local,
-                                                           e->vocab_local < m.vocab ? e->cfg.rank * e->vocab_local : 0, seen,
-                                                           e->seen_words, e->d_lp_rep + slot, e->d_lp_ban + slot * kMaxBadIds,
-                                                           e->d_lp_end + slot * kMaxEndIds, k_len, e->d_lp_minlen + slot, st)));
-        }
-        if (e->sampling_on && (!e->use_comm || ((e->comm || e->p2p_ready) && e->d_logits_full))) {
-            // parameters are indexed by batch slot, the counter (context length) by the row of this forward
-            const half_t* lg = logits;
-            int           V  = e->vocab_local;
-            if (e->use_comm) {
-                // tp > 1: the vocabulary shards are all-gathered into full rows (the reference gathers the logits too,
-                // models/language_model.cc:304-333) and EVERY rank draws from the same distribution with the same Philox
-                // number -> the same token everywhere, no further exchange
-                const size_t cnt = (size_t)n * e->vocab_local;
-                if (!e->comm) {
-                    // native communicator alone: the shards travel through the P2P segments, as many whole rows per exchange as
-                    // one segment buffer holds; rank q's rows land in its [n][vocab / tp] plane of d_logits_gather
-                    half_t*   data[8];
-                    uint32_t* flags[8];
-                    p2p_tables(e, data, flags);
-                    const size_t tile = (size_t)e->p2p_rows * e->hidden;  // fp16 elements of one segment buffer
-                    const int    per  = (int)std::min<size_t>(n, tile / e->vocab_local);
-                    TM_REQUIRE(per >= 1, "native communicator: one logits row does not fit a segment buffer (export more rows)");
-                    for (int r0 = 0; r0 < n; r0 += per) {
-                        const int rows = std::min(per, n - r0);
-                        TM_TRY(launch_p2p_allgather(data, flags, e->cfg.tp, e->cfg.rank, e->p2p_state, tile, logits + (size_t)r0 * e->vocab_local,
-                                                    e->d_logits_gather + (size_t)r0 * e->vocab_local, rows * e->vocab_local / 2, st,
-                                                    cnt / 2));
-                    }
-                }
-                else {
-                    TM_NCCL_CHECK(ncclAllGather(logits, e->d_logits_gather, cnt, ncclHalf, e->comm, st));
-                }
-                V = e->vocab_local * e->cfg.tp;
-                gather_vocab_kernel<<<std::min<size_t>(1024, (cnt * e->cfg.tp / 8 + 255) / 256), 256, 0, st>>>(
-                    e->d_logits_full, e->d_logits_gather, n, e->vocab_local, e->cfg.tp);
-                TM_HIP_CHECK(hipGetLastError());
-                lg = e->d_logits_full;
-            }
-            TM_PROF(P_SAMPLE, TM_TRY(launch_sample_uniform(e->d_u + slot, e->d_seed + slot, k_len, n, st)));
-            // static batch with tm_engine_set_logprobs: the kept candidates' logprobs of this step join the record of (slot, step)
-            // continuous batching with tm_engine_request_logprobs: the record of (slot, this step), handed to the host behind the step
-            const bool           lpr_cb = e->sched && e->cb_logprobs_on;
-            const bool           lpr    = (e->logprobs_on && !e->sched) || lpr_cb;
-            const SampleLogprobs lp = lpr_cb ? SampleLogprobs{e->d_cb_lp_vals, e->d_cb_lp_idx, e->d_cb_lp_num, e->d_cb_lp_sel, kMaxLogProb, nullptr, 0, 1, slot, 1}
-                                             : SampleLogprobs{e->d_lpr_vals, e->d_lpr_idx, e->d_lpr_num, e->d_lpr_sel, e->logprobs_n, e->d_step, 1, e->max_new,
-                                                              slot, e->max_new};
-            TM_PROF(P_SAMPLE, TM_TRY(launch_sample(ids, lpr ? e->d_kept + slot : nullptr, lg, n, V, V, e->d_temp + slot, e->d_topk + slot,
-                                                   e->d_topp + slot, e->d_minp + slot, e->d_u + slot, e->d_sample_ws, st, lpr ? &lp : nullptr)));
-        }
-        else if (!e->use_comm) {
-            TM_PROF(P_SAMPLE, TM_TRY(launch_argmax(ids, nullptr, logits, n, e->vocab_local, e->vocab_local, 0, st)));
+        else if (L.is_moe) {
+            TM_TRY(tail_moe(e, L, M, next_norm));
         }
         else {
-            TM_TRY(launch_argmax(ids, e->d_argmax_val, logits, n, e->vocab_local, e->vocab_local, e->cfg.rank * e->vocab_local, st));
-            pack_candidates_kernel<<<(n + 63) / 64, 64, 0, st>>>(e->d_cand, ids, e->d_argmax_val, n);
-            TM_HIP_CHECK(hipGetLastError());
-            if (e->p2p_ready) {
-                half_t*   data[8];
-                uint32_t* flags[8];
-                p2p_tables(e, data, flags);
-                TM_TRY(launch_p2p_allgather(data, flags, e->cfg.tp, e->cfg.rank, e->p2p_state, (size_t)e->p2p_rows * e->hidden, e->d_cand,
-                                            e->d_cand_all, n * 2, st));
-            }
-            else {
-                TM_NCCL_CHECK(ncclAllGather(e->d_cand, e->d_cand_all, (size_t)n * 2, ncclFloat, e->comm, st));
-            }
-            pick_kernel<<<(n + 63) / 64, 64, 0, st>>>(ids, e->d_cand_all, e->cfg.tp, n);
-            TM_HIP_CHECK(hipGetLastError());
+            TM_TRY(tail_dense(e, L, M, next_norm));
         }
-        return 0;
-    };
+    }
+    if (e->scoring) {
+        TM_REQUIRE(!decode && !md && !e->use_comm, "internal: scoring forward");
+        return score_rows(e, M);
+    }
     if (decode) {
-        return head(e->d_x, nseq, slot0, d_ids, nullptr, M, e->d_k_len);
+        return head(e, e->d_x, nseq, slot0, d_ids, nullptr, M, e->d_k_len);
     }
     if (md) {  // the decode rows first: their slots are 0 .. nd-1; the prefilled slots' entries are overwritten right after
-        TM_TRY(head(e->d_x, nd, 0, d_ids, nullptr, nd, md->k_len, md->active));
+        TM_TRY(head(e, e->d_x, nd, 0, d_ids, nullptr, nd, md->k_len, md->active));
     }
     TM_TRY(launch_gather_rows(e->d_last, e->d_x, e->d_rows, nseq, e->hidden, st));
-    return head(e->d_last, nseq, slot0, d_ids + nd, e->d_cu_q, M - nd, e->d_k_len);
+    return head(e, e->d_last, nseq, slot0, d_ids + nd, e->d_cu_q, M - nd, e->d_k_len);
 }
 
 // next ids become the current ids and are appended to generated[b][step]

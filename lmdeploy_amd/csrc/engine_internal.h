@@ -387,6 +387,11 @@ int rope_reset(tm_engine* e, int slot0, int n);
 size_t prof_event(tm_engine* e);
 void p2p_tables(tm_engine* e, half_t** data, uint32_t** flags);
 int reduce_residual_norm(tm_engine* e, int M, const half_t* norm_w, const half_t* bias = nullptr);
+// the split-K count a launch may use: fp32 slabs that do not fit the engine's workspace leave one slice
+inline int fit_splits(const tm_engine* e, int M, int N, int splits)
+{
+    return gemm_workspace_bytes(M, N, splits) > e->gemm_ws_bytes ? 1 : splits;
+}
 bool prefill_pipe_ok(const tm_engine* e, int M);
 int allreduce_rows_side(tm_engine* e, int r0, int rows, hipEvent_t* done);
 int pipe_wait(tm_engine* e, hipEvent_t done);

@@ -100,7 +100,7 @@ int tune_decode_gemms(tm_engine* e, int M, bool verbose)
             cfg.kphases   = 1;
             cfg.d32_shape = cand[i][0];
             cfg.splits    = cand[i][1];
-            if (gemm_workspace_bytes(M, w0.N, cfg.splits) > e->gemm_ws_bytes) {
+            if (fit_splits(e, M, w0.N, cfg.splits) != cfg.splits) {
                 continue;
             }
             const bool norm_consumer = (r.which == 1 || (r.which == 3 && !shared_ffn)) && !e->use_comm;
@@ -369,7 +369,7 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
         GemmConfig bc = heur;
         for (int i = 0; i < nc; ++i) {
             const GemmConfig cfg = cand[i];
-            if (gemm_workspace_bytes(M, w0.N, cfg.splits) > e->gemm_ws_bytes) {
+            if (fit_splits(e, M, w0.N, cfg.splits) != cfg.splits) {
                 continue;
             }
             auto chain = [&]() -> int {
