@@ -58,10 +58,15 @@ typedef struct tm_kv_cache {
     int             kv_heads;      /* local kv heads                                               */
     int             head_dim;      /* 64 | 128                                                     */
     int             block_len;     /* 64 tokens (lmdeploy/messages.py:323)                         */
-    int             bits;          /* quant_policy: 16 (none) | 8 | 4 (lmdeploy/messages.py:20-27) */
+    int             bits;          /* quant_policy: 16 (none) | 8 | 4 | 42 (lmdeploy/messages.py:20-27) */
 } tm_kv_cache;
 
-/* bytes of one layer inside a block: kv_heads*2*block_len*(head_dim*bits/8) + kv_heads*2*block_len*4*[bits<16] */
+/* bytes of one layer inside a block: kv_heads*2*block_len*(head_dim*bits/8) + kv_heads*2*block_len*4*[bits<16].
+ * bits 42 (TurboQuant, head_dim 128 only): K rows of head_dim/2 bytes (3-bit Lloyd-Max code of the Hadamard-rotated row + the sign of
+ * the residual per element), V rows of head_dim/4 bytes (2-bit code), one fp16 pair per row each (K: norm, residual norm; V: norm, 0):
+ * kv_heads*block_len*(head_dim/2 + head_dim/4 + 8).  Per kv head K data [block_len][head_dim/2], then V data [block_len][head_dim/4];
+ * behind the data of all heads, per head, K params then V params.  tm_kv_rope_store*, tm_flatten_kv and tm_decode_attention serve it;
+ * head_dim 64, the fused decode prologue, a window > 0 and sinks return TM_INVALID with bits 42. */
 int64_t tm_kv_layer_size(int kv_heads, int head_dim, int block_len, int bits);
 
 /* ----------------------------------------------------------------------------------------------
@@ -578,7 +583,7 @@ typedef struct tm_engine_config {
     int   device;             /* HIP device ordinal                                          */
     int   max_batch_size;     /* TurbomindEngineConfig.max_batch_size                        */
     int   session_len;        /* max context per sequence                                    */
-    int   quant_policy;       /* 0 | 4 | 8  (lmdeploy/messages.py:20-27)                     */
+    int   quant_policy;       /* 0 | 4 | 8 | 42 (lmdeploy/messages.py:20-27); 42 = TurboQuant KV: head_dim 128, no window / sinks, tp 1 */
     int   cache_block_seq_len;/* 64                                                          */
     float cache_max_entry_count; /* fraction of free HBM for KV blocks if cache_blocks == 0 */
     int   cache_blocks;       /* explicit number of KV blocks (0 = derive)                   */

@@ -474,6 +474,10 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     if (p.batch == 0) {
         return 0;
     }
+    if (L.bits == 42) {
+        // TurboQuant KV: a kernel of its own in the rotated domain (attention_decode_tq.hip), which names what it refuses
+        return launch_decode_attention_tq(p, st);
+    }
     const bool fused = p.qkv_slabs || p.qkv_f16;
     TM_REQUIRE(!fused || L.bits == 8 || L.bits == 4, "fused decode prologue: int8 / int4 KV only");
     // the Qwen prologue (bias / q-k norm) exists only in the fused MFMA path; unfused kernels read q after launch_kv_rope_store applied it

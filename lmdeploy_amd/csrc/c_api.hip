@@ -337,6 +337,8 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
     TM_REQUIRE(out && qkv && k_len && cache, "null pointer");
     TM_REQUIRE(cache->head_dim == 128,
                "fused decode prologue: head_dim must be 128 (head_dim 64: tm_kv_rope_store + tm_decode_attention)");
+    TM_REQUIRE(cache->bits != 42,
+               "fused decode prologue with kv bits 42 (TurboQuant) is not built: run tm_kv_rope_store + tm_decode_attention");
     TM_REQUIRE(cache->bits == 8 || cache->bits == 4, "fused decode prologue: int8 / int4 KV only");
     TM_REQUIRE(qkv_n == (q_heads + 2 * cache->kv_heads) * 128, "qkv_n != (q_heads + 2 kv_heads) * 128");
     DecodeAttnParams p{};

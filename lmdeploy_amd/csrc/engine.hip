@@ -308,8 +308,13 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
     TM_REQUIRE(m.kv_heads % c->tp == 0 || c->tp % m.kv_heads == 0, "kv_heads vs tp");
     TM_REQUIRE(m.rope_type >= 0 && m.rope_type <= 4, "rope_type in {0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic}");
-    TM_REQUIRE(c->quant_policy == 0 || c->quant_policy == 4 || c->quant_policy == 8,
-               "quant_policy in {0,4,8} (lmdeploy/messages.py:351-358)");
+    TM_REQUIRE(c->quant_policy == 0 || c->quant_policy == 4 || c->quant_policy == 8 || c->quant_policy == 42,
+               "quant_policy in {0,4,8,42} (lmdeploy/messages.py:351-358)");
+    // TurboQuant KV (turboquant.h): the 128-wide rotation, full attention, one rank
+    TM_REQUIRE(c->quant_policy != 42 || m.head_dim == 128, "quant_policy 42 (TurboQuant KV) needs head_dim 128: head_dim 64 is not built");
+    TM_REQUIRE(c->quant_policy != 42 || (m.attn_window == 0 && m.attn_sinks == 0),
+               "quant_policy 42 (TurboQuant KV) with a sliding window or attention sinks is not built");
+    TM_REQUIRE(c->quant_policy != 42 || c->tp == 1, "quant_policy 42 (TurboQuant KV) with tp > 1 is not built (run with tp = 1)");
     TM_REQUIRE(c->cache_block_seq_len == 64, "cache_block_seq_len must be 64");
     TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8, "weight_type");
     TM_REQUIRE(m.fp8_scale_mode == 0 || (m.fp8_scale_mode == 1 && m.weight_type == TM_WEIGHT_FP8),
@@ -789,6 +794,8 @@ int tm_engine_start(tm_engine* e)
             e->layers[i].window = w >= c.session_len ? 0 : w;
             e->windowed |= e->layers[i].window > 0;
         }
+        TM_REQUIRE(c.quant_policy != 42 || !e->windowed,
+                   "quant_policy 42 (TurboQuant KV) with a sliding window or attention sinks is not built");
         // the folded norm divides by hidden and has no bias term: a zero-padded model or an o_proj bias runs the norm launches
         if (e->windowed || e->hidden_valid != e->hidden || m.attn_out_bias) {
             e->fold_norm = 0;

@@ -841,7 +841,8 @@ void setup_decode(tm_engine* e, int batch)
         // 1.547 .. 1.587 with 64 x 8 (Llama-3-8B shard), 5.06 against 5.26 (Llama-3-70B shard).  fp16 KV (VALU kernel, <= 4
         // heads per workgroup): two workgroups per CU as before.
         // head_dim 64 decodes on the VALU kernel for every KV width: its head-per-workgroup rule
-        const bool mfma  = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128 && !e->windowed;
+        // quant_policy 42 (TurboQuant KV): a VALU kernel of the same workgroup shape (attention_decode_tq.hip), never the fused prologue
+        const bool mfma = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128 && !e->windowed;
         const int  group = e->q_heads / e->kv_heads;
         int        hpw   = 1;
         if (mfma) {

@@ -8,6 +8,8 @@
 //   mn = min x, mx = max x; scale = h((f32(mx)-f32(mn)) * (1/(2^b-1))); zero = mn;
 //   inv = h(1/f32(scale)); q = sat_u8(rne(h(h(x-zero)*inv))); b==4: min(q,15), nibbles [0,2,4,6,1,3,5,7].
 // Byte layout of a block: kernels/attention/block.h:126-219 (KvLayout in tm_kernels.h).
+// KV bits 42 (TurboQuant: Hadamard rotation, K 4-bit / V 2-bit Lloyd-Max codes, fp16 norms) has a contract of its own, stated in
+// turboquant.h; both kernels below carry an `if constexpr` arm for it on the same lane mapping (head_dim 128 only).
 //
 // Work mapping: D/8 lanes own one D-wide head row (8 halves = 16 B each, one coalesced row): 16 lanes (256 B) at head_dim 128,
 // 8 lanes (128 B) at head_dim 64; min/max are wave-level DPP reductions inside that lane row -- no LDS.  HBM-bound byte work.
@@ -15,6 +17,7 @@
 // 16-lane row would mix two tokens), a 256-thread workgroup holds 2048 / D token rows.
 #include "tm_common.h"
 #include "tm_kernels.h"
+#include "turboquant.h"
 #include <tuple>
 
 namespace tmk {
@@ -138,10 +141,27 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
     const int blk     = pos / L.block_len;
     const int ti      = pos - blk * L.block_len;
     char*     block   = (char*)cache.block_ptrs[cache.cu_block_nums[b] + blk] + cache.layer_offset;
-    const int doff    = is_k ? L.k_data(kv_head, ti) : L.v_data(kv_head, ti);
+    int       doff;
+    if constexpr (BITS == kTqBits) {
+        doff = is_k ? L.tq_k_data(kv_head, ti) : L.tq_v_data(kv_head, ti);
+    }
+    else {
+        doff = is_k ? L.k_data(kv_head, ti) : L.v_data(kv_head, ti);
+    }
 
     if constexpr (BITS == 16) {
         *(half8_t*)(block + doff + lane16 * 16) = x;
+    }
+    else if constexpr (BITS == kTqBits) {
+        // TurboQuant (turboquant.h): the row's 16 lanes rotate, code and pack it; whole rows got here together
+        static_assert(D == 128, "TurboQuant KV: head_dim 128");
+        char* par = block + (is_k ? L.tq_k_param(kv_head, ti) : L.tq_v_param(kv_head, ti));
+        if (is_k) {
+            tq_store_row<true>(x, lane16, block + doff, par);
+        }
+        else {
+            tq_store_row<false>(x, lane16, block + doff, par);
+        }
     }
     else {
         float mx = -INFINITY, mnn = -INFINITY;  // mnn tracks max(-x)
@@ -209,7 +229,9 @@ int launch_kv_rope_store(half_t*        qkv,
     TM_REQUIRE(hd == 64 || hd == 128, "kv_rope_store: head_dim must be 64 or 128");
     TM_REQUIRE(hd == 128 || (q_norm == nullptr && k_norm == nullptr), "kv_rope_store: q/k RMSNorm (qk_norm) needs head_dim 128");
     TM_REQUIRE(rope_row0 == nullptr || cos_sin != nullptr, "rope_row0 needs a table");
-    TM_REQUIRE(cache.layout.bits == 16 || cache.layout.bits == 8 || cache.layout.bits == 4, "kv bits in {16,8,4}");
+    const int kvb = cache.layout.bits;
+    TM_REQUIRE(kvb == 16 || kvb == 8 || kvb == 4 || kvb == kTqBits, "kv bits in {16,8,4,42}");
+    TM_REQUIRE(kvb != kTqBits || hd == 128, "kv_rope_store: kv bits 42 (TurboQuant) needs head_dim 128, head_dim 64 is not built");
     TM_REQUIRE((q_norm == nullptr) == (k_norm == nullptr), "q_norm and k_norm come together");
     if (total_tokens == 0) {
         return 0;
@@ -241,6 +263,18 @@ int launch_kv_rope_store(half_t*        qkv,
         case 8:
             if (qkx) TM_KV_STORE(8, true);
             else TM_KV_STORE(8, false);
+            break;
+        case kTqBits:  // head_dim 128 only (checked above)
+            if (qkx) {
+                if (rope_row0 != nullptr) TM_KV_STORE_D(kTqBits, true, true, 128);
+                else TM_KV_STORE_D(kTqBits, true, false, 128);
+            }
+            else if (rope_row0 != nullptr) {
+                TM_KV_STORE_D(kTqBits, false, true, 128);
+            }
+            else {
+                TM_KV_STORE_D(kTqBits, false, false, 128);
+            }
             break;
         default:
             if (qkx) TM_KV_STORE(4, true);
@@ -370,8 +404,15 @@ __global__ __launch_bounds__(256) void flatten_kv_kernel(half_t* __restrict__ k_
         const bool valid = t0 + ti < n;
         half8_t    kk = {}, vv = {};
         if (valid) {
-            kk = load_dequant_flatten<BITS>(block + L.k_data(hd, ti), block + L.k_param(hd, ti), lane16);
-            vv = load_dequant_flatten<BITS>(block + L.v_data(hd, ti), block + L.v_param(hd, ti), lane16);
+            if constexpr (BITS == kTqBits) {  // the 16 lanes of a row share `valid`: the row butterflies run with all of them
+                static_assert(D == 128, "TurboQuant KV: head_dim 128");
+                kk = tq_flatten_row<true>(block + L.tq_k_data(hd, ti), block + L.tq_k_param(hd, ti), lane16);
+                vv = tq_flatten_row<false>(block + L.tq_v_data(hd, ti), block + L.tq_v_param(hd, ti), lane16);
+            }
+            else {
+                kk = load_dequant_flatten<BITS>(block + L.k_data(hd, ti), block + L.k_param(hd, ti), lane16);
+                vv = load_dequant_flatten<BITS>(block + L.v_data(hd, ti), block + L.v_param(hd, ti), lane16);
+            }
             *(half8_t*)(k_out + (obase + t0 + ti) * D + lane16 * 8) = kk;
             if constexpr (!VT) {
                 *(half8_t*)(v_out + (obase + t0 + ti) * D + lane16 * 8) = vv;
@@ -436,6 +477,17 @@ static int launch_flatten_kv_impl(half_t*     k_out,
         else TM_FLATTEN_D(B_, T_, 128);         \
     } while (0)
     const int bits = cache.layout.bits;
+    TM_REQUIRE(bits == 16 || bits == 8 || bits == 4 || bits == kTqBits, "kv bits in {16,8,4,42}");
+    if (bits == kTqBits) {
+        TM_REQUIRE(hd == 128, "flatten_kv: kv bits 42 (TurboQuant) needs head_dim 128, head_dim 64 is not built");
+        TM_REQUIRE(!WIN, "flatten_kv: kv bits 42 (TurboQuant) with a sliding window is not built (window must be 0)");
+        if constexpr (!WIN) {
+            if (transpose_v) TM_FLATTEN_D(kTqBits, true, 128);
+            else TM_FLATTEN_D(kTqBits, false, 128);
+        }
+        TM_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     if (transpose_v) {
         if (bits == 16) TM_FLATTEN(16, true);
         else if (bits == 8) TM_FLATTEN(8, true);

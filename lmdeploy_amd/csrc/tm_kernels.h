@@ -11,15 +11,20 @@ struct KvLayout {
     int kv_heads;
     int head_dim;   // 64 | 128
     int block_len;  // 64
-    int bits;       // 16 | 8 | 4
+    int bits;       // 16 | 8 | 4 | 42 (TurboQuant: K rows of 4-bit codes, V rows of 2-bit codes; turboquant.h)
+    // K and V rows have sizes of their own: equal (bits * head_dim / 8) for 16 / 8 / 4, head_dim / 2 and head_dim / 4 for 42
+    __host__ __device__ int k_token_size() const { return bits == 42 ? head_dim / 2 : token_data_size(); }
+    __host__ __device__ int v_token_size() const { return bits == 42 ? head_dim / 4 : token_data_size(); }
+    __host__ __device__ int layer_size() const
+    {
+        return bits == 42 ? kv_heads * tq_head_data_size() + kv_heads * 2 * tq_head_param_size() :
+                            kv_heads * 2 * head_data_size() + kv_heads * 2 * head_param_size();
+    }
+    // ---- bits 16 / 8 / 4: the offsets the kernels of those widths compile (unchanged by the TurboQuant rows below) ----
     __host__ __device__ int token_data_size() const { return bits * head_dim / 8; }
     __host__ __device__ int token_param_size() const { return bits < 16 ? 4 : 0; }
     __host__ __device__ int head_data_size() const { return block_len * token_data_size(); }
     __host__ __device__ int head_param_size() const { return block_len * token_param_size(); }
-    __host__ __device__ int layer_size() const
-    {
-        return kv_heads * 2 * head_data_size() + kv_heads * 2 * head_param_size();
-    }
     __host__ __device__ int k_data(int head, int ti) const { return head * 2 * head_data_size() + ti * token_data_size(); }
     __host__ __device__ int v_data(int head, int ti) const { return k_data(head, ti) + head_data_size(); }
     __host__ __device__ int k_param(int head, int ti) const
@@ -27,6 +32,20 @@ struct KvLayout {
         return kv_heads * 2 * head_data_size() + head * 2 * head_param_size() + ti * token_param_size();
     }
     __host__ __device__ int v_param(int head, int ti) const { return k_param(head, ti) + head_param_size(); }
+    // ---- bits 42: per kv head K rows [block_len][head_dim / 2], then V rows [block_len][head_dim / 4]; behind the data of all heads,
+    // per head, K params [block_len][4 B], then V params.  Only the code paths of bits 42 call these. ----
+    __host__ __device__ int tq_head_data_size() const { return block_len * (head_dim / 2 + head_dim / 4); }
+    __host__ __device__ int tq_head_param_size() const { return block_len * 4; }
+    __host__ __device__ int tq_k_data(int head, int ti) const { return head * tq_head_data_size() + ti * (head_dim / 2); }
+    __host__ __device__ int tq_v_data(int head, int ti) const
+    {
+        return head * tq_head_data_size() + block_len * (head_dim / 2) + ti * (head_dim / 4);
+    }
+    __host__ __device__ int tq_k_param(int head, int ti) const
+    {
+        return kv_heads * tq_head_data_size() + head * 2 * tq_head_param_size() + ti * 4;
+    }
+    __host__ __device__ int tq_v_param(int head, int ti) const { return tq_k_param(head, ti) + tq_head_param_size(); }
 };
 
 struct KvCacheView {
@@ -114,6 +133,8 @@ struct DecodeAttnParams {
 };
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip
+// attention_decode_tq.hip: KV bits 42 (TurboQuant), head_dim 128, in the rotated domain; no window, sinks or fused prologue
+int launch_decode_attention_tq(const DecodeAttnParams& p, hipStream_t st);
 size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, int splits);
 
 // ---- attention_prefill.hip --------------------------------------------------------------

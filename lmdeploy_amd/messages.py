@@ -177,7 +177,10 @@ class TurbomindEngineConfig:
     """TurboMind Engine config -- same field names and defaults as the reference (lmdeploy/messages.py:302-343).
 
     Models: the attention path serves head_dim 128 and, through the Llama reader (Llama-3.2-1B, TinyLlama, SmolLM2: fp16 / bf16 or
-    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  model_format='fp8' with 128x128 block scales needs head_dim
+    model_format='awq'), head_dim 64 with every quant_policy (0 / 4 / 8).  quant_policy=42 (QuantPolicy.TURBO_QUANT) keeps the
+    TurboQuant KV cache: per row a Hadamard rotation, K as a 3-bit Lloyd-Max code plus the sign of the residual (4 bits), V as a 2-bit
+    code, two fp16 norms -- 104 bytes per token and kv head at head_dim 128 instead of 136 (int4) / 264 (int8).  It needs head_dim 128,
+    full attention (no sliding window, no sinks) and tp = 1; anything else raises NotImplementedError with the reason.  model_format='fp8' with 128x128 block scales needs head_dim
     128.  FP8 checkpoints with one scale per tensor (`quant_method: "fp8"` without weight_block_size: AutoFP8 / `*-FP8`) or per output
     channel (`quant_method: "compressed-tensors"`, `format: "float-quantized"`: llm-compressor `*-FP8-dynamic`) load as they are, dense
     and Mixtral alike, head_dim 64 included: every decoder linear and expert runs on the fp8 matrix cores with its activations quantised
@@ -256,8 +259,8 @@ class TurbomindEngineConfig:
         assert self.num_tokens_per_iter >= 0, 'invalid num_tokens_per_iter'
         assert self.async_ in (0, 1), 'async_ must be 0 (disabled) or 1 (enabled)'
         # ... plus: everything outside the hot path must be asked for explicitly and fails loudly
-        if self.quant_policy == QuantPolicy.TURBO_QUANT:
-            raise NotImplementedError('quant_policy=TURBO_QUANT')
+        if self.quant_policy == QuantPolicy.TURBO_QUANT and self.tp > 1:
+            raise NotImplementedError('quant_policy=TURBO_QUANT (42) with tp > 1: the TurboQuant KV cache is built for tp = 1')
         if self.dtype == 'bfloat16':
             raise NotImplementedError('dtype=bfloat16: the AWQ path is fp16 (lmdeploy/turbomind/converter.py:40-48)')
         if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel'):

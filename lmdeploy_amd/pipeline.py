@@ -96,6 +96,8 @@ class Pipeline:
                                                                                   'fp8_channel': ('fp8_channel',)}[cfg.model_format]:
                 raise ValueError(f'model_format="{cfg.model_format}" but the checkpoint\'s quantization_config says {have} '
                                  f'(lmdeploy/turbomind/converter.py:174-176)')
+        # the TurboQuant KV cache (quant_policy=42): head_dim 128, full attention, tp = 1 -- refused here, by name, before any GPU work
+        checkpoint.check_kv_quant_policy(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
         session_len = cfg.session_len or self.model_cfg.max_position_embeddings
         self.session_len = int(session_len)
         devices = cfg.devices or list(range(cfg.tp))

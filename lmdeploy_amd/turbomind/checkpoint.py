@@ -86,6 +86,22 @@ class ModelConfig:
     layer_windows: list | None = None  # gpt-oss: one sliding window per layer (0 = full attention), from `layer_types`
 
 
+def check_kv_quant_policy(cfg, quant_policy: int, tp: int = 1, what: str = 'this model'):
+    """quant_policy 42 (TurboQuant KV cache: a 128-wide Hadamard rotation per row, decode attention in the rotated domain) serves
+    head_dim 128 with full attention on one rank; NotImplementedError with the reason for anything else.  Every other policy passes."""
+    if int(quant_policy) != 42:
+        return
+    if cfg.head_dim != 128:
+        raise NotImplementedError(f'quant_policy=42 (TurboQuant KV) with {what} of head_dim {cfg.head_dim}: the rotation and its '
+                                  f'kernels are built for head_dim 128')
+    windows = [int(w) for w in (getattr(cfg, 'layer_windows', None) or [])]
+    if int(getattr(cfg, 'window', 0) or 0) > 0 or any(w > 0 for w in windows) or getattr(cfg, 'attn_sinks', 0):
+        raise NotImplementedError(f'quant_policy=42 (TurboQuant KV) with {what}, which has a sliding window or attention sinks: '
+                                  f'the TurboQuant decode attention serves full attention only')
+    if tp > 1:
+        raise NotImplementedError('quant_policy=42 (TurboQuant KV) with tp > 1: built for tp = 1')
+
+
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
 # in every layer) and Qwen2-MoE (the Qwen2 prologue; routed experts plus a shared expert behind a sigmoid gate in every layer)
 QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM', 'Qwen2MoeForCausalLM')
