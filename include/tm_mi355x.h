@@ -271,7 +271,7 @@ int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st
 
 /* ---- Linear (mirrors _tm.LinearWeight / LlamaLinear.forward_dense / QuantizeGroupwise) -------- */
 typedef struct tm_linear tm_linear;
-enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* MoE expert weights only */ };
+enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* experts weight-only (tm_moe); dense linears W4A4 (tm_linear_prepare_mxfp4) */ };
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size);
 /* Boundary ("TM") layout, device pointers: qweight int32 [K][N/8] (nibble j of word c = column 8c+j,
  * lmdeploy/turbomind/weight_format.py:63-74), scales / zeros fp16 [K/g][N].  For TM_WEIGHT_F16: weight fp16
@@ -341,6 +341,24 @@ int    tm_quant_fp8_token(void* xq, float* sx, const void* x, int ldx, int M, in
 size_t tm_linear_fp8_grouped_workspace(int experts, int x_rows, int K);
 int    tm_linear_forward_fp8_grouped(const tm_linear* const* experts, int E, const void* x, int ldx, int x_rows, void* y, int ldy,
                                      int m_cap, int gated_silu, const int* seg, const int* row_idx, void* workspace, tm_stream_t st);
+/* MXFP4 dense linears, FP4 weights and FP4 activations ("W4A4") on the block-scaled FP4 matrix cores
+ * (v_mfma_scale_f32_32x32x64_f8f6f4).  tm_linear_create(..., TM_WEIGHT_MXFP4, 32); limits: K % 128 == 0, N % 32 == 0, K * N / 2 < 2^31.
+ * Weights arrive in the checkpoint layout of the gpt-oss experts: blocks uint8 [N][K/2] (byte j of row n = k 2j in the low nibble, 2j + 1
+ * in the high nibble; e2m1 code c & 7 -> {0, .5, 1, 1.5, 2, 3, 4, 6}, bit 3 = sign) and scales uint8 [N][K/32] (e8m0: 2^(b - 127), 255 is
+ * never accepted).  Activations are quantised on the fly per row and group of 32 k (tm_quant_mxfp4_rows: codes [M][K/2] in the same
+ * nibble order, scale bytes [M][K/32]): e = floor(log2(amax)) - 2 (-127 for a zero group), byte e + 127, code = e2m1_rne_sat(x / 2^e)
+ * with ties to the even mantissa, saturation to 6 and the sign of zero kept (the OCP MX v1.0 rule), and
+ *   y[m, n] = h( sum_g 2^(sx[m,g] - 127) 2^(sw[n,g] - 127) sum_{k in g} xq[m,k] wq[n,k] )
+ * with the whole sum chained in fp32 on the matrix core, both scale bytes operands of the instruction.  gated_silu as tm_linear_forward
+ * ((gate_j, up_j)-interleaved columns, y [M][N/2]); splits = 0: heuristic, else 1..16 split-K slices through fp32 slabs.
+ * tm_linear_forward_mxfp4 quantises, runs the GEMM and reduces; workspace >= tm_linear_mxfp4_workspace(w, M) bytes.
+ * tm_linear_dequant_f16 on such a weight writes the fp16 [N][K] image lut[code] * 2^(s - 127) rebuilt from the repacked units;
+ * tm_linear_forward returns TM_INVALID: there is no weight-only arm. */
+int    tm_linear_prepare_mxfp4(tm_linear* w, const void* blocks, const void* scales, tm_stream_t st);
+int    tm_quant_mxfp4_rows(void* xq, void* sx, const void* x, int ldx, int M, int K, tm_stream_t st);
+size_t tm_linear_mxfp4_workspace(const tm_linear* w, int M);
+int    tm_linear_forward_mxfp4(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
+                               void* workspace, tm_stream_t st);
 size_t tm_linear_fp8_workspace(const tm_linear* w, int M);
 int    tm_quant_fp8_rows(void* xq, float* sx, const void* x, int ldx, int M, int K, int ldsx, tm_stream_t st);
 int    tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
@@ -531,7 +549,12 @@ typedef struct tm_model_config {
     int   rope_max_position_embeddings;
     float rope_yarn_beta_fast, rope_yarn_beta_slow, rope_yarn_attention_factor;
     int   group_size;   /* 128 */
-    int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16 or TM_WEIGHT_FP8 for the decoder linears; lm_head is fp16 */
+    int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16, TM_WEIGHT_FP8 or TM_WEIGHT_MXFP4 for the decoder linears; lm_head is fp16.
+                         * TM_WEIGHT_MXFP4 (W4A4, tm_linear_prepare_mxfp4's form): dense models at tp = 1, any head_dim the engine serves;
+                         * slots "*.blocks" uint8 [N][K/2] and "*.scales" uint8 [N][K/32] for w_qkv (q | k | v rows stacked), wo, w1w3
+                         * ((gate_j, up_j) rows interleaved) and w2; every such linear runs tm_quant_mxfp4_rows + the block-scaled FP4 MFMA
+                         * GEMM for every M, eager and in the decode graph; the GEMM tuner and the folded norm pass them by; refused
+                         * with TM_INVALID: tp > 1, moe_experts > 0, hidden_valid (padded widths) */
     /* mixture of experts (0 experts = dense FFN): every layer's FFN is a router + `moe_experts` expert FFNs of width
      * `inter` (sharded over tp like the dense FFN), `moe_top_k` per token (Mixtral: 8 / 2, norm_topk = 1) */
     int   moe_experts, moe_top_k, moe_norm_topk;

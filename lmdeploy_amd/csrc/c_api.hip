@@ -437,8 +437,15 @@ int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size)
 {
     TM_REQUIRE(out, "null pointer");
-    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_FP8, "weight_type");
+    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_MXFP4,
+               "weight_type");
     TM_REQUIRE(in_features > 0 && out_features > 0, "shape");
+    if (weight_type == TM_WEIGHT_MXFP4) {
+        TM_REQUIRE(group_size == 32, "mxfp4 dense linear: group_size 32");
+        TM_REQUIRE(in_features % 128 == 0 && out_features % 32 == 0 && (size_t)in_features * out_features / 2 < ((size_t)1 << 31),
+                   "mxfp4 dense linear " + std::to_string(in_features) + " x " + std::to_string(out_features)
+                       + ": K % 128 == 0, N % 32 == 0 and K * N / 2 < 2^31");
+    }
     TM_REQUIRE(gemm_general_image_bytes(in_features, out_features, weight_type) < kGeneralImageLimit,
                "linear " + std::to_string(in_features) + " x " + std::to_string(out_features) + ": its general-kernel image of "
                    + std::to_string(gemm_general_image_bytes(in_features, out_features, weight_type))
@@ -455,6 +462,7 @@ int tm_linear_create(tm_linear** out, int in_features, int out_features, int wei
 int tm_linear_prepare(tm_linear* w, const void* weight, const void* scales, const void* zeros, tm_stream_t st)
 {
     TM_REQUIRE(w && weight, "null pointer");
+    TM_REQUIRE(w->w.type != TM_WEIGHT_MXFP4, "mxfp4 dense linear: tm_linear_prepare_mxfp4 takes its blocks and scale bytes");
     if (w->w.type == TM_WEIGHT_U4) {
         TM_REQUIRE(scales && zeros, "u4 weights need scales and zeros");
         return linear_weight_prepare_u4(w->w, (const int32_t*)weight, (const half_t*)scales, (const half_t*)zeros,
@@ -478,6 +486,9 @@ size_t tm_linear_workspace(const tm_linear* w, int M)
 int tm_linear_dequant_f16(const tm_linear* w, void* out_nk, tm_stream_t st)
 {
     TM_REQUIRE(w && out_nk, "null pointer");
+    if (w->w.type == TM_WEIGHT_MXFP4) {
+        return launch_dequant_p4_f16((half_t*)out_nk, w->w, (hipStream_t)st);
+    }
     return launch_dequant_p32_f16((half_t*)out_nk, w->w, (hipStream_t)st);
 }
 
@@ -487,6 +498,7 @@ int tm_linear_forward(const tm_linear* w, const void* x, int ldx, void* y, int l
 {
     TM_REQUIRE(w && x && y, "null pointer");
     TM_REQUIRE(!w->w.cscale, "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
+    TM_REQUIRE(w->w.type != TM_WEIGHT_MXFP4, "mxfp4 dense linears have no weight-only arm: tm_linear_forward_mxfp4 runs them");
     GemmConfig cfg = gemm_pick_config(w->w, M);  // (workspace: tm_linear_workspace(w, M) bytes)
     if (nt > 0) {
         cfg.nt = nt;
@@ -689,6 +701,46 @@ int tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, i
     if (rc) {
         return rc;
     }
+    if (nslab > 1) {
+        return launch_splitk_reduce((half_t*)y, ldy, slab, nslab, M, w->w.N, gated_silu != 0, (hipStream_t)st);
+    }
+    return 0;
+}
+
+int tm_linear_prepare_mxfp4(tm_linear* w, const void* blocks, const void* scales, tm_stream_t st)
+{
+    TM_REQUIRE(w && blocks && scales, "null pointer");
+    TM_REQUIRE(w->w.type == TM_WEIGHT_MXFP4, "tm_linear_prepare_mxfp4: mxfp4 weights only");
+    return linear_weight_prepare_mxfp4_dense(w->w, (const uint8_t*)blocks, (const uint8_t*)scales, (hipStream_t)st);
+}
+
+int tm_quant_mxfp4_rows(void* xq, void* sx, const void* x, int ldx, int M, int K, tm_stream_t st)
+{
+    TM_REQUIRE(xq && sx && x, "null pointer");
+    return launch_quant_mxfp4_rows((uint8_t*)xq, (uint8_t*)sx, (const half_t*)x, ldx, M, K, (hipStream_t)st);
+}
+
+size_t tm_linear_mxfp4_workspace(const tm_linear* w, int M)
+{
+    if (!w) {
+        return 0;
+    }
+    return (mxfp4_act_workspace_bytes(M, w->w.K) + 255) / 256 * 256 + gemm_workspace_bytes(M, w->w.N, 16);
+}
+
+int tm_linear_forward_mxfp4(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
+                            void* workspace, tm_stream_t st)
+{
+    TM_REQUIRE(w && x && y && workspace, "null pointer");
+    TM_REQUIRE(mxfp4_dense_prepared(w->w), "mxfp4 x mxfp4 linear: a weight prepared by tm_linear_prepare_mxfp4");
+    TM_REQUIRE(splits >= 0 && splits <= 16, "0 <= splits <= 16");
+    const int K    = w->w.K;
+    uint8_t*  xq   = (uint8_t*)workspace;
+    uint8_t*  sx   = xq + (size_t)M * (K / 2);
+    float*    slab = (float*)((char*)workspace + (mxfp4_act_workspace_bytes(M, K) + 255) / 256 * 256);
+    TM_TRY_RC(launch_quant_mxfp4_rows(xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st));
+    int nslab = 1;
+    TM_TRY_RC(launch_linear_mxfp4(w->w, xq, sx, (half_t*)y, ldy, M, gated_silu != 0, splits, slab, &nslab, (hipStream_t)st));
     if (nslab > 1) {
         return launch_splitk_reduce((half_t*)y, ldy, slab, nslab, M, w->w.N, gated_silu != 0, (hipStream_t)st);
     }

@@ -258,7 +258,12 @@ static int prepare_linear(tm_engine* e, LinearSlots& l)
     else if (l.w.type == TM_WEIGHT_MXFP4) {
         Slot &w = e->slots[l.prefix + ".blocks"], &s = e->slots[l.prefix + ".scales"];
         TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
-        TM_TRY(linear_weight_prepare_mxfp4(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
+        if (l.prefix.find(".experts.") == std::string::npos) {  // a dense decoder linear: W4A4 on the block-scaled FP4 matrix cores
+            TM_TRY(linear_weight_prepare_mxfp4_dense(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
+        }
+        else {
+            TM_TRY(linear_weight_prepare_mxfp4(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
+        }
         TM_HIP_CHECK(hipStreamSynchronize(e->stream));
         for (Slot* p : {&w, &s}) {
             TM_HIP_CHECK(hipFree(p->dev));
@@ -316,7 +321,17 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
                "quant_policy 42 (TurboQuant KV) with a sliding window or attention sinks is not built");
     TM_REQUIRE(c->quant_policy != 42 || c->tp == 1, "quant_policy 42 (TurboQuant KV) with tp > 1 is not built (run with tp = 1)");
     TM_REQUIRE(c->cache_block_seq_len == 64, "cache_block_seq_len must be 64");
-    TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8, "weight_type");
+    TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8
+                   || m.weight_type == TM_WEIGHT_MXFP4,
+               "weight_type");
+    if (m.weight_type == TM_WEIGHT_MXFP4) {  // dense W4A4 models on the block-scaled FP4 matrix cores
+        TM_REQUIRE(c->tp == 1, "weight_type mxfp4 (W4A4 dense linears) with tp > 1 is not built (run with tp = 1)");
+        TM_REQUIRE(m.moe_experts == 0,
+                   "weight_type mxfp4 (W4A4 dense linears) with moe_experts > 0 is not built: MXFP4 experts run weight-only under "
+                   "moe_expert_format 3 with fp16 dense linears");
+        TM_REQUIRE(m.hidden_valid == 0 || m.hidden_valid == m.hidden,
+                   "weight_type mxfp4 (W4A4 dense linears) with padded widths (hidden_valid) is not built");
+    }
     TM_REQUIRE(m.fp8_scale_mode == 0 || (m.fp8_scale_mode == 1 && m.weight_type == TM_WEIGHT_FP8),
                "fp8_scale_mode: 0 (128 x 128 blocks) or, with weight_type fp8, 1 (one scale per output channel)");
     TM_REQUIRE(m.fp8_scale_mode == 0 || std::max(m.hidden, std::max(m.inter, m.moe_shared_inter)) <= kFp8TokenMaxK,
@@ -492,12 +507,15 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
         }
         if (l.w.type == TM_WEIGHT_MXFP4) {
             // uniform e2m1 codes (E|value| = 2.25) under scale bytes around 127 - 6: weights of the other synthetic formats' magnitude
+            // (dense W4A4 linears: around the byte that puts 2.25 * 2^(s - 127) next to their 0.1 / sqrt(K))
+            const bool dense = l.prefix.find(".experts.") == std::string::npos;
+            const int  sbase = dense ? 127 + (int)std::lround(std::log2(0.1 / std::sqrt((double)l.w.K) / 2.25)) : 127 - 6;
             Slot *w = nullptr, *sc = nullptr;
             TM_TRY(ensure_slot(e, l.prefix + ".blocks", &w));
             TM_TRY(ensure_slot(e, l.prefix + ".scales", &sc));
             fill_mxfp4_kernel<<<((size_t)w->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)w->dev, (size_t)w->bytes, ++sd, 0);
             TM_HIP_CHECK(hipGetLastError());
-            fill_mxfp4_kernel<<<((size_t)sc->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)sc->dev, (size_t)sc->bytes, ++sd, 127 - 6);
+            fill_mxfp4_kernel<<<((size_t)sc->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)sc->dev, (size_t)sc->bytes, ++sd, sbase);
             TM_HIP_CHECK(hipGetLastError());
             w->filled = sc->filled = true;
             TM_TRY(prepare_linear(e, l));
@@ -765,6 +783,13 @@ int tm_engine_start(tm_engine* e)
         const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), std::max(e->inter, e->shared_inter));
         TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_xq, T * wide_k));
         TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_sx, T * sizeof(float)));
+    }
+    if (m.weight_type == TM_WEIGHT_MXFP4) {
+        // W4A4: e2m1 codes and e8m0 scale bytes of ONE GEMM input (the widest K of a dense linear), written by the quantiser in front of
+        // every dense GEMM -- sized here, nothing is allocated in a forward
+        const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), e->inter);
+        TM_HIP_CHECK(hipMalloc((void**)&e->d_mx_xq, T * (wide_k / 2)));
+        TM_HIP_CHECK(hipMalloc((void**)&e->d_mx_sx, T * (wide_k / 32)));
     }
     {
         const size_t tiles = (size_t)(e->hidden + 63) / 64;
@@ -1107,7 +1132,7 @@ int tm_engine_destroy(tm_engine* e)
         }
     }
     void* bufs[] = {e->pool, e->d_block_ptrs, e->d_cu_block_nums, e->d_resid, e->d_x, e->d_qkv, e->d_attn, e->d_act,
-                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_f8_xq, e->d_f8_sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
+                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_f8_xq, e->d_f8_sx, e->d_mx_xq, e->d_mx_sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
                     e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
                     e->d_rope_row0};

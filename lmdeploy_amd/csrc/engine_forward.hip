@@ -137,8 +137,30 @@ static int linear_fp8_channel(tm_engine* e, const LinearWeight& w, const half_t*
     return 0;
 }
 
+// MXFP4 dense linear (weight_type 3): the GEMM input is quantised per row and group of 32 into the engine's code / scale-byte buffers,
+// then the block-scaled FP4 MFMA kernel runs, for every M.  Slabs as linear_fp8_channel.
+static int linear_mxfp4(tm_engine* e, const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
+                        int* slabs)
+{
+    TM_REQUIRE(e->d_mx_xq && e->d_mx_sx && M <= e->max_tokens, "internal: mxfp4 dense linear without its activation buffers");
+    TM_TRY(launch_quant_mxfp4_rows(e->d_mx_xq, e->d_mx_sx, x, ldx, M, w.K, e->stream));
+    float* const ws    = fit_splits(e, M, w.N, 16) == 16 ? e->d_gemm_ws : nullptr;  // room for the launcher's 16 slabs, or one slice
+    int          nslab = 1;
+    TM_TRY(launch_linear_mxfp4(w, e->d_mx_xq, e->d_mx_sx, y, ldy, M, gated, 0, ws, &nslab, e->stream));
+    if (nslab > 1 && !defer) {
+        TM_TRY(launch_splitk_reduce(y, ldy, ws, nslab, M, w.N, gated, e->stream));
+        nslab = 1;
+    }
+    *slabs = nslab;
+    return 0;
+}
+
 static int linear_plain(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated)
 {
+    if (l.w.type == TM_WEIGHT_MXFP4) {
+        int one;
+        return linear_mxfp4(e, l.w, x, ldx, y, ldy, M, gated, false, &one);
+    }
     if (l.w.cscale) {
         int one;  // the slab count behind a launch that defers nothing
         return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, false, &one);
@@ -157,6 +179,9 @@ static int linear_deferrable(tm_engine* e, LinearSlots& l, const half_t* x, int 
 {
     if (l.w.cscale) {
         return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, defer, slabs);
+    }
+    if (l.w.type == TM_WEIGHT_MXFP4) {
+        return linear_mxfp4(e, l.w, x, ldx, y, ldy, M, gated, defer, slabs);
     }
     GemmConfig cfg = gemm_pick_config(l.w, M);
     cfg.splits     = fit_splits(e, M, l.w.N, cfg.splits);

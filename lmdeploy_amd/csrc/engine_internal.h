@@ -156,6 +156,8 @@ struct tm_engine {
     float*  d_gemm_ws = nullptr;
     uint8_t* d_f8_xq  = nullptr;  // channel-scaled fp8 (fp8_scale_mode 1): e4m3 codes [max_tokens][widest K] of the current GEMM input ...
     float*   d_f8_sx  = nullptr;  // ... and its per-token scales [max_tokens]
+    uint8_t* d_mx_xq  = nullptr;  // MXFP4 dense (weight_type 3): e2m1 codes [max_tokens][widest K / 2] of the current GEMM input ...
+    uint8_t* d_mx_sx  = nullptr;  // ... and its e8m0 scale bytes [max_tokens][widest K / 32]
     size_t  gemm_ws_bytes = 0;
     // RMSNorm folded into the decode GEMMs (NormFold, tm_kernels.h): per-tile sums of squares [hidden / 64][64] and the split-K
     // arrival counters of the producing GEMM; TM_FOLD_NORM=0 keeps the reduce-norm launches

@@ -163,7 +163,7 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 struct LinearWeight {
     int       K = 0, N = 0, group = 128;
     int       type = 0;          // 0 = u4 (AWQ), 1 = f16 dense, 2 = fp8 e4m3 with 128x128 block scales, 3 = MXFP4 (e2m1 codes, one ue8m0
-                                 // scale byte per 32 k; expert weights only: gemm_mxfp4.hip)
+                                 // scale byte per 32 k; experts weight-only: gemm_mxfp4.hip, dense linears W4A4: gemm_mxfp4_mfma.hip)
     int       role = 0;          // key of the measured dispatch table next to (K, N, M): 0 = any (operator-level handles, imported
                                  // tables without a role column), 1 w_qkv, 2 wo, 3 w1w3, 4 w2 -- two roles of equal (K, N) are timed
                                  // with DIFFERENT consumers by the tuner and keep separate winners
@@ -176,6 +176,8 @@ struct LinearWeight {
     size_t    packed32_bytes = 0;
     // fp8 only, N % 32 == 0: the fp8 x fp8 kernel's layout (gemm_fp8.hip, "P8": 4224-byte units of 32 columns x 128 k with
     // their even / odd column block scales)
+    // MXFP4 dense (linear_weight_prepare_mxfp4_dense): the "P4" image of gemm_mxfp4_mfma.hip lives here too (2176-byte units of
+    // 32 columns x 128 k with their scale bytes); such a weight has no `packed` / `sz` image
     void*     packed8 = nullptr;
     size_t    packed8_bytes = 0;
     // fp8 only, channel-scaled weights (linear_weight_prepare_fp8_channel): the N fp32 column scales, stored behind the last
@@ -310,6 +312,16 @@ int    launch_linear_fp8(const LinearWeight& w, const uint8_t* xq, const float* 
 int    launch_linear_fp8_grouped(const LinearWeight& proto, const void* d_groups, int E, const uint8_t* xq, const float* sx, int ldsx,
                                  int x_rows, half_t* y, int ldy, int m_cap, int m_hint, bool gated_silu, const int* seg,
                                  const int* row_idx, hipStream_t st);
+
+// ---- gemm_mxfp4_mfma.hip: MXFP4 x MXFP4 dense linear on v_mfma_scale_f32_32x32x64_f8f6f4 (activations quantised per row and 32 channels) ---
+size_t p4_bytes(int K, int N);
+int    linear_weight_prepare_mxfp4_dense(LinearWeight& w, const uint8_t* blocks /*[N][K/2]*/, const uint8_t* scales /*[N][K/32]*/, hipStream_t st);
+bool   mxfp4_dense_prepared(const LinearWeight& w);
+int    launch_dequant_p4_f16(half_t* out_nk /*[N][K]*/, const LinearWeight& w, hipStream_t st);
+size_t mxfp4_act_workspace_bytes(int rows, int K);
+int    launch_quant_mxfp4_rows(uint8_t* xq /*[M][K/2]*/, uint8_t* sx /*[M][K/32]*/, const half_t* x, int ldx, int M, int K, hipStream_t st);
+int    launch_linear_mxfp4(const LinearWeight& w, const uint8_t* xq, const uint8_t* sx, half_t* y, int ldy, int M, bool gated_silu, int splits,
+                           float* workspace, int* slabs_out, hipStream_t st);
 
 // ---- comm_p2p.hip: fused one-shot all-reduce + residual + RMSNorm over peer-mapped buffers (TM_COMM=native) ------------
 int launch_p2p_allreduce_norm(half_t* const* data, uint32_t* const* flags, int tp, int me, uint32_t* state, size_t tile,

@@ -187,7 +187,13 @@ class TurbomindEngineConfig:
     per token (never coarser than a per-tensor static scale: `input_scale` / `activation_scheme: "static"` and `k_scale` / `v_scale` /
     `kv_cache_scheme` in such a checkpoint are read past; the KV cache follows quant_policy, and quant_policy=16 stays refused);
     lm_head and router gates stay fp16; TM_FP8_MFMA=0 is refused for them.  model_format='fp8_channel' asks for that form (a
-    `synthetic:` model is built in it).  Mistral / Mixtral
+    `synthetic:` model is built in it).  MXFP4 W4A4 checkpoints in AMD Quark's layout (`quant_method: "quark"`: fp4 per-group weights,
+    group 32, e8m0 scales, dynamic fp4 input activations; `<proj>.weight` uint8 [out][in/2] and `<proj>.weight_scale` uint8 [out][in/32])
+    load through the Llama and the dense Qwen2 / Qwen3 readers with tp = 1, head_dim 64 included: the four decoder linears run on the
+    block-scaled FP4 matrix cores with their inputs quantised per row and group of 32 by the OCP MX rule (not claimed to match Quark's own
+    rounding of the scale); lm_head, embeddings and norms stay fp16; KV-cache scales and `output_tensors` entries are read past, the cache
+    follows quant_policy; mixture-of-experts models, tp > 1 and a `layer_quant_config` that changes a decoder linear are refused.
+    model_format='mxfp4' asks for that form (a dense `synthetic:` model is built in it).  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
     on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
     R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
@@ -263,9 +269,10 @@ class TurbomindEngineConfig:
             raise NotImplementedError('quant_policy=TURBO_QUANT (42) with tp > 1: the TurboQuant KV cache is built for tp = 1')
         if self.dtype == 'bfloat16':
             raise NotImplementedError('dtype=bfloat16: the AWQ path is fp16 (lmdeploy/turbomind/converter.py:40-48)')
-        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel'):
+        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel', 'mxfp4'):
             raise NotImplementedError(f'model_format={self.model_format!r}: only "awq" (W4A16 g128), "fp8" (e4m3, 128x128 '
-                                      f'block scales), "fp8_channel" (e4m3, one scale per tensor / output channel) and "hf" (fp16)')
+                                      f'block scales), "fp8_channel" (e4m3, one scale per tensor / output channel), "mxfp4" (W4A4: '
+                                      f'e2m1 weights and activations, one e8m0 scale per 32) and "hf" (fp16)')
         if self.cache_block_seq_len != 64:
             raise NotImplementedError('cache_block_seq_len must be 64')
         unsupported = {'dp': 1, 'cp': 1, 'ep': 1, 'attn_tp_size': None, 'attn_cp_size': None, 'attn_dp_size': None,

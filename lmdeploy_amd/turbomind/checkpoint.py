@@ -65,7 +65,7 @@ class ModelConfig:
     group: int = 128
     arch: str = 'llama'
     quantized: bool = True
-    weight_format: str = 'u4'          # 'u4' (AWQ) | 'fp8' (block 128x128, or one scale per channel: fp8_scale_mode) | 'f16'
+    weight_format: str = 'u4'          # 'u4' (AWQ) | 'fp8' (block 128x128, or one scale per channel: fp8_scale_mode) | 'f16' | 'mxfp4' (W4A4)
     fp8_scale_mode: int = 0            # weight_format 'fp8': 0 = 128x128 block scales, 1 = channel (per-tensor / per-channel checkpoints)
     moe_experts: int = 0               # Mixtral: num_local_experts
     moe_top_k: int = 0                 # num_experts_per_tok
@@ -276,6 +276,61 @@ def _check_compressed_tensors(q: dict):
             raise no('ignore', name, 'only lm_head and router gates may stay unquantised: every decoder linear is e4m3')
 
 
+# Every key of a Quark MXFP4 export this reader depends on, in one place.  The layout was written down from memory of Quark's exports
+# and of how other engines read them and could not be checked against a published checkpoint: a correction is one edit here.
+QUARK = dict(
+    method='quark',                                  # quantization_config.quant_method
+    global_cfg='global_quant_config',                # the config every linear follows ...
+    layer_cfg='layer_quant_config',                  # ... unless a per-layer entry (glob pattern -> config) changes it
+    exclude='exclude',                               # layers left unquantised
+    weight='weight', inputs='input_tensors', outputs='output_tensors',
+    spec=dict(dtype='fp4', qscheme='per_group', group_size=32, scale_format='e8m0'),   # what weight and input_tensors must say
+    dynamic='is_dynamic',                            # False for the weights, True for the input activations
+    weight_suffix='.weight',                         # uint8 [out][in / 2], k = 2j in the low nibble
+    scale_suffix='.weight_scale',                    # uint8 [out][in / 32], e8m0
+    exclude_ok=('lm_head', '*lm_head', 're:.*lm_head'),
+    decoder_linears=('q_proj', 'k_proj', 'v_proj', 'o_proj', 'gate_proj', 'up_proj', 'down_proj'),
+    kv_outputs=('k_proj', 'v_proj'),                 # layer_quant_config entries that only add output_tensors (KV-cache scales): read past
+)
+
+
+def _check_quark(q: dict, arch: str):
+    """quantization_config of an AMD Quark MXFP4 W4A4 export (the QUARK table): fp4 per-group weights (group 32, e8m0 scales, not
+    dynamic) and the same for the input activations, dynamic.  Anything else is refused with the offending key."""
+    Q = QUARK
+
+    def no(key, val, want):
+        return NotImplementedError(f'quark quantization_config: {key} = {val!r} is not served ({want})')
+    if 'Mixtral' in arch or 'Moe' in arch or 'MoE' in arch:
+        raise NotImplementedError(f'{arch} with quant_method "quark": MXFP4 W4A4 is served for dense models only (mixture-of-experts '
+                                  f'architectures are not built)')
+    g = q.get(Q['global_cfg'])
+    if not isinstance(g, dict):
+        raise no(Q['global_cfg'], g, 'the global MXFP4 config is required')
+
+    def check(where, spec, dynamic):
+        if not isinstance(spec, dict):
+            raise no(where, spec, 'an fp4 per-group config is required')
+        for key, want in Q['spec'].items():
+            if spec.get(key) != want:
+                raise no(f'{where}.{key}', spec.get(key), repr(want))
+        if bool(spec.get(Q['dynamic'], False)) != dynamic:
+            raise no(f'{where}.{Q["dynamic"]}', spec.get(Q['dynamic']), repr(dynamic))
+    check(f'{Q["global_cfg"]}.{Q["weight"]}', g.get(Q['weight']), False)
+    check(f'{Q["global_cfg"]}.{Q["inputs"]}', g.get(Q['inputs']), True)
+    # (global output_tensors, KV-cache scales: read past -- the cache follows quant_policy)
+    for name in q.get(Q['exclude']) or []:
+        if name not in Q['exclude_ok'] and not name.endswith('lm_head'):
+            raise no(Q['exclude'], name, 'only lm_head may stay unquantised: every decoder linear is MXFP4')
+    for pat, lc in (q.get(Q['layer_cfg']) or {}).items():
+        lc = lc or {}
+        same = all(lc.get(k) in (None, g.get(k)) for k in (Q['weight'], Q['inputs']))
+        if same and pat.rstrip('*').rstrip('.').endswith(Q['kv_outputs']):
+            continue                                 # k_proj / v_proj with output_tensors only: KV-cache scales, read past
+        if any(n in pat for n in Q['decoder_linears']) or not same:
+            raise no(f'{Q["layer_cfg"]}[{pat!r}]', lc, 'a per-layer config that changes a decoder linear is not built')
+
+
 def read_config(model_path: str, tp: int = 1) -> ModelConfig:
     with open(os.path.join(model_path, 'config.json')) as f:
         c = json.load(f)
@@ -320,7 +375,12 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
     q = c.get('quantization_config')
     wfmt, fp8_mode = 'f16', 0
     if q is not None:
-        if q.get('quant_method') == 'compressed-tensors':
+        if q.get('quant_method') == QUARK['method']:
+            _check_quark(q, arch)
+            if tp != 1:
+                raise NotImplementedError(f'{arch} with quant_method "quark" (MXFP4 W4A4) and tp = {tp}: not built (run with tp = 1)')
+            wfmt = 'mxfp4'
+        elif q.get('quant_method') == 'compressed-tensors':
             _check_compressed_tensors(q)
             wfmt, fp8_mode = 'fp8', 1
         elif q.get('quant_method') == 'fp8' and q.get('weight_block_size') is None:
@@ -339,8 +399,8 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                                           f'projections straddle heads; fp8 needs head_dim 128')
             wfmt = 'fp8'
         elif q.get('quant_method') != 'awq' or q.get('bits', 4) != 4 or q.get('group_size', 128) != 128:
-            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, block-128 FP8, per-tensor FP8 or '
-                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92)')
+            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, block-128 FP8, per-tensor FP8, '
+                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92) or Quark MXFP4')
         else:
             wfmt = 'u4'
     rope = RopeConfig(dim=D, base=float(c.get('rope_theta', 10000.0)))
@@ -500,7 +560,7 @@ class _Tensors:
         t = self._index[k].get_tensor(k)
         if t.dtype == torch.bfloat16:
             t = t.float()
-        elif t.dtype in (torch.float8_e4m3fn,):
+        elif t.dtype in (torch.float8_e4m3fn, getattr(torch, 'float8_e8m0fnu', torch.float8_e4m3fn)):
             t = t.view(torch.uint8)
         return t.numpy().copy()     # own the memory: the tensor is a view into the file mapping
 
@@ -508,6 +568,15 @@ class _Tensors:
 def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
     """-> {'q','s','z'} (uint8 [K,N], fp16 [K/g,N] x2), {'f8','bs'} (e4m3 codes [K,N], fp32 block scales
     [K/128, ceil(N/128)]), {'f8','cs'} (e4m3 codes [K,N], one fp32 scale per output channel [N]) or {'w'} fp16 [K,N]."""
+    if quantized and (prefix + QUARK['scale_suffix']) in t and t.get(prefix + QUARK['scale_suffix']).dtype == np.uint8:
+        # Quark MXFP4 (e8m0 scale bytes; the FP8 forms below carry float scales): the checkpoint layout IS the engine's (output-major)
+        w, s = t.get(prefix + QUARK['weight_suffix']), t.get(prefix + QUARK['scale_suffix'])
+        if w.dtype != np.uint8 or w.ndim != 2 or s.shape != (w.shape[0], w.shape[1] // 16):
+            raise ValueError(f'{prefix}: expected {QUARK["weight_suffix"]} uint8 [out][in / 2] and {QUARK["scale_suffix"]} uint8 '
+                             f'[out][in / 32], got {w.dtype} {tuple(w.shape)} and {s.dtype} {tuple(s.shape)}')
+        if (s == 255).any():
+            raise ValueError(f'{prefix}{QUARK["scale_suffix"]}: scale byte 255 (the e8m0 NaN) is not accepted')
+        return dict(blocks=np.ascontiguousarray(w), scales=np.ascontiguousarray(s))
     if quantized and (prefix + '.weight_scale') in t:           # per-tensor ([] / [1]) or per-channel ([N] / [N, 1]) scale
         w = t.get(prefix + '.weight')
         if w.dtype != np.uint8:
@@ -531,18 +600,24 @@ def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
 
 
 def _cat(parts: list) -> dict:
+    if 'blocks' in parts[0]:                                    # MXFP4, output-major: stack the rows
+        return {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
     return {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]}
 
 
 def _map(lin: dict, fn) -> dict:
     """apply a per-output-channel permutation; fp8 block scales cover whole heads (128 channels) and stay put (channel scales
     'cs' move with their columns)"""
+    if 'blocks' in lin:                                         # MXFP4, output-major: the permutation moves rows
+        return {k: np.ascontiguousarray(fn(v.T).T) for k, v in lin.items()}
     return {k: (v if k == 'bs' else fn(v)) for k, v in lin.items()}
 
 
 def _fuse_w1w3(w1: dict, w3: dict) -> dict:
     """(gate_j, up_j) column interleave (builders/ffn.py:31-34).  fp8: codes interleaved, the scale row becomes
     [w1 blocks | w3 blocks] -- the engine's layout for *.w1w3.scales (include/tm_mi355x.h, tm_moe_set_expert)."""
+    if 'blocks' in w1:                                          # MXFP4, output-major: rows (2j, 2j + 1) = (gate_j, up_j)
+        return {k: np.ascontiguousarray(interleave_gate_up(w1[k].T, w3[k].T).T) for k in w1}
     if 'cs' in w1:
         return dict(f8=interleave_gate_up(w1['f8'], w3['f8']), cs=interleave_gate_up(w1['cs'], w3['cs']))
     if 'f8' in w1:

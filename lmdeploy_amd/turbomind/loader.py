@@ -129,6 +129,10 @@ def _shard_linear(lin: dict, kind: str, tp: int, rank: int, group: int, col_slic
     """lin: {'q','s','z'} (u4 as uint8 [K,N], fp16 [K/g,N]) or {'w'} fp16 [K,N].
     kind 'col': take `col_slices` (list of (lo,hi)) of the output dim; 'row': split the input dim evenly."""
     out = {}
+    if 'blocks' in lin:      # MXFP4 dense linears, output-major byte images: nothing to slice
+        if tp != 1:
+            raise ValueError(f'MXFP4 dense linears do not shard over tp = {tp}: W4A4 is served with tp = 1')
+        return lin
     if 'cs' in lin:
         # e4m3 codes [K,N] + one fp32 scale per output channel [N]: column shards slice the scales with their columns (whole
         # (gate, up) pairs for w1w3: its slice bounds are even), row shards keep them whole
@@ -172,7 +176,7 @@ def _shard_linear(lin: dict, kind: str, tp: int, rank: int, group: int, col_slic
 
 
 def _emit(slots: dict, prefix: str, lin: dict):
-    if 'blocks' in lin:      # MXFP4 experts in the checkpoint layout: e2m1 codes [N, K/2] + ue8m0 scale bytes [N, K/32]
+    if 'blocks' in lin:      # MXFP4 experts and W4A4 dense linears in the checkpoint layout: e2m1 codes [N, K/2] + ue8m0 scale bytes [N, K/32]
         slots[prefix + '.blocks'] = np.ascontiguousarray(lin['blocks'], dtype=np.uint8)
         slots[prefix + '.scales'] = np.ascontiguousarray(lin['scales'], dtype=np.uint8)
     elif 'q' in lin:
