@@ -136,6 +136,31 @@ struct tm_linear {
     LinearWeight w;
 };
 
+// A prepare entry point names the format of what it is handed (a handle created fp8 learns its scale mode and row layout from the first
+// one); a failed prepare leaves the handle's format as it was.  Parts in linear_staging order.
+static int prepare_as(LinearWeight& w, LinearFormat fmt, bool gated, const void* p0, const void* p1, const void* p2, tm_stream_t st)
+{
+    const LinearWeight was      = w;
+    const void* const  parts[3] = {p0, p1, p2};
+    w.fmt = fmt, w.gated = gated;
+    const int rc = linear_weight_prepare(w, parts, (hipStream_t)st);
+    if (rc) {
+        w.fmt = was.fmt, w.gated = was.gated;
+    }
+    return rc;
+}
+
+// tm_linear_forward_fp8 / _mxfp4: the workspace is the quantised input (codes, `code_bytes`, then scales; act_bytes in all), 256-aligned,
+// then the 16 slabs
+static int forward_quantised(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits, void* workspace,
+                             size_t code_bytes, size_t act_bytes, tm_stream_t st)
+{
+    LinearScratch s;
+    s.xq = workspace, s.sx = (char*)workspace + code_bytes, s.ldsx = (M + 3) / 4 * 4, s.rows = M, s.splits = splits;
+    s.ws = (float*)((char*)workspace + (act_bytes + 255) / 256 * 256), s.ws_bytes = gemm_workspace_bytes(M, w->w.N, 16);
+    return linear_forward(w->w, (const half_t*)x, ldx, (half_t*)y, ldy, M, gated_silu != 0, s, false, nullptr, (hipStream_t)st);
+}
+
 extern "C" {
 
 int tm_version(void)
@@ -455,6 +480,7 @@ int tm_linear_create(tm_linear** out, int in_features, int out_features, int wei
     l->w.N      = out_features;
     l->w.group  = group_size;
     l->w.type   = weight_type;
+    l->w.fmt    = linear_format(weight_type, 0, false);
     *out        = l;
     return 0;
 }
@@ -463,16 +489,9 @@ int tm_linear_prepare(tm_linear* w, const void* weight, const void* scales, cons
 {
     TM_REQUIRE(w && weight, "null pointer");
     TM_REQUIRE(w->w.type != TM_WEIGHT_MXFP4, "mxfp4 dense linear: tm_linear_prepare_mxfp4 takes its blocks and scale bytes");
-    if (w->w.type == TM_WEIGHT_U4) {
-        TM_REQUIRE(scales && zeros, "u4 weights need scales and zeros");
-        return linear_weight_prepare_u4(w->w, (const int32_t*)weight, (const half_t*)scales, (const half_t*)zeros,
-                                        (hipStream_t)st);
-    }
-    if (w->w.type == TM_WEIGHT_FP8) {
-        TM_REQUIRE(scales, "fp8 weights need their 128x128 block scales");
-        return linear_weight_prepare_fp8(w->w, (const uint8_t*)weight, (const float*)scales, false, (hipStream_t)st);
-    }
-    return linear_weight_prepare_f16(w->w, (const half_t*)weight, (hipStream_t)st);
+    TM_REQUIRE(w->w.type != TM_WEIGHT_U4 || (scales && zeros), "u4 weights need scales and zeros");
+    TM_REQUIRE(w->w.type != TM_WEIGHT_FP8 || scales, "fp8 weights need their 128x128 block scales");
+    return prepare_as(w->w, linear_format(w->w.type, 0, false), false, weight, scales, zeros, st);
 }
 
 size_t tm_linear_workspace(const tm_linear* w, int M)
@@ -497,8 +516,9 @@ int tm_linear_forward(const tm_linear* w, const void* x, int ldx, void* y, int l
                       int splits, int waves, void* workspace, tm_stream_t st)
 {
     TM_REQUIRE(w && x && y, "null pointer");
-    TM_REQUIRE(!w->w.cscale, "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
-    TM_REQUIRE(w->w.type != TM_WEIGHT_MXFP4, "mxfp4 dense linears have no weight-only arm: tm_linear_forward_mxfp4 runs them");
+    TM_REQUIRE(w->w.fmt != LinearFormat::FP8_CHANNEL,
+               "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
+    TM_REQUIRE(w->w.fmt != LinearFormat::MXFP4_DENSE, "mxfp4 dense linears have no weight-only arm: tm_linear_forward_mxfp4 runs them");
     GemmConfig cfg = gemm_pick_config(w->w, M);  // (workspace: tm_linear_workspace(w, M) bytes)
     if (nt > 0) {
         cfg.nt = nt;
@@ -581,14 +601,7 @@ static int fold_tile_pick(const tm_linear* w, int M, int* shape, int* splits, bo
 {
     int sh = *shape, sp = *splits;
     if (sh < 0) {
-        dec32_pick(w->w, M, &sh, &sp);
-        if (!dec32_fold_shape_m(sh, M, producer)) {
-            dec32_pick_ex(w->w, M, &sh, &sp, false);
-        }
-        if (!dec32_fold_shape_m(sh, M, producer)) {
-            sh = M <= 64 ? 0 : (producer ? 7 : 4);
-            sp = 1;
-        }
+        dec32_pick_fold(w->w, M, producer, &sh, &sp);
         if (*splits > 0) {
             sp = *splits;
         }
@@ -650,7 +663,7 @@ int tm_linear_prepare_fp8_channel(tm_linear* w, const void* weight, const void* 
 {
     TM_REQUIRE(w && weight && scales, "null pointer");
     TM_REQUIRE(w->w.type == TM_WEIGHT_FP8, "tm_linear_prepare_fp8_channel: fp8 weights only");
-    return linear_weight_prepare_fp8_channel(w->w, (const uint8_t*)weight, (const float*)scales, (hipStream_t)st);
+    return prepare_as(w->w, LinearFormat::FP8_CHANNEL, false, weight, scales, nullptr, st);
 }
 
 int tm_quant_fp8_token(void* xq, float* sx, const void* x, int ldx, int M, int K, tm_stream_t st)
@@ -663,7 +676,7 @@ int tm_linear_prepare_fp8_gated(tm_linear* w, const void* weight, const void* sc
 {
     TM_REQUIRE(w && weight && scales, "null pointer");
     TM_REQUIRE(w->w.type == TM_WEIGHT_FP8, "tm_linear_prepare_fp8_gated: fp8 weights only");
-    return linear_weight_prepare_fp8(w->w, (const uint8_t*)weight, (const float*)scales, true, (hipStream_t)st);
+    return prepare_as(w->w, LinearFormat::FP8_BLOCK, true, weight, scales, nullptr, st);
 }
 
 size_t tm_linear_fp8_workspace(const tm_linear* w, int M)
@@ -686,32 +699,15 @@ int tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, i
     TM_REQUIRE(w && x && y && workspace, "null pointer");
     TM_REQUIRE(fp8_mfma_supported(w->w), "fp8 x fp8 linear: e4m3 weights, N % 32 == 0 (TM_FP8_MFMA=0 disables the path)");
     TM_REQUIRE(splits >= 0 && splits <= 16, "0 <= splits <= 16");
-    const int K    = w->w.K;
-    uint8_t*  xq   = (uint8_t*)workspace;
-    const int ldsx = (M + 3) / 4 * 4;
-    float*    sx   = (float*)(xq + (size_t)M * K);
-    float*    slab = (float*)((char*)workspace + (fp8_act_workspace_bytes(M, K) + 255) / 256 * 256);
-    int       rc   = w->w.cscale ? launch_quant_fp8_token(xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st)
-                                 : launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, M, K, ldsx, (hipStream_t)st);
-    if (rc) {
-        return rc;
-    }
-    int nslab = 1;
-    rc        = launch_linear_fp8(w->w, xq, sx, ldsx, (half_t*)y, ldy, M, gated_silu != 0, splits, slab, &nslab, (hipStream_t)st);
-    if (rc) {
-        return rc;
-    }
-    if (nslab > 1) {
-        return launch_splitk_reduce((half_t*)y, ldy, slab, nslab, M, w->w.N, gated_silu != 0, (hipStream_t)st);
-    }
-    return 0;
+    // codes [M][K] | scales [K / 128][M rounded up to 4] (channel-scaled weights: [M])
+    return forward_quantised(w, x, ldx, y, ldy, M, gated_silu, splits, workspace, (size_t)M * w->w.K, fp8_act_workspace_bytes(M, w->w.K), st);
 }
 
 int tm_linear_prepare_mxfp4(tm_linear* w, const void* blocks, const void* scales, tm_stream_t st)
 {
     TM_REQUIRE(w && blocks && scales, "null pointer");
     TM_REQUIRE(w->w.type == TM_WEIGHT_MXFP4, "tm_linear_prepare_mxfp4: mxfp4 weights only");
-    return linear_weight_prepare_mxfp4_dense(w->w, (const uint8_t*)blocks, (const uint8_t*)scales, (hipStream_t)st);
+    return prepare_as(w->w, LinearFormat::MXFP4_DENSE, false, blocks, scales, nullptr, st);
 }
 
 int tm_quant_mxfp4_rows(void* xq, void* sx, const void* x, int ldx, int M, int K, tm_stream_t st)
@@ -734,17 +730,9 @@ int tm_linear_forward_mxfp4(const tm_linear* w, const void* x, int ldx, void* y,
     TM_REQUIRE(w && x && y && workspace, "null pointer");
     TM_REQUIRE(mxfp4_dense_prepared(w->w), "mxfp4 x mxfp4 linear: a weight prepared by tm_linear_prepare_mxfp4");
     TM_REQUIRE(splits >= 0 && splits <= 16, "0 <= splits <= 16");
-    const int K    = w->w.K;
-    uint8_t*  xq   = (uint8_t*)workspace;
-    uint8_t*  sx   = xq + (size_t)M * (K / 2);
-    float*    slab = (float*)((char*)workspace + (mxfp4_act_workspace_bytes(M, K) + 255) / 256 * 256);
-    TM_TRY_RC(launch_quant_mxfp4_rows(xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st));
-    int nslab = 1;
-    TM_TRY_RC(launch_linear_mxfp4(w->w, xq, sx, (half_t*)y, ldy, M, gated_silu != 0, splits, slab, &nslab, (hipStream_t)st));
-    if (nslab > 1) {
-        return launch_splitk_reduce((half_t*)y, ldy, slab, nslab, M, w->w.N, gated_silu != 0, (hipStream_t)st);
-    }
-    return 0;
+    // codes [M][K / 2] | scale bytes [M][K / 32]
+    return forward_quantised(w, x, ldx, y, ldy, M, gated_silu, splits, workspace, (size_t)M * (w->w.K / 2), mxfp4_act_workspace_bytes(M, w->w.K),
+                             st);
 }
 
 size_t tm_linear_fp8_grouped_workspace(int experts, int x_rows, int K)
@@ -760,7 +748,7 @@ int tm_linear_forward_fp8_grouped(const tm_linear* const* experts, int E, const 
     for (int e = 0; e < E; ++e) {
         TM_REQUIRE(experts[e] && fp8_mfma_supported(experts[e]->w), "grouped fp8 linear: e4m3 experts with their P8 image (TM_FP8_MFMA=0 disables the path)");
         TM_REQUIRE(experts[e]->w.K == experts[0]->w.K && experts[e]->w.N == experts[0]->w.N
-                       && (experts[e]->w.cscale != nullptr) == (experts[0]->w.cscale != nullptr),
+                       && experts[e]->w.fmt == experts[0]->w.fmt,
                    "grouped fp8 linear: experts of one shape and one scale mode");
         h[e] = experts[e]->w.packed8;
     }
@@ -772,8 +760,9 @@ int tm_linear_forward_fp8_grouped(const tm_linear* const* experts, int E, const 
     float*    sx   = (float*)(xq + (size_t)x_rows * proto.K);
     TM_HIP_CHECK(hipMemcpyAsync(ws, h.data(), sizeof(void*) * E, hipMemcpyHostToDevice, (hipStream_t)st));
     TM_HIP_CHECK(hipStreamSynchronize((hipStream_t)st));  // `h` is a host temporary
-    TM_TRY_RC(proto.cscale ? launch_quant_fp8_token(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, (hipStream_t)st)
-                           : launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, ldsx, (hipStream_t)st));
+    const bool chan = proto.fmt == LinearFormat::FP8_CHANNEL;
+    TM_TRY_RC(chan ? launch_quant_fp8_token(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, (hipStream_t)st)
+                   : launch_quant_fp8_rows(xq, sx, (const half_t*)x, ldx, x_rows, proto.K, ldsx, (hipStream_t)st));
     return launch_linear_fp8_grouped(proto, ws, E, xq, sx, ldsx, x_rows, (half_t*)y, ldy, m_cap, m_cap, gated_silu != 0, seg, row_idx,
                                      (hipStream_t)st);
 }
@@ -836,7 +825,6 @@ struct tm_moe {
     tmk::MoeBlock m;
     int           type = 0;
     bool          prepared = false;
-    bool          fp8_channel = false;  // tm_moe_set_fp8_scale_mode(1)
 };
 
 int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk, float routed_scale)
@@ -856,8 +844,9 @@ int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, i
     o->m.w13.resize(experts);
     o->m.w2.resize(experts);
     for (int e = 0; e < experts; ++e) {
-        o->m.w13[e].K = hidden, o->m.w13[e].N = 2 * inter, o->m.w13[e].type = weight_type;
+        o->m.w13[e].K = hidden, o->m.w13[e].N = 2 * inter, o->m.w13[e].type = weight_type, o->m.w13[e].gated = true;
         o->m.w2[e].K = inter, o->m.w2[e].N = hidden, o->m.w2[e].type = weight_type;
+        o->m.w13[e].fmt = o->m.w2[e].fmt = linear_format(weight_type, 0, true);
     }
     o->type = weight_type;
     *out    = o;
@@ -892,28 +881,14 @@ int tm_moe_set_expert(tm_moe* m, int expert, const void* w13_weight, const void*
     TM_REQUIRE(m && w13_weight && w2_weight, "null pointer");
     TM_REQUIRE(expert >= 0 && expert < m->m.experts, "expert index");
     m->prepared = false;
-    if (m->type == TM_WEIGHT_F16) {  // fp16 [K][N], no scales / zeros: the 16-column image of the plain fp16 linears
-        TM_TRY_RC(linear_weight_prepare_f16(m->m.w13[expert], (const half_t*)w13_weight, (hipStream_t)st));
-        return linear_weight_prepare_f16(m->m.w2[expert], (const half_t*)w2_weight, (hipStream_t)st);
-    }
-    TM_REQUIRE(w13_scales && w2_scales, "null pointer");
-    if (m->type == TM_WEIGHT_MXFP4) {  // blocks uint8 [N][K/2] + scales uint8 [N][K/32] (the checkpoint layout); zeros unused
-        TM_TRY_RC(linear_weight_prepare_mxfp4(m->m.w13[expert], (const uint8_t*)w13_weight, (const uint8_t*)w13_scales, (hipStream_t)st));
-        return linear_weight_prepare_mxfp4(m->m.w2[expert], (const uint8_t*)w2_weight, (const uint8_t*)w2_scales, (hipStream_t)st);
-    }
-    if (m->type == TM_WEIGHT_U4) {
-        TM_REQUIRE(w13_zeros && w2_zeros, "u4 experts need zeros");
-        TM_TRY_RC(linear_weight_prepare_u4(m->m.w13[expert], (const int32_t*)w13_weight, (const half_t*)w13_scales,
-                                           (const half_t*)w13_zeros, (hipStream_t)st));
-        return linear_weight_prepare_u4(m->m.w2[expert], (const int32_t*)w2_weight, (const half_t*)w2_scales,
-                                        (const half_t*)w2_zeros, (hipStream_t)st);
-    }
-    if (m->fp8_channel) {  // fp32 column scales [2 * inter] ((gate_j, up_j)-interleaved like the columns) and [hidden]
-        TM_TRY_RC(linear_weight_prepare_fp8_channel(m->m.w13[expert], (const uint8_t*)w13_weight, (const float*)w13_scales, (hipStream_t)st));
-        return linear_weight_prepare_fp8_channel(m->m.w2[expert], (const uint8_t*)w2_weight, (const float*)w2_scales, (hipStream_t)st);
-    }
-    TM_TRY_RC(linear_weight_prepare_fp8(m->m.w13[expert], (const uint8_t*)w13_weight, (const float*)w13_scales, true, (hipStream_t)st));
-    return linear_weight_prepare_fp8(m->m.w2[expert], (const uint8_t*)w2_weight, (const float*)w2_scales, false, (hipStream_t)st);
+    // parts as the expert format stages them (linear_staging): fp16 [K][N] alone; u4 qweight + scales + zeros; fp8 e4m3 + block scales or
+    // fp32 column scales [2 * inter] ((gate_j, up_j)-interleaved like the columns) / [hidden]; mxfp4 blocks + scale bytes, zeros unused
+    TM_REQUIRE(m->type == TM_WEIGHT_F16 || (w13_scales && w2_scales), "null pointer");
+    TM_REQUIRE(m->type != TM_WEIGHT_U4 || (w13_zeros && w2_zeros), "u4 experts need zeros");
+    const void* const p13[3] = {w13_weight, w13_scales, w13_zeros};
+    const void* const p2[3]  = {w2_weight, w2_scales, w2_zeros};
+    TM_TRY_RC(linear_weight_prepare(m->m.w13[expert], p13, (hipStream_t)st));
+    return linear_weight_prepare(m->m.w2[expert], p2, (hipStream_t)st);
 }
 
 int tm_moe_set_fp8_scale_mode(tm_moe* m, int mode)
@@ -922,9 +897,11 @@ int tm_moe_set_fp8_scale_mode(tm_moe* m, int mode)
     TM_REQUIRE(mode == 0 || mode == 1, "moe fp8 scale mode: 0 (128 x 128 blocks) or 1 (channel)");
     TM_REQUIRE(m->type == TM_WEIGHT_FP8 || mode == 0, "moe fp8 scale mode: fp8 experts only");
     for (int e = 0; e < m->m.experts; ++e) {
-        TM_REQUIRE(!m->m.w13[e].packed8 && !m->m.w13[e].packed, "moe fp8 scale mode: set it before the first tm_moe_set_expert");
+        TM_REQUIRE(!linear_weight_prepared(m->m.w13[e]), "moe fp8 scale mode: set it before the first tm_moe_set_expert");
     }
-    m->fp8_channel = mode == 1;
+    for (int e = 0; e < m->m.experts; ++e) {
+        m->m.w13[e].fmt = m->m.w2[e].fmt = linear_format(m->type, mode, true);
+    }
     return 0;
 }
 

@@ -147,41 +147,23 @@ int rope_reset(tm_engine* e, int slot0, int n)
     return 0;
 }
 
-static int64_t slot_bytes_linear(const tm_engine* e, int K, int N, const char* part)
-{
-    if (!strcmp(part, "qweight")) return (int64_t)K * N / 2;
-    if (!strcmp(part, "scales") || !strcmp(part, "zeros")) return (int64_t)(K / e->cfg.model.group_size) * N * 2;
-    if (!strcmp(part, "weight")) return (int64_t)K * N * 2;
-    if (!strcmp(part, "weight_fp8")) return (int64_t)K * N;
-    if (!strcmp(part, "scales_fp8")) {  // 128 x 128 block scales, or (fp8_scale_mode 1) one fp32 scale per output column
-        return e->cfg.model.fp8_scale_mode == 1 ? (int64_t)N * 4 : (int64_t)(K / 128) * ((N + 127) / 128) * 4;
-    }
-    return 0;
-}
-
-static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, int K, int N, int type, int role = 0)
+// declares a linear: its format is resolved here, once, and its staging slots are the format's parts (linear_staging)
+static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, int K, int N, int type, int role = 0, bool gated = false,
+                       bool expert = false)
 {
     l.prefix  = prefix;
+    l.gated   = gated;
+    l.expert  = expert;
     l.w.role  = role;  // dispatch-table key next to (K, N, M): the tuner times each role with its own consumer
     l.w.K     = K;
     l.w.N     = N;
     l.w.group = e->cfg.model.group_size;
     l.w.type  = type;
-    if (type == TM_WEIGHT_U4) {
-        for (const char* part : {"qweight", "scales", "zeros"}) {
-            e->slots[prefix + "." + part].bytes = slot_bytes_linear(e, K, N, part);
-        }
-    }
-    else if (type == TM_WEIGHT_MXFP4) {  // the checkpoint layout: e2m1 codes [N][K/2] + one ue8m0 byte per 32 k [N][K/32]
-        e->slots[prefix + ".blocks"].bytes = (int64_t)N * (K / 2);
-        e->slots[prefix + ".scales"].bytes = (int64_t)N * (K / 32);
-    }
-    else if (type == TM_WEIGHT_FP8) {  // e4m3 [K][N] + fp32 128x128 block scales (weight_format.py:349-393)
-        e->slots[prefix + ".weight"].bytes = slot_bytes_linear(e, K, N, "weight_fp8");
-        e->slots[prefix + ".scales"].bytes = slot_bytes_linear(e, K, N, "scales_fp8");
-    }
-    else {
-        e->slots[prefix + ".weight"].bytes = slot_bytes_linear(e, K, N, "weight");
+    l.w.fmt   = linear_format(type, e->cfg.model.fp8_scale_mode, expert);
+    l.w.gated = gated;
+    const LinearStaging sg = linear_staging(l.w.fmt, K, N, l.w.group);
+    for (int i = 0; i < sg.n; ++i) {
+        e->slots[prefix + "." + sg.suffix[i]].bytes = (int64_t)sg.bytes[i];
     }
 }
 
@@ -229,70 +211,36 @@ static int fill_normal(tm_engine* e, void* dst, size_t n, float mean, float stdd
     return 0;
 }
 
+// staged parts -> device image(s): check filled, prepare, synchronise, free the parts
 static int prepare_linear(tm_engine* e, LinearSlots& l)
 {
-    if (l.w.type == TM_WEIGHT_U4) {
-        Slot &q = e->slots[l.prefix + ".qweight"], &s = e->slots[l.prefix + ".scales"], &z = e->slots[l.prefix + ".zeros"];
-        TM_REQUIRE(q.filled && s.filled && z.filled, "weight not loaded: " + l.prefix);
-        // dense linears whose every M goes to gemm_decode.hip keep ONE HBM image (P32); MoE experts run the grouped mode of
-        // gemm_kernel and keep the 16-column image as well
-        const bool p32_only = l.prefix.find(".experts.") == std::string::npos && dec32_serves_every_m(l.w.K, l.w.N);
-        TM_TRY(linear_weight_prepare_u4(l.w, (const int32_t*)q.dev, (const half_t*)s.dev, (const half_t*)z.dev, e->stream, p32_only));
-        // the resident fp16 image for prefill-sized forwards (gemm_prefill_f16.hip): dense linears of engines whose prefill forwards are
-        // large enough to use it (the 256 x 256 tile is proposed from 1024 rows); TM_PREFILL_F16_IMAGE=1 builds it
-        // (opt-in: measured +15 % on w_qkv, +2 % on wo, -1 .. -5 % on w1w3 / w2 against the fused tiles at M = 8192 -- the tile is bound by the
-        // CU's load path, not by the dequantisation it removes: profiles/r06_prefill_f16_image_ablations.txt -- for 2 bytes per parameter)
-        static const bool f16img = [] {
-            const char* v = getenv("TM_PREFILL_F16_IMAGE");
-            return v && atoi(v) != 0;
-        }();
-        if (f16img && p32_only && l.w.packed32 && e->cfg.max_prefill_token_num >= 1024 && l.w.N >= 256) {
-            TM_TRY(linear_weight_build_f16_image(l.w, e->stream));
-        }
-        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
-        for (Slot* p : {&q, &s, &z}) {
-            TM_HIP_CHECK(hipFree(p->dev));
-            p->dev = nullptr;
-        }
+    if (l.w.K == 0 || linear_weight_prepared(l.w)) {  // not declared (the dense FFN of a MoE layer without a shared expert) / done
+        return 0;
     }
-    else if (l.w.type == TM_WEIGHT_MXFP4) {
-        Slot &w = e->slots[l.prefix + ".blocks"], &s = e->slots[l.prefix + ".scales"];
-        TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
-        if (l.prefix.find(".experts.") == std::string::npos) {  // a dense decoder linear: W4A4 on the block-scaled FP4 matrix cores
-            TM_TRY(linear_weight_prepare_mxfp4_dense(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
-        }
-        else {
-            TM_TRY(linear_weight_prepare_mxfp4(l.w, (const uint8_t*)w.dev, (const uint8_t*)s.dev, e->stream));
-        }
-        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
-        for (Slot* p : {&w, &s}) {
-            TM_HIP_CHECK(hipFree(p->dev));
-            p->dev = nullptr;
-        }
+    const LinearStaging sg = linear_staging(l.w.fmt, l.w.K, l.w.N, l.w.group);
+    Slot*               slot[3];
+    const void*         part[3];
+    for (int i = 0; i < sg.n; ++i) {
+        slot[i] = &e->slots[l.prefix + "." + sg.suffix[i]];
+        TM_REQUIRE(slot[i]->filled, "weight not loaded: " + l.prefix);
+        part[i] = slot[i]->dev;
     }
-    else if (l.w.type == TM_WEIGHT_FP8) {
-        Slot &w = e->slots[l.prefix + ".weight"], &s = e->slots[l.prefix + ".scales"];
-        TM_REQUIRE(w.filled && s.filled, "weight not loaded: " + l.prefix);
-        const bool gated = l.prefix.size() >= 5 && l.prefix.compare(l.prefix.size() - 5, 5, ".w1w3") == 0;
-        if (e->cfg.model.fp8_scale_mode == 1) {  // channel: the scales of a fused linear are concatenated / interleaved like its columns
-            TM_TRY(linear_weight_prepare_fp8_channel(l.w, (const uint8_t*)w.dev, (const float*)s.dev, e->stream));
-        }
-        else {
-            TM_TRY(linear_weight_prepare_fp8(l.w, (const uint8_t*)w.dev, (const float*)s.dev, gated, e->stream));
-        }
-        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
-        for (Slot* p : {&w, &s}) {
-            TM_HIP_CHECK(hipFree(p->dev));
-            p->dev = nullptr;
-        }
-    }
-    else {
-        Slot& w = e->slots[l.prefix + ".weight"];
-        TM_REQUIRE(w.filled, "weight not loaded: " + l.prefix);
-        TM_TRY(linear_weight_prepare_f16(l.w, (const half_t*)w.dev, e->stream));
-        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
-        TM_HIP_CHECK(hipFree(w.dev));
-        w.dev = nullptr;
+    // u4 policy: dense linears whose every M goes to gemm_decode.hip keep ONE HBM image (P32); MoE experts run the grouped mode of
+    // gemm_kernel and keep the 16-column image as well
+    const bool p32_only = !l.expert && dec32_serves_every_m(l.w.K, l.w.N);
+    // the resident fp16 image for prefill-sized forwards (gemm_prefill_f16.hip): dense linears of engines whose prefill forwards are
+    // large enough to use it (the 256 x 256 tile is proposed from 1024 rows); TM_PREFILL_F16_IMAGE=1 builds it
+    // (opt-in: measured +15 % on w_qkv, +2 % on wo, -1 .. -5 % on w1w3 / w2 against the fused tiles at M = 8192 -- the tile is bound by the
+    // CU's load path, not by the dequantisation it removes: profiles/r06_prefill_f16_image_ablations.txt -- for 2 bytes per parameter)
+    static const bool f16img = [] {
+        const char* v = getenv("TM_PREFILL_F16_IMAGE");
+        return v && atoi(v) != 0;
+    }();
+    TM_TRY(linear_weight_prepare(l.w, part, e->stream, p32_only, f16img && p32_only && e->cfg.max_prefill_token_num >= 1024 && l.w.N >= 256));
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < sg.n; ++i) {
+        TM_HIP_CHECK(hipFree(slot[i]->dev));
+        slot[i]->dev = nullptr;
     }
     return 0;
 }
@@ -406,8 +354,8 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
             for (int x = 0; x < m.moe_experts; ++x) {
                 const std::string q = p + ".moe_ffn.experts." + std::to_string(x);
                 const int xt = m.moe_expert_format ? m.moe_expert_format : m.weight_type;
-                add_linear(e, L.ex13[x], q + ".w1w3", m.hidden, 2 * e->inter, xt);
-                add_linear(e, L.ex2[x], q + ".w2", e->inter, m.hidden, xt);
+                add_linear(e, L.ex13[x], q + ".w1w3", m.hidden, 2 * e->inter, xt, 0, true, true);
+                add_linear(e, L.ex2[x], q + ".w2", e->inter, m.hidden, xt, 0, false, true);
                 if (m.moe_bias) {
                     e->slots[q + ".w1w3.bias"].bytes = (int64_t)2 * e->inter * 2;  // fp16, (gate_j, up_j)-interleaved
                     e->slots[q + ".w2.bias"].bytes   = (int64_t)m.hidden * 2;
@@ -418,13 +366,13 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
             }
             if (e->shared_inter > 0) {  // the shared expert: the layer's dense feed_forward at its own width + the sigmoid gate [H]
                 L.has_shared = true;
-                add_linear(e, L.w13, p + ".feed_forward.w1w3", m.hidden, 2 * e->shared_inter, m.weight_type, 3);
+                add_linear(e, L.w13, p + ".feed_forward.w1w3", m.hidden, 2 * e->shared_inter, m.weight_type, 3, true);
                 add_linear(e, L.w2, p + ".feed_forward.w2", e->shared_inter, m.hidden, m.weight_type, 4);
                 e->slots[p + ".moe_ffn.shared_gate.weight"].bytes = (int64_t)m.hidden * 2;  // fp16 [H], replicated
             }
         }
         else {
-            add_linear(e, L.w13, p + ".feed_forward.w1w3", m.hidden, 2 * e->inter, m.weight_type, 3);
+            add_linear(e, L.w13, p + ".feed_forward.w1w3", m.hidden, 2 * e->inter, m.weight_type, 3, true);
             add_linear(e, L.w2, p + ".feed_forward.w2", e->inter, m.hidden, m.weight_type, 4);
         }
         e->slots[p + ".attention_norm.weight"].bytes = (int64_t)m.hidden * 2;
@@ -497,68 +445,56 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
     half_t*                master = nullptr;  // fp16 master of the largest linear, reused
     size_t                 master_elems = 0;
     auto                   linear = [&](LinearSlots& l) -> int {
-        const size_t n = (size_t)l.w.K * l.w.N;
-        if (l.w.type == TM_WEIGHT_F16) {
-            Slot* w = nullptr;
-            TM_TRY(ensure_slot(e, l.prefix + ".weight", &w));
-            TM_TRY(fill_normal(e, w->dev, n, 0.f, 0.1f / std::sqrt((float)l.w.K), ++sd));
-            w->filled = true;
-            return 0;
+        const size_t        n  = (size_t)l.w.K * l.w.N;
+        const LinearStaging sg = linear_staging(l.w.fmt, l.w.K, l.w.N, l.w.group);
+        Slot*               part[3];
+        for (int i = 0; i < sg.n; ++i) {
+            TM_TRY(ensure_slot(e, l.prefix + "." + sg.suffix[i], &part[i]));
+            part[i]->filled = true;
         }
-        if (l.w.type == TM_WEIGHT_MXFP4) {
-            // uniform e2m1 codes (E|value| = 2.25) under scale bytes around 127 - 6: weights of the other synthetic formats' magnitude
-            // (dense W4A4 linears: around the byte that puts 2.25 * 2^(s - 127) next to their 0.1 / sqrt(K))
-            const bool dense = l.prefix.find(".experts.") == std::string::npos;
-            const int  sbase = dense ? 127 + (int)std::lround(std::log2(0.1 / std::sqrt((double)l.w.K) / 2.25)) : 127 - 6;
-            Slot *w = nullptr, *sc = nullptr;
-            TM_TRY(ensure_slot(e, l.prefix + ".blocks", &w));
-            TM_TRY(ensure_slot(e, l.prefix + ".scales", &sc));
-            fill_mxfp4_kernel<<<((size_t)w->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)w->dev, (size_t)w->bytes, ++sd, 0);
-            TM_HIP_CHECK(hipGetLastError());
-            fill_mxfp4_kernel<<<((size_t)sc->bytes + 255) / 256, 256, 0, e->stream>>>((uint8_t*)sc->dev, (size_t)sc->bytes, ++sd, sbase);
-            TM_HIP_CHECK(hipGetLastError());
-            w->filled = sc->filled = true;
-            TM_TRY(prepare_linear(e, l));
-            return 0;
-        }
-        if (l.w.type == TM_WEIGHT_FP8) {
-            // random e4m3 codes (no NaN), one constant block scale: E|code value| ~ 30 -> weights ~ 0.1 / sqrt(K)
-            Slot *w = nullptr, *sc = nullptr;
-            TM_TRY(ensure_slot(e, l.prefix + ".weight", &w));
-            TM_TRY(ensure_slot(e, l.prefix + ".scales", &sc));
-            fill_fp8_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>((uint8_t*)w->dev, n, ++sd);
-            TM_HIP_CHECK(hipGetLastError());
-            const size_t nsc = (size_t)sc->bytes / 4;
-            fill_const_f32_kernel<<<(nsc + 255) / 256, 256, 0, e->stream>>>((float*)sc->dev, nsc, 0.0027f / std::sqrt((float)l.w.K));
-            TM_HIP_CHECK(hipGetLastError());
-            w->filled = sc->filled = true;
-            TM_TRY(prepare_linear(e, l));
-            return 0;
-        }
-        if (n > master_elems) {
-            if (master) {
-                TM_HIP_CHECK(hipStreamSynchronize(e->stream));
-                TM_HIP_CHECK(hipFree(master));
+        const float std_w = 0.1f / std::sqrt((float)l.w.K);  // the weights' magnitude in every format
+        for (int i = 0; i < sg.n; ++i) {  // random values of what each part holds (LinearStaging::kind)
+            const size_t nb = (size_t)part[i]->bytes;
+            const dim3   grid((unsigned)((nb + 255) / 256));
+            switch (sg.kind[i]) {
+                case PartKind::F16: TM_TRY(fill_normal(e, part[i]->dev, n, 0.f, std_w, ++sd)); break;
+                case PartKind::E4M3: fill_fp8_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd); break;  // random e4m3 codes (no NaN) ...
+                case PartKind::F32_SCALES:  // ... under one constant scale: E|code value| ~ 30 -> weights ~ 0.1 / sqrt(K)
+                    fill_const_f32_kernel<<<(nb / 4 + 255) / 256, 256, 0, e->stream>>>((float*)part[i]->dev, nb / 4, 0.0027f / std::sqrt((float)l.w.K));
+                    break;
+                case PartKind::E2M1: fill_mxfp4_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd, 0); break;
+                case PartKind::UE8M0: {
+                    // uniform e2m1 codes (E|value| = 2.25) under scale bytes around 127 - 6: weights of the other synthetic formats' magnitude
+                    // (dense W4A4 linears: around the byte that puts 2.25 * 2^(s - 127) next to their 0.1 / sqrt(K))
+                    const int sbase = !l.expert ? 127 + (int)std::lround(std::log2(0.1 / std::sqrt((double)l.w.K) / 2.25)) : 127 - 6;
+                    fill_mxfp4_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd, sbase);
+                    break;
+                }
+                case PartKind::AWQ_QWEIGHT: {  // an fp16 master, quantised group-wise into this part and the two behind it
+                    if (n > master_elems) {
+                        if (master) {
+                            TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+                            TM_HIP_CHECK(hipFree(master));
+                        }
+                        TM_HIP_CHECK(hipMalloc((void**)&master, n * 2));
+                        master_elems = n;
+                    }
+                    // TM_SYNTH_WEIGHT_SCALE (diagnostics only: `0` = all-zero linear weights, the low-toggle arm of the power experiment in DESIGN 3.8)
+                    static const float wscale = [] {
+                        const char* v = getenv("TM_SYNTH_WEIGHT_SCALE");
+                        return v ? (float)atof(v) : 1.0f;
+                    }();
+                    TM_TRY(fill_normal(e, master, n, 0.f, wscale * 0.1f / std::sqrt((float)l.w.K), ++sd));
+                    TM_TRY(launch_quantize_groupwise_u4((int32_t*)part[0]->dev, (half_t*)part[1]->dev, (half_t*)part[2]->dev, nullptr, master,
+                                                        l.w.K, l.w.N, l.w.group, e->stream));
+                    break;
+                }
+                case PartKind::AWQ_SCALES:
+                case PartKind::AWQ_ZEROS: break;  // written with the qweight part
             }
-            TM_HIP_CHECK(hipMalloc((void**)&master, n * 2));
-            master_elems = n;
+            TM_HIP_CHECK(hipGetLastError());
         }
-        // TM_SYNTH_WEIGHT_SCALE (diagnostics only: `0` = all-zero linear weights, the low-toggle arm of the power experiment in DESIGN 3.8)
-        static const float wscale = [] {
-            const char* v = getenv("TM_SYNTH_WEIGHT_SCALE");
-            return v ? (float)atof(v) : 1.0f;
-        }();
-        TM_TRY(fill_normal(e, master, n, 0.f, wscale * 0.1f / std::sqrt((float)l.w.K), ++sd));
-        Slot *q = nullptr, *s = nullptr, *z = nullptr;
-        TM_TRY(ensure_slot(e, l.prefix + ".qweight", &q));
-        TM_TRY(ensure_slot(e, l.prefix + ".scales", &s));
-        TM_TRY(ensure_slot(e, l.prefix + ".zeros", &z));
-        TM_TRY(launch_quantize_groupwise_u4((int32_t*)q->dev, (half_t*)s->dev, (half_t*)z->dev, nullptr, master, l.w.K,
-                                            l.w.N, l.w.group, e->stream));
-        q->filled = s->filled = z->filled = true;
-        // repack right away so that staging never holds more than one linear
-        TM_TRY(prepare_linear(e, l));
-        return 0;
+        return prepare_linear(e, l);  // repack right away so that staging never holds more than one linear
     };
     auto vec = [&](const std::string& name, size_t n, float mean, float stddev) -> int {
         Slot* s = nullptr;
@@ -647,10 +583,8 @@ int tm_engine_process_weights(tm_engine* e)
     for (int i = 0; i < m.layers; ++i) {
         const std::string p = "layers." + std::to_string(i);
         Layer&            L = e->layers[i];
-        for (LinearSlots* l : {&L.qkv, &L.wo}) {
-            if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
-                TM_TRY(prepare_linear(e, *l));
-            }
+        for (LinearSlots* l : {&L.qkv, &L.wo, &L.w13, &L.w2}) {
+            TM_TRY(prepare_linear(e, *l));
         }
         if (L.is_moe) {
             L.moe.hidden       = m.hidden;
@@ -662,15 +596,10 @@ int tm_engine_process_weights(tm_engine* e)
             L.moe.w13.resize(m.moe_experts);
             L.moe.w2.resize(m.moe_experts);
             for (int x = 0; x < m.moe_experts; ++x) {
-                for (LinearSlots* l : {&L.ex13[x], &L.ex2[x]}) {
-                    if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
-                        TM_TRY(prepare_linear(e, *l));
-                    }
-                }
-                L.moe.w13[x] = L.ex13[x].w;  // the MoE block owns the packed weights from here on
-                L.moe.w2[x]  = L.ex2[x].w;
-                L.ex13[x].w.packed = nullptr, L.ex13[x].w.sz = nullptr, L.ex13[x].w.packed32 = nullptr, L.ex13[x].w.packed8 = nullptr, L.ex13[x].w.cscale = nullptr;
-                L.ex2[x].w.packed = nullptr, L.ex2[x].w.sz = nullptr, L.ex2[x].w.packed32 = nullptr, L.ex2[x].w.packed8 = nullptr, L.ex2[x].w.cscale = nullptr;
+                TM_TRY(prepare_linear(e, L.ex13[x]));
+                TM_TRY(prepare_linear(e, L.ex2[x]));
+                linear_weight_take(L.moe.w13[x], L.ex13[x].w);  // the MoE block owns the packed weights from here on
+                linear_weight_take(L.moe.w2[x], L.ex2[x].w);
             }
             L.moe.act = m.moe_act;
             if (m.moe_bias) {  // the experts' biases side by side ([E][2I], [E][H]: what the grouped GEMM and the combine index)
@@ -700,24 +629,12 @@ int tm_engine_process_weights(tm_engine* e)
             L.moe.gate = (half_t*)g.dev;  // used in place (freed by moe_free)
             g.dev      = nullptr;
             if (L.has_shared) {
-                for (LinearSlots* l : {&L.w13, &L.w2}) {
-                    if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
-                        TM_TRY(prepare_linear(e, *l));
-                    }
-                }
                 Slot& sg = e->slots[p + ".moe_ffn.shared_gate.weight"];
                 TM_REQUIRE(sg.filled, "weight not loaded: " + p + ".moe_ffn.shared_gate.weight");
                 L.moe.shared_gate = (half_t*)sg.dev;  // used in place (freed by moe_free)
                 sg.dev            = nullptr;
             }
             TM_TRY(moe_prepare(L.moe, e->stream));
-        }
-        else {
-            for (LinearSlots* l : {&L.w13, &L.w2}) {
-                if (!l->w.packed && !l->w.packed32 && !l->w.packed8) {
-                    TM_TRY(prepare_linear(e, *l));
-                }
-            }
         }
         TM_TRY(norm(p + ".attention_norm.weight", &L.attn_norm));
         TM_TRY(norm(p + ".ffn_norm.weight", &L.ffn_norm));
@@ -737,9 +654,7 @@ int tm_engine_process_weights(tm_engine* e)
     }
     TM_TRY(norm("tok_embeddings.weight", &e->tok_embeddings));
     TM_TRY(norm("norm.weight", &e->final_norm));
-    if (!e->output.w.packed) {
-        TM_TRY(prepare_linear(e, e->output));
-    }
+    TM_TRY(prepare_linear(e, e->output));
     e->weights_ready = true;
     return 0;
 }
@@ -777,19 +692,14 @@ int tm_engine_start(tm_engine* e)
     const int wide_n = std::max(std::max(e->qkv_n, 2 * std::max(e->inter, e->shared_inter)), e->hidden);  // widest linear output
     e->gemm_ws_bytes = (size_t)16 * 64 * wide_n * sizeof(float);
     TM_HIP_CHECK(hipMalloc((void**)&e->d_gemm_ws, e->gemm_ws_bytes));
-    if (m.weight_type == TM_WEIGHT_FP8 && m.fp8_scale_mode == 1) {
-        // channel-scaled fp8: codes and per-token scales of ONE GEMM input (the widest K of a dense linear), written by the quantiser
-        // in front of every dense GEMM -- sized here, nothing is allocated in a forward
+    e->scratch.ws = e->d_gemm_ws, e->scratch.ws_bytes = e->gemm_ws_bytes, e->scratch.rows = e->max_tokens;
+    // a dense format that needs its GEMM input quantised (the engine brings buffers to no other): codes and scales of ONE GEMM input (the
+    // widest K of a dense linear), written by the quantiser in front of every dense GEMM -- sized here, nothing is allocated in a forward
+    if (const ActQuant q = linear_act_quant(linear_format(m.weight_type, m.fp8_scale_mode, false), false); q != ActQuant::NONE) {
         const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), std::max(e->inter, e->shared_inter));
-        TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_xq, T * wide_k));
-        TM_HIP_CHECK(hipMalloc((void**)&e->d_f8_sx, T * sizeof(float)));
-    }
-    if (m.weight_type == TM_WEIGHT_MXFP4) {
-        // W4A4: e2m1 codes and e8m0 scale bytes of ONE GEMM input (the widest K of a dense linear), written by the quantiser in front of
-        // every dense GEMM -- sized here, nothing is allocated in a forward
-        const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), e->inter);
-        TM_HIP_CHECK(hipMalloc((void**)&e->d_mx_xq, T * (wide_k / 2)));
-        TM_HIP_CHECK(hipMalloc((void**)&e->d_mx_sx, T * (wide_k / 32)));
+        const bool   mx     = q == ActQuant::MXFP4_ROW32;  // e2m1 pairs + an e8m0 byte per 32 channels; else e4m3 + one fp32 scale per token
+        TM_HIP_CHECK(hipMalloc(&e->scratch.xq, T * (mx ? wide_k / 2 : wide_k)));
+        TM_HIP_CHECK(hipMalloc(&e->scratch.sx, T * (mx ? wide_k / 32 : sizeof(float))));
     }
     {
         const size_t tiles = (size_t)(e->hidden + 63) / 64;
@@ -1047,16 +957,15 @@ int tm_engine_stats(tm_engine* e, int64_t* weight_bytes, int64_t* kv_bytes_per_t
     int64_t wb = 0;
     for (auto& L : e->layers) {
         for (const LinearSlots* l : {&L.qkv, &L.wo, &L.w13, &L.w2}) {
-            wb += (int64_t)l->w.packed_bytes + (int64_t)l->w.sz_bytes;
+            wb += (int64_t)linear_weight_bytes(l->w);
         }
         if (L.is_moe) {
             for (int x = 0; x < L.moe.experts; ++x) {
-                wb += (int64_t)L.moe.w13[x].packed_bytes + (int64_t)L.moe.w13[x].sz_bytes + (int64_t)L.moe.w2[x].packed_bytes
-                      + (int64_t)L.moe.w2[x].sz_bytes;
+                wb += (int64_t)linear_weight_bytes(L.moe.w13[x]) + (int64_t)linear_weight_bytes(L.moe.w2[x]);
             }
         }
     }
-    wb += (int64_t)e->output.w.packed_bytes;
+    wb += (int64_t)linear_weight_bytes(e->output.w);
     if (weight_bytes) *weight_bytes = wb;
     if (kv_bytes_per_token) *kv_bytes_per_token = e->started ? e->block_bytes / 64 : 0;
     if (num_blocks) *num_blocks = e->num_blocks;
@@ -1132,7 +1041,7 @@ int tm_engine_destroy(tm_engine* e)
         }
     }
     void* bufs[] = {e->pool, e->d_block_ptrs, e->d_cu_block_nums, e->d_resid, e->d_x, e->d_qkv, e->d_attn, e->d_act,
-                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->d_f8_xq, e->d_f8_sx, e->d_mx_xq, e->d_mx_sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
+                    e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->scratch.xq, e->scratch.sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
                     e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
                     e->d_rope_row0};

@@ -118,76 +118,23 @@ size_t prof_event(tm_engine* e)
     return e->prof_used++;
 }
 
-// Channel-scaled fp8 linear (fp8_scale_mode 1; LinearWeight::cscale): the GEMM input is quantised per token into the engine's code /
-// scale buffers, then the fp8 x fp8 kernel runs, for every M -- one tile choice per M class, nothing to pick from a table.  Split-K
-// slabs are written scaled; `defer` leaves them in d_gemm_ws for the consumer (*slabs > 1), else they are reduced into y here.
-static int linear_fp8_channel(tm_engine* e, const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
-                              int* slabs)
-{
-    TM_REQUIRE(e->d_f8_xq && e->d_f8_sx && M <= e->max_tokens, "internal: channel-scaled fp8 linear without its activation buffers");
-    TM_TRY(launch_quant_fp8_token(e->d_f8_xq, e->d_f8_sx, x, ldx, M, w.K, e->stream));
-    float* const ws    = fit_splits(e, M, w.N, 16) == 16 ? e->d_gemm_ws : nullptr;  // room for the launcher's 16 slabs, or one slice
-    int          nslab = 1;
-    TM_TRY(launch_linear_fp8(w, e->d_f8_xq, e->d_f8_sx, 0, y, ldy, M, gated, 0, ws, &nslab, e->stream));
-    if (nslab > 1 && !defer) {
-        TM_TRY(launch_splitk_reduce(y, ldy, ws, nslab, M, w.N, gated, e->stream));
-        nslab = 1;
-    }
-    *slabs = nslab;
-    return 0;
-}
-
-// MXFP4 dense linear (weight_type 3): the GEMM input is quantised per row and group of 32 into the engine's code / scale-byte buffers,
-// then the block-scaled FP4 MFMA kernel runs, for every M.  Slabs as linear_fp8_channel.
-static int linear_mxfp4(tm_engine* e, const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
-                        int* slabs)
-{
-    TM_REQUIRE(e->d_mx_xq && e->d_mx_sx && M <= e->max_tokens, "internal: mxfp4 dense linear without its activation buffers");
-    TM_TRY(launch_quant_mxfp4_rows(e->d_mx_xq, e->d_mx_sx, x, ldx, M, w.K, e->stream));
-    float* const ws    = fit_splits(e, M, w.N, 16) == 16 ? e->d_gemm_ws : nullptr;  // room for the launcher's 16 slabs, or one slice
-    int          nslab = 1;
-    TM_TRY(launch_linear_mxfp4(w, e->d_mx_xq, e->d_mx_sx, y, ldy, M, gated, 0, ws, &nslab, e->stream));
-    if (nslab > 1 && !defer) {
-        TM_TRY(launch_splitk_reduce(y, ldy, ws, nslab, M, w.N, gated, e->stream));
-        nslab = 1;
-    }
-    *slabs = nslab;
-    return 0;
-}
-
+// A dense linear of the model's format (linear_forward, linear.hip), reduced into y.  It alone hands the arrival counters on, so only
+// it may run a measured in-launch merge shape.
 static int linear_plain(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated)
 {
-    if (l.w.type == TM_WEIGHT_MXFP4) {
-        int one;
-        return linear_mxfp4(e, l.w, x, ldx, y, ldy, M, gated, false, &one);
-    }
-    if (l.w.cscale) {
-        int one;  // the slab count behind a launch that defers nothing
-        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, false, &one);
-    }
-    GemmConfig cfg = gemm_pick_config(l.w, M);
-    cfg.splits     = fit_splits(e, M, l.w.N, cfg.splits);
-    cfg.tickets    = e->d_tickets;
-    return launch_linear(l.w, x, ldx, y, ldy, M, gated, cfg, e->d_gemm_ws, false, nullptr, e->stream);
+    LinearScratch s = e->scratch;
+    s.tickets       = e->d_tickets;
+    return linear_forward(l.w, x, ldx, y, ldy, M, gated, s, false, nullptr, e->stream);
 }
 
 // A linear whose consumer can sum the split-K slices itself (the residual-norm launch, the decode attention's fused prologue):
 // `defer` and a split launch leave the fp32 slabs in d_gemm_ws, *slabs > 1; otherwise y holds the result and *slabs = 1.
-// (No arrival counters here, unlike linear_plain: launch_linear then runs a merge shape as the plain form of the same tile.)
+// (No arrival counters here, unlike linear_plain, even when nothing is deferred: launch_linear then runs a merge shape as the plain form
+// of the same tile.)
 static int linear_deferrable(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated, bool defer,
                              int* slabs)
 {
-    if (l.w.cscale) {
-        return linear_fp8_channel(e, l.w, x, ldx, y, ldy, M, gated, defer, slabs);
-    }
-    if (l.w.type == TM_WEIGHT_MXFP4) {
-        return linear_mxfp4(e, l.w, x, ldx, y, ldy, M, gated, defer, slabs);
-    }
-    GemmConfig cfg = gemm_pick_config(l.w, M);
-    cfg.splits     = fit_splits(e, M, l.w.N, cfg.splits);
-    defer          = defer && cfg.splits > 1;
-    *slabs         = 1;  // (not deferred: launch_linear would report the slabs it reduced itself)
-    return launch_linear(l.w, x, ldx, y, ldy, M, gated, cfg, e->d_gemm_ws, defer, defer ? slabs : nullptr, e->stream);
+    return linear_forward(l.w, x, ldx, y, ldy, M, gated, e->scratch, defer, slabs, e->stream);
 }
 
 // row-parallel linear followed by (all-reduce +) residual + RMSNorm; without a communicator the norm launch sums the slabs
@@ -206,19 +153,10 @@ static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, i
 }
 
 // ---- RMSNorm folded into the decode GEMMs (tp = 1, dense u4 layers, M <= 64; NormFold in tm_kernels.h) ----------------------------
-// the tiling of a folded launch: the measured / heuristic pick when its kernel carries the folded epilogue, else the heuristic's
+// the tiling of a folded launch: dec32_pick_fold's, its split-K fitted to the engine's workspace
 static void fold_tiling(tm_engine* e, const LinearWeight& w, int M, int* shape, int* splits, bool producer)
 {
-    dec32_pick(w, M, shape, splits);
-    if (!dec32_fold_shape_m(*shape, M, producer)) {
-        dec32_pick_ex(w, M, shape, splits, false);
-    }
-    if (!dec32_fold_shape_m(*shape, M, producer)) {
-        // M <= 64: the 128-column tile over the whole k range; above (batch 128): the same tile on 32-row blocks for a producer, the 128-row
-        // tile for a consumer (every weight unit read once)
-        *shape  = M <= 64 ? 0 : (producer ? 7 : 4);
-        *splits = 1;
-    }
+    dec32_pick_fold(w, M, producer, shape, splits);
     *splits = fit_splits(e, M, w.N, *splits);
 }
 

@@ -55,6 +55,8 @@ struct Slot {
 struct LinearSlots {
     LinearWeight w;
     std::string  prefix;
+    bool         expert = false;  // one expert of a MoE layer (tm_engine_create knows; add_linear resolves the format from it)
+    bool         gated  = false;  // a w1w3: gate / up columns interleaved
 };
 
 struct Layer {
@@ -154,10 +156,10 @@ struct tm_engine {
     half_t* d_logits = nullptr;
     half_t* d_last   = nullptr;
     float*  d_gemm_ws = nullptr;
-    uint8_t* d_f8_xq  = nullptr;  // channel-scaled fp8 (fp8_scale_mode 1): e4m3 codes [max_tokens][widest K] of the current GEMM input ...
-    float*   d_f8_sx  = nullptr;  // ... and its per-token scales [max_tokens]
-    uint8_t* d_mx_xq  = nullptr;  // MXFP4 dense (weight_type 3): e2m1 codes [max_tokens][widest K / 2] of the current GEMM input ...
-    uint8_t* d_mx_sx  = nullptr;  // ... and its e8m0 scale bytes [max_tokens][widest K / 32]
+    // what linear_forward may use (tm_engine_start): d_gemm_ws and, for a dense format that quantises its GEMM input (linear_act_quant:
+    // channel-scaled fp8, MXFP4 dense), the codes [max_tokens][widest K of a dense linear] of the current GEMM input and its scales (per
+    // token / one e8m0 byte per 32 channels), nullptr otherwise.  No arrival counters: linear_plain alone adds d_tickets
+    LinearScratch scratch;
     size_t  gemm_ws_bytes = 0;
     // RMSNorm folded into the decode GEMMs (NormFold, tm_kernels.h): per-tile sums of squares [hidden / 64][64] and the split-K
     // arrival counters of the producing GEMM; TM_FOLD_NORM=0 keeps the reduce-norm launches

@@ -1534,6 +1534,20 @@ void dec32_pick(const LinearWeight& w, int M, int* shape_out, int* splits_out)
     dec32_pick_ex(w, M, shape_out, splits_out, true);
 }
 
+void dec32_pick_fold(const LinearWeight& w, int M, bool producer, int* shape_out, int* splits_out)
+{
+    dec32_pick(w, M, shape_out, splits_out);
+    if (!dec32_fold_shape_m(*shape_out, M, producer)) {
+        dec32_pick_ex(w, M, shape_out, splits_out, false);
+    }
+    if (!dec32_fold_shape_m(*shape_out, M, producer)) {
+        // M <= 64: the 128-column tile over the whole k range; above (batch 128): the same tile on 32-row blocks for a producer, the 128-row
+        // tile for a consumer (every weight unit read once)
+        *shape_out  = M <= 64 ? 0 : (producer ? 7 : 4);
+        *splits_out = 1;
+    }
+}
+
 void dec32_pick_ex(const LinearWeight& w, int M, int* shape_out, int* splits_out, bool use_table)
 {
     const int ncg = w.N / 32;

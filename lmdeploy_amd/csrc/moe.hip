@@ -670,7 +670,7 @@ int moe_prepare(MoeBlock& m, hipStream_t st)
     TM_REQUIRE((m.b13 != nullptr) == (m.b2 != nullptr), "moe: expert biases come for both linears (w1w3 and w2)");
     TM_REQUIRE(!m.b13 || m.act == 1, "moe: expert biases are built with the gpt-oss activation only");
     TM_REQUIRE(!m.shared_gate || (!m.b2 && m.act == 0), "moe: a shared expert with the gpt-oss activation or expert biases is not built");
-    TM_REQUIRE(!m.w13[0].cscale || (fp8_mfma_supported(m.w13[0]) && fp8_mfma_supported(m.w2[0])),
+    TM_REQUIRE(m.w13[0].fmt != LinearFormat::FP8_CHANNEL || (fp8_mfma_supported(m.w13[0]) && fp8_mfma_supported(m.w2[0])),
                "moe: channel-scaled fp8 experts run on the fp8 matrix cores only (TM_FP8_MFMA=0 is not offered for them)");
     TM_TRY_RC(moe_build_groups(&m.groups13, m.w13.data(), m.experts, st));
     TM_TRY_RC(moe_build_groups(&m.groups2, m.w2.data(), m.experts, st));
@@ -678,7 +678,7 @@ int moe_prepare(MoeBlock& m, hipStream_t st)
         std::vector<const void*> h13(m.experts), h2(m.experts);
         for (int e = 0; e < m.experts; ++e) {
             TM_REQUIRE(m.w13[e].packed8 && m.w2[e].packed8, "moe: fp8 expert without its P8 image");
-            TM_REQUIRE((m.w13[e].cscale != nullptr) == (m.w13[0].cscale != nullptr) && (m.w2[e].cscale != nullptr) == (m.w13[0].cscale != nullptr),
+            TM_REQUIRE(m.w13[e].fmt == m.w13[0].fmt && m.w2[e].fmt == m.w13[0].fmt,
                        "moe: fp8 experts of one block share one scale mode (block 128 or channel)");
             h13[e] = m.w13[e].packed8;
             h2[e]  = m.w2[e].packed8;
@@ -740,7 +740,7 @@ int moe_forward(const MoeBlock& m, half_t* out, int ldo, const half_t* x, int ld
         const int    ldsx2 = ((int)pairs + 3) / 4 * 4;
         float*       sx2   = (float*)(aq + pairs * m.inter);
         TM_REQUIRE(ldx == m.hidden || tokens == 1, "moe fp8: x must be row-contiguous");
-        const bool chan = m.w13[0].cscale != nullptr;  // channel-scaled experts: one activation scale per row, over all of K
+        const bool chan = m.w13[0].fmt == LinearFormat::FP8_CHANNEL;  // channel-scaled experts: one activation scale per row, over all of K
         if (stages & kMoeW13) {
             TM_TRY_RC(chan ? launch_quant_fp8_token(xq, sx1, x, ldx, tokens, m.hidden, st)
                            : launch_quant_fp8_rows(xq, sx1, x, ldx, tokens, m.hidden, ldsx1, st));

@@ -160,8 +160,13 @@ struct PrefillAttnParams {
 int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 
 // ---- gemm_w4a16.hip ---------------------------------------------------------------------
+// What a linear IS, resolved once where it is declared from (weight_type, fp8_scale_mode, expert?) by linear_format(): the key of the
+// format table in linear.hip, which owns everything that depends on it (staging parts, repack, activation quantisation, run, bytes).
+enum class LinearFormat : int { U4, F16, FP8_BLOCK, FP8_CHANNEL, MXFP4_EXPERT, MXFP4_DENSE, COUNT };
 struct LinearWeight {
     int       K = 0, N = 0, group = 128;
+    LinearFormat fmt = LinearFormat::U4;
+    bool      gated = false;     // FP8_BLOCK only: a w1w3 whose block-scale row is [w1 blocks | w3 blocks] for interleaved columns
     int       type = 0;          // 0 = u4 (AWQ), 1 = f16 dense, 2 = fp8 e4m3 with 128x128 block scales, 3 = MXFP4 (e2m1 codes, one ue8m0
                                  // scale byte per 32 k; experts weight-only: gemm_mxfp4.hip, dense linears W4A4: gemm_mxfp4_mfma.hip)
     int       role = 0;          // key of the measured dispatch table next to (K, N, M): 0 = any (operator-level handles, imported
@@ -240,12 +245,49 @@ GemmConfig gemm_pick_config_general(const LinearWeight& w, int M);  // ... the t
 int launch_linear(const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated_silu,
                   GemmConfig cfg, float* workspace, bool defer_reduce, int* slabs, hipStream_t st);
 
+// ---- linear.hip: the one place that knows the linear formats (a table with one row per LinearFormat) --------------
+LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert);
+enum class PartKind : int { AWQ_QWEIGHT, AWQ_SCALES, AWQ_ZEROS, F16, E4M3, F32_SCALES, E2M1, UE8M0 };  // what a staging part holds
+struct LinearStaging {  // the parts a checkpoint fills for one linear, in the order linear_weight_prepare takes them
+    int         n = 0;
+    const char* suffix[3];  // slot name behind the linear's prefix: "qweight", "scales", ...
+    PartKind    kind[3];
+    size_t      bytes[3];
+};
+LinearStaging linear_staging(LinearFormat fmt, int K, int N, int group);
+// The table's quantisation column: how the GEMM input is quantised in front of the launch.  A format that also keeps a weight-only image
+// (FP8_BLOCK) quantises, and runs on the matrix cores, only for a caller that brings activation buffers; without them it answers NONE.
+enum class ActQuant : int { NONE, FP8_ROW128, FP8_TOKEN, MXFP4_ROW32 };
+ActQuant linear_act_quant(LinearFormat fmt, bool have_act_buffers);
+// repack the staged parts (device pointers, linear_staging order) into the device image(s) of w.fmt.  The u4 policy of the caller (the
+// engine's dense linears; ignored by every other format): p32_only as linear_weight_prepare_u4, f16_image = linear_weight_build_f16_image too
+int    linear_weight_prepare(LinearWeight& w, const void* const* parts, hipStream_t st, bool p32_only = false, bool f16_image = false);
+bool   linear_weight_prepared(const LinearWeight& w);
+void   linear_weight_take(LinearWeight& dst, LinearWeight& src);  // dst owns src's images, src is left unprepared
+size_t linear_weight_bytes(const LinearWeight& w);  // codes + scales of a prepared weight as the checkpoint carries them (0: not prepared)
+struct LinearScratch {
+    float*    ws = nullptr;  // split-K slabs; a split that does not fit ws_bytes runs as one slice
+    size_t    ws_bytes = 0;
+    unsigned* tickets  = nullptr;  // arrival counters (GemmConfig::tickets): with them a measured in-launch merge shape may run
+    void *    xq = nullptr, *sx = nullptr;  // codes and scales of the quantised GEMM input (FP8_ROW128 scales: [K / 128][ldsx]) ...
+    int       ldsx = 0, rows = 0;           // ... and the rows both hold
+    int       splits = 0;  // quantised-input formats: an explicit split-K (operator-level callers); 0 = the launcher's own
+};
+// y[M][N (or N/2 if gated_silu)] = x[M][K] . W for every format.  A quantised input (linear_act_quant of what the scratch carries) is
+// quantised, launched with 16 slabs if they fit or one slice, and reduced unless `defer`; the others run gemm_pick_config's tiling through
+// launch_linear.  `defer` and a split launch leave the fp32 slabs in scratch.ws, *slabs > 1; otherwise y holds the result, *slabs = 1.
+int linear_forward(const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated_silu, const LinearScratch& scratch,
+                   bool defer, int* slabs, hipStream_t st);
+
 // ---- gemm_decode.hip: W4A16 decode GEMM (M <= 64), 32x32x16 MFMA, 16 waves per CU ------------------------------
 size_t p32_bytes(int K, int N);
 int    launch_repack_p32(void* out, const int32_t* qweight, const half_t* scales, const half_t* zeros, int K, int N, hipStream_t st);
 bool   dec32_supported(const LinearWeight& w, int M);
 void   dec32_pick(const LinearWeight& w, int M, int* shape_out, int* splits_out);  // measured table first, then the heuristic
 void   dec32_pick_ex(const LinearWeight& w, int M, int* shape_out, int* splits_out, bool use_table);
+// the tiling of a folded-norm launch (NormFold below): the measured / heuristic pick when its kernel carries the folded epilogue, else
+// the heuristic's, else the tile that always does
+void   dec32_pick_fold(const LinearWeight& w, int M, bool producer, int* shape_out, int* splits_out);
 // measured dispatch table of the decode linears: key (K, N, M <= 64) -> (shape, splits)
 void   dec32_table_set(int K, int N, int M, int shape, int splits, int role = 0);
 bool   dec32_table_get(int K, int N, int M, int* shape, int* splits, int role = 0);  // the role's entry, else the role-0 entry

@@ -11,6 +11,7 @@ from lmdeploy_amd import _ffi
 from lmdeploy_amd.turbomind.engine import Engine
 from lmdeploy_amd.turbomind.loader import export_weights
 from oracle import tm_oracle as o
+from tests.linear_bytes import engine_weight_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,7 @@ def test_engine_matches_oracle(cuda, monkeypatch, kv_bits, use_graph, fold):
         eng.decode(1)
         logits.append(eng.fetch_logits())
     toks = eng.fetch()          # [B, steps+1]
+    weight_bytes = eng.stats()['weight_bytes']
     eng.close()
 
     om = o.OracleModel(cfg, w, batch=len(prompts), max_ctx=256)
@@ -61,6 +63,7 @@ def test_engine_matches_oracle(cuda, monkeypatch, kv_bits, use_graph, fold):
         safe = (top2[:, 1] - top2[:, 0]) > 6e-2
         assert np.array_equal(toks[safe, s], ref_toks[s][safe]), f'step {s}: greedy tokens differ'
     print(f'[engine vs oracle] kv_bits {kv_bits} graph {use_graph} folded norm {fold}: max logit diff over {steps + 1} steps {worst:.5f}')
+    assert weight_bytes == engine_weight_bytes(cfg, 'u4')
 
 
 @pytest.mark.parametrize('batch,fold_max', [(100, 128), (128, 128), (100, 64)])
@@ -894,6 +897,7 @@ def test_engine_moe_matches_oracle(cuda, fmt):
         eng.decode(1)
         logits.append(eng.fetch_logits())
     toks = eng.fetch()
+    weight_bytes = eng.stats()['weight_bytes']
     eng.close()
     om = o.OracleModel(cfg, w, batch=len(prompts), max_ctx=128)
     ids, lg = om.forward(prompts)
@@ -904,6 +908,7 @@ def test_engine_moe_matches_oracle(cuda, fmt):
     for s_ in range(steps + 1):
         d = np.abs(logits[s_].astype(np.float32) - ref[s_].astype(np.float32))
         assert d.max() <= 3e-2, f'step {s_}: max logit diff {d.max()}'
+    assert weight_bytes == engine_weight_bytes(cfg, fmt)
 
 
 @pytest.mark.parametrize('fmt', ['fp8', 'u4'])

@@ -325,11 +325,14 @@ def test_checkpoint_through_pipeline(cuda, tmp_path_factory):
 
 
 def test_synthetic_channel_engine_runs(cuda):
-    """tm_engine_init_synthetic fills channel-mode slots with usable values: finite logits that differ between prompts, dense and MoE"""
+    """tm_engine_init_synthetic fills channel-mode slots with usable values: finite logits that differ between prompts, dense and MoE;
+    stats() counts every linear's codes and column scales (K N + 4 N) next to the fp16 lm_head"""
     from lmdeploy_amd import GenerationConfig, TurbomindEngineConfig, pipeline
+    from tests.linear_bytes import engine_weight_bytes
     for model in ('synthetic:tiny', 'synthetic:tiny_moe'):
         pipe = pipeline(model, backend_config=TurbomindEngineConfig(model_format='fp8_channel', quant_policy=8, max_batch_size=2, session_len=128))
         try:
+            assert pipe.engine.stats()['weight_bytes'] == engine_weight_bytes(pipe.model_cfg, 'fp8_channel')
             out = pipe([[1, 2, 3, 4, 5], [9, 8, 7]], GenerationConfig(max_new_tokens=3, ignore_eos=True, output_logits='generation'))
             lg = np.stack([x.logits for x in out]).astype(f32)
             assert np.isfinite(lg).all() and lg.std() > 1e-3 and not np.array_equal(lg[0], lg[1])

@@ -12,6 +12,7 @@ import pytest
 from lmdeploy_amd.turbomind.engine import Engine
 from lmdeploy_amd.turbomind.loader import export_weights
 from oracle import tm_oracle as o
+from tests.linear_bytes import engine_weight_bytes
 from tests.qwen2_moe_reference import QWEN2_MOE_CFG, Qwen2MoeConfig, Qwen2MoeOracleModel
 from tests.qwen_moe_reference import QWEN3_MOE_CFG, QwenMoeConfig, QwenMoeOracleModel
 from tests.qwen_reference import make_qwen_weights
@@ -59,6 +60,7 @@ def _engine_vs_oracle(cfg, w, oracle_cls, use_graph, prompt_lens=(70, 5, 64), st
         eng.decode(1)
         logits.append(eng.fetch_logits().copy())
     toks = eng.fetch()
+    weight_bytes = eng.stats()['weight_bytes']
     eng.close()
     om = oracle_cls(cfg, w, batch=len(prompts), max_ctx=session_len)
     ids, lg = om.forward(prompts)
@@ -73,6 +75,7 @@ def _engine_vs_oracle(cfg, w, oracle_cls, use_graph, prompt_lens=(70, 5, 64), st
         assert np.array_equal(toks[safe, s], ids[safe]), f'step {s}: greedy tokens differ'
         if s < steps:
             ids, lg = om.forward([[int(t)] for t in toks[:, s]])
+    assert weight_bytes == engine_weight_bytes(cfg, 'f16')
     return worst
 
 

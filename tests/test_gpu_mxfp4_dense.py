@@ -315,10 +315,13 @@ def test_checkpoint_through_pipeline(cuda, tmp_path_factory):
 
 
 def test_synthetic_engine_runs(cuda):
-    """tm_engine_init_synthetic fills the blocks / scales slots with usable values: finite logits that differ between prompts"""
+    """tm_engine_init_synthetic fills the blocks / scales slots with usable values: finite logits that differ between prompts;
+    stats() counts every linear's codes and scale bytes (K N / 2 + N K / 32) next to the fp16 lm_head"""
     from lmdeploy_amd import GenerationConfig, TurbomindEngineConfig, pipeline
+    from tests.linear_bytes import engine_weight_bytes
     pipe = pipeline('synthetic:tiny', backend_config=TurbomindEngineConfig(model_format='mxfp4', quant_policy=8, max_batch_size=2, session_len=128))
     try:
+        assert pipe.engine.stats()['weight_bytes'] == engine_weight_bytes(pipe.model_cfg, 'mxfp4')
         out = pipe([[1, 2, 3, 4, 5], [9, 8, 7]], GenerationConfig(max_new_tokens=3, ignore_eos=True, output_logits='generation'))
         lg = np.stack([x.logits for x in out]).astype(f32)
         assert np.isfinite(lg).all() and lg.std() > 1e-3 and not np.array_equal(lg[0], lg[1])
