@@ -271,7 +271,8 @@ int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st
 
 /* ---- Linear (mirrors _tm.LinearWeight / LlamaLinear.forward_dense / QuantizeGroupwise) -------- */
 typedef struct tm_linear tm_linear;
-enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* experts weight-only (tm_moe); dense linears W4A4 (tm_linear_prepare_mxfp4) */ };
+enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* experts weight-only (tm_moe); dense linears W4A4 (tm_linear_prepare_mxfp4) */,
+       TM_WEIGHT_I8 = 4 /* dense linears W8A8 (tm_linear_prepare_int8); never experts */ };
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size);
 /* Boundary ("TM") layout, device pointers: qweight int32 [K][N/8] (nibble j of word c = column 8c+j,
  * lmdeploy/turbomind/weight_format.py:63-74), scales / zeros fp16 [K/g][N].  For TM_WEIGHT_F16: weight fp16
@@ -359,6 +360,23 @@ int    tm_quant_mxfp4_rows(void* xq, void* sx, const void* x, int ldx, int M, in
 size_t tm_linear_mxfp4_workspace(const tm_linear* w, int M);
 int    tm_linear_forward_mxfp4(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
                                void* workspace, tm_stream_t st);
+/* INT8 dense linears, int8 weights and int8 activations ("W8A8") on the int8 matrix cores (v_mfma_i32_32x32x32_i8): the form
+ * `lmdeploy lite smooth_quant` writes and compressed-tensors publishes as "int-quantized".  tm_linear_create(..., TM_WEIGHT_I8, 128);
+ * limits: K % 128 == 0, K <= 32768, N % 32 == 0.  weight = int8 codes [K][N], scales = device fp32 [N], one per output column (a
+ * per-tensor scale is that scalar repeated; fused linears concatenate / interleave their parts' scales like their columns).
+ * Activations are quantised per token over the whole row (tm_quant_int8_token: codes int8 [M][K], sx fp32 [M]; K % 128 == 0,
+ * K <= 32768), per fp16 row in fp32: absmax = max(max|x|, 1e-7), sx = absmax / 127, q = clamp(round(x / sx), -127, 127) with the
+ * IEEE division and ties rounded away from zero (the reference's per_token_quant_int8), and
+ *   y[m, n] = h( (float(acc) * sx[m]) * sw[n] ),   acc = sum_k xq[m, k] * wq[k, n]  in int32 over ALL of K (exact),
+ * float() rounding to nearest even.  gated_silu as tm_linear_forward; splits = 0: heuristic, else 1..16 split-K slices whose raw int32
+ * accumulators are summed as integers before the one conversion: y is the same bits for every split.
+ * tm_linear_forward_int8 quantises, runs the GEMM and reduces; workspace >= tm_linear_int8_workspace(w, M) bytes.
+ * tm_linear_forward returns TM_INVALID on such a handle: there is no weight-only arm. */
+int    tm_linear_prepare_int8(tm_linear* w, const void* weight, const void* scales_f32_N, tm_stream_t st);
+int    tm_quant_int8_token(void* xq, float* sx, const void* x, int ldx, int M, int K, tm_stream_t st);
+size_t tm_linear_int8_workspace(const tm_linear* w, int M);
+int    tm_linear_forward_int8(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
+                              void* workspace, tm_stream_t st);
 size_t tm_linear_fp8_workspace(const tm_linear* w, int M);
 int    tm_quant_fp8_rows(void* xq, float* sx, const void* x, int ldx, int M, int K, int ldsx, tm_stream_t st);
 int    tm_linear_forward_fp8(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
@@ -549,12 +567,15 @@ typedef struct tm_model_config {
     int   rope_max_position_embeddings;
     float rope_yarn_beta_fast, rope_yarn_beta_slow, rope_yarn_attention_factor;
     int   group_size;   /* 128 */
-    int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16, TM_WEIGHT_FP8 or TM_WEIGHT_MXFP4 for the decoder linears; lm_head is fp16.
+    int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16, TM_WEIGHT_FP8, TM_WEIGHT_MXFP4 or TM_WEIGHT_I8 for the decoder linears; lm_head is fp16.
                          * TM_WEIGHT_MXFP4 (W4A4, tm_linear_prepare_mxfp4's form): dense models at tp = 1, any head_dim the engine serves;
                          * slots "*.blocks" uint8 [N][K/2] and "*.scales" uint8 [N][K/32] for w_qkv (q | k | v rows stacked), wo, w1w3
                          * ((gate_j, up_j) rows interleaved) and w2; every such linear runs tm_quant_mxfp4_rows + the block-scaled FP4 MFMA
                          * GEMM for every M, eager and in the decode graph; the GEMM tuner and the folded norm pass them by; refused
-                         * with TM_INVALID: tp > 1, moe_experts > 0, hidden_valid (padded widths) */
+                         * with TM_INVALID: tp > 1, moe_experts > 0, hidden_valid (padded widths).
+                         * TM_WEIGHT_I8 (W8A8, tm_linear_prepare_int8's form): dense models; slots "*.weight" int8 [K][N] and "*.scales"
+                         * fp32 [N] for the four decoder linears; each runs tm_quant_int8_token + the int8 MFMA GEMM for every M and
+                         * reduces its own split-K; refused with TM_INVALID: moe_experts > 0, hidden_valid (padded widths) */
     /* mixture of experts (0 experts = dense FFN): every layer's FFN is a router + `moe_experts` expert FFNs of width
      * `inter` (sharded over tp like the dense FFN), `moe_top_k` per token (Mixtral: 8 / 2, norm_topk = 1) */
     int   moe_experts, moe_top_k, moe_norm_topk;

@@ -185,6 +185,10 @@ _SIGNATURES = {
     'tm_linear_forward_fp8_grouped': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
     'tm_moe_set_fp8_scale_mode': (c_int, [c_void_p, c_int]),
+    'tm_linear_prepare_int8': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tm_quant_int8_token': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tm_linear_int8_workspace': (c_size_t, [c_void_p, c_int]),
+    'tm_linear_forward_int8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'tm_linear_prepare_mxfp4': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'tm_quant_mxfp4_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'tm_linear_mxfp4_workspace': (c_size_t, [c_void_p, c_int]),

@@ -150,7 +150,7 @@ static int prepare_as(LinearWeight& w, LinearFormat fmt, bool gated, const void*
     return rc;
 }
 
-// tm_linear_forward_fp8 / _mxfp4: the workspace is the quantised input (codes, `code_bytes`, then scales; act_bytes in all), 256-aligned,
+// tm_linear_forward_fp8 / _mxfp4 / _int8: the workspace is the quantised input (codes, `code_bytes`, then scales; act_bytes in all), 256-aligned,
 // then the 16 slabs
 static int forward_quantised(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits, void* workspace,
                              size_t code_bytes, size_t act_bytes, tm_stream_t st)
@@ -462,16 +462,23 @@ int tm_silu_mul(void* out, const void* gate_up, int M, int inter, tm_stream_t st
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size)
 {
     TM_REQUIRE(out, "null pointer");
-    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_MXFP4,
+    TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_MXFP4
+                   || weight_type == TM_WEIGHT_I8,
                "weight_type");
     TM_REQUIRE(in_features > 0 && out_features > 0, "shape");
+    if (weight_type == TM_WEIGHT_I8) {
+        TM_REQUIRE(in_features % 128 == 0 && in_features <= kFp8TokenMaxK && out_features % 32 == 0,
+                   "int8 linear " + std::to_string(in_features) + " x " + std::to_string(out_features)
+                       + ": K % 128 == 0, K <= 32768 and N % 32 == 0");
+    }
     if (weight_type == TM_WEIGHT_MXFP4) {
         TM_REQUIRE(group_size == 32, "mxfp4 dense linear: group_size 32");
         TM_REQUIRE(in_features % 128 == 0 && out_features % 32 == 0 && (size_t)in_features * out_features / 2 < ((size_t)1 << 31),
                    "mxfp4 dense linear " + std::to_string(in_features) + " x " + std::to_string(out_features)
                        + ": K % 128 == 0, N % 32 == 0 and K * N / 2 < 2^31");
     }
-    TM_REQUIRE(gemm_general_image_bytes(in_features, out_features, weight_type) < kGeneralImageLimit,
+    // (an int8 linear has no general-kernel image: its P8 image is checked where it is built)
+    TM_REQUIRE(weight_type == TM_WEIGHT_I8 || gemm_general_image_bytes(in_features, out_features, weight_type) < kGeneralImageLimit,
                "linear " + std::to_string(in_features) + " x " + std::to_string(out_features) + ": its general-kernel image of "
                    + std::to_string(gemm_general_image_bytes(in_features, out_features, weight_type))
                    + " bytes reaches 2^31 (the kernel addresses it with 32-bit offsets)");
@@ -489,6 +496,7 @@ int tm_linear_prepare(tm_linear* w, const void* weight, const void* scales, cons
 {
     TM_REQUIRE(w && weight, "null pointer");
     TM_REQUIRE(w->w.type != TM_WEIGHT_MXFP4, "mxfp4 dense linear: tm_linear_prepare_mxfp4 takes its blocks and scale bytes");
+    TM_REQUIRE(w->w.type != TM_WEIGHT_I8, "int8 linear: tm_linear_prepare_int8 takes its codes and column scales");
     TM_REQUIRE(w->w.type != TM_WEIGHT_U4 || (scales && zeros), "u4 weights need scales and zeros");
     TM_REQUIRE(w->w.type != TM_WEIGHT_FP8 || scales, "fp8 weights need their 128x128 block scales");
     return prepare_as(w->w, linear_format(w->w.type, 0, false), false, weight, scales, zeros, st);
@@ -505,6 +513,7 @@ size_t tm_linear_workspace(const tm_linear* w, int M)
 int tm_linear_dequant_f16(const tm_linear* w, void* out_nk, tm_stream_t st)
 {
     TM_REQUIRE(w && out_nk, "null pointer");
+    TM_REQUIRE(w->w.type != TM_WEIGHT_I8, "int8 linears have no fp16 image to rebuild");
     if (w->w.type == TM_WEIGHT_MXFP4) {
         return launch_dequant_p4_f16((half_t*)out_nk, w->w, (hipStream_t)st);
     }
@@ -519,6 +528,7 @@ int tm_linear_forward(const tm_linear* w, const void* x, int ldx, void* y, int l
     TM_REQUIRE(w->w.fmt != LinearFormat::FP8_CHANNEL,
                "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
     TM_REQUIRE(w->w.fmt != LinearFormat::MXFP4_DENSE, "mxfp4 dense linears have no weight-only arm: tm_linear_forward_mxfp4 runs them");
+    TM_REQUIRE(w->w.fmt != LinearFormat::INT8_CHANNEL, "int8 linears have no weight-only arm: tm_linear_forward_int8 runs them");
     GemmConfig cfg = gemm_pick_config(w->w, M);  // (workspace: tm_linear_workspace(w, M) bytes)
     if (nt > 0) {
         cfg.nt = nt;
@@ -735,6 +745,37 @@ int tm_linear_forward_mxfp4(const tm_linear* w, const void* x, int ldx, void* y,
                              st);
 }
 
+int tm_linear_prepare_int8(tm_linear* w, const void* weight, const void* scales, tm_stream_t st)
+{
+    TM_REQUIRE(w && weight && scales, "null pointer");
+    TM_REQUIRE(w->w.type == TM_WEIGHT_I8, "tm_linear_prepare_int8: int8 weights only");
+    return prepare_as(w->w, LinearFormat::INT8_CHANNEL, false, weight, scales, nullptr, st);
+}
+
+int tm_quant_int8_token(void* xq, float* sx, const void* x, int ldx, int M, int K, tm_stream_t st)
+{
+    TM_REQUIRE(xq && sx && x, "null pointer");
+    return launch_quant_int8_token((uint8_t*)xq, sx, (const half_t*)x, ldx, M, K, (hipStream_t)st);
+}
+
+size_t tm_linear_int8_workspace(const tm_linear* w, int M)
+{
+    if (!w) {
+        return 0;
+    }
+    return (fp8_act_workspace_bytes(M, w->w.K) + 255) / 256 * 256 + gemm_workspace_bytes(M, w->w.N, 16);  // (int32 slabs: 4 bytes too)
+}
+
+int tm_linear_forward_int8(const tm_linear* w, const void* x, int ldx, void* y, int ldy, int M, int gated_silu, int splits,
+                           void* workspace, tm_stream_t st)
+{
+    TM_REQUIRE(w && x && y && workspace, "null pointer");
+    TM_REQUIRE(int8_prepared(w->w), "int8 x int8 linear: a weight prepared by tm_linear_prepare_int8");
+    TM_REQUIRE(splits >= 0 && splits <= 16, "0 <= splits <= 16");
+    // codes [M][K] | scales [M]
+    return forward_quantised(w, x, ldx, y, ldy, M, gated_silu, splits, workspace, (size_t)M * w->w.K, fp8_act_workspace_bytes(M, w->w.K), st);
+}
+
 size_t tm_linear_fp8_grouped_workspace(int experts, int x_rows, int K)
 {
     return (size_t)(experts + 31) / 32 * 256 + (fp8_act_workspace_bytes(x_rows, K) + 255) / 256 * 256;
@@ -830,6 +871,7 @@ struct tm_moe {
 int tm_moe_create(tm_moe** out, int hidden, int inter, int experts, int top_k, int weight_type, int norm_topk, float routed_scale)
 {
     TM_REQUIRE(out, "null pointer");
+    TM_REQUIRE(weight_type != TM_WEIGHT_I8, "moe experts: int8 (W8A8) experts are not built: int8 serves dense linears only");
     TM_REQUIRE(weight_type == TM_WEIGHT_U4 || weight_type == TM_WEIGHT_FP8 || weight_type == TM_WEIGHT_F16 || weight_type == TM_WEIGHT_MXFP4,
                "moe experts: u4, fp8, fp16 or mxfp4 weights");
     TM_REQUIRE(hidden % 128 == 0 && inter % 128 == 0 && experts >= 1 && experts <= 256 && top_k >= 1 && top_k <= 8 && top_k <= experts,

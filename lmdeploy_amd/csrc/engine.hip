@@ -183,6 +183,12 @@ static int check_linear_images(const tm_model_config& m, int tp)
         if (l.K == 0 || l.N == 0) {  // no shared expert
             continue;
         }
+        if (l.type == TM_WEIGHT_I8) {  // no general-kernel image: the P8 image + column scales of gemm_int8.hip, same limit
+            TM_REQUIRE(l.K % 128 == 0 && l.N % 32 == 0 && p8_bytes(l.K, l.N) + (size_t)l.N * 4 < kGeneralImageLimit,
+                       std::string(l.name) + " " + std::to_string(l.K) + " x " + std::to_string(l.N)
+                           + ": an int8 linear needs K % 128 == 0, N % 32 == 0 and an image below 2^31 bytes");
+            continue;
+        }
         const size_t bytes = gemm_general_image_bytes(l.K, l.N, l.type);
         TM_REQUIRE(bytes < kGeneralImageLimit, std::string(l.name) + " " + std::to_string(l.K) + " x " + std::to_string(l.N)
                                                    + ": its general-kernel image of " + std::to_string(bytes)
@@ -270,8 +276,13 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(c->quant_policy != 42 || c->tp == 1, "quant_policy 42 (TurboQuant KV) with tp > 1 is not built (run with tp = 1)");
     TM_REQUIRE(c->cache_block_seq_len == 64, "cache_block_seq_len must be 64");
     TM_REQUIRE(m.weight_type == TM_WEIGHT_U4 || m.weight_type == TM_WEIGHT_F16 || m.weight_type == TM_WEIGHT_FP8
-                   || m.weight_type == TM_WEIGHT_MXFP4,
+                   || m.weight_type == TM_WEIGHT_MXFP4 || m.weight_type == TM_WEIGHT_I8,
                "weight_type");
+    if (m.weight_type == TM_WEIGHT_I8) {  // dense W8A8 models on the int8 matrix cores
+        TM_REQUIRE(m.moe_experts == 0, "weight_type int8 (W8A8 dense linears) with moe_experts > 0 is not built: int8 experts are not served");
+        TM_REQUIRE(m.hidden_valid == 0 || m.hidden_valid == m.hidden, "weight_type int8 (W8A8 dense linears) with padded widths (hidden_valid) is not built");
+        TM_REQUIRE(std::max(m.hidden, m.inter) <= kFp8TokenMaxK, "weight_type int8: the per-token quantiser serves rows of up to 32768 channels");
+    }
     if (m.weight_type == TM_WEIGHT_MXFP4) {  // dense W4A4 models on the block-scaled FP4 matrix cores
         TM_REQUIRE(c->tp == 1, "weight_type mxfp4 (W4A4 dense linears) with tp > 1 is not built (run with tp = 1)");
         TM_REQUIRE(m.moe_experts == 0,
@@ -459,8 +470,10 @@ int tm_engine_init_synthetic(tm_engine* e, uint64_t seed)
             switch (sg.kind[i]) {
                 case PartKind::F16: TM_TRY(fill_normal(e, part[i]->dev, n, 0.f, std_w, ++sd)); break;
                 case PartKind::E4M3: fill_fp8_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd); break;  // random e4m3 codes (no NaN) ...
-                case PartKind::F32_SCALES:  // ... under one constant scale: E|code value| ~ 30 -> weights ~ 0.1 / sqrt(K)
-                    fill_const_f32_kernel<<<(nb / 4 + 255) / 256, 256, 0, e->stream>>>((float*)part[i]->dev, nb / 4, 0.0027f / std::sqrt((float)l.w.K));
+                case PartKind::I8: fill_mxfp4_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd, 0); break;  // uniform int8 codes ...
+                case PartKind::F32_SCALES:  // ... under one constant scale: E|code value| ~ 30 (e4m3) / rms 74 (int8) -> weights ~ 0.1 / sqrt(K)
+                    fill_const_f32_kernel<<<(nb / 4 + 255) / 256, 256, 0, e->stream>>>(
+                        (float*)part[i]->dev, nb / 4, (sg.kind[0] == PartKind::I8 ? 0.00135f : 0.0027f) / std::sqrt((float)l.w.K));
                     break;
                 case PartKind::E2M1: fill_mxfp4_kernel<<<grid, 256, 0, e->stream>>>((uint8_t*)part[i]->dev, nb, ++sd, 0); break;
                 case PartKind::UE8M0: {
@@ -697,7 +710,7 @@ int tm_engine_start(tm_engine* e)
     // widest K of a dense linear), written by the quantiser in front of every dense GEMM -- sized here, nothing is allocated in a forward
     if (const ActQuant q = linear_act_quant(linear_format(m.weight_type, m.fp8_scale_mode, false), false); q != ActQuant::NONE) {
         const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), std::max(e->inter, e->shared_inter));
-        const bool   mx     = q == ActQuant::MXFP4_ROW32;  // e2m1 pairs + an e8m0 byte per 32 channels; else e4m3 + one fp32 scale per token
+        const bool   mx     = q == ActQuant::MXFP4_ROW32;  // e2m1 pairs + an e8m0 byte per 32 channels; else e4m3 / int8 codes + one fp32 scale per token
         TM_HIP_CHECK(hipMalloc(&e->scratch.xq, T * (mx ? wide_k / 2 : wide_k)));
         TM_HIP_CHECK(hipMalloc(&e->scratch.sx, T * (mx ? wide_k / 32 : sizeof(float))));
     }

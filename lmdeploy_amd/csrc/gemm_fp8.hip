@@ -34,8 +34,6 @@ namespace tmk {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-constexpr int kP8Unit = 4096 + 128;
-
 // ---- activation quantiser ----------------------------------------------------------------------------------------
 // 16 lanes = one (row, 128-channel group): 8 halves per lane, absmax by DPP, 8 codes (one 8-byte store) per lane.
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(uint8_t* __restrict__ xq, float* __restrict__ sx, const half_t* __restrict__ x,
@@ -567,7 +565,7 @@ size_t fp8_act_workspace_bytes(int rows, int K)
     return (size_t)rows * K + (size_t)(K / 128) * ((rows + 3) / 4 * 4) * sizeof(float) + 256;
 }
 
-static int fp8_splits(int col_wgs, int KB, int want)
+int fp8_splits(int col_wgs, int KB, int want)
 {
     if (want > 0) {
         return want;

@@ -26,9 +26,11 @@ struct FormatRow {
 using PK = PartKind;
 constexpr const char* kNoFp8Act = "internal: channel-scaled fp8 linear without its activation buffers";
 constexpr const char* kNoMxAct  = "internal: mxfp4 dense linear without its activation buffers";
+constexpr const char* kNoI8Act  = "internal: int8 linear without its activation buffers";
 size_t mx_codes(int K, int N, int) { return (size_t)N * (K / 2); }    // the checkpoint layout: e2m1 codes [N][K/2] ...
 size_t mx_scales(int K, int N, int) { return (size_t)N * (K / 32); }  // ... + one ue8m0 byte per 32 k [N][K/32]
-size_t e4m3_codes(int K, int N, int) { return (size_t)K * N; }
+size_t e4m3_codes(int K, int N, int) { return (size_t)K * N; }  // (int8 codes too: one byte each)
+size_t col_scales(int, int N, int) { return (size_t)N * 4; }
 size_t sz_u4(int K, int N, int g) { return (size_t)(K / g) * N * 2; }  // fp16 [K/group][N]
 
 const FormatRow kFormats[] = {  // index = LinearFormat
@@ -42,7 +44,7 @@ const FormatRow kFormats[] = {  // index = LinearFormat
     {{{"weight", PK::E4M3, e4m3_codes}, {"scales", PK::F32_SCALES, [](int K, int N, int) { return (size_t)(K / 128) * ((N + 127) / 128) * 4; }}},
      ActQuant::FP8_ROW128, nullptr, [](int K, int N) { return (size_t)K * N + (size_t)(K / 128) * N * 4; }},
     // FP8_CHANNEL: e4m3 [K][N] + one fp32 scale per output column (those of a fused linear concatenated / interleaved like its columns)
-    {{{"weight", PK::E4M3, e4m3_codes}, {"scales", PK::F32_SCALES, [](int, int N, int) { return (size_t)N * 4; }}},
+    {{{"weight", PK::E4M3, e4m3_codes}, {"scales", PK::F32_SCALES, col_scales}},
      ActQuant::FP8_TOKEN, kNoFp8Act, [](int K, int N) { return (size_t)K * N + (size_t)N * 4; }},
     // MXFP4_EXPERT: weight-only grouped GEMM
     {{{"blocks", PK::E2M1, mx_codes}, {"scales", PK::UE8M0, mx_scales}},
@@ -50,6 +52,9 @@ const FormatRow kFormats[] = {  // index = LinearFormat
     // MXFP4_DENSE: the same parts; W4A4 on the block-scaled FP4 matrix cores
     {{{"blocks", PK::E2M1, mx_codes}, {"scales", PK::UE8M0, mx_scales}},
      ActQuant::MXFP4_ROW32, kNoMxAct, [](int K, int N) { return (size_t)K * N / 2 + (size_t)N * (K / 32); }},
+    // INT8_CHANNEL: int8 [K][N] + one fp32 scale per output column (fused linears as FP8_CHANNEL); W8A8 on the int8 matrix cores
+    {{{"weight", PK::I8, e4m3_codes}, {"scales", PK::F32_SCALES, col_scales}},
+     ActQuant::INT8_TOKEN, kNoI8Act, [](int K, int N) { return (size_t)K * N + (size_t)N * 4; }},
 };
 static_assert(sizeof(kFormats) / sizeof(kFormats[0]) == (size_t)LinearFormat::COUNT, "one row per LinearFormat, in its order");
 
@@ -62,6 +67,7 @@ LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert)
     return weight_type == TM_WEIGHT_F16   ? LinearFormat::F16 :
            weight_type == TM_WEIGHT_FP8   ? (fp8_scale_mode == 1 ? LinearFormat::FP8_CHANNEL : LinearFormat::FP8_BLOCK) :
            weight_type == TM_WEIGHT_MXFP4 ? (expert ? LinearFormat::MXFP4_EXPERT : LinearFormat::MXFP4_DENSE) :
+           weight_type == TM_WEIGHT_I8    ? LinearFormat::INT8_CHANNEL :
                                             LinearFormat::U4;
 }
 
@@ -93,6 +99,7 @@ int linear_weight_prepare(LinearWeight& w, const void* const* p, hipStream_t st,
         case LinearFormat::FP8_CHANNEL: return linear_weight_prepare_fp8_channel(w, (const uint8_t*)p[0], (const float*)p[1], st);
         case LinearFormat::MXFP4_EXPERT: return linear_weight_prepare_mxfp4(w, (const uint8_t*)p[0], (const uint8_t*)p[1], st);
         case LinearFormat::MXFP4_DENSE: return linear_weight_prepare_mxfp4_dense(w, (const uint8_t*)p[0], (const uint8_t*)p[1], st);
+        case LinearFormat::INT8_CHANNEL: return linear_weight_prepare_int8(w, (const uint8_t*)p[0], (const float*)p[1], st);
         default: break;
     }
     TM_REQUIRE(false, "internal: linear format without a prepare case");
@@ -125,10 +132,14 @@ int linear_forward(const LinearWeight& w, const half_t* x, int ldx, half_t* y, i
     }
     else {
         // The GEMM input is quantised into the caller's code / scale buffers, then the format's matrix-core kernel runs, for every M --
-        // one tile choice per M class, nothing to pick from a table.  Split-K slabs are written scaled.
+        // one tile choice per M class, nothing to pick from a table.  Split-K slabs are written scaled (int8: raw, and reduced by its launcher).
         TM_REQUIRE(have, row_of(w.fmt).needs_act);  // (a format that quantises without them needs them)
         float* const ws = gemm_workspace_bytes(M, w.N, 16) <= s.ws_bytes ? s.ws : nullptr;  // room for the launcher's 16 slabs, or one slice
-        if (q == ActQuant::MXFP4_ROW32) {
+        if (q == ActQuant::INT8_TOKEN) {
+            rc = launch_quant_int8_token((uint8_t*)s.xq, (float*)s.sx, x, ldx, M, w.K, st);
+            rc = rc ? rc : launch_linear_int8(w, (const uint8_t*)s.xq, (const float*)s.sx, y, ldy, M, gated_silu, s.splits, ws, st);
+        }
+        else if (q == ActQuant::MXFP4_ROW32) {
             rc = launch_quant_mxfp4_rows((uint8_t*)s.xq, (uint8_t*)s.sx, x, ldx, M, w.K, st);
             rc = rc ? rc : launch_linear_mxfp4(w, (const uint8_t*)s.xq, (const uint8_t*)s.sx, y, ldy, M, gated_silu, s.splits, ws, &nslab, st);
         }

@@ -162,13 +162,14 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 // ---- gemm_w4a16.hip ---------------------------------------------------------------------
 // What a linear IS, resolved once where it is declared from (weight_type, fp8_scale_mode, expert?) by linear_format(): the key of the
 // format table in linear.hip, which owns everything that depends on it (staging parts, repack, activation quantisation, run, bytes).
-enum class LinearFormat : int { U4, F16, FP8_BLOCK, FP8_CHANNEL, MXFP4_EXPERT, MXFP4_DENSE, COUNT };
+enum class LinearFormat : int { U4, F16, FP8_BLOCK, FP8_CHANNEL, MXFP4_EXPERT, MXFP4_DENSE, INT8_CHANNEL, COUNT };
 struct LinearWeight {
     int       K = 0, N = 0, group = 128;
     LinearFormat fmt = LinearFormat::U4;
     bool      gated = false;     // FP8_BLOCK only: a w1w3 whose block-scale row is [w1 blocks | w3 blocks] for interleaved columns
     int       type = 0;          // 0 = u4 (AWQ), 1 = f16 dense, 2 = fp8 e4m3 with 128x128 block scales, 3 = MXFP4 (e2m1 codes, one ue8m0
-                                 // scale byte per 32 k; experts weight-only: gemm_mxfp4.hip, dense linears W4A4: gemm_mxfp4_mfma.hip)
+                                 // scale byte per 32 k; experts weight-only: gemm_mxfp4.hip, dense linears W4A4: gemm_mxfp4_mfma.hip),
+                                 // 4 = int8 codes with one fp32 scale per output column (W8A8: gemm_int8.hip)
     int       role = 0;          // key of the measured dispatch table next to (K, N, M): 0 = any (operator-level handles, imported
                                  // tables without a role column), 1 w_qkv, 2 wo, 3 w1w3, 4 w2 -- two roles of equal (K, N) are timed
                                  // with DIFFERENT consumers by the tuner and keep separate winners
@@ -187,6 +188,7 @@ struct LinearWeight {
     size_t    packed8_bytes = 0;
     // fp8 only, channel-scaled weights (linear_weight_prepare_fp8_channel): the N fp32 column scales, stored behind the last
     // P8 unit of `packed8` (not owned).  Such a weight has no `packed` / `sz` image: it runs on the fp8 matrix cores only.
+    // int8 (linear_weight_prepare_int8): the same P8 image and column scales, run on the int8 matrix cores only.
     float*    cscale = nullptr;
     // u4 only, optional (linear_weight_build_f16_image; the engine builds it for dense linears unless TM_PREFILL_F16_IMAGE=0): the fp16
     // [N][K] image of the dequantised weights -- bit for bit the operand the fused tiles build on chip -- that prefill-sized forwards
@@ -247,7 +249,7 @@ int launch_linear(const LinearWeight& w, const half_t* x, int ldx, half_t* y, in
 
 // ---- linear.hip: the one place that knows the linear formats (a table with one row per LinearFormat) --------------
 LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert);
-enum class PartKind : int { AWQ_QWEIGHT, AWQ_SCALES, AWQ_ZEROS, F16, E4M3, F32_SCALES, E2M1, UE8M0 };  // what a staging part holds
+enum class PartKind : int { AWQ_QWEIGHT, AWQ_SCALES, AWQ_ZEROS, F16, E4M3, F32_SCALES, E2M1, UE8M0, I8 };  // what a staging part holds
 struct LinearStaging {  // the parts a checkpoint fills for one linear, in the order linear_weight_prepare takes them
     int         n = 0;
     const char* suffix[3];  // slot name behind the linear's prefix: "qweight", "scales", ...
@@ -257,7 +259,7 @@ struct LinearStaging {  // the parts a checkpoint fills for one linear, in the o
 LinearStaging linear_staging(LinearFormat fmt, int K, int N, int group);
 // The table's quantisation column: how the GEMM input is quantised in front of the launch.  A format that also keeps a weight-only image
 // (FP8_BLOCK) quantises, and runs on the matrix cores, only for a caller that brings activation buffers; without them it answers NONE.
-enum class ActQuant : int { NONE, FP8_ROW128, FP8_TOKEN, MXFP4_ROW32 };
+enum class ActQuant : int { NONE, FP8_ROW128, FP8_TOKEN, MXFP4_ROW32, INT8_TOKEN };
 ActQuant linear_act_quant(LinearFormat fmt, bool have_act_buffers);
 // repack the staged parts (device pointers, linear_staging order) into the device image(s) of w.fmt.  The u4 policy of the caller (the
 // engine's dense linears; ignored by every other format): p32_only as linear_weight_prepare_u4, f16_image = linear_weight_build_f16_image too
@@ -274,7 +276,8 @@ struct LinearScratch {
     int       splits = 0;  // quantised-input formats: an explicit split-K (operator-level callers); 0 = the launcher's own
 };
 // y[M][N (or N/2 if gated_silu)] = x[M][K] . W for every format.  A quantised input (linear_act_quant of what the scratch carries) is
-// quantised, launched with 16 slabs if they fit or one slice, and reduced unless `defer`; the others run gemm_pick_config's tiling through
+// quantised, launched with 16 slabs if they fit or one slice, and reduced unless `defer` (an int8 linear always reduces itself: its slabs are
+// raw int32 accumulators, the deferred hand-off carries fp32); the others run gemm_pick_config's tiling through
 // launch_linear.  `defer` and a split launch leave the fp32 slabs in scratch.ws, *slabs > 1; otherwise y holds the result, *slabs = 1.
 int linear_forward(const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated_silu, const LinearScratch& scratch,
                    bool defer, int* slabs, hipStream_t st);
@@ -339,7 +342,9 @@ int    launch_linear_dec32(const LinearWeight& w, const half_t* x, int ldx, half
                            int splits, float* workspace, int* slabs_out, hipStream_t st, NormFold* nf = nullptr);
 
 // ---- gemm_fp8.hip: fp8 x fp8 linear on v_mfma_f32_32x32x16_fp8_fp8 (activations quantised per row and 128 channels) ---
+constexpr int kP8Unit = 4096 + 128;  // a P8 unit: 32 columns x 128 k of codes + its scale words
 size_t p8_bytes(int K, int N);
+int    fp8_splits(int col_wgs, int KB, int want);  // split-K of the P8 kernels: `want` if > 0, else the heuristic
 int    launch_repack_p8(void* out, const uint8_t* weight, const float* block_scales, int K, int N, bool gated, hipStream_t st);
 bool   fp8_mfma_supported(const LinearWeight& w);
 size_t fp8_act_workspace_bytes(int rows, int K);
@@ -364,6 +369,17 @@ size_t mxfp4_act_workspace_bytes(int rows, int K);
 int    launch_quant_mxfp4_rows(uint8_t* xq /*[M][K/2]*/, uint8_t* sx /*[M][K/32]*/, const half_t* x, int ldx, int M, int K, hipStream_t st);
 int    launch_linear_mxfp4(const LinearWeight& w, const uint8_t* xq, const uint8_t* sx, half_t* y, int ldy, int M, bool gated_silu, int splits,
                            float* workspace, int* slabs_out, hipStream_t st);
+
+// ---- gemm_int8.hip: int8 x int8 linear (W8A8) on v_mfma_i32_32x32x32_i8: per-column weight scales, per-token activation scales ---
+// the P8 image of gemm_fp8.hip (opaque bytes) + the N column scales behind it; K % 128 == 0, K <= kFp8TokenMaxK, N % 32 == 0
+int    linear_weight_prepare_int8(LinearWeight& w, const uint8_t* weight /*[K][N] int8*/, const float* scales /*[N] fp32, device*/, hipStream_t st);
+bool   int8_prepared(const LinearWeight& w);
+// sx = max(max|x|, 1e-7) / 127 per row, q = clamp(round_half_away(x / sx), -127, 127); the limits of launch_quant_fp8_token
+int    launch_quant_int8_token(uint8_t* xq, float* sx, const half_t* x, int ldx, int M, int K, hipStream_t st);
+// y = h((float(acc) * sx[m]) * sw[n]); workspace: 16 int32 slabs [M][N] (gemm_workspace_bytes(M, N, 16)) or nullptr = one slice.  A split
+// launch sums its raw int32 slabs in a reduce kernel of its own: y always holds the result, the same bits for every split
+int    launch_linear_int8(const LinearWeight& w, const uint8_t* xq, const float* sx, half_t* y, int ldy, int M, bool gated_silu, int splits,
+                          void* workspace, hipStream_t st);
 
 // ---- comm_p2p.hip: fused one-shot all-reduce + residual + RMSNorm over peer-mapped buffers (TM_COMM=native) ------------
 int launch_p2p_allreduce_norm(half_t* const* data, uint32_t* const* flags, int tp, int me, uint32_t* state, size_t tile,

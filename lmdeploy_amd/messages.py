@@ -193,7 +193,17 @@ class TurbomindEngineConfig:
     block-scaled FP4 matrix cores with their inputs quantised per row and group of 32 by the OCP MX rule (not claimed to match Quark's own
     rounding of the scale); lm_head, embeddings and norms stay fp16; KV-cache scales and `output_tensors` entries are read past, the cache
     follows quant_policy; mixture-of-experts models, tp > 1 and a `layer_quant_config` that changes a decoder linear are refused.
-    model_format='mxfp4' asks for that form (a dense `synthetic:` model is built in it).  Mistral / Mixtral
+    model_format='mxfp4' asks for that form (a dense `synthetic:` model is built in it).  INT8 W8A8 checkpoints -- int8 weights with one
+    scale per tensor / output channel, int8 activations -- load in two dialects: `quant_method: "smooth_quant"` as `lmdeploy lite
+    smooth_quant` writes it (`<proj>.weight` int8 [out][in] next to `<proj>.scale` fp32 [out, 1]; the reference serves it on its PyTorch
+    engine only) and `quant_method: "compressed-tensors"` with `format: "int-quantized"` (`<proj>.weight_scale`; symmetric weights per
+    channel / tensor, symmetric int8 activations per token / tensor, static `input_scale` read past), through the Llama (head_dim 64
+    and 128), InternLM2 / InternLM3 and dense Qwen2 / Qwen3 readers, tp > 1 included.  The four decoder linears run on the int8 matrix
+    cores: the input is quantised per token (absmax clamped at 1e-7, / 127, IEEE division, ties away from zero: the reference's
+    per_token_quant_int8), the int32 sum over all of K is exact and scaled once, so the result does not depend on the split-K.  Unlike
+    the reference, which fuses the quantiser into RMSNorm without the clamp (an all-zero row gives NaN there), the quantiser is a launch
+    of its own on the fp16 norm output.  lm_head, embeddings and norms stay fp16; mixture-of-experts models, asymmetric activations and
+    4-bit / grouped weights are refused.  model_format='int8' asks for that form (a dense `synthetic:` model is built in it).  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
     on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
     R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
@@ -269,10 +279,11 @@ class TurbomindEngineConfig:
             raise NotImplementedError('quant_policy=TURBO_QUANT (42) with tp > 1: the TurboQuant KV cache is built for tp = 1')
         if self.dtype == 'bfloat16':
             raise NotImplementedError('dtype=bfloat16: the AWQ path is fp16 (lmdeploy/turbomind/converter.py:40-48)')
-        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel', 'mxfp4'):
+        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel', 'mxfp4', 'int8'):
             raise NotImplementedError(f'model_format={self.model_format!r}: only "awq" (W4A16 g128), "fp8" (e4m3, 128x128 '
                                       f'block scales), "fp8_channel" (e4m3, one scale per tensor / output channel), "mxfp4" (W4A4: '
-                                      f'e2m1 weights and activations, one e8m0 scale per 32) and "hf" (fp16)')
+                                      f'e2m1 weights and activations, one e8m0 scale per 32), "int8" (W8A8: int8 weights with one '
+                                      f'scale per output channel, activations per token) and "hf" (fp16)')
         if self.cache_block_seq_len != 64:
             raise NotImplementedError('cache_block_seq_len must be 64')
         unsupported = {'dp': 1, 'cp': 1, 'ep': 1, 'attn_tp_size': None, 'attn_cp_size': None, 'attn_dp_size': None,

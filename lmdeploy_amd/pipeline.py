@@ -85,16 +85,19 @@ class Pipeline:
         if synthetic:
             self.model_cfg = checkpoint.ModelConfig(**SYNTHETIC[model_path.split(':', 1)[1]],
                                                     quantized=cfg.model_format != 'hf',
-                                                    weight_format={'hf': 'f16', 'fp8': 'fp8', 'fp8_channel': 'fp8', 'mxfp4': 'mxfp4'}.get(cfg.model_format, 'u4'),
+                                                    weight_format={'hf': 'f16', 'fp8': 'fp8', 'fp8_channel': 'fp8', 'mxfp4': 'mxfp4',
+                                                                   'int8': 'int8'}.get(cfg.model_format, 'u4'),
                                                     fp8_scale_mode=int(cfg.model_format == 'fp8_channel'))
+            if cfg.model_format == 'int8' and self.model_cfg.moe_experts:
+                raise NotImplementedError(f'{model_path} with model_format="int8": INT8 W8A8 is served for dense models only (int8 '
+                                          f'experts are not built)')
         else:
             self.model_cfg = checkpoint.read_config(model_path, cfg.tp)
             have = self.model_cfg.weight_format if self.model_cfg.quantized else 'f16'
             have += '_channel' if have == 'fp8' and self.model_cfg.fp8_scale_mode == 1 else ''
             # ('fp8' takes either scale form of an e4m3 checkpoint, 'fp8_channel' only the per-tensor / per-channel one)
-            if cfg.model_format in ('awq', 'fp8', 'fp8_channel', 'mxfp4') and have not in {'awq': ('u4',), 'fp8': ('fp8', 'fp8_channel'),
-                                                                                           'fp8_channel': ('fp8_channel',),
-                                                                                           'mxfp4': ('mxfp4',)}[cfg.model_format]:
+            accepts = {'awq': ('u4',), 'fp8': ('fp8', 'fp8_channel'), 'fp8_channel': ('fp8_channel',), 'mxfp4': ('mxfp4',), 'int8': ('int8',)}
+            if cfg.model_format in accepts and have not in accepts[cfg.model_format]:
                 raise ValueError(f'model_format="{cfg.model_format}" but the checkpoint\'s quantization_config says {have} '
                                  f'(lmdeploy/turbomind/converter.py:174-176)')
         # the TurboQuant KV cache (quant_policy=42): head_dim 128, full attention, tp = 1 -- refused here, by name, before any GPU work
@@ -106,7 +109,7 @@ class Pipeline:
         if per_dev > 1:     # ranks share a device (bring-up on a smaller box): their persistent two-shot all-reduce grids must fit TOGETHER
             os.environ.setdefault('TM_P2P_2SHOT_GRID', str(max(8, 256 // per_dev // 2)))     # (read by this rank's engine and inherited by the workers)
         self.engine = Engine.from_model_config(
-            self.model_cfg, weight_type={'u4': 0, 'f16': 1, 'fp8': 2, 'mxfp4': 3}[self.model_cfg.weight_format if self.model_cfg.quantized
+            self.model_cfg, weight_type={'u4': 0, 'f16': 1, 'fp8': 2, 'mxfp4': 3, 'int8': 4}[self.model_cfg.weight_format if self.model_cfg.quantized
                                                                         else 'f16'], tp=cfg.tp, rank=rank,
             device=devices[rank % len(devices)], max_batch_size=cfg.max_batch_size or 64, session_len=session_len,
             quant_policy=int(cfg.quant_policy), cache_max_entry_count=cfg.cache_max_entry_count,

@@ -3,7 +3,9 @@
 Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
 FP8 (e4m3: 128x128 block scales, `.weight_scale_inv`; or one scale per tensor / per output channel, `.weight_scale` -- AutoFP8
 `quant_method: "fp8"` without weight_block_size and compressed-tensors `float-quantized`; their static `input_scale` / `k_scale` /
-`v_scale` tensors are read past: activations are quantised per token, the KV cache follows quant_policy) or fp16 / bf16 weights
+`v_scale` tensors are read past: activations are quantised per token, the KV cache follows quant_policy), INT8 W8A8 (int8 codes with
+one scale per tensor / output channel: `quant_method: "smooth_quant"` with `.scale`, compressed-tensors `int-quantized` with
+`.weight_scale`; dense models; the INT8 table below) or fp16 / bf16 weights
 (dense linears and MoE experts alike), and for gpt-oss
 (GptOssForCausalLM: MXFP4 experts as published, or the bf16 experts transformers' save_pretrained writes; served zero-padded):
   * source models                    lmdeploy/turbomind/models/llama.py:45-101, internlm2.py:34-87, mixtral.py:57-106,
@@ -66,6 +68,7 @@ class ModelConfig:
     arch: str = 'llama'
     quantized: bool = True
     weight_format: str = 'u4'          # 'u4' (AWQ) | 'fp8' (block 128x128, or one scale per channel: fp8_scale_mode) | 'f16' | 'mxfp4' (W4A4)
+                                       # | 'int8' (W8A8: one scale per output channel, activations per token)
     fp8_scale_mode: int = 0            # weight_format 'fp8': 0 = 128x128 block scales, 1 = channel (per-tensor / per-channel checkpoints)
     moe_experts: int = 0               # Mixtral: num_local_experts
     moe_top_k: int = 0                 # num_experts_per_tok
@@ -250,30 +253,80 @@ def _read_gpt_oss(arch: str, c: dict, model_path: str, tp: int) -> ModelConfig:
 _CT_IGNORE_OK = ('lm_head', 're:.*lm_head', 're:.*block_sparse_moe.gate', 're:.*mlp.gate$', 're:.*mlp.shared_expert_gate$')
 
 
-def _check_compressed_tensors(q: dict):
-    """quantization_config of llm-compressor's FP8 exports (`format: float-quantized`): ONE config group, 8-bit float symmetric
-    weights with a per-tensor or per-channel scale, input activations absent or 8-bit float per token / per tensor.  Anything else
-    is refused with the offending key."""
+# The two INT8 W8A8 dialects (int8 weights with one scale per tensor / output channel, int8 activations quantised per token), every key
+# and accepted value in one place.  smooth_quant is what `lmdeploy lite smooth_quant` writes (lite/apis/smooth_quant.py:121-126, tensors
+# as pytorch/models/q_modules.py:97-98 declares them).  The compressed-tensors names (llm-compressor's *-quantized.w8a8 exports) were
+# written down from memory and could not be checked against a published checkpoint, like the QUARK table: a correction is one edit here.
+INT8 = {
+    'smooth_quant': dict(
+        dtype_key='quant_dtype', dtype='int8',           # float8_e4m3fn / float8_e5m2 (the reference's fp8 smooth-quant) are refused by name
+        skip_key='modules_to_not_convert', skip_ok=('lm_head',),
+        scale_suffix='.scale',                           # fp32 [out, 1] next to .weight int8 [out][in]
+    ),
+    'compressed-tensors': dict(
+        format='int-quantized',
+        weights=(('num_bits', (8,)), ('type', ('int',)), ('symmetric', (True,)), ('strategy', ('tensor', 'channel'))),
+        input_activations=(('num_bits', (8,)), ('type', ('int',)), ('symmetric', (True, None)), ('strategy', ('token', 'tensor'))),
+        scale_suffix='.weight_scale',                    # any float dtype, [out, 1] / [out] / [] / [1], next to .weight int8 [out][in]
+    ),
+}
+# what `format` of a compressed-tensors config selects: the element type both sides must name, and whether activations may be absent
+_CT_FORMATS = {
+    'float-quantized': dict(weights=(('num_bits', (8,)), ('type', ('float',)), ('symmetric', (True,)), ('strategy', ('tensor', 'channel'))),
+                            input_activations=(('num_bits', (8,)), ('type', ('float',)), ('strategy', ('token', 'tensor'))),
+                            weight_only_ok=True, codes='e4m3'),
+    'int-quantized': dict(weights=INT8['compressed-tensors']['weights'], input_activations=INT8['compressed-tensors']['input_activations'],
+                          weight_only_ok=False, codes='int8'),
+}
+
+
+def _refuse_int8_moe(arch: str, method: str):
+    if 'Mixtral' in arch or 'Moe' in arch or 'MoE' in arch:
+        raise NotImplementedError(f'{arch} with quant_method "{method}" (INT8 W8A8): served for dense models only (int8 experts are not '
+                                  f'built)')
+
+
+def _check_compressed_tensors(q: dict) -> str:
+    """quantization_config of llm-compressor's 8-bit exports -> 'float-quantized' (FP8: e4m3 weights) or 'int-quantized' (INT8 W8A8, the
+    INT8 table): ONE config group, 8-bit symmetric weights of the format's type with a per-tensor or per-channel scale, input activations
+    of the same type per token / per tensor (static scales are read past; float: may be absent; int: symmetric).  Anything else is
+    refused with the offending key."""
     def no(key, val, want):
         return NotImplementedError(f'compressed-tensors quantization_config: {key} = {val!r} is not served ({want})')
-    if q.get('format') != 'float-quantized':
-        raise no('format', q.get('format'), 'only "float-quantized": e4m3 weights with .weight_scale')
+    fmt = _CT_FORMATS.get(q.get('format'))
+    if fmt is None:
+        raise no('format', q.get('format'), 'only "float-quantized": e4m3 weights with .weight_scale, or "int-quantized": int8 W8A8')
     groups = q.get('config_groups') or {}
     if len(groups) != 1:
         raise no('config_groups', sorted(groups), 'exactly one config group')
     (gname, g), = groups.items()
     w = g.get('weights') or {}
-    for key, ok in (('num_bits', (8,)), ('type', ('float',)), ('symmetric', (True,)), ('strategy', ('tensor', 'channel'))):
+    for key, ok in fmt['weights']:
         if w.get(key) not in ok:
             raise no(f'config_groups.{gname}.weights.{key}', w.get(key), ' | '.join(map(repr, ok)))
     a = g.get('input_activations')
+    if a is None and not fmt['weight_only_ok']:
+        raise no(f'config_groups.{gname}.input_activations', a, 'int8 weights are served with int8 activations (W8A8) only')
     if a is not None:
-        for key, ok in (('num_bits', (8,)), ('type', ('float',)), ('strategy', ('token', 'tensor'))):
+        for key, ok in fmt['input_activations']:
             if a.get(key) not in ok:
-                raise no(f'config_groups.{gname}.input_activations.{key}', a.get(key), ' | '.join(map(repr, ok)))
+                raise no(f'config_groups.{gname}.input_activations.{key}', a.get(key), ' | '.join(repr(x) for x in ok if x is not None))
     for name in q.get('ignore') or []:
         if name not in _CT_IGNORE_OK and not name.endswith('lm_head'):
-            raise no('ignore', name, 'only lm_head and router gates may stay unquantised: every decoder linear is e4m3')
+            raise no('ignore', name, f'only lm_head and router gates may stay unquantised: every decoder linear is {fmt["codes"]}')
+    return q.get('format')
+
+
+def _check_smooth_quant(q: dict):
+    """quantization_config of `lmdeploy lite smooth_quant` (INT8['smooth_quant']): int8 only, nothing but lm_head left unconverted"""
+    S = INT8['smooth_quant']
+    if q.get(S['dtype_key'], S['dtype']) != S['dtype']:
+        raise NotImplementedError(f'smooth_quant quantization_config: {S["dtype_key"]} = {q.get(S["dtype_key"])!r} is not served (only '
+                                  f'"int8": the fp8 smooth-quant form is not built)')
+    for name in q.get(S['skip_key']) or []:
+        if name not in S['skip_ok']:
+            raise NotImplementedError(f'smooth_quant quantization_config: {S["skip_key"]} = {name!r} is not served (only lm_head may stay '
+                                      f'unconverted: every decoder linear is int8)')
 
 
 # Every key of a Quark MXFP4 export this reader depends on, in one place.  The layout was written down from memory of Quark's exports
@@ -381,8 +434,15 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                 raise NotImplementedError(f'{arch} with quant_method "quark" (MXFP4 W4A4) and tp = {tp}: not built (run with tp = 1)')
             wfmt = 'mxfp4'
         elif q.get('quant_method') == 'compressed-tensors':
-            _check_compressed_tensors(q)
-            wfmt, fp8_mode = 'fp8', 1
+            if _check_compressed_tensors(q) == INT8['compressed-tensors']['format']:
+                _refuse_int8_moe(arch, 'compressed-tensors')
+                wfmt = 'int8'
+            else:
+                wfmt, fp8_mode = 'fp8', 1
+        elif q.get('quant_method') == 'smooth_quant':
+            _check_smooth_quant(q)
+            _refuse_int8_moe(arch, 'smooth_quant')
+            wfmt = 'int8'
         elif q.get('quant_method') == 'fp8' and q.get('weight_block_size') is None:
             # AutoFP8 / neuralmagic *-FP8: one scale per tensor (`.weight_scale`).  head_dim 64 is fine: no scale block straddles a head
             for name in q.get('ignored_layers') or []:
@@ -400,7 +460,8 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
             wfmt = 'fp8'
         elif q.get('quant_method') != 'awq' or q.get('bits', 4) != 4 or q.get('group_size', 128) != 128:
             raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, block-128 FP8, per-tensor FP8, '
-                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92) or Quark MXFP4')
+                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92), Quark MXFP4 or '
+                                      f'INT8 W8A8 (smooth_quant, compressed-tensors int-quantized)')
         else:
             wfmt = 'u4'
     rope = RopeConfig(dim=D, base=float(c.get('rope_theta', 10000.0)))
@@ -567,7 +628,8 @@ class _Tensors:
 
 def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
     """-> {'q','s','z'} (uint8 [K,N], fp16 [K/g,N] x2), {'f8','bs'} (e4m3 codes [K,N], fp32 block scales
-    [K/128, ceil(N/128)]), {'f8','cs'} (e4m3 codes [K,N], one fp32 scale per output channel [N]) or {'w'} fp16 [K,N]."""
+    [K/128, ceil(N/128)]), {'f8','cs'} (e4m3 codes [K,N], one fp32 scale per output channel [N]), {'i8','cs'} (int8 codes [K,N] with
+    the same scales: both INT8 dialects) or {'w'} fp16 [K,N]."""
     if quantized and (prefix + QUARK['scale_suffix']) in t and t.get(prefix + QUARK['scale_suffix']).dtype == np.uint8:
         # Quark MXFP4 (e8m0 scale bytes; the FP8 forms below carry float scales): the checkpoint layout IS the engine's (output-major)
         w, s = t.get(prefix + QUARK['weight_suffix']), t.get(prefix + QUARK['scale_suffix'])
@@ -577,17 +639,20 @@ def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
         if (s == 255).any():
             raise ValueError(f'{prefix}{QUARK["scale_suffix"]}: scale byte 255 (the e8m0 NaN) is not accepted')
         return dict(blocks=np.ascontiguousarray(w), scales=np.ascontiguousarray(s))
-    if quantized and (prefix + '.weight_scale') in t:           # per-tensor ([] / [1]) or per-channel ([N] / [N, 1]) scale
+    sq = prefix + INT8['smooth_quant']['scale_suffix']
+    if quantized and ((prefix + '.weight_scale') in t or sq in t):  # per-tensor ([] / [1]) or per-channel ([N] / [N, 1]) scale
+        sname = sq if sq in t else prefix + '.weight_scale'
         w = t.get(prefix + '.weight')
-        if w.dtype != np.uint8:
-            raise ValueError(f'{prefix}.weight: expected float8_e4m3fn codes next to .weight_scale, got {w.dtype}')
+        if w.dtype not in (np.uint8, np.int8) or (sname == sq and w.dtype != np.int8):
+            raise ValueError(f'{prefix}.weight: expected float8_e4m3fn or int8 codes next to {sname.rsplit(".", 1)[1]}, got {w.dtype}')
         N = w.shape[0]
-        s = t.get(prefix + '.weight_scale').astype(np.float32)
+        s = t.get(sname).astype(np.float32)
         if s.shape not in ((), (1,), (N,), (N, 1)):
-            raise ValueError(f'{prefix}.weight_scale: shape {tuple(s.shape)} is neither a per-tensor ([] / [1]) nor a per-channel '
+            raise ValueError(f'{sname}: shape {tuple(s.shape)} is neither a per-tensor ([] / [1]) nor a per-channel '
                              f'([{N}] / [{N}, 1]) scale')
         # (.input_scale / .k_scale / .v_scale of static checkpoints are not read)
-        return dict(f8=np.ascontiguousarray(w.T), cs=np.ascontiguousarray(np.broadcast_to(s.reshape(-1), (N,))))
+        return {'i8' if w.dtype == np.int8 else 'f8': np.ascontiguousarray(w.T),
+                'cs': np.ascontiguousarray(np.broadcast_to(s.reshape(-1), (N,)))}
     if quantized and (prefix + '.weight_scale_inv') in t:       # FP8Format.normalize: transpose weight and scales
         w = t.get(prefix + '.weight')
         assert w.dtype == np.uint8, f'{prefix}.weight: expected float8_e4m3fn / uint8 codes, got {w.dtype}'
@@ -618,9 +683,7 @@ def _fuse_w1w3(w1: dict, w3: dict) -> dict:
     [w1 blocks | w3 blocks] -- the engine's layout for *.w1w3.scales (include/tm_mi355x.h, tm_moe_set_expert)."""
     if 'blocks' in w1:                                          # MXFP4, output-major: rows (2j, 2j + 1) = (gate_j, up_j)
         return {k: np.ascontiguousarray(interleave_gate_up(w1[k].T, w3[k].T).T) for k in w1}
-    if 'cs' in w1:
-        return dict(f8=interleave_gate_up(w1['f8'], w3['f8']), cs=interleave_gate_up(w1['cs'], w3['cs']))
-    if 'f8' in w1:
+    if 'f8' in w1 and 'bs' in w1:
         assert w1['f8'].shape[1] % 128 == 0, 'fp8 w1/w3: intermediate size must be a multiple of the 128-column block'
         return dict(f8=interleave_gate_up(w1['f8'], w3['f8']), bs=np.concatenate([w1['bs'], w3['bs']], axis=1), gated=True)
     return {kk: interleave_gate_up(w1[kk], w3[kk]) for kk in w1}
@@ -701,6 +764,9 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
             w2 = _linear(t, p + '.feed_forward.w2', cfg.quantized)
             n1 = t.get(p + '.attention_norm.weight')
             n2 = t.get(p + '.ffn_norm.weight')
+        if ('i8' in wo) != (getattr(cfg, 'weight_format', None) == 'int8'):       # the tensors must be what the quantization_config announced
+            raise ValueError(f'{p}: the o projection holds {"int8" if "i8" in wo else "no int8"} codes but the quantization_config '
+                             f'describes weight format {getattr(cfg, "weight_format", None)!r}')
         q = _map(q, lambda a: permute_qk_for_interleaved_rope(a, Hq, D))
         k = _map(k, lambda a: permute_qk_for_interleaved_rope(a, Hkv, D))
         ffn = moe if moe is not None else dict(w1w3=_fuse_w1w3(w1, w3), w2=w2)

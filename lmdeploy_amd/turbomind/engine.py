@@ -23,7 +23,7 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
     .beta_slow, .attention_factor: yarn / dynamic), group; optional moe_* (moe_shared_inter: Qwen2-MoE's shared expert;
     moe_expert_format 3 = MXFP4 experts, moe_act 1 = the gpt-oss activation, moe_bias = router and expert biases), attn_bias,
     qk_norm, window (sliding window of every layer, 0 = none), attn_sinks, attn_out_bias (o_proj bias), rope.truncate (YaRN: False =
-    fractional correction range), fp8_scale_mode (weight_type 2: 0 = 128x128 block scales, 1 = one scale per output channel); weight_type 3 = MXFP4 W4A4 dense linears (tp = 1, no experts).  hidden / inter that are no multiple of 128 (gpt-oss: 2880) are handed over as the next multiple,
+    fractional correction range), fp8_scale_mode (weight_type 2: 0 = 128x128 block scales, 1 = one scale per output channel); weight_type 3 = MXFP4 W4A4 dense linears (tp = 1, no experts), 4 = INT8 W8A8 dense linears (no experts).  hidden / inter that are no multiple of 128 (gpt-oss: 2880) are handed over as the next multiple,
     the width the loader pads every tensor to (loader.pad_model_weights), with hidden_valid = the model's own hidden size."""
     r = cfg.rope
     Hp, Ip = -(-cfg.hidden // 128) * 128, -(-cfg.inter // 128) * 128

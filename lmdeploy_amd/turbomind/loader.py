@@ -134,15 +134,16 @@ def _shard_linear(lin: dict, kind: str, tp: int, rank: int, group: int, col_slic
             raise ValueError(f'MXFP4 dense linears do not shard over tp = {tp}: W4A4 is served with tp = 1')
         return lin
     if 'cs' in lin:
-        # e4m3 codes [K,N] + one fp32 scale per output channel [N]: column shards slice the scales with their columns (whole
-        # (gate, up) pairs for w1w3: its slice bounds are even), row shards keep them whole
-        f8, cs = lin['f8'], lin['cs']
+        # e4m3 ('f8') or int8 ('i8') codes [K,N] + one fp32 scale per output channel [N]: column shards slice the scales with their
+        # columns (whole (gate, up) pairs for w1w3: its slice bounds are even), row shards keep them whole
+        ck = 'i8' if 'i8' in lin else 'f8'
+        f8, cs = lin[ck], lin['cs']
         if kind == 'col':
-            return {'f8': np.concatenate([f8[:, lo:hi] for lo, hi in col_slices], axis=1),
+            return {ck: np.concatenate([f8[:, lo:hi] for lo, hi in col_slices], axis=1),
                     'cs': np.concatenate([cs[lo:hi] for lo, hi in col_slices])}
         K = f8.shape[0]
-        assert K % tp == 0 and (K // tp) % 128 == 0, 'fp8 row-parallel shards must keep whole 128-row k-blocks'
-        return {'f8': f8[rank * (K // tp):(rank + 1) * (K // tp)], 'cs': cs}
+        assert K % tp == 0 and (K // tp) % 128 == 0, 'fp8 / int8 row-parallel shards must keep whole 128-row k-blocks'
+        return {ck: f8[rank * (K // tp):(rank + 1) * (K // tp)], 'cs': cs}
     if 'f8' in lin:
         # e4m3 codes [K,N] + fp32 scales of 128x128 blocks [K/128, ceil(N/128)]: a shard must keep whole blocks
         f8, bs = lin['f8'], lin['bs']
@@ -186,6 +187,9 @@ def _emit(slots: dict, prefix: str, lin: dict):
     elif 'f8' in lin:        # e4m3 codes [K,N] + fp32 128x128 block scales (lmdeploy/turbomind/weight_format.py:349-393) or [N] channel scales
         slots[prefix + '.weight'] = np.ascontiguousarray(lin['f8'], dtype=np.uint8)
         slots[prefix + '.scales'] = np.ascontiguousarray(lin['cs'] if 'cs' in lin else lin['bs'], dtype=np.float32)
+    elif 'i8' in lin:        # int8 codes [K,N] + [N] channel scales (W8A8)
+        slots[prefix + '.weight'] = np.ascontiguousarray(lin['i8'], dtype=np.int8)
+        slots[prefix + '.scales'] = np.ascontiguousarray(lin['cs'], dtype=np.float32)
     else:
         slots[prefix + '.weight'] = np.ascontiguousarray(lin['w'], dtype=np.float16)
 
