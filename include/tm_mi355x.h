@@ -274,6 +274,15 @@ typedef struct tm_linear tm_linear;
 enum { TM_WEIGHT_U4 = 0, TM_WEIGHT_F16 = 1, TM_WEIGHT_FP8 = 2, TM_WEIGHT_MXFP4 = 3 /* experts weight-only (tm_moe); dense linears W4A4 (tm_linear_prepare_mxfp4) */,
        TM_WEIGHT_I8 = 4 /* dense linears W8A8 (tm_linear_prepare_int8); never experts */ };
 int tm_linear_create(tm_linear** out, int in_features, int out_features, int weight_type, int group_size);
+/* TM_WEIGHT_U4 comes in two group sizes.  group_size 128: the AWQ / GPTQ / compressed-tensors g128 form on the decode, prefill and
+ * general kernels.  group_size 32 (compressed-tensors pack-quantized g32): a format of its own on gemm_u4_g32.hip
+ * (v_mfma_f32_32x32x16_f16; K % 128 == 0, N % 32 == 0, image K N / 2 + K N / 8 bytes below 2^31) -- the same three parts with scales /
+ * zeros [K/32][N], the same arithmetic w = h(fma(h(q), s, h(-z*s))), fp32 accumulation, one rounding.  Its tm_linear_forward picks its
+ * own tile (nt = waves = 0; M <= 32 / <= 64 / 128-row tiles) and takes `splits` (0 = its heuristic, evened out over the k-blocks);
+ * a split launch is reduced before the call returns, so y always holds the finished fp16 result, and tm_linear_residual_norm / the
+ * folded-norm entries refuse such a handle.  tm_linear_dequant_f16 reads its image back.  Any other u4 group_size is refused here by
+ * name (before: accepted here, refused by tm_linear_prepare); tm_moe_create has no group parameter (experts: 128), and an engine with
+ * group_size 32 and moe_experts > 0 is refused at creation. */
 /* Boundary ("TM") layout, device pointers: qweight int32 [K][N/8] (nibble j of word c = column 8c+j,
  * lmdeploy/turbomind/weight_format.py:63-74), scales / zeros fp16 [K/g][N].  For TM_WEIGHT_F16: weight fp16
  * [K][N], scales = zeros = NULL.  For TM_WEIGHT_FP8 (lmdeploy/turbomind/weight_format.py:349-393): weight = e4m3 bytes
@@ -566,7 +575,7 @@ typedef struct tm_model_config {
      * does not exceed it runs exactly as rope_type 0) */
     int   rope_max_position_embeddings;
     float rope_yarn_beta_fast, rope_yarn_beta_slow, rope_yarn_attention_factor;
-    int   group_size;   /* 128 */
+    int   group_size;   /* 128; u4 weights: 128 or -- dense models, gemm_u4_g32.hip -- 32 */
     int   weight_type;  /* TM_WEIGHT_U4 (AWQ), TM_WEIGHT_F16, TM_WEIGHT_FP8, TM_WEIGHT_MXFP4 or TM_WEIGHT_I8 for the decoder linears; lm_head is fp16.
                          * TM_WEIGHT_MXFP4 (W4A4, tm_linear_prepare_mxfp4's form): dense models at tp = 1, any head_dim the engine serves;
                          * slots "*.blocks" uint8 [N][K/2] and "*.scales" uint8 [N][K/32] for w_qkv (q | k | v rows stacked), wo, w1w3

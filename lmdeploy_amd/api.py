@@ -14,8 +14,9 @@ def pipeline(model_path: str,
              speculative_config=None,
              allowed_media_domains=None,
              **kwargs) -> Pipeline:
-    """Create a pipeline for inference.  `model_path` is an HF checkpoint directory (Llama / InternLM2, AWQ W4A16
-    group 128 or fp16) or `synthetic:<llama3_8b|internlm2_1_8b|internlm2_20b|llama3_70b|tiny|tiny_window|tiny_moe>` for random weights
+    """Create a pipeline for inference.  `model_path` is an HF checkpoint directory (Llama / InternLM2 / Qwen ...; W4A16 as AWQ
+    or GPTQ group 128 or compressed-tensors pack-quantized group 128 / 32 -- the dialect is read from config.json --, or fp16; the other
+    formats: TurbomindEngineConfig) or `synthetic:<llama3_8b|internlm2_1_8b|internlm2_20b|llama3_70b|tiny|tiny_window|tiny_moe>` for random weights
     with the real shapes."""
     if allowed_media_domains is not None:
         raise NotImplementedError('multimodal inputs are outside the MI355X hot path')

@@ -471,6 +471,13 @@ int tm_linear_create(tm_linear** out, int in_features, int out_features, int wei
                    "int8 linear " + std::to_string(in_features) + " x " + std::to_string(out_features)
                        + ": K % 128 == 0, K <= 32768 and N % 32 == 0");
     }
+    if (weight_type == TM_WEIGHT_U4) {
+        TM_REQUIRE(group_size == 128 || group_size == 32,
+                   "u4 linear: group_size " + std::to_string(group_size) + " is not served (128: the AWQ / GPTQ kernels; 32: gemm_u4_g32.hip)");
+        TM_REQUIRE(group_size == 128 || (in_features % 128 == 0 && out_features % 32 == 0 && g32_bytes(in_features, out_features) < ((size_t)1 << 31)),
+                   "u4 group-32 linear " + std::to_string(in_features) + " x " + std::to_string(out_features)
+                       + ": K % 128 == 0, N % 32 == 0 and an image below 2^31 bytes");
+    }
     if (weight_type == TM_WEIGHT_MXFP4) {
         TM_REQUIRE(group_size == 32, "mxfp4 dense linear: group_size 32");
         TM_REQUIRE(in_features % 128 == 0 && out_features % 32 == 0 && (size_t)in_features * out_features / 2 < ((size_t)1 << 31),
@@ -487,7 +494,7 @@ int tm_linear_create(tm_linear** out, int in_features, int out_features, int wei
     l->w.N      = out_features;
     l->w.group  = group_size;
     l->w.type   = weight_type;
-    l->w.fmt    = linear_format(weight_type, 0, false);
+    l->w.fmt    = linear_format(weight_type, 0, false, group_size);
     *out        = l;
     return 0;
 }
@@ -499,7 +506,7 @@ int tm_linear_prepare(tm_linear* w, const void* weight, const void* scales, cons
     TM_REQUIRE(w->w.type != TM_WEIGHT_I8, "int8 linear: tm_linear_prepare_int8 takes its codes and column scales");
     TM_REQUIRE(w->w.type != TM_WEIGHT_U4 || (scales && zeros), "u4 weights need scales and zeros");
     TM_REQUIRE(w->w.type != TM_WEIGHT_FP8 || scales, "fp8 weights need their 128x128 block scales");
-    return prepare_as(w->w, linear_format(w->w.type, 0, false), false, weight, scales, zeros, st);
+    return prepare_as(w->w, linear_format(w->w.type, 0, false, w->w.group), false, weight, scales, zeros, st);
 }
 
 size_t tm_linear_workspace(const tm_linear* w, int M)
@@ -517,6 +524,9 @@ int tm_linear_dequant_f16(const tm_linear* w, void* out_nk, tm_stream_t st)
     if (w->w.type == TM_WEIGHT_MXFP4) {
         return launch_dequant_p4_f16((half_t*)out_nk, w->w, (hipStream_t)st);
     }
+    if (w->w.fmt == LinearFormat::U4_G32) {
+        return launch_dequant_g32_f16((half_t*)out_nk, w->w, (hipStream_t)st);
+    }
     return launch_dequant_p32_f16((half_t*)out_nk, w->w, (hipStream_t)st);
 }
 
@@ -529,6 +539,10 @@ int tm_linear_forward(const tm_linear* w, const void* x, int ldx, void* y, int l
                "channel-scaled fp8 weights have no weight-only image: tm_linear_forward_fp8 runs them");
     TM_REQUIRE(w->w.fmt != LinearFormat::MXFP4_DENSE, "mxfp4 dense linears have no weight-only arm: tm_linear_forward_mxfp4 runs them");
     TM_REQUIRE(w->w.fmt != LinearFormat::INT8_CHANNEL, "int8 linears have no weight-only arm: tm_linear_forward_int8 runs them");
+    if (w->w.fmt == LinearFormat::U4_G32) {  // one tile per M class: nt / waves do not apply; splits = 0 is the launcher's heuristic
+        TM_REQUIRE(nt <= 0 && waves <= 0, "u4 group-32 linear: the kernel picks its own tile (nt = 0, waves = 0); splits may be given");
+        return launch_linear_u4_g32(w->w, (const half_t*)x, ldx, (half_t*)y, ldy, M, gated_silu != 0, splits, (float*)workspace, (hipStream_t)st);
+    }
     GemmConfig cfg = gemm_pick_config(w->w, M);  // (workspace: tm_linear_workspace(w, M) bytes)
     if (nt > 0) {
         cfg.nt = nt;
@@ -582,6 +596,7 @@ int tm_linear_residual_norm(const tm_linear* w, const void* x, int ldx, void* y,
                             int shape, int splits, void* workspace, tm_stream_t st)
 {
     TM_REQUIRE(w && x && y && resid && norm_w && workspace, "null pointer");
+    TM_REQUIRE(w->w.fmt != LinearFormat::U4_G32, "u4 group-32 linears always reduce themselves: no fused residual-norm arm (tm_linear_forward runs them)");
     const int N = w->w.N;
     GemmConfig cfg = gemm_pick_config(w->w, M);
     if (shape >= 0) {

@@ -159,7 +159,7 @@ static void add_linear(tm_engine* e, LinearSlots& l, const std::string& prefix, 
     l.w.N     = N;
     l.w.group = e->cfg.model.group_size;
     l.w.type  = type;
-    l.w.fmt   = linear_format(type, e->cfg.model.fp8_scale_mode, expert);
+    l.w.fmt   = linear_format(type, e->cfg.model.fp8_scale_mode, expert, l.w.group);
     l.w.gated = gated;
     const LinearStaging sg = linear_staging(l.w.fmt, K, N, l.w.group);
     for (int i = 0; i < sg.n; ++i) {
@@ -181,6 +181,12 @@ static int check_linear_images(const tm_model_config& m, int tp)
                {"shared w1w3", m.hidden, 2 * shared, m.weight_type}, {"shared w2", shared, m.hidden, m.weight_type}};
     for (const auto& l : lin) {
         if (l.K == 0 || l.N == 0) {  // no shared expert
+            continue;
+        }
+        if (l.type == TM_WEIGHT_U4 && m.group_size == 32) {  // no general-kernel image: the G32 image of gemm_u4_g32.hip
+            TM_REQUIRE(l.K % 128 == 0 && l.N % 32 == 0 && g32_bytes(l.K, l.N) < kGeneralImageLimit,
+                       std::string(l.name) + " " + std::to_string(l.K) + " x " + std::to_string(l.N)
+                           + ": a u4 group-32 linear needs K % 128 == 0, N % 32 == 0 and an image below 2^31 bytes");
             continue;
         }
         if (l.type == TM_WEIGHT_I8) {  // no general-kernel image: the P8 image + column scales of gemm_int8.hip, same limit
@@ -262,7 +268,13 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.head_dim == 64 || m.head_dim == 128, "head_dim must be 64 or 128");
     TM_REQUIRE(m.head_dim == 128 || !m.qk_norm, "qk_norm (per-head q/k RMSNorm) needs head_dim 128: not built for head_dim 64");
     TM_REQUIRE(m.attn_window >= 0, "attn_window must be >= 0 (0 = full attention)");
-    TM_REQUIRE(m.group_size == 128, "AWQ group size must be 128");
+    TM_REQUIRE(m.group_size == 128 || (m.group_size == 32 && m.weight_type == TM_WEIGHT_U4),
+               "group_size " + std::to_string(m.group_size) + " is not served: u4 weights come in groups of 128 or -- dense models -- 32, every "
+               "other weight_type is created with 128");
+    if (m.weight_type == TM_WEIGHT_U4 && m.group_size == 32) {  // gemm_u4_g32.hip: dense linears only
+        TM_REQUIRE(m.moe_experts == 0, "group_size 32 with moe_experts > 0 is not built: the group-32 u4 kernel serves dense linears only");
+        TM_REQUIRE(m.hidden_valid == 0 || m.hidden_valid == m.hidden, "group_size 32 with padded widths (hidden_valid) is not built");
+    }
     TM_REQUIRE(c->tp >= 1 && c->rank >= 0 && c->rank < c->tp, "0 <= rank < tp");
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
     TM_REQUIRE(m.kv_heads % c->tp == 0 || c->tp % m.kv_heads == 0, "kv_heads vs tp");
@@ -708,7 +720,7 @@ int tm_engine_start(tm_engine* e)
     e->scratch.ws = e->d_gemm_ws, e->scratch.ws_bytes = e->gemm_ws_bytes, e->scratch.rows = e->max_tokens;
     // a dense format that needs its GEMM input quantised (the engine brings buffers to no other): codes and scales of ONE GEMM input (the
     // widest K of a dense linear), written by the quantiser in front of every dense GEMM -- sized here, nothing is allocated in a forward
-    if (const ActQuant q = linear_act_quant(linear_format(m.weight_type, m.fp8_scale_mode, false), false); q != ActQuant::NONE) {
+    if (const ActQuant q = linear_act_quant(linear_format(m.weight_type, m.fp8_scale_mode, false, m.group_size), false); q != ActQuant::NONE) {
         const size_t wide_k = std::max(std::max(e->hidden, e->q_heads * e->D), std::max(e->inter, e->shared_inter));
         const bool   mx     = q == ActQuant::MXFP4_ROW32;  // e2m1 pairs + an e8m0 byte per 32 channels; else e4m3 / int8 codes + one fp32 scale per token
         TM_HIP_CHECK(hipMalloc(&e->scratch.xq, T * (mx ? wide_k / 2 : wide_k)));

@@ -841,8 +841,11 @@ void setup_decode(tm_engine* e, int batch)
     // decode path -- kv_rope_store with the row offsets, then plain decode attention
     // head_dim 64: no MFMA kernel, so no fused prologue either -- the same unfused path
     // a sliding window or attention sinks (e->windowed): the VALU kernel's variant serves them, the same unfused path for every layer
+    // u4 weights in groups of 32 (gemm_u4_g32.hip): the linear always finishes its own fp16 rows, no slab reaches the attention kernel -- such
+    // a model runs kv_rope_store, then plain decode attention, the same unfused path
+    const bool g32   = e->cfg.model.weight_type == TM_WEIGHT_U4 && e->cfg.model.group_size == 32;
     e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse))
-                  && !e->d_rope_row0 && e->D == 128 && !e->windowed;
+                  && !e->d_rope_row0 && e->D == 128 && !e->windowed && !g32;
 }
 
 // Chunked prefill of `batch` sequences into the batch slots [slot0, slot0 + batch): whole sequences,

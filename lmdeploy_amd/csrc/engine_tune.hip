@@ -338,7 +338,7 @@ static int tune_aux_gemms(tm_engine* e, int M, bool verbose)
                     continue;
                 }
                 const LinearWeight* w = r.which == 0 ? &L.qkv.w : r.which == 1 ? &L.wo.w : r.which == 2 ? &L.w13.w : &L.w2.w;
-                if (!dec32_supported(*w, M) && linear_act_quant(w->fmt, e->scratch.xq != nullptr) == ActQuant::NONE) {  // (a quantised input: one tile choice per M class, nothing to time)
+                if (!dec32_supported(*w, M) && !linear_own_tiling(w->fmt, e->scratch.xq != nullptr)) {  // (a quantised input, u4 group 32: one tile choice per M class, nothing to time)
                     ws.push_back(w);
                 }
             }

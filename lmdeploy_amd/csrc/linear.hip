@@ -55,6 +55,9 @@ const FormatRow kFormats[] = {  // index = LinearFormat
     // INT8_CHANNEL: int8 [K][N] + one fp32 scale per output column (fused linears as FP8_CHANNEL); W8A8 on the int8 matrix cores
     {{{"weight", PK::I8, e4m3_codes}, {"scales", PK::F32_SCALES, col_scales}},
      ActQuant::INT8_TOKEN, kNoI8Act, [](int K, int N) { return (size_t)K * N + (size_t)N * 4; }},
+    // U4_G32: the parts of U4 sized with group 32 (compressed-tensors pack-quantized); weight-only on a kernel of its own (gemm_u4_g32.hip)
+    {{{"qweight", PK::AWQ_QWEIGHT, [](int K, int N, int) { return (size_t)K * N / 2; }}, {"scales", PK::AWQ_SCALES, sz_u4}, {"zeros", PK::AWQ_ZEROS, sz_u4}},
+     ActQuant::NONE, nullptr, [](int K, int N) { return (size_t)K * N / 2 + (size_t)(K / 32) * N * 4; }},
 };
 static_assert(sizeof(kFormats) / sizeof(kFormats[0]) == (size_t)LinearFormat::COUNT, "one row per LinearFormat, in its order");
 
@@ -62,12 +65,13 @@ const FormatRow& row_of(LinearFormat fmt) { return kFormats[(int)fmt]; }
 
 }  // namespace
 
-LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert)
+LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert, int group)
 {
     return weight_type == TM_WEIGHT_F16   ? LinearFormat::F16 :
            weight_type == TM_WEIGHT_FP8   ? (fp8_scale_mode == 1 ? LinearFormat::FP8_CHANNEL : LinearFormat::FP8_BLOCK) :
            weight_type == TM_WEIGHT_MXFP4 ? (expert ? LinearFormat::MXFP4_EXPERT : LinearFormat::MXFP4_DENSE) :
            weight_type == TM_WEIGHT_I8    ? LinearFormat::INT8_CHANNEL :
+           group == 32                    ? LinearFormat::U4_G32 :
                                             LinearFormat::U4;
 }
 
@@ -100,12 +104,18 @@ int linear_weight_prepare(LinearWeight& w, const void* const* p, hipStream_t st,
         case LinearFormat::MXFP4_EXPERT: return linear_weight_prepare_mxfp4(w, (const uint8_t*)p[0], (const uint8_t*)p[1], st);
         case LinearFormat::MXFP4_DENSE: return linear_weight_prepare_mxfp4_dense(w, (const uint8_t*)p[0], (const uint8_t*)p[1], st);
         case LinearFormat::INT8_CHANNEL: return linear_weight_prepare_int8(w, (const uint8_t*)p[0], (const float*)p[1], st);
+        case LinearFormat::U4_G32: return linear_weight_prepare_u4_g32(w, (const int32_t*)p[0], (const half_t*)p[1], (const half_t*)p[2], st);
         default: break;
     }
     TM_REQUIRE(false, "internal: linear format without a prepare case");
 }
 
 bool linear_weight_prepared(const LinearWeight& w) { return w.packed || w.packed32 || w.packed8; }
+
+bool linear_own_tiling(LinearFormat fmt, bool have_act_buffers)
+{
+    return fmt == LinearFormat::U4_G32 || linear_act_quant(fmt, have_act_buffers) != ActQuant::NONE;
+}
 
 void linear_weight_take(LinearWeight& dst, LinearWeight& src)
 {
@@ -122,7 +132,11 @@ int linear_forward(const LinearWeight& w, const half_t* x, int ldx, half_t* y, i
     const bool     have = s.xq && s.sx && M <= s.rows;
     const ActQuant q    = linear_act_quant(w.fmt, have);
     int            nslab = 1, rc;
-    if (q == ActQuant::NONE) {
+    if (w.fmt == LinearFormat::U4_G32) {
+        // one tile per M class, the launcher's own split-K and reduce: y holds the finished result, nothing is deferred
+        rc = launch_linear_u4_g32(w, x, ldx, y, ldy, M, gated_silu, s.splits, gemm_workspace_bytes(M, w.N, 16) <= s.ws_bytes ? s.ws : nullptr, st);
+    }
+    else if (q == ActQuant::NONE) {
         GemmConfig cfg = gemm_pick_config(w, M);
         cfg.splits     = gemm_workspace_bytes(M, w.N, cfg.splits) > s.ws_bytes ? 1 : cfg.splits;
         cfg.tickets    = s.tickets;

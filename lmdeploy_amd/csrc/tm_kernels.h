@@ -162,7 +162,7 @@ int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 // ---- gemm_w4a16.hip ---------------------------------------------------------------------
 // What a linear IS, resolved once where it is declared from (weight_type, fp8_scale_mode, expert?) by linear_format(): the key of the
 // format table in linear.hip, which owns everything that depends on it (staging parts, repack, activation quantisation, run, bytes).
-enum class LinearFormat : int { U4, F16, FP8_BLOCK, FP8_CHANNEL, MXFP4_EXPERT, MXFP4_DENSE, INT8_CHANNEL, COUNT };
+enum class LinearFormat : int { U4, F16, FP8_BLOCK, FP8_CHANNEL, MXFP4_EXPERT, MXFP4_DENSE, INT8_CHANNEL, U4_G32, COUNT };
 struct LinearWeight {
     int       K = 0, N = 0, group = 128;
     LinearFormat fmt = LinearFormat::U4;
@@ -189,6 +189,8 @@ struct LinearWeight {
     // fp8 only, channel-scaled weights (linear_weight_prepare_fp8_channel): the N fp32 column scales, stored behind the last
     // P8 unit of `packed8` (not owned).  Such a weight has no `packed` / `sz` image: it runs on the fp8 matrix cores only.
     // int8 (linear_weight_prepare_int8): the same P8 image and column scales, run on the int8 matrix cores only.
+    // u4 with groups of 32 (U4_G32, linear_weight_prepare_u4_g32): the "G32" image of gemm_u4_g32.hip lives here too (2560-byte units of
+    // 32 columns x 128 k with their four (s, -z*s) pairs per column); such a weight has no `packed` / `packed32` / `sz` image
     float*    cscale = nullptr;
     // u4 only, optional (linear_weight_build_f16_image; the engine builds it for dense linears unless TM_PREFILL_F16_IMAGE=0): the fp16
     // [N][K] image of the dequantised weights -- bit for bit the operand the fused tiles build on chip -- that prefill-sized forwards
@@ -248,7 +250,7 @@ int launch_linear(const LinearWeight& w, const half_t* x, int ldx, half_t* y, in
                   GemmConfig cfg, float* workspace, bool defer_reduce, int* slabs, hipStream_t st);
 
 // ---- linear.hip: the one place that knows the linear formats (a table with one row per LinearFormat) --------------
-LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert);
+LinearFormat linear_format(int weight_type, int fp8_scale_mode, bool expert, int group = 128);  // (group: u4 only -- 32 is a format of its own)
 enum class PartKind : int { AWQ_QWEIGHT, AWQ_SCALES, AWQ_ZEROS, F16, E4M3, F32_SCALES, E2M1, UE8M0, I8 };  // what a staging part holds
 struct LinearStaging {  // the parts a checkpoint fills for one linear, in the order linear_weight_prepare takes them
     int         n = 0;
@@ -265,6 +267,8 @@ ActQuant linear_act_quant(LinearFormat fmt, bool have_act_buffers);
 // engine's dense linears; ignored by every other format): p32_only as linear_weight_prepare_u4, f16_image = linear_weight_build_f16_image too
 int    linear_weight_prepare(LinearWeight& w, const void* const* parts, hipStream_t st, bool p32_only = false, bool f16_image = false);
 bool   linear_weight_prepared(const LinearWeight& w);
+// formats whose launcher picks its own tile per M class: nothing for the measured dispatch tables to time (quantised inputs, U4_G32)
+bool   linear_own_tiling(LinearFormat fmt, bool have_act_buffers);
 void   linear_weight_take(LinearWeight& dst, LinearWeight& src);  // dst owns src's images, src is left unprepared
 size_t linear_weight_bytes(const LinearWeight& w);  // codes + scales of a prepared weight as the checkpoint carries them (0: not prepared)
 struct LinearScratch {
@@ -380,6 +384,19 @@ int    launch_quant_int8_token(uint8_t* xq, float* sx, const half_t* x, int ldx,
 // launch sums its raw int32 slabs in a reduce kernel of its own: y always holds the result, the same bits for every split
 int    launch_linear_int8(const LinearWeight& w, const uint8_t* xq, const float* sx, half_t* y, int ldy, int M, bool gated_silu, int splits,
                           void* workspace, hipStream_t st);
+
+// ---- gemm_u4_g32.hip: W4A16 with quantisation groups of 32 along K on v_mfma_f32_32x32x16_f16 (dense linears) ---
+// the "G32" image: 2560-byte units of 32 columns x 128 k (codes + four (s, -z*s) pairs per column); K % 128 == 0, N % 32 == 0, image < 2^31 bytes
+size_t g32_bytes(int K, int N);
+int    linear_weight_prepare_u4_g32(LinearWeight& w, const int32_t* qweight /*[K][N/8]*/, const half_t* scales /*[K/32][N]*/,
+                                    const half_t* zeros, hipStream_t st);
+bool   u4_g32_prepared(const LinearWeight& w);
+int    launch_dequant_g32_f16(half_t* out_nk /*[N][K]*/, const LinearWeight& w, hipStream_t st);
+int    u4_g32_splits(int K, int N, int M, int want);  // the split-K depth launch_linear_u4_g32 runs for `want` (0: its heuristic), given a workspace
+// workspace: 16 fp32 slabs [M][N] (gemm_workspace_bytes(M, N, 16)) or nullptr = one slice.  A split launch is reduced by the launcher:
+// y always holds the finished fp16 result
+int    launch_linear_u4_g32(const LinearWeight& w, const half_t* x, int ldx, half_t* y, int ldy, int M, bool gated_silu, int splits,
+                            float* workspace, hipStream_t st);
 
 // ---- comm_p2p.hip: fused one-shot all-reduce + residual + RMSNorm over peer-mapped buffers (TM_COMM=native) ------------
 int launch_p2p_allreduce_norm(half_t* const* data, uint32_t* const* flags, int tp, int me, uint32_t* state, size_t tile,

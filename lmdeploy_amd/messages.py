@@ -203,7 +203,17 @@ class TurbomindEngineConfig:
     per_token_quant_int8), the int32 sum over all of K is exact and scaled once, so the result does not depend on the split-K.  Unlike
     the reference, which fuses the quantiser into RMSNorm without the clamp (an all-zero row gives NaN there), the quantiser is a launch
     of its own on the fp16 norm output.  lm_head, embeddings and norms stay fp16; mixture-of-experts models, asymmetric activations and
-    4-bit / grouped weights are refused.  model_format='int8' asks for that form (a dense `synthetic:` model is built in it).  Mistral / Mixtral
+    grouped 8-bit weights are refused.  model_format='int8' asks for that form (a dense `synthetic:` model is built in it).  W4A16
+    checkpoints load in three dialects, told apart by config.json: AWQ (`quant_method: "awq"`, group 128), GPTQ (`quant_method: "gptq"`:
+    bits 4, group_size 128, sym true, desc_act false; `<proj>.qweight` int32 [K/8][N], `.scales`, `.qzeros` int32 [K/g][N/8] holding
+    zero - 1, or the zero itself when `checkpoint_format` / `format` says "gptq_v2"; a `.g_idx` other than k // g is act-order and refused)
+    and compressed-tensors `format: "pack-quantized"` (one config group of 4-bit int group weights, group_size 128 or 32, static, no
+    act-order, no input activations; `<proj>.weight_packed` int32 [N][K/8], `.weight_scale` fp16 / bf16 [N][K/g], `.weight_zero_point`
+    for asymmetric weights, zeros of 8 otherwise).  All three become the same u4 codes / scales / zeros, so at group 128 they run on the
+    AWQ kernels through every reader that serves AWQ, MoE experts and tp > 1 included; group 32 runs dense models on an MFMA kernel of its
+    own (gemm_u4_g32.hip), and is refused for mixture-of-experts models.  model_format='compressed-tensors' (the reference's name) asks
+    for a pack-quantized checkpoint; model_format='gptq' is not a value of this field (a GPTQ directory loads with model_format=None),
+    and model_format='awq' on a GPTQ or compressed-tensors checkpoint is the reference's mismatch error.  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
     on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
     R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
@@ -279,8 +289,10 @@ class TurbomindEngineConfig:
             raise NotImplementedError('quant_policy=TURBO_QUANT (42) with tp > 1: the TurboQuant KV cache is built for tp = 1')
         if self.dtype == 'bfloat16':
             raise NotImplementedError('dtype=bfloat16: the AWQ path is fp16 (lmdeploy/turbomind/converter.py:40-48)')
-        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel', 'mxfp4', 'int8'):
-            raise NotImplementedError(f'model_format={self.model_format!r}: only "awq" (W4A16 g128), "fp8" (e4m3, 128x128 '
+        if self.model_format not in (None, 'awq', 'hf', 'fp8', 'fp8_channel', 'mxfp4', 'int8', 'compressed-tensors'):
+            raise NotImplementedError(f'model_format={self.model_format!r}: only "awq" (W4A16 g128), "compressed-tensors" (a '
+                                      f'pack-quantized W4A16 checkpoint, g128 or g32; a GPTQ checkpoint loads with model_format=None), '
+                                      f'"fp8" (e4m3, 128x128 '
                                       f'block scales), "fp8_channel" (e4m3, one scale per tensor / output channel), "mxfp4" (W4A4: '
                                       f'e2m1 weights and activations, one e8m0 scale per 32), "int8" (W8A8: int8 weights with one '
                                       f'scale per output channel, activations per token) and "hf" (fp16)')

@@ -95,8 +95,11 @@ class Pipeline:
             self.model_cfg = checkpoint.read_config(model_path, cfg.tp)
             have = self.model_cfg.weight_format if self.model_cfg.quantized else 'f16'
             have += '_channel' if have == 'fp8' and self.model_cfg.fp8_scale_mode == 1 else ''
+            # (the 4-bit dialects are kinds of their own: 'awq' does not take a GPTQ or compressed-tensors checkpoint, nor the reverse)
+            have = {'gptq': 'gptq', 'compressed-tensors': 'compressed-tensors'}.get(self.model_cfg.w4_dialect, have) if have == 'u4' else have
             # ('fp8' takes either scale form of an e4m3 checkpoint, 'fp8_channel' only the per-tensor / per-channel one)
-            accepts = {'awq': ('u4',), 'fp8': ('fp8', 'fp8_channel'), 'fp8_channel': ('fp8_channel',), 'mxfp4': ('mxfp4',), 'int8': ('int8',)}
+            accepts = {'awq': ('u4',), 'fp8': ('fp8', 'fp8_channel'), 'fp8_channel': ('fp8_channel',), 'mxfp4': ('mxfp4',), 'int8': ('int8',),
+                       'compressed-tensors': ('compressed-tensors',)}
             if cfg.model_format in accepts and have not in accepts[cfg.model_format]:
                 raise ValueError(f'model_format="{cfg.model_format}" but the checkpoint\'s quantization_config says {have} '
                                  f'(lmdeploy/turbomind/converter.py:174-176)')

@@ -1,6 +1,7 @@
 """HF checkpoint -> logical TM-layout weights (the on-disk side of the boundary).
 
-Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with AWQ (W4A16 g128),
+Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2 / Qwen3 / Qwen2-MoE / Qwen3-MoE with W4A16 weights (AWQ
+g128; GPTQ g128, symmetric, no act-order; compressed-tensors `pack-quantized` g128 or -- dense models -- g32: the W4 table below),
 FP8 (e4m3: 128x128 block scales, `.weight_scale_inv`; or one scale per tensor / per output channel, `.weight_scale` -- AutoFP8
 `quant_method: "fp8"` without weight_block_size and compressed-tensors `float-quantized`; their static `input_scale` / `k_scale` /
 `v_scale` tensors are read past: activations are quantised per token, the KV cache follows quant_policy), INT8 W8A8 (int8 codes with
@@ -14,6 +15,7 @@ one scale per tensor / output channel: `quant_method: "smooth_quant"` with `.sca
                                      Qwen2-MoE adds mlp.shared_expert.* and mlp.shared_expert_gate, qwen2.py:110-128)
   * FP8 normalize / dequant          lmdeploy/turbomind/weight_format.py:349-384 (HF [out, in] -> [in, out], scales alike)
   * AWQ normalize (unpack order)     lmdeploy/turbomind/weight_format.py:200-234
+  * GPTQ / compressed-tensors        lmdeploy/turbomind/weight_format.py:250-346 (sequential nibbles; zeros + 1; [N, K/8] -> [K, N])
   * RoPE q/k channel permutation     lmdeploy/turbomind/models/utils.py:306-373 (weight, scales and zeros alike)
   * QKV fusion / w1w3 interleave     lmdeploy/turbomind/builders/attention.py:65-108, ffn.py:31-65,138-170
   * config -> engine model config    lmdeploy/turbomind/converter.py:154-259
@@ -29,7 +31,8 @@ from glob import glob
 
 import numpy as np
 
-from .loader import interleave_gate_up, pad_model_weights, permute_qk_for_interleaved_rope, unpack_awq_gemm
+from .loader import (interleave_gate_up, pad_model_weights, permute_qk_for_interleaved_rope, unpack_awq_gemm, unpack_u4_cols,
+                     unpack_u4_rows)
 
 
 @dataclass
@@ -87,6 +90,13 @@ class ModelConfig:
     attn_out_bias: int = 0             # gpt-oss: the o projection carries a bias
     attn_sinks: int = 0                # gpt-oss: one sink logit per q head joins every softmax
     layer_windows: list | None = None  # gpt-oss: one sliding window per layer (0 = full attention), from `layer_types`
+    w4_dialect: str = 'awq'            # weight_format 'u4': how the checkpoint packs its 4-bit linears: 'awq' | 'gptq' | 'compressed-tensors'
+    w4_zero_offset: int = 1            # GPTQ: what is added to a stored qzeros nibble (1: the v1 form; 0: gptq_v2)
+
+    @property
+    def group_size(self) -> int:
+        """the u4 quantisation group along K: 128, or 32 (compressed-tensors pack-quantized; dense models, a kernel of its own)"""
+        return self.group
 
 
 def check_kv_quant_policy(cfg, quant_policy: int, tp: int = 1, what: str = 'this model'):
@@ -280,8 +290,78 @@ _CT_FORMATS = {
 }
 
 
+# The two further W4A16 dialects next to AWQ (u4 codes [K,N], fp16 scales [K/g,N], zeros [K/g,N] once read), every key and accepted value in
+# one place.  GPTQ: the config keys are those of transformers' GPTQConfig (bits, group_size, sym, desc_act; `checkpoint_format` in
+# AutoGPTQ / older transformers, `format` in newer ones, "gptq_v2" = zeros stored without the -1), checked against the installed
+# transformers by tests/test_host_w4_formats.py; the tensor names and layouts are the reference's reader (GPTQFormat,
+# lmdeploy/turbomind/weight_format.py:250-291).  compressed-tensors: the compressed_tensors package was not available to check
+# against, so the names come from the reference's reader (CompressedTensorFormat, weight_format.py:294-346; converter.py:190-201) and
+# could not be checked against the library or a published checkpoint: a correction is one edit here.
+W4 = {
+    'gptq': dict(
+        method='gptq',
+        config=(('bits', 4, (4,)), ('group_size', 128, (128,)), ('sym', True, (True,)), ('desc_act', False, (False,))),   # key, default, accepted
+        v2_keys=('checkpoint_format', 'format'), v2='gptq_v2',
+        qweight='.qweight',                              # int32 [K/8][N], nibble i of word r = row 8r+i
+        scales='.scales',                                # fp16 [K/g][N]
+        qzeros='.qzeros',                                # int32 [K/g][N/8], nibble j of word c = column 8c+j; zero = stored + 1 (v2: + 0)
+        g_idx='.g_idx',                                  # int32 [K], must be k // g (anything else is act-order)
+    ),
+    'compressed-tensors': dict(
+        method='compressed-tensors', format='pack-quantized',
+        weights=(('strategy', ('group',)), ('group_size', (32, 128)), ('dynamic', (False, None)), ('actorder', (None, False))),
+        weight='.weight_packed',                         # int32 [N][K/8], nibble j of word c = input channel 8c+j; the code is the nibble
+        scales='.weight_scale',                          # fp16 / bf16 [N][K/g]
+        zeros='.weight_zero_point',                      # asymmetric only: int32 [N/8][K/g], nibble i of word r = output channel 8r+i
+        shape='.weight_shape',                           # [2] = (N, K)
+        symmetric_zero=8,
+    ),
+}
+
+
+def _is_moe(arch: str) -> bool:
+    return 'Mixtral' in arch or 'Moe' in arch or 'MoE' in arch
+
+
+def _check_gptq(q: dict) -> int:
+    """quantization_config of a GPTQ export (W4['gptq']): the reference's conditions (converter.py:183-185 and the group sizes of
+    converter.py:86-92).  Returns the offset of the stored zeros."""
+    G = W4['gptq']
+    for key, default, ok in G['config']:
+        if q.get(key, default) not in ok:
+            raise NotImplementedError(f'gptq quantization_config: {key} = {q.get(key)!r} is not served ({" | ".join(map(repr, ok))}'
+                                      f'{": act-order permutes the groups along K" if key == "desc_act" else ""})')
+    return 0 if any(q.get(k) == G['v2'] for k in G['v2_keys']) else 1
+
+
+def _check_pack_quantized(q: dict) -> int:
+    """quantization_config of a compressed-tensors `pack-quantized` export (W4['compressed-tensors']): ONE config group of 4-bit int
+    group weights (group 128 or 32, static, no act-order) without input activations.  Returns the group size.  A pack-quantized config
+    that is not 4-bit int weight-only is refused under `format`, as before."""
+    C = W4['compressed-tensors']
+
+    def no(key, val, want):
+        return NotImplementedError(f'compressed-tensors quantization_config: {key} = {val!r} is not served ({want})')
+    groups = q.get('config_groups') or {}
+    if len(groups) != 1:
+        raise no('config_groups', sorted(groups), 'exactly one config group')
+    (gname, g), = groups.items()
+    w = g.get('weights') or {}
+    if w.get('num_bits') != 4 or w.get('type') != 'int' or g.get('input_activations') is not None \
+            or g.get('format', C['format']) != C['format']:
+        raise no('format', q.get('format'), '"pack-quantized" holds 4-bit int group weights without input activations (W4A16); 8-bit '
+                 'weights come as "float-quantized": e4m3 weights with .weight_scale, or "int-quantized": int8 W8A8')
+    for key, ok in C['weights']:
+        if w.get(key) not in ok:
+            raise no(f'config_groups.{gname}.weights.{key}', w.get(key), ' | '.join('absent' if x is None else repr(x) for x in ok))
+    for name in q.get('ignore') or []:
+        if name not in _CT_IGNORE_OK and not name.endswith('lm_head'):
+            raise no('ignore', name, 'only lm_head and router gates may stay unquantised: every decoder linear is 4-bit')
+    return int(w['group_size'])
+
+
 def _refuse_int8_moe(arch: str, method: str):
-    if 'Mixtral' in arch or 'Moe' in arch or 'MoE' in arch:
+    if _is_moe(arch):
         raise NotImplementedError(f'{arch} with quant_method "{method}" (INT8 W8A8): served for dense models only (int8 experts are not '
                                   f'built)')
 
@@ -354,7 +434,7 @@ def _check_quark(q: dict, arch: str):
 
     def no(key, val, want):
         return NotImplementedError(f'quark quantization_config: {key} = {val!r} is not served ({want})')
-    if 'Mixtral' in arch or 'Moe' in arch or 'MoE' in arch:
+    if _is_moe(arch):
         raise NotImplementedError(f'{arch} with quant_method "quark": MXFP4 W4A4 is served for dense models only (mixture-of-experts '
                                   f'architectures are not built)')
     g = q.get(Q['global_cfg'])
@@ -426,13 +506,18 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                 raise ValueError(f'{arch}: sliding_window {sw!r} must be a non-negative integer or null')
             window = sw
     q = c.get('quantization_config')
-    wfmt, fp8_mode = 'f16', 0
+    wfmt, fp8_mode, w4, group, zero_offset = 'f16', 0, 'awq', 128, 1
     if q is not None:
         if q.get('quant_method') == QUARK['method']:
             _check_quark(q, arch)
             if tp != 1:
                 raise NotImplementedError(f'{arch} with quant_method "quark" (MXFP4 W4A4) and tp = {tp}: not built (run with tp = 1)')
             wfmt = 'mxfp4'
+        elif q.get('quant_method') == 'compressed-tensors' and q.get('format') == W4['compressed-tensors']['format']:
+            wfmt, w4, group = 'u4', 'compressed-tensors', _check_pack_quantized(q)
+            if group != 128 and _is_moe(arch):
+                raise NotImplementedError(f'{arch} with compressed-tensors weights.group_size = {group}: the group-{group} kernel serves '
+                                          f'dense models only (mixture-of-experts models need group_size 128)')
         elif q.get('quant_method') == 'compressed-tensors':
             if _check_compressed_tensors(q) == INT8['compressed-tensors']['format']:
                 _refuse_int8_moe(arch, 'compressed-tensors')
@@ -458,10 +543,13 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                 raise NotImplementedError(f'{arch} with fp8 weights and head_dim 64: the 128-column scale blocks of the q / k / v '
                                           f'projections straddle heads; fp8 needs head_dim 128')
             wfmt = 'fp8'
+        elif q.get('quant_method') == W4['gptq']['method']:
+            wfmt, w4, zero_offset = 'u4', 'gptq', _check_gptq(q)
         elif q.get('quant_method') != 'awq' or q.get('bits', 4) != 4 or q.get('group_size', 128) != 128:
-            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, block-128 FP8, per-tensor FP8, '
-                                      f'compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92), Quark MXFP4 or '
-                                      f'INT8 W8A8 (smooth_quant, compressed-tensors int-quantized)')
+            raise NotImplementedError(f'quantization_config {q}: only AWQ 4-bit group 128, GPTQ 4-bit group 128 (symmetric, no '
+                                      f'act-order), compressed-tensors pack-quantized 4-bit (group 128 or 32), block-128 FP8, per-tensor '
+                                      f'FP8, compressed-tensors float-quantized FP8 (lmdeploy/turbomind/converter.py:82-92), Quark MXFP4 '
+                                      f'or INT8 W8A8 (smooth_quant, compressed-tensors int-quantized)')
         else:
             wfmt = 'u4'
     rope = RopeConfig(dim=D, base=float(c.get('rope_theta', 10000.0)))
@@ -491,7 +579,7 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                        vocab=c['vocab_size'], rms_eps=float(c.get('rms_norm_eps', 1e-5)), rope=rope, arch=kind,
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
                        max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, fp8_scale_mode=fp8_mode,
-                       **moe,
+                       **moe, group=group, w4_dialect=w4, w4_zero_offset=zero_offset,
                        attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
 
 
@@ -626,10 +714,60 @@ class _Tensors:
         return t.numpy().copy()     # own the memory: the tensor is a view into the file mapping
 
 
+def _linear_gptq(t: '_Tensors', prefix: str, group: int, zero_offset: int) -> dict:
+    """a GPTQ linear (W4['gptq']; GPTQFormat.normalize, weight_format.py:269-282) -> {'q','s','z'} like an AWQ one"""
+    G = W4['gptq']
+    qw, sc, qz = (t.get(prefix + G[n]) for n in ('qweight', 'scales', 'qzeros'))
+    if qw.ndim != 2 or sc.ndim != 2 or qw.shape[1] != sc.shape[1] or qw.shape[0] * 8 != sc.shape[0] * group:
+        raise ValueError(f'{prefix}{G["qweight"]}: expected GPTQ int32 [K/8][N] next to scales [K/{group}][N], got {tuple(qw.shape)} and '
+                         f'{tuple(sc.shape)}')
+    K, N = qw.shape[0] * 8, qw.shape[1]
+    if qz.shape != (K // group, N // 8):
+        raise ValueError(f'{prefix}{G["qzeros"]}: expected int32 [{K // group}][{N // 8}], got {tuple(qz.shape)}')
+    if (prefix + G['g_idx']) in t:
+        g_idx = t.get(prefix + G['g_idx']).reshape(-1)
+        if g_idx.shape != (K,) or not np.array_equal(g_idx, np.arange(K) // group):
+            raise NotImplementedError(f'{prefix}{G["g_idx"]}: not k // {group} -- an act-order (desc_act) checkpoint permutes the '
+                                      f'groups along K, which is not served')
+    z = unpack_u4_cols(qz).astype(np.int16) + zero_offset
+    if z.max() > 15:
+        raise ValueError(f'{prefix}{G["qzeros"]}: a stored zero of 15 + {zero_offset} leaves [0, 15] (a gptq_v2 checkpoint says so in '
+                         f'checkpoint_format / format)')
+    return dict(q=unpack_u4_rows(qw), s=sc.astype(np.float16), z=z.astype(np.float16))
+
+
+def _linear_pack_quantized(t: '_Tensors', prefix: str, group: int) -> dict:
+    """a compressed-tensors pack-quantized linear (W4['compressed-tensors']; CompressedTensorFormat.normalize, weight_format.py:310-321:
+    unpack along the input dim, transpose to [K][N]; symmetric weights get zeros of 8) -> {'q','s','z'} like an AWQ one"""
+    C = W4['compressed-tensors']
+    wp, sc = t.get(prefix + C['weight']), t.get(prefix + C['scales'])
+    if wp.ndim != 2 or sc.ndim != 2 or wp.shape[0] != sc.shape[0] or wp.shape[1] * 8 != sc.shape[1] * group:
+        raise ValueError(f'{prefix}{C["weight"]}: expected int32 [N][K/8] next to {C["scales"]} [N][K/{group}], got {tuple(wp.shape)} and '
+                         f'{tuple(sc.shape)}')
+    N, K = wp.shape[0], wp.shape[1] * 8
+    if (prefix + C['shape']) in t and tuple(int(x) for x in t.get(prefix + C['shape']).reshape(-1)) != (N, K):
+        raise ValueError(f'{prefix}{C["shape"]}: {t.get(prefix + C["shape"]).reshape(-1).tolist()} is not (N, K) = ({N}, {K}) of '
+                         f'{C["weight"]}')
+    s = np.ascontiguousarray(sc.astype(np.float16).T)
+    if (prefix + C['zeros']) in t:
+        zp = t.get(prefix + C['zeros'])
+        if zp.shape != (N // 8, K // group):
+            raise ValueError(f'{prefix}{C["zeros"]}: expected int32 [{N // 8}][{K // group}], got {tuple(zp.shape)}')
+        z = np.ascontiguousarray(unpack_u4_rows(zp).T).astype(np.float16)
+    else:
+        z = np.full(s.shape, C['symmetric_zero'], np.float16)
+    return dict(q=np.ascontiguousarray(unpack_u4_cols(wp).T), s=s, z=z)
+
+
 def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
-    """-> {'q','s','z'} (uint8 [K,N], fp16 [K/g,N] x2), {'f8','bs'} (e4m3 codes [K,N], fp32 block scales
+    """-> {'q','s','z'} (uint8 [K,N], fp16 [K/g,N] x2: AWQ, GPTQ and compressed-tensors pack-quantized alike), {'f8','bs'} (e4m3 codes [K,N], fp32 block scales
     [K/128, ceil(N/128)]), {'f8','cs'} (e4m3 codes [K,N], one fp32 scale per output channel [N]), {'i8','cs'} (int8 codes [K,N] with
     the same scales: both INT8 dialects) or {'w'} fp16 [K,N]."""
+    w4 = getattr(t, 'w4', None) or {}
+    if quantized and w4.get('dialect') == 'gptq' and (prefix + W4['gptq']['qweight']) in t:
+        return _linear_gptq(t, prefix, w4['group'], w4['zero_offset'])
+    if quantized and (prefix + W4['compressed-tensors']['weight']) in t:      # (its .weight_scale is not the 8-bit forms' below)
+        return _linear_pack_quantized(t, prefix, w4.get('group', 128))
     if quantized and (prefix + QUARK['scale_suffix']) in t and t.get(prefix + QUARK['scale_suffix']).dtype == np.uint8:
         # Quark MXFP4 (e8m0 scale bytes; the FP8 forms below carry float scales): the checkpoint layout IS the engine's (output-major)
         w, s = t.get(prefix + QUARK['weight_suffix']), t.get(prefix + QUARK['scale_suffix'])
@@ -658,6 +796,10 @@ def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
         assert w.dtype == np.uint8, f'{prefix}.weight: expected float8_e4m3fn / uint8 codes, got {w.dtype}'
         return dict(f8=np.ascontiguousarray(w.T), bs=np.ascontiguousarray(t.get(prefix + '.weight_scale_inv').astype(np.float32).T))
     if quantized and (prefix + '.qweight') in t:
+        qw, sc = t.get(prefix + '.qweight'), t.get(prefix + '.scales')
+        if qw.ndim != 2 or sc.ndim != 2 or qw.shape[1] * 8 != sc.shape[1]:
+            raise ValueError(f'{prefix}.qweight: expected AWQ int32 [K][N/8] next to scales [K/g][N], got {tuple(qw.shape)} and '
+                             f'{tuple(sc.shape)}')
         return dict(q=unpack_awq_gemm(t.get(prefix + '.qweight')),
                     s=t.get(prefix + '.scales').astype(np.float16),
                     z=unpack_awq_gemm(t.get(prefix + '.qzeros')).astype(np.float16))
@@ -693,6 +835,11 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
     t = _Tensors(model_path)
     if cfg.arch == 'gpt_oss':
         return _load_gpt_oss(t, cfg)
+    # `.qweight` is AWQ's and GPTQ's alike: the 4-bit dialect comes from the quantization_config, not from the key
+    t.w4 = dict(dialect=getattr(cfg, 'w4_dialect', 'awq'), group=cfg.group, zero_offset=getattr(cfg, 'w4_zero_offset', 1))
+    if cfg.group != 128 and cfg.moe_experts:
+        raise NotImplementedError(f'group_size {cfg.group} with moe_experts {cfg.moe_experts}: the group-{cfg.group} kernel serves dense '
+                                  f'models only')
     D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
     layers = []
     llama_names = cfg.arch != 'internlm2'        # Llama / Mixtral / Qwen2 / Qwen3
@@ -718,7 +865,7 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
                 if getattr(cfg, 'moe_shared_inter', 0):
                     # Qwen2-MoE: the shared expert is a dense FFN (the engine's feed_forward slots), its gate an unquantised [1, H] row
                     sg = m + '.shared_expert_gate'
-                    if (sg + '.qweight') in t or (sg + '.weight_scale_inv') in t:
+                    if (sg + '.qweight') in t or (sg + '.weight_scale_inv') in t or (sg + W4['compressed-tensors']['weight']) in t:
                         raise NotImplementedError(f'{sg}: a quantised shared-expert gate is not implemented (the gate is read as '
                                                   f'fp16 / bf16 [1, hidden])')
                     s1, s3, s2 = (_linear(t, f'{m}.shared_expert.{n}', cfg.quantized) for n in names)

@@ -24,6 +24,21 @@ def unpack_awq_gemm(qw: np.ndarray) -> np.ndarray:
     return np.stack([nib[i] for i in AWQ_ORDER], axis=-1).reshape(*w.shape[:-1], -1)
 
 
+def unpack_u4_cols(w: np.ndarray) -> np.ndarray:
+    """int32[..., C] -> uint8[..., 8C]: element 8c+j of the last dim is nibble j of word c (sequential order: GPTQ qzeros,
+    compressed-tensors weight_packed; the inverse of pack_u4_row)."""
+    w = np.asarray(w).view(np.uint32).astype(np.uint64)
+    nib = [((w >> np.uint64(4 * j)) & np.uint64(15)).astype(np.uint8) for j in range(8)]
+    return np.stack(nib, axis=-1).reshape(*w.shape[:-1], -1)
+
+
+def unpack_u4_rows(w: np.ndarray) -> np.ndarray:
+    """int32[R, N] -> uint8[8R, N]: row 8r+i is nibble i of word row r (GPTQ qweight, compressed-tensors weight_zero_point)."""
+    w = np.asarray(w).view(np.uint32).astype(np.uint64)
+    nib = [((w >> np.uint64(4 * i)) & np.uint64(15)).astype(np.uint8) for i in range(8)]
+    return np.stack(nib, axis=1).reshape(-1, w.shape[-1])
+
+
 def pack_u4_row(q: np.ndarray) -> np.ndarray:
     """uint8[..., N] -> int32[..., N/8] with nibble j of word c = element 8c+j (the engine's boundary layout)."""
     g = np.asarray(q, np.uint8).reshape(*q.shape[:-1], -1, 8).astype(np.uint64)
