@@ -142,6 +142,17 @@ int tm_kv_rope_store_qk(void* qkv, int q_heads, const int* cu_q_len, const int* 
 int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
                          const void* cos_sin, int max_pos, const int* rope_row0, const void* qkv_bias, const void* q_norm,
                          const void* k_norm, float qk_eps, const tm_kv_cache* cache, tm_stream_t st);
+/* tm_kv_rope_store_qk with multimodal RoPE in sections (Qwen2-VL; the reference's RopeType::kMrope / FastRoPE mode kChunked,
+ * src/turbomind/kernels/attention/rotary_embedding.h:112-193).  Frequency pair j = (x[2j], x[2j+1]) of every q / k head takes table
+ * row clamp(c, 0, max_pos - 1) of ONE of three coordinates -- t for j < sec_t, h for j < sec_t + sec_h, w behind -- and entry j of
+ * that row; the rotation is tm_kv_rope_store's.  mrope_pos: device int [total_tokens][3] (t, h, w) for the rows of this call, or
+ * NULL: all three are the row's linear position + pos_delta[b] (pos_delta device int [batch], NULL = 0).  K / V land at the linear
+ * position either way.  Equal coordinates = the linear position and no delta give tm_kv_rope_store_qk's bits.  head_dim 128, kv bits
+ * 16 / 8 / 4, one table: kv bits 42, head_dim 64, a NULL table and sections that do not sum to 64 return TM_INVALID by name. */
+int tm_kv_rope_store_mrope(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                           const void* cos_sin, int max_pos, const int* mrope_pos, const int* pos_delta, int sec_t, int sec_h,
+                           int sec_w, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                           const tm_kv_cache* cache, tm_stream_t st);
 /* FlattenKV_v2: dequantise the whole context into linear fp16 scratch.  k_out [kv_heads][k_stride][head_dim];
  * v_out the same, or transposed [kv_heads][head_dim][k_stride] when transpose_v != 0 (head_dim 64 or 128; the transposed rows are
  * zero-filled from k_len up to the next multiple of 64).  Sequence b starts at
@@ -183,6 +194,13 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
                                  const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps, const int* k_len,
                                  int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
                                  tm_stream_t st);
+/* tm_decode_attention_fused_qk with a per-sequence position delta (M-RoPE models: a decode token sits at linear position + delta on
+ * all three axes): the new token's RoPE row is clamp(k_len[b] - 1 + pos_delta[b], 0, max_pos - 1); pos_delta device int [batch].
+ * NULL is tm_decode_attention_fused_qk (the same kernel instantiation); a delta array of zeros gives its bits.  Needs cos_sin. */
+int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
+                                    const int* pos_delta, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                                    const int* k_len, int batch, int q_heads, float softmax_scale, int splits, void* workspace,
+                                    const tm_kv_cache* cache, tm_stream_t st);
 /* tm_decode_attention with a sliding window and attention sinks (AttentionParams::window_size / ::sinks,
  * src/turbomind/kernels/attention/attention_params.h:55-72; the tile skip of decoding_template.h:29 and
  * attention_universal.h:411,474-480; the sink term L += expf(sink - M * scale) of attention_universal.h:529-535).
@@ -214,6 +232,11 @@ int tm_prefill_attention_window(void* out, const void* q, int q_stride, const vo
                                 tm_stream_t st);
 
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st);
+/* tm_embedding for multimodal prompts (the reference's input_embeddings / input_embedding_ranges, lmdeploy/turbomind/turbomind.py:632-674):
+ * emb_index device int [tokens]; row t is row emb_index[t] of emb_rows (device fp16 [n][hidden], copied bit for bit, ids[t] is not
+ * read) when emb_index[t] >= 0, the table row of ids[t] when it is -1.  All -1 is tm_embedding. */
+int tm_embedding_mixed(void* out, const void* table, const int* ids, const void* emb_rows, const int* emb_index, int tokens, int hidden,
+                       int vocab, tm_stream_t st);
 /* greedy top-1 on fp32-cast logits (generation/sampling.cc:92-183); out_val (fp16 [batch]) may be NULL */
 int tm_argmax(int* out_ids, void* out_val, const void* logits, int batch, int vocab, int ld, tm_stream_t st);
 /* Per-row cross-entropy (kernels/cross_entropy_kernels.cu:31-73): nll fp32 [rows] = logf(sum_v exp(x_v - max) + 1e-9f) + max
@@ -660,6 +683,14 @@ int tm_engine_destroy(tm_engine* e);
 /* Per-layer sliding windows (gpt-oss alternates sliding and full layers): window[i] replaces attn_window for layer i, 0 = full
  * attention.  Before tm_engine_start; layers must equal the model's; a negative window is TM_INVALID. */
 int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers);
+/* Multimodal RoPE sections (Qwen2-VL / Qwen2.5-VL mrope_section): a setter like tm_engine_set_layer_windows rather than three more ints
+ * in struct tm_model_config -- a choice, not a constraint (every caller that fills the struct positionally stays as it is).  Frequency pair j of a head rotates by the t coordinate for j < sec_t, by h for the next sec_h
+ * pairs, by w for the rest (tm_kv_rope_store_mrope).  Before tm_engine_start.  0 / 0 / 0 = none (the engine as created); otherwise
+ * three non-negative sizes that sum to head_dim / 2, head_dim 128, rope_type 0 .. 3 (one shared table) -- TM_INVALID by name else.
+ * Such an engine (tp 1, quant_policy != 42) accepts coordinates and a position delta in tm_engine_set_multimodal and decodes every
+ * static batch with a per-slot delta array (zeros for text): the fused prologue's pos_delta for int8 / int4 KV, tm_kv_rope_store_mrope
+ * otherwise.  Without multimodal input it computes what the engine without sections computes, bit for bit. */
+int tm_engine_set_mrope_section(tm_engine* e, int sec_t, int sec_h, int sec_w);
 /* RCCL bootstrap for tp > 1: rank 0 calls tm_comm_unique_id (128 bytes, host), broadcasts it out of band
  * (torch.distributed / TCPStore), then every rank calls tm_engine_comm_init. */
 int tm_comm_unique_id(void* host_out128);
@@ -751,6 +782,27 @@ int tm_engine_set_sampling(tm_engine* e, const tm_sampling* host_params, int bat
  * tm_engine_release.  tm_engine_fetch_logprobs copies the records to the host: vals / idx [batch][max_new_tokens][n] (entries beyond
  * num are undefined), num / sel [batch][max_new_tokens] (columns beyond the generated steps: num = 0). */
 int tm_engine_set_logprobs(tm_engine* e, int n);
+/* Multimodal input of ONE sequence of a static batch (the reference's input_embeddings, input_embedding_ranges, mrope_position_ids and
+ * mrope_position_delta: lmdeploy/turbomind/turbomind.py:632-674).  Host pointers, copied by tm_engine_set_multimodal. */
+typedef struct tm_mm_input {
+    int         prompt_len;     /* tokens of this sequence's prompt, as tm_engine_prefill will get it */
+    const void* emb_rows;       /* fp16 [n_rows][hidden]: the rows that replace the token-table lookup, in prompt order (NULL: none) */
+    int         n_rows;
+    const int*  ranges;         /* [n_ranges][2]: [begin, end) in prompt coordinates, sorted, disjoint, lengths summing to n_rows */
+    int         n_ranges;
+    const int*  mrope_pos;      /* [n_pos][3]: (t, h, w) of the first n_pos prompt tokens, all >= 0 (NULL / 0: none) */
+    int         n_pos;          /* <= prompt_len */
+    int         position_delta; /* every later token (rest of the prompt, decode) sits at linear position + delta on all axes; >= -prompt_len */
+} tm_mm_input;
+/* Static batch: multimodal inputs of the NEXT tm_engine_prefill (host array [batch], one entry per sequence, copied), which must have
+ * the same batch and prompt lengths and consumes them -- also when it fails, for whatever reason: nothing stays armed behind a
+ * tm_engine_prefill call; NULL clears.  A prompt row inside a range takes its fp16 row from emb_rows, bit
+ * for bit, and its token id is not read.  Coordinates and a non-zero delta need a model with sections (tm_engine_set_mrope_section).  Chunked prompts continue
+ * across prefill iterations; decode steps use the delta.  tm_engine_release or the next prefill clears the state.  TM_INVALID with the
+ * reason in tm_last_error: ranges unsorted, overlapping, outside the prompt or not summing to n_rows; n_pos > prompt_len; a negative
+ * coordinate; position_delta < -prompt_len; coordinates or a non-zero delta on a model without sections; tp > 1; quant_policy 42.
+ * Continuous batching (tm_engine_submit*) and tm_engine_score do not take multimodal input. */
+int tm_engine_set_multimodal(tm_engine* e, const tm_mm_input* host, int batch);
 /* Continuous batching: the same records for ONE queued request (call right after its submit, before the next scheduler step): every
  * token the request generates from then on carries its first n kept candidates.  tm_engine_poll_logprobs copies the records of the
  * first min(max_tokens, generated) tokens: vals / idx [tokens][n] (entries beyond num[t]: 0 / -1), num / sel [tokens]; *n_tokens =

@@ -84,6 +84,12 @@ class ModelConfig(C.Structure):
         super().__init__(*args, **kw)
 
 
+class MmInput(C.Structure):
+    """struct tm_mm_input: the multimodal input of one sequence of a static batch (host pointers)"""
+    _fields_ = [('prompt_len', c_int), ('emb_rows', c_void_p), ('n_rows', c_int), ('ranges', c_void_p), ('n_ranges', c_int),
+                ('mrope_pos', c_void_p), ('n_pos', c_int), ('position_delta', c_int)]
+
+
 class EngineConfig(C.Structure):
     """struct tm_engine_config"""
     _fields_ = [('model', ModelConfig), ('tp', c_int), ('rank', c_int), ('device', c_int),
@@ -118,6 +124,13 @@ _SIGNATURES = {
                                  POINTER(KvCache), c_void_p]),
     'tm_kv_rope_store_qk': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_void_p, c_float, POINTER(KvCache), c_void_p]),
+    'tm_kv_rope_store_mrope': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_float, POINTER(KvCache), c_void_p]),
+    'tm_decode_attention_fused_delta': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_float, c_void_p, c_int, c_int, c_float, c_int, c_void_p, POINTER(KvCache), c_void_p]),
+    'tm_embedding_mixed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tm_engine_set_multimodal': (c_int, [c_void_p, c_void_p, c_int]),
+    'tm_engine_set_mrope_section': (c_int, [c_void_p, c_int, c_int, c_int]),
     'tm_flatten_kv': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(KvCache),
                               c_void_p]),
     'tm_flatten_kv_window': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(KvCache),

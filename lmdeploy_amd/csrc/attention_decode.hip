@@ -482,6 +482,7 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     TM_REQUIRE(!fused || L.bits == 8 || L.bits == 4, "fused decode prologue: int8 / int4 KV only");
     // the Qwen prologue (bias / q-k norm) exists only in the fused MFMA path; unfused kernels read q after launch_kv_rope_store applied it
     TM_REQUIRE(fused || (!p.qkv_bias && !p.q_norm && !p.k_norm), "qkv bias / q-k norm need the fused decode prologue");
+    TM_REQUIRE(fused || !p.pos_delta, "pos_delta needs the fused decode prologue (unfused: launch_kv_rope_store_mrope applies it)");
     TM_REQUIRE(p.window >= 0, "decode attention: window must be >= 0 (0 = full attention)");
     if (p.window > 0 || p.sinks) {
         // the MFMA kernel and its fused prologue know neither: such a call runs kv_rope_store + the VALU kernel

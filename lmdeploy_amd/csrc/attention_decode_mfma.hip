@@ -149,7 +149,9 @@ __device__ __forceinline__ void expand_u4x32(u32x4 w, u32x4& a, u32x4& b)
 // one byte per code when the block is written to the wave's LDS image, everything after that is the int8 path
 // (scales / zeros are per token either way, quantization.h:316-366).
 // QKX (FUSED only): the Qwen prologue -- per-head RMSNorm of q / k, then the q / k / v bias, then RoPE (DecodeAttnParams).
-template<bool FUSED, int BITS, bool QKX = false>
+// PD (FUSED only): p.pos_delta [batch] shifts the new token's RoPE row (M-RoPE models: every decode token sits at its linear position
+// + the sequence's delta on all three axes, so one row serves the whole head); without PD the field is never read.
+template<bool FUSED, int BITS, bool QKX = false, bool PD = false>
 __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(DecodeAttnParams p, int head_chunks, int hpw)
 {
     static_assert(BITS == 8 || BITS == 4, "int8 / int4 KV");
@@ -297,7 +299,10 @@ __global__ __launch_bounds__(256, 2) void decode_attention_i8_mfma_kernel(Decode
         // One fixed order, no branch around a load (round 5): q slice, the new token's K / V slice (every wave loads one, the owner uses
         // it), the RoPE rows, then the first cache block -- all in flight together, waited for one by one with exact counts.  Before, each
         // of these waited for the one in front of it (k_len -> pointer window -> qkv slabs -> cache block: four VMEM round trips).
-        const int     pos   = min(ctx - 1, p.max_pos - 1);
+        int pos = min(ctx - 1, p.max_pos - 1);
+        if constexpr (PD) {
+            pos = max(min(ctx - 1 + *(const CONST_AS int*)(p.pos_delta + b), p.max_pos - 1), 0);
+        }
         const int     l16   = lane & 15;
         const bool    isv   = (lane & 16) != 0;
         const int     qcol  = (head0 + (hv ? i16 : 0)) * D + wave * 32 + g * 8;
@@ -666,47 +671,46 @@ int launch_decode_attention_i8_mfma(const DecodeAttnParams& p_in, hipStream_t st
         TM_REQUIRE(p.qkv_n % 8 == 0 && (p.qkv_splits == 0) == (p.qkv_slabs == nullptr), "fused qkv input");
     }
     TM_REQUIRE((p.q_norm == nullptr) == (p.k_norm == nullptr), "q_norm and k_norm come together");
+    TM_REQUIRE(p.pos_delta == nullptr || (fused && p.cos_sin != nullptr), "pos_delta belongs to the fused prologue with a RoPE table");
+    const bool b4 = p.cache.layout.bits == 4;
+    // one launch site for every instantiation: K is the kernel, L its dynamic LDS
+#define TM_ATTN_LAUNCH(L, ...)                                                  \
+    do {                                                                        \
+        const auto K = decode_attention_i8_mfma_kernel<__VA_ARGS__>;            \
+        if (const int rc = ensure_dynamic_lds((const void*)K, L)) {             \
+            return rc;                                                          \
+        }                                                                       \
+        K<<<grid, 256, L, st>>>(p, chunks, hpw);                                \
+    } while (0)
     if (fused && (p.qkv_bias || p.q_norm)) {
         // + the four waves' partial sums of squares of the q-norm ([4][16] fp32)
-        const int   lds_x = lds + 4 * 16 * 4;
-        const void* kx    = p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<true, 4, true> :
-                                                       (const void*)decode_attention_i8_mfma_kernel<true, 8, true>;
-        if (const int rc = ensure_dynamic_lds(kx, lds_x)) {
-            return rc;
+        const int lds_x = lds + 4 * 16 * 4;
+        if (p.pos_delta) {
+            if (b4) TM_ATTN_LAUNCH(lds_x, true, 4, true, true);
+            else TM_ATTN_LAUNCH(lds_x, true, 8, true, true);
         }
-        if (p.cache.layout.bits == 4) {
-            decode_attention_i8_mfma_kernel<true, 4, true><<<grid, 256, lds_x, st>>>(p, chunks, hpw);
-        }
-        else {
-            decode_attention_i8_mfma_kernel<true, 8, true><<<grid, 256, lds_x, st>>>(p, chunks, hpw);
-        }
-        TM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    const void* const k = fused ?
-                              (p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<true, 4> :
-                                                          (const void*)decode_attention_i8_mfma_kernel<true, 8>) :
-                              (p.cache.layout.bits == 4 ? (const void*)decode_attention_i8_mfma_kernel<false, 4> :
-                                                          (const void*)decode_attention_i8_mfma_kernel<false, 8>);
-    if (const int rc = ensure_dynamic_lds(k, lds)) {
-        return rc;
-    }
-    if (fused) {
-        if (p.cache.layout.bits == 4) {
-            decode_attention_i8_mfma_kernel<true, 4><<<grid, 256, lds, st>>>(p, chunks, hpw);
+        else if (b4) {
+            TM_ATTN_LAUNCH(lds_x, true, 4, true);
         }
         else {
-            decode_attention_i8_mfma_kernel<true, 8><<<grid, 256, lds, st>>>(p, chunks, hpw);
+            TM_ATTN_LAUNCH(lds_x, true, 8, true);
         }
+    }
+    else if (fused && p.pos_delta) {
+        if (b4) TM_ATTN_LAUNCH(lds, true, 4, false, true);
+        else TM_ATTN_LAUNCH(lds, true, 8, false, true);
+    }
+    else if (fused) {
+        if (b4) TM_ATTN_LAUNCH(lds, true, 4);
+        else TM_ATTN_LAUNCH(lds, true, 8);
+    }
+    else if (b4) {
+        TM_ATTN_LAUNCH(lds, false, 4);
     }
     else {
-        if (p.cache.layout.bits == 4) {
-            decode_attention_i8_mfma_kernel<false, 4><<<grid, 256, lds, st>>>(p, chunks, hpw);
-        }
-        else {
-            decode_attention_i8_mfma_kernel<false, 8><<<grid, 256, lds, st>>>(p, chunks, hpw);
-        }
+        TM_ATTN_LAUNCH(lds, false, 8);
     }
+#undef TM_ATTN_LAUNCH
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -292,6 +292,17 @@ int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int*
                                 (const half_t*)k_norm, qk_eps, rope_row0);
 }
 
+int tm_kv_rope_store_mrope(void* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                           const void* cos_sin, int max_pos, const int* mrope_pos, const int* pos_delta, int sec_t, int sec_h,
+                           int sec_w, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                           const tm_kv_cache* cache, tm_stream_t st)
+{
+    TM_REQUIRE(qkv && cu_q_len && k_len && cache, "null pointer");
+    return launch_kv_rope_store_mrope((half_t*)qkv, q_heads, cu_q_len, k_len, batch, total_tokens, (const half2_t*)cos_sin, max_pos,
+                                      mrope_pos, pos_delta, sec_t, sec_h, sec_w, to_view(cache), (hipStream_t)st,
+                                      (const half_t*)qkv_bias, (const half_t*)q_norm, (const half_t*)k_norm, qk_eps);
+}
+
 int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
                   int max_k_len, int k_stride, const tm_kv_cache* cache, tm_stream_t st)
 {
@@ -359,7 +370,17 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
                                  int batch, int q_heads, float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache,
                                  tm_stream_t st)
 {
+    return tm_decode_attention_fused_delta(out, qkv, qkv_splits, qkv_n, cos_sin, max_pos, nullptr, qkv_bias, q_norm, k_norm, qk_eps, k_len,
+                                           batch, q_heads, softmax_scale, splits, workspace, cache, st);
+}
+
+int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
+                                    const int* pos_delta, const void* qkv_bias, const void* q_norm, const void* k_norm, float qk_eps,
+                                    const int* k_len, int batch, int q_heads, float softmax_scale, int splits, void* workspace,
+                                    const tm_kv_cache* cache, tm_stream_t st)
+{
     TM_REQUIRE(out && qkv && k_len && cache, "null pointer");
+    TM_REQUIRE(pos_delta == nullptr || cos_sin != nullptr, "fused decode prologue: pos_delta needs a RoPE table");
     TM_REQUIRE(cache->head_dim == 128,
                "fused decode prologue: head_dim must be 128 (head_dim 64: tm_kv_rope_store + tm_decode_attention)");
     TM_REQUIRE(cache->bits != 42,
@@ -387,6 +408,7 @@ int tm_decode_attention_fused_qk(void* out, const void* qkv, int qkv_splits, int
     p.q_norm     = (const half_t*)q_norm;
     p.k_norm     = (const half_t*)k_norm;
     p.qk_eps     = qk_eps;
+    p.pos_delta  = pos_delta;
     return launch_decode_attention(p, (hipStream_t)st);
 }
 
@@ -440,6 +462,14 @@ int tm_embedding(void* out, const void* table, const int* ids, int tokens, int h
 {
     TM_REQUIRE(out && table && ids, "null pointer");
     return launch_embedding((half_t*)out, (const half_t*)table, ids, tokens, hidden, vocab, (hipStream_t)st);
+}
+
+int tm_embedding_mixed(void* out, const void* table, const int* ids, const void* emb_rows, const int* emb_index, int tokens, int hidden,
+                       int vocab, tm_stream_t st)
+{
+    TM_REQUIRE(out && table && ids && emb_rows && emb_index, "null pointer");
+    return launch_embedding_mixed((half_t*)out, (const half_t*)table, ids, (const half_t*)emb_rows, emb_index, tokens, hidden, vocab,
+                                  (hipStream_t)st);
 }
 
 int tm_argmax(int* out_ids, void* out_val, const void* logits, int batch, int vocab, int ld, tm_stream_t st)

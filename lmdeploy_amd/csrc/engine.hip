@@ -433,6 +433,23 @@ int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers)
     return 0;
 }
 
+int tm_engine_set_mrope_section(tm_engine* e, int sec_t, int sec_h, int sec_w)
+{
+    TM_REQUIRE(e, "null pointer");
+    TM_REQUIRE(!e->started, "tm_engine_set_mrope_section: call before tm_engine_start");
+    const tm_model_config& m = e->cfg.model;
+    TM_REQUIRE(sec_t >= 0 && sec_h >= 0 && sec_w >= 0, "mrope_section: three non-negative sizes (0 / 0 / 0 = none)");
+    if (sec_t + sec_h + sec_w > 0) {
+        TM_REQUIRE(m.head_dim == 128, "mrope_section needs head_dim 128: M-RoPE is not built for head_dim 64");
+        TM_REQUIRE(sec_t + sec_h + sec_w == m.head_dim / 2, "mrope_section must sum to head_dim / 2");
+        TM_REQUIRE(m.rope_type != 4, "mrope_section with rope_type 4 (dynamic NTK, per-sequence tables) is not built");
+    }
+    e->mrope_section[0] = sec_t;
+    e->mrope_section[1] = sec_h;
+    e->mrope_section[2] = sec_w;
+    return 0;
+}
+
 int64_t tm_engine_weight_bytes(tm_engine* e, const char* name)
 {
     if (!e || !name) {
@@ -800,6 +817,11 @@ int tm_engine_start(tm_engine* e)
             return TM_OOM;
         }
         TM_HIP_CHECK(hipMemcpy(e->d_rope, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+        if (e->mrope_section[0] + e->mrope_section[1] + e->mrope_section[2] > 0 && c.tp == 1 && c.quant_policy != 42) {
+            // M-RoPE model that can take multimodal input: the slots' position deltas, read by every static decode step
+            TM_TRY(dmalloc(&e->d_pos_delta, (size_t)B));
+            TM_HIP_CHECK(hipMemset(e->d_pos_delta, 0, (size_t)B * sizeof(int)));
+        }
         if (per_seq) {
             TM_TRY(dmalloc(&e->d_rope_row0, (size_t)B));
             TM_HIP_CHECK(hipMemset(e->d_rope_row0, 0, (size_t)B * sizeof(int)));
@@ -1069,7 +1091,7 @@ int tm_engine_destroy(tm_engine* e)
                     e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->scratch.xq, e->scratch.sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
                     e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
-                    e->d_rope_row0};
+                    e->d_rope_row0, e->d_pos_delta, e->d_emb_rows, e->d_emb_index, e->d_mrope_pos};
     for (void* p : bufs) {
         if (p) {
             (void)hipFree(p);

@@ -228,8 +228,18 @@ static int qkv_project(tm_engine* e, Layer& L, const Rows& R, bool fold, bool fu
 }
 
 // RoPE + K/V quantise-store of R's rows of d_qkv (rope_row0: the forward's per-sequence table rows, nullptr: one table)
+// (M-RoPE: a multimodal prefill forward carries coordinates per row, e->fw_mrope_pos; a static decode step of a model with sections the
+// slots' position deltas, e->fw_pos_delta -- either one selects the sectioned store, neither: the plain kernel as before)
 static int kv_store(tm_engine* e, const Layer& L, const KvCacheView& cv, const Rows& R, hipStream_t st, const int* rope_row0)
 {
+    if (e->fw_mrope_pos || e->fw_pos_delta) {
+        TM_REQUIRE(!rope_row0, "internal: M-RoPE sections with per-sequence RoPE tables");  // tm_engine_set_mrope_section refuses rope_type 4
+        const int* sec = e->mrope_section;
+        return launch_kv_rope_store_mrope(e->d_qkv + (size_t)R.r0 * e->qkv_n, e->q_heads, R.cu_q, R.k_len, R.nseq, R.rows, e->d_rope,
+                                          e->rope_max_pos, e->fw_mrope_pos ? e->fw_mrope_pos + (size_t)R.r0 * 3 : nullptr,
+                                          e->fw_pos_delta ? e->fw_pos_delta + R.s0 : nullptr, sec[0], sec[1], sec[2], cv, st, L.qkv_bias,
+                                          L.q_norm, L.k_norm, e->cfg.model.rms_eps);
+    }
     return launch_kv_rope_store(e->d_qkv + (size_t)R.r0 * e->qkv_n, e->q_heads, R.cu_q, R.k_len, R.nseq, R.rows, e->d_rope, e->rope_max_pos, cv,
                                 st, L.qkv_bias, L.q_norm, L.k_norm, e->cfg.model.rms_eps, rope_row0 ? rope_row0 + R.s0 : nullptr);
 }
@@ -284,6 +294,7 @@ static int decode_attention_block(tm_engine* e, const Layer& L, const KvCacheVie
         p.q_norm     = L.q_norm;
         p.k_norm     = L.k_norm;
         p.qk_eps     = e->cfg.model.rms_eps;
+        p.pos_delta  = e->fw_pos_delta ? e->fw_pos_delta + R.s0 : nullptr;
     }
     p.q          = e->d_qkv;
     p.q_stride   = e->qkv_n;
@@ -582,7 +593,16 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     const float scale_log2 = (1.0f / std::sqrt((float)e->D)) * 1.4426950408889634f;
     const Rows  own{nd, M - nd, 0, nseq, e->d_cu_q, e->d_k_len};  // the forward's own sequences: every row unless it is mixed
     const Rows  dec{0, nd, 0, nd, md ? md->cu_q : nullptr, md ? md->k_len : nullptr};  // mixed: decode rows = batch slots 0 .. nd-1
-    TM_PROF(P_EMBED, TM_TRY(launch_embedding(e->d_resid, e->tok_embeddings, d_ids, M, e->hidden, m.vocab, st)));
+    // a static decode step of a model with M-RoPE sections: the slots' position deltas (zeros for text) shift the new token's RoPE row
+    e->fw_pos_delta = decode && !e->sched && e->d_pos_delta ? e->d_pos_delta + slot0 : nullptr;
+    TM_REQUIRE(!(e->fw_emb_index || e->fw_mrope_pos) || (!decode && !md && !e->scoring && !e->use_comm), "internal: multimodal forward");
+    if (e->fw_emb_index) {  // a multimodal prefill forward: rows inside an embedding range come from the request's buffer
+        TM_PROF(P_EMBED, TM_TRY(launch_embedding_mixed(e->d_resid, e->tok_embeddings, d_ids, e->d_emb_rows, e->fw_emb_index, M, e->hidden,
+                                                       m.vocab, st)));
+    }
+    else {
+        TM_PROF(P_EMBED, TM_TRY(launch_embedding(e->d_resid, e->tok_embeddings, d_ids, M, e->hidden, m.vocab, st)));
+    }
     TM_PROF(P_RES_NORM, TM_TRY(launch_rmsnorm(e->d_x, e->d_resid, e->layers[0].attn_norm, m.rms_eps, M, e->hidden, st, e->hidden_valid)));
     // tp > 1 prefill through RCCL: whole dense layers as two micro-batches, or their row-wise part as two row halves (side-stream all-reduces)
     e->pipe_events_used = 0;
@@ -870,6 +890,8 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
     int consumed   = 0;  // tokens of the concatenated sequences prefilled by earlier iterations (the scoring rows' positions)
     while (b0 < batch) {
         std::vector<int> cu_q{0}, klen, koff{0}, rows, ids;
+        std::vector<int> emb_index, coords;  // multimodal batch: per row, next to ids (a chunked sequence continues at `start`)
+        const bool       mm = !e->mm_coords.empty() && !mix && !e->scoring;
         int b1 = b0, tokens = 0, max_q = 0, max_k = 0;
         bool partial_last = false;
         while (b1 < batch) {
@@ -880,6 +902,12 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
                 break;
             }
             ids.insert(ids.end(), seq_ids[b1] + start, seq_ids[b1] + start + take);
+            if (mm) {
+                const std::vector<int>& ei = e->mm_emb_index[b1];
+                const std::vector<int>& co = e->mm_coords[b1];
+                emb_index.insert(emb_index.end(), ei.begin() + start, ei.begin() + start + take);
+                coords.insert(coords.end(), co.begin() + (size_t)start * 3, co.begin() + (size_t)(start + take) * 3);
+            }
             tokens += take;
             cu_q.push_back(tokens);
             klen.push_back(start + take);
@@ -912,6 +940,18 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
         TM_HIP_CHECK(hipMemcpyAsync(e->d_k_len, klen.data(), klen.size() * 4, hipMemcpyHostToDevice, e->stream));
         TM_HIP_CHECK(hipMemcpyAsync(e->d_cu_koff, koff.data(), koff.size() * 4, hipMemcpyHostToDevice, e->stream));
         TM_HIP_CHECK(hipMemcpyAsync(e->d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, e->stream));
+        if (mm) {
+            // an iteration without a single embedding row keeps the plain lookup; coordinates reach the store only on a model with sections
+            const bool any_emb = std::any_of(emb_index.begin(), emb_index.end(), [](int v) { return v >= 0; });
+            if (any_emb) {
+                TM_HIP_CHECK(hipMemcpyAsync(e->d_emb_index, emb_index.data(), emb_index.size() * 4, hipMemcpyHostToDevice, e->stream));
+                e->fw_emb_index = e->d_emb_index;
+            }
+            if (e->d_pos_delta) {
+                TM_HIP_CHECK(hipMemcpyAsync(e->d_mrope_pos, coords.data(), coords.size() * 4, hipMemcpyHostToDevice, e->stream));
+                e->fw_mrope_pos = e->d_mrope_pos;
+            }
+        }
         // tensor-parallel forward through RCCL: the sequence boundary nearest to half the rows makes two micro-batches that leapfrog
         // through the layers (forward_layers_two_microbatches); none with both sides >= pipe_min_rows / 2 -> the row-half schedule
         e->mb = {};
@@ -940,7 +980,10 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
                                   merge ? &md : nullptr);
         e->d_block_ptrs = saved_ptrs;
         e->mb           = {};
+        e->fw_emb_index = nullptr;
+        e->fw_mrope_pos = nullptr;
         if (rc) {
+            (void)hipStreamSynchronize(e->stream);  // the pageable vectors above must outlive every copy queued from them
             return rc;
         }
         if (mix) {
@@ -976,6 +1019,136 @@ int prefill_slots(tm_engine* e, const int* const* seq_ids, const int* host_lens,
     return 0;
 }
 
+// multimodal state back to "text": nothing armed, nothing admitted, every slot's position delta 0
+static int multimodal_reset(tm_engine* e)
+{
+    e->h_mm.clear();
+    e->mm_emb_index.clear();
+    e->mm_coords.clear();
+    if (e->d_pos_delta) {
+        TM_HIP_CHECK(hipMemsetAsync(e->d_pos_delta, 0, (size_t)e->cfg.max_batch_size * sizeof(int), e->stream));
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    }
+    return 0;
+}
+
+// tm_engine_prefill: the armed multimodal inputs (`mm`: tm_engine_prefill took them out of e->h_mm on entry, so a prefill that fails
+// anywhere leaves nothing armed) become what prefill_slots slices per iteration -- per sequence
+// the row of d_emb_rows behind every prompt position (-1: token table) and three coordinates per position (the given ones, then linear
+// position + delta) -- the rows go to the device in one buffer, the deltas into the batch slots.  Without armed inputs: deltas 0.
+static int multimodal_admit(tm_engine* e, const std::vector<tmk::MmSeqT>& mm, const int* host_lens, int batch)
+{
+    e->mm_emb_index.clear();
+    e->mm_coords.clear();
+    if (mm.empty()) {
+        if (e->d_pos_delta) {
+            TM_HIP_CHECK(hipMemsetAsync(e->d_pos_delta, 0, (size_t)e->cfg.max_batch_size * sizeof(int), e->stream));
+        }
+        return 0;
+    }
+    TM_REQUIRE((int)mm.size() == batch, "tm_engine_set_multimodal: batch size differs from the prefill's");
+    const int           H = e->hidden;
+    std::vector<half_t> rows;
+    std::vector<int>    delta(batch, 0);
+    e->mm_emb_index.resize(batch);
+    e->mm_coords.resize(batch);
+    for (int b = 0; b < batch; ++b) {
+        const auto& s = mm[b];
+        if (s.prompt_len != host_lens[b]) {
+            e->mm_emb_index.clear();
+            e->mm_coords.clear();
+            TM_REQUIRE(false, "tm_engine_set_multimodal: prompt_len differs from the prefill's prompt length");
+        }
+        const int n = host_lens[b];
+        auto&     ei = e->mm_emb_index[b];
+        auto&     co = e->mm_coords[b];
+        ei.assign(n, -1);
+        int row = (int)(rows.size() / H);
+        for (size_t r = 0; r < s.ranges.size() / 2; ++r) {
+            for (int p = s.ranges[2 * r]; p < s.ranges[2 * r + 1]; ++p) {
+                ei[p] = row++;
+            }
+        }
+        rows.insert(rows.end(), s.rows.begin(), s.rows.end());
+        co.resize((size_t)n * 3);
+        std::copy(s.pos.begin(), s.pos.end(), co.begin());
+        for (int p = s.n_pos; p < n; ++p) {
+            co[3 * p] = co[3 * p + 1] = co[3 * p + 2] = p + s.delta;  // the store clamps to [0, max_pos - 1]
+        }
+        delta[b] = s.delta;
+    }
+    if (!e->d_emb_index) {
+        TM_TRY(dmalloc(&e->d_emb_index, (size_t)e->max_tokens));
+        TM_TRY(dmalloc(&e->d_mrope_pos, (size_t)e->max_tokens * 3));
+    }
+    if (rows.size() > e->emb_rows_cap) {
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->d_emb_rows);
+        e->d_emb_rows   = nullptr;
+        e->emb_rows_cap = 0;
+        TM_TRY(dmalloc(&e->d_emb_rows, rows.size()));
+        e->emb_rows_cap = rows.size();
+    }
+    if (!rows.empty()) {
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_emb_rows, rows.data(), rows.size() * sizeof(half_t), hipMemcpyHostToDevice, e->stream));
+    }
+    if (e->d_pos_delta) {
+        TM_HIP_CHECK(hipMemsetAsync(e->d_pos_delta, 0, (size_t)e->cfg.max_batch_size * sizeof(int), e->stream));
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_pos_delta, delta.data(), (size_t)batch * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));  // rows / delta are pageable locals
+    return 0;
+}
+
+int tm_engine_set_multimodal(tm_engine* e, const tm_mm_input* host, int batch)
+{
+    TM_REQUIRE(e, "null pointer");
+    TM_REQUIRE(e->batch == 0 && !e->sched, "set the multimodal inputs before tm_engine_prefill");
+    e->h_mm.clear();
+    if (!host) {
+        return 0;
+    }
+    TM_REQUIRE(e->cfg.tp == 1 && !e->use_comm, "multimodal input with tp > 1 is not built");
+    TM_REQUIRE(e->cfg.quant_policy != 42, "multimodal input with quant_policy 42 (TurboQuant KV) is not built");
+    TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
+    const bool sections = e->mrope_section[0] + e->mrope_section[1] + e->mrope_section[2] > 0;
+    std::vector<tmk::MmSeqT> mm(batch);
+    for (int b = 0; b < batch; ++b) {
+        const tm_mm_input& in = host[b];
+        TM_REQUIRE(in.prompt_len >= 1, "multimodal input: prompt_len >= 1");
+        TM_REQUIRE(in.n_rows >= 0 && in.n_ranges >= 0 && in.n_pos >= 0, "multimodal input: negative count");
+        TM_REQUIRE(in.n_rows == 0 || in.emb_rows, "multimodal input: n_rows > 0 without emb_rows");
+        TM_REQUIRE(in.n_ranges == 0 || in.ranges, "multimodal input: n_ranges > 0 without ranges");
+        TM_REQUIRE(in.n_pos == 0 || in.mrope_pos, "multimodal input: n_pos > 0 without mrope_pos");
+        int prev_end = 0, total = 0;
+        for (int r = 0; r < in.n_ranges; ++r) {
+            const int b0 = in.ranges[2 * r], b1 = in.ranges[2 * r + 1];
+            TM_REQUIRE(b0 >= 0 && b1 <= in.prompt_len, "multimodal input: embedding range outside the prompt");
+            TM_REQUIRE(b0 < b1, "multimodal input: empty or reversed embedding range");
+            TM_REQUIRE(b0 >= prev_end, "multimodal input: embedding ranges unsorted or overlapping");
+            prev_end = b1;
+            total += b1 - b0;
+        }
+        TM_REQUIRE(total == in.n_rows, "multimodal input: embedding ranges do not add up to the row count");
+        TM_REQUIRE(in.n_pos <= in.prompt_len, "multimodal input: n_pos larger than the prompt length");
+        for (int i = 0; i < in.n_pos * 3; ++i) {
+            TM_REQUIRE(in.mrope_pos[i] >= 0, "multimodal input: negative M-RoPE coordinate");
+        }
+        TM_REQUIRE(in.position_delta >= -in.prompt_len, "multimodal input: position_delta < -prompt_len");
+        TM_REQUIRE(sections || (in.n_pos == 0 && in.position_delta == 0),
+                   "multimodal input: M-RoPE coordinates or a position delta on a model without mrope_section (tm_engine_set_mrope_section)");
+        auto& s      = mm[b];
+        s.prompt_len = in.prompt_len;
+        s.n_pos      = in.n_pos;
+        s.delta      = in.position_delta;
+        s.rows.assign((const half_t*)in.emb_rows, (const half_t*)in.emb_rows + (size_t)in.n_rows * e->hidden);
+        s.ranges.assign(in.ranges, in.ranges + (size_t)in.n_ranges * 2);
+        s.pos.assign(in.mrope_pos, in.mrope_pos + (size_t)in.n_pos * 3);
+    }
+    e->h_mm.swap(mm);
+    return 0;
+}
+
 int tm_engine_release(tm_engine* e)
 {
     if (e && e->loop_on.load()) {
@@ -988,6 +1161,7 @@ int tm_engine_release(tm_engine* e)
     }
     e->pending.valid = false;  // a look-ahead decode step of the session that ends here: its tokens belong to nobody
     TM_TRY(rope_reset(e, 0, e->cfg.max_batch_size));
+    TM_TRY(multimodal_reset(e));
     for (auto& blks : e->h_blocks) {
         for (int b : blks) {
             e->free_blocks.push_back(b);
@@ -1025,6 +1199,8 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
         return TM_CONFLICT;
     }
     TM_REQUIRE(e && host_ids && host_lens, "null pointer");
+    std::vector<tmk::MmSeqT> mm;
+    mm.swap(e->h_mm);  // tm_engine_set_multimodal's input belongs to THIS call: consumed, whatever happens below
     TM_REQUIRE(e->started, "engine not started");
     TM_REQUIRE(e->batch == 0 && !e->sched, "a batch is already admitted (release it first)");
     TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
@@ -1110,6 +1286,7 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     for (int b = 0; b < batch; ++b) {
         TM_TRY(rope_admit(e, b, host_lens[b]));
     }
+    TM_TRY(multimodal_admit(e, mm, host_lens, batch));
     {
         std::vector<const int*> seq_ids(batch);
         int                     off = 0;
@@ -1117,7 +1294,10 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
             seq_ids[b] = host_ids + off;
             off += host_lens[b];
         }
-        TM_TRY(prefill_slots(e, seq_ids.data(), host_lens, batch, 0, e->h_ttft_ms.data()));
+        const int rc = prefill_slots(e, seq_ids.data(), host_lens, batch, 0, e->h_ttft_ms.data());
+        e->mm_emb_index.clear();  // the prompt is in the cache: decode needs the slots' deltas only
+        e->mm_coords.clear();
+        TM_TRY(rc);
     }
 
     // ---- steady-state decode layout: one token per sequence ------------------------------------------
@@ -1156,6 +1336,7 @@ int tm_engine_score(tm_engine* e, const int* host_ids, const int* host_lens, int
     TM_REQUIRE(e->started, "engine not started");
     TM_REQUIRE(e->batch == 0 && !e->sched, "a batch is already admitted (release it first)");
     TM_REQUIRE(e->cfg.tp == 1 && !e->use_comm, "scoring at tp > 1 is not supported (the vocabulary is sharded across the ranks)");
+    TM_REQUIRE(e->h_mm.empty(), "tm_engine_score does not take multimodal input (tm_engine_set_multimodal(e, NULL, 0) clears it)");
     TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));
     const tm_engine_config& c = e->cfg;

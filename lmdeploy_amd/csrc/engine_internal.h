@@ -79,6 +79,14 @@ struct Layer {
     MoeBlock                 moe;
 };
 
+// host copy of one sequence's tm_mm_input (tm_engine_set_multimodal)
+struct MmSeqT {
+    int                 prompt_len = 0, n_pos = 0, delta = 0;
+    std::vector<half_t> rows;    // [n_rows][hidden]
+    std::vector<int>    ranges;  // [n_ranges][2]
+    std::vector<int>    pos;     // [n_pos][3]
+};
+
 }  // namespace tmk
 
 using namespace tmk;
@@ -180,6 +188,24 @@ struct tm_engine {
     // (rope_admit); a persistent device array, so a captured decode step sees the updates like it sees d_k_len.  nullptr: one table.
     int*             d_rope_row0 = nullptr;
     std::vector<int> h_rope_row0;
+    // Multimodal input (tm_engine_set_multimodal; static batch only).  A model with M-RoPE sections (tp 1, quant_policy != 42) keeps
+    // d_pos_delta [max_batch_size], the position delta of every batch slot: zeros unless the admitted batch carried deltas, read by
+    // every decode step of a static batch -- the fused prologue's pos_delta or the M-RoPE store -- so one captured graph serves text
+    // and multimodal batches.  nullptr: the engine launches exactly what it launched before the feature.
+    int              mrope_section[3] = {0, 0, 0};  // tm_engine_set_mrope_section (0 / 0 / 0: none)
+    int*             d_pos_delta = nullptr;
+    std::vector<tmk::MmSeqT> h_mm;       // armed by tm_engine_set_multimodal for the next tm_engine_prefill, which consumes it
+    // what tm_engine_prefill made of h_mm for prefill_slots (empty: no sequence of the batch carries multimodal input):
+    std::vector<std::vector<int>> mm_emb_index;  // per sequence [prompt_len]: row of d_emb_rows, -1 = the token table
+    std::vector<std::vector<int>> mm_coords;     // per sequence [prompt_len][3]: given coordinates, then linear position + delta
+    half_t* d_emb_rows   = nullptr;  // the batch's embedding rows, concatenated (grown on demand)
+    size_t  emb_rows_cap = 0;        // halves allocated
+    int*    d_emb_index  = nullptr;  // [max_tokens] of the current prefill iteration (allocated by the first multimodal prefill)
+    int*    d_mrope_pos  = nullptr;  // [max_tokens][3]
+    // set by prefill_slots() around ONE forward (nullptr: plain embedding / plain RoPE) and by forward() for a static decode step
+    const int* fw_emb_index = nullptr;
+    const int* fw_mrope_pos = nullptr;
+    const int* fw_pos_delta = nullptr;
 
     // batch state (device)
     int *d_next_ids = nullptr;

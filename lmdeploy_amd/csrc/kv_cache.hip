@@ -57,7 +57,15 @@ __device__ __forceinline__ float row_max(float v)
 // exists at D = 128 only (head_norm8 fixes 1/128 and the 16-partial tree); the launcher refuses it at D = 64, the bias works there.
 // SEQ: per-sequence RoPE tables (dynamic NTK) -- sequence b reads the rows [rope_row0[b], rope_row0[b] + max_pos) of cos_sin; the
 // position is clamped first, so a position past the end stays inside the sequence's own region.  Without SEQ rope_row0 is not read.
-template<int BITS, bool QKX, bool SEQ = false, int D = 128>
+// MROPE: multimodal RoPE in sections (Qwen2-VL; the reference's kChunked mode, rotary_embedding.h:112-193).  Frequency pair j of a head
+// takes its table row from one of three coordinates: t for j < sec_t, h for j < sec_th = sec_t + sec_h, w behind; the row is
+// clamp(c, 0, max_pos - 1), the (cos, sin) is entry j of that row, the rotation is the one below.  mrope_pos [total_tokens][3] holds
+// the coordinates of this launch's rows; nullptr: every row's three coordinates are its linear position + pos_delta[b] (decode, and
+// pos_delta == nullptr is a delta of 0).  The K/V row still lands at the LINEAR position.  A lane owns pairs [4 lane, 4 lane + 4):
+// when they lie in one section (always, for boundaries that are multiples of 4) it reads one 16-byte vector as the plain arm does,
+// a lane that straddles a boundary reads its four pairs one by one.  The variant's arguments are the pack M, empty without MROPE:
+// those instantiations keep the kernel arguments they had before the variant existed.
+template<int BITS, bool QKX, bool SEQ = false, int D = 128, bool MROPE = false, typename... M>
 __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__ qkv,
                                                             int q_heads,
                                                             const int* __restrict__ cu_q_len,
@@ -71,9 +79,12 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
                                                             const half_t* __restrict__ q_norm,
                                                             const half_t* __restrict__ k_norm,
                                                             float qk_eps,
-                                                            const int* __restrict__ rope_row0)
+                                                            const int* __restrict__ rope_row0,
+                                                            M... mr)
 {
     static_assert(D == 64 || D == 128, "head_dim 64 or 128");
+    static_assert(sizeof...(M) == (MROPE ? 4 : 0), "MROPE: (const int* mrope_pos, const int* pos_delta, int sec_t, int sec_th)");
+    static_assert(!MROPE || (!SEQ && D == 128 && BITS != kTqBits), "MROPE: one table, head_dim 128, KV bits 16 / 8 / 4");
     constexpr int  LPR     = D / 8;  // lanes per head row
     const KvLayout L       = cache.layout;
     const int      lane16  = threadIdx.x & (LPR - 1);  // lane inside the head row (0..7 at D = 64)
@@ -117,7 +128,46 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
         if constexpr (SEQ) {
             row += (size_t)rope_row0[b];  // 64-bit: max_batch x (session_len + 1) rows of 2 D bytes pass 2 GiB
         }
-        const half8_t cs = *(const half8_t*)(cos_sin + row * (D / 2) + lane16 * 4);
+        half8_t       cs;
+        if constexpr (MROPE) {
+            const auto mt        = std::tuple<const int*, const int*, int, int>(mr...);
+            const int* mrope_pos = std::get<0>(mt);
+            const int* pos_delta = std::get<1>(mt);
+            const int  sec_t = std::get<2>(mt), sec_th = std::get<3>(mt);
+            int c[3];
+            if (mrope_pos != nullptr) {  // grid-uniform
+                c[0] = mrope_pos[(size_t)token * 3];
+                c[1] = mrope_pos[(size_t)token * 3 + 1];
+                c[2] = mrope_pos[(size_t)token * 3 + 2];
+            }
+            else {
+                c[0] = c[1] = c[2] = pos + (pos_delta != nullptr ? pos_delta[b] : 0);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                c[a] = c[a] < 0 ? 0 : (c[a] < max_pos ? c[a] : max_pos - 1);
+            }
+            const int  j0   = lane16 * 4;  // this lane's first frequency pair
+            const auto axis = [&](int j) { return j < sec_t ? 0 : (j < sec_th ? 1 : 2); };
+            const int  a0   = axis(j0);
+            if (a0 == axis(j0 + 3)) {
+                const int r = a0 == 0 ? c[0] : (a0 == 1 ? c[1] : c[2]);
+                cs          = *(const half8_t*)(cos_sin + (size_t)r * (D / 2) + j0);
+            }
+            else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int     ai = axis(j0 + i);
+                    const int     r  = ai == 0 ? c[0] : (ai == 1 ? c[1] : c[2]);
+                    const half2_t e  = cos_sin[(size_t)r * (D / 2) + j0 + i];
+                    cs[2 * i]        = e[0];
+                    cs[2 * i + 1]    = e[1];
+                }
+            }
+        }
+        else {
+            cs = *(const half8_t*)(cos_sin + row * (D / 2) + lane16 * 4);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const half_t c  = cs[2 * i];
@@ -282,6 +332,66 @@ int launch_kv_rope_store(half_t*        qkv,
     }
 #undef TM_KV_STORE
 #undef TM_KV_STORE_D
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// launch_kv_rope_store with M-RoPE sections (kv_rope_store_kernel<.., MROPE = true>): one shared table, head_dim 128, KV bits 16 / 8 / 4.
+// No rope_row0: per-sequence tables (dynamic NTK) and sections do not meet -- tm_engine_set_mrope_section refuses rope_type 4.
+int launch_kv_rope_store_mrope(half_t*        qkv,
+                               int            q_heads,
+                               const int*     cu_q_len,
+                               const int*     k_len,
+                               int            batch,
+                               int            total_tokens,
+                               const half2_t* cos_sin,
+                               int            max_pos,
+                               const int*     mrope_pos,
+                               const int*     pos_delta,
+                               int            sec_t,
+                               int            sec_h,
+                               int            sec_w,
+                               KvCacheView    cache,
+                               hipStream_t    st,
+                               const half_t*  qkv_bias,
+                               const half_t*  q_norm,
+                               const half_t*  k_norm,
+                               float          qk_eps)
+{
+    const int hd  = cache.layout.head_dim;
+    const int kvb = cache.layout.bits;
+    TM_REQUIRE(kvb != kTqBits, "kv_rope_store: M-RoPE with kv bits 42 (TurboQuant) is not built");
+    TM_REQUIRE(hd != 64, "kv_rope_store: M-RoPE with head_dim 64 is not built (head_dim must be 128)");
+    TM_REQUIRE(hd == 128, "kv_rope_store: M-RoPE needs head_dim 128");
+    TM_REQUIRE(kvb == 16 || kvb == 8 || kvb == 4, "kv_rope_store: M-RoPE serves kv bits 16 / 8 / 4");
+    TM_REQUIRE(cos_sin != nullptr && max_pos >= 1, "kv_rope_store: M-RoPE needs a table");
+    TM_REQUIRE(sec_t >= 0 && sec_h >= 0 && sec_w >= 0 && sec_t + sec_h + sec_w == hd / 2,
+               "kv_rope_store: mrope sections must be three non-negative sizes that sum to head_dim / 2");
+    TM_REQUIRE((q_norm == nullptr) == (k_norm == nullptr), "q_norm and k_norm come together");
+    if (total_tokens == 0) {
+        return 0;
+    }
+    dim3       grid((total_tokens + 15) / 16, q_heads + 2 * cache.layout.kv_heads);
+    const bool qkx    = qkv_bias != nullptr || q_norm != nullptr;
+    const int  sec_th = sec_t + sec_h;
+#define TM_KV_STORE_M(B_, X_)                                                                                                     \
+    kv_rope_store_kernel<B_, X_, false, 128, true><<<grid, 256, 0, st>>>(qkv, q_heads, cu_q_len, k_len, batch, total_tokens, cos_sin, \
+                                                                         max_pos, cache, qkv_bias, q_norm, k_norm, qk_eps, nullptr,    \
+                                                                         mrope_pos, pos_delta, sec_t, sec_th)
+    switch (kvb) {
+        case 16:
+            if (qkx) TM_KV_STORE_M(16, true);
+            else TM_KV_STORE_M(16, false);
+            break;
+        case 8:
+            if (qkx) TM_KV_STORE_M(8, true);
+            else TM_KV_STORE_M(8, false);
+            break;
+        default:
+            if (qkx) TM_KV_STORE_M(4, true);
+            else TM_KV_STORE_M(4, false);
+    }
+#undef TM_KV_STORE_M
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -37,6 +37,45 @@ int launch_embedding(half_t* out, const half_t* table, const int* ids, int T, in
     return 0;
 }
 
+// Multimodal prompts (the reference's input_embeddings / input_embedding_ranges, turbomind.py:632-674 -> updateEmbedding,
+// LlamaBatch.cc): row t is row emb_index[t] of the request's rows when emb_index[t] >= 0 -- ids[t] is not read -- else the table row.
+__global__ __launch_bounds__(256) void embedding_mixed_kernel(half_t* __restrict__ out,
+                                                              const half_t* __restrict__ table,
+                                                              const int* __restrict__ ids,
+                                                              const half_t* __restrict__ emb_rows,
+                                                              const int* __restrict__ emb_index,
+                                                              int H,
+                                                              int vocab)
+{
+    const int     t  = blockIdx.x;
+    const int     ei = emb_index[t];
+    const half_t* src;
+    if (ei >= 0) {
+        src = emb_rows + (size_t)ei * H;
+    }
+    else {
+        int id = ids[t];
+        id     = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        src    = table + (size_t)id * H;
+    }
+    for (int v = threadIdx.x; v < H / 8; v += 256) {
+        *(half8_t*)(out + (size_t)t * H + v * 8) = *(const half8_t*)(src + v * 8);
+    }
+}
+
+int launch_embedding_mixed(half_t* out, const half_t* table, const int* ids, const half_t* emb_rows, const int* emb_index, int T, int H,
+                           int vocab, hipStream_t st)
+{
+    TM_REQUIRE(H % 8 == 0, "H % 8");
+    TM_REQUIRE(emb_rows != nullptr && emb_index != nullptr, "embedding_mixed: null emb_rows / emb_index");
+    if (T == 0) {
+        return 0;
+    }
+    embedding_mixed_kernel<<<T, 256, 0, st>>>(out, table, ids, emb_rows, emb_index, H, vocab);
+    TM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void gather_rows_kernel(half_t* __restrict__ out,
                                                           const half_t* __restrict__ in,
                                                           const int* __restrict__ rows,

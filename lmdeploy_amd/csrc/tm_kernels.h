@@ -75,6 +75,13 @@ int launch_kv_rope_store(half_t* qkv, int q_heads, const int* cu_q_len, const in
                          const half2_t* cos_sin, int max_pos, KvCacheView cache, hipStream_t st,
                          const half_t* qkv_bias = nullptr, const half_t* q_norm = nullptr, const half_t* k_norm = nullptr,
                          float qk_eps = 0.f, const int* rope_row0 = nullptr);
+// The same with M-RoPE in sections (Qwen2-VL): frequency pair j reads table row clamp(c, 0, max_pos - 1) of its section's coordinate
+// (t: j < sec_t, h: j < sec_t + sec_h, w behind).  mrope_pos device int [total_tokens][3]; nullptr: all three = linear position +
+// pos_delta[b] (pos_delta device int [batch], nullptr = 0).  One shared table (no per-sequence rows), head_dim 128, kv bits 16 / 8 / 4.
+int launch_kv_rope_store_mrope(half_t* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                               const half2_t* cos_sin, int max_pos, const int* mrope_pos, const int* pos_delta, int sec_t, int sec_h,
+                               int sec_w, KvCacheView cache, hipStream_t st, const half_t* qkv_bias = nullptr,
+                               const half_t* q_norm = nullptr, const half_t* k_norm = nullptr, float qk_eps = 0.f);
 
 // per-pair inverse frequencies of one RoPE recipe (rope_inv_freq, c_api.hip) + the factor on cos / sin (YaRN; 1 otherwise): what the
 // host table builder and rope_table_kernel share, so both build the same table
@@ -130,6 +137,9 @@ struct DecodeAttnParams {
     // join the softmax denominator and carry no value (nullptr = none).
     int            window = 0;
     const half_t*  sinks  = nullptr;
+    // Fused prologue only: per-sequence position delta (M-RoPE models, device int [batch]); the new token's RoPE row becomes
+    // clamp(k_len - 1 + pos_delta[b], 0, max_pos - 1).  nullptr: the prologue as it was (its own kernel instantiations).
+    const int*     pos_delta = nullptr;
 };
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip
@@ -523,6 +533,9 @@ inline uint64_t* gemm_trace_for(size_t workgroups, const char* tag = "", int gx 
 
 // ---- misc.hip ---------------------------------------------------------------------------
 int launch_embedding(half_t* out, const half_t* table, const int* ids, int T, int H, int vocab, hipStream_t st);
+// rows with emb_index[t] >= 0 are row emb_index[t] of emb_rows ([n][H] fp16, bit for bit; ids[t] is not read), the others the table's
+int launch_embedding_mixed(half_t* out, const half_t* table, const int* ids, const half_t* emb_rows, const int* emb_index, int T, int H,
+                           int vocab, hipStream_t st);
 int launch_fill_uniform_f16(half_t* out, size_t n, float amp, uint32_t seed, hipStream_t st);  // tuner stand-in activations
 int launch_argmax(int* out_ids, half_t* out_val, const half_t* logits, int B, int V, int ld, int id_offset,
                   hipStream_t st);

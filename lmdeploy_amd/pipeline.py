@@ -167,7 +167,7 @@ class Pipeline:
         return self.infer(prompts, gen_config, **kwargs)
 
     def infer(self, prompts, gen_config: GenerationConfig | None = None, **kwargs) -> list[Response] | Response:
-        single = isinstance(prompts, str) or (len(prompts) > 0 and isinstance(prompts[0], (int, np.integer)))
+        single = isinstance(prompts, (str, dict)) or (len(prompts) > 0 and isinstance(prompts[0], (int, np.integer)))
         batch = [prompts] if single else list(prompts)
         out = []
         for res in self._generate(batch, gen_config or GenerationConfig()):
@@ -224,11 +224,59 @@ class Pipeline:
 
     # ---- static batcher ----------------------------------------------------------------------------------
     def _encode(self, p) -> np.ndarray:
+        if isinstance(p, dict):     # a multimodal prompt (see _multimodal): its token ids
+            if 'input_ids' not in p:
+                raise ValueError('a dict prompt needs input_ids')
+            return np.asarray(p['input_ids'], np.int32).reshape(-1)
         if isinstance(p, str):
             if self.tokenizer is None:
                 raise ValueError('string prompts need a tokenizer in the model directory; pass token ids instead')
             return np.asarray(self.tokenizer.encode(p), np.int32)
         return np.asarray(p, np.int32)
+
+    MM_KEYS = ('input_ids', 'input_embeddings', 'input_embedding_ranges', 'mrope_position_ids', 'mrope_position_delta')
+
+    def _multimodal(self, p):
+        """A dict prompt, named as the reference names the engine's inputs (lmdeploy/turbomind/turbomind.py:632-674): input_ids;
+        input_embeddings, a list of [n_i, hidden] arrays, with input_embedding_ranges, a list of (begin, end) in prompt positions
+        (sorted, disjoint, range i as long as array i); mrope_position_ids [3, n] (n <= prompt length) and mrope_position_delta, both
+        optional.  Returns what Engine.set_multimodal takes, or None for a prompt without multimodal content; malformed input raises
+        ValueError here, before any engine call."""
+        if not isinstance(p, dict):
+            return None
+        unknown = sorted(set(p) - set(self.MM_KEYS))
+        if unknown:
+            raise ValueError(f'dict prompt: unknown keys {unknown} (known: {", ".join(self.MM_KEYS)})')
+        n, hidden = len(self._encode(p)), self.model_cfg.hidden
+        embs = [np.asarray(e) for e in (p.get('input_embeddings') if p.get('input_embeddings') is not None else [])]
+        ranges = [tuple(int(v) for v in r) for r in (p.get('input_embedding_ranges') if p.get('input_embedding_ranges') is not None else [])]
+        if len(embs) != len(ranges):
+            raise ValueError(f'dict prompt: {len(embs)} input_embeddings for {len(ranges)} input_embedding_ranges')
+        end = 0
+        for k, (e, r) in enumerate(zip(embs, ranges)):
+            if len(r) != 2 or not 0 <= r[0] < r[1] <= n:
+                raise ValueError(f'dict prompt: input_embedding_ranges[{k}] = {r} is not a non-empty [begin, end) inside the prompt of {n} tokens')
+            if r[0] < end:
+                raise ValueError(f'dict prompt: input_embedding_ranges[{k}] = {r} is unsorted or overlaps the range before it')
+            if e.ndim != 2 or e.shape != (r[1] - r[0], hidden):
+                raise ValueError(f'dict prompt: input_embeddings[{k}] has shape {tuple(e.shape)}, its range {r} needs ({r[1] - r[0]}, {hidden})')
+            end = r[1]
+        pos, delta = p.get('mrope_position_ids'), int(p.get('mrope_position_delta') or 0)
+        if pos is not None:
+            pos = np.asarray(pos)
+            if pos.ndim == 3 and pos.shape[1] == 1:     # [3, 1, n] as transformers hands it out
+                pos = pos[:, 0]
+            if pos.ndim != 2 or pos.shape[0] != 3 or pos.shape[1] > n or (pos < 0).any():
+                raise ValueError(f'dict prompt: mrope_position_ids must be [3, n <= {n}] non-negative integers, got shape {tuple(pos.shape)}')
+            pos = pos.astype(np.int32)
+        if delta < -n:
+            raise ValueError(f'dict prompt: mrope_position_delta {delta} < -{n} (the prompt length)')
+        if (pos is not None or delta) and not getattr(self.model_cfg, 'mrope_section', None):
+            raise ValueError('dict prompt: mrope_position_ids / mrope_position_delta on a model without M-RoPE sections')
+        if not embs and pos is None and not delta:
+            return None
+        return dict(prompt_len=n, input_embeddings=[e.astype(np.float16) for e in embs], input_embedding_ranges=ranges,
+                    mrope_position_ids=pos, mrope_position_delta=delta)
 
     def _stop_ids(self, g: GenerationConfig) -> set:
         ids = set(g.stop_token_ids or [])
@@ -248,6 +296,21 @@ class Pipeline:
             raise ValueError(f'at most {_ffi.MAX_BAD_IDS} bad token ids per request')
 
     def _generate(self, prompts: Sequence, g):
+        if any(self._multimodal(p) is not None for p in prompts):     # (validates every dict prompt before any engine call)
+            # multimodal input is a static-batch feature of the engine: what cannot run as one static batch is refused by name
+            if isinstance(g, (list, tuple)):
+                raise NotImplementedError('multimodal prompts with one GenerationConfig per prompt: those requests run through continuous '
+                                          'batching, which does not take multimodal input (pass one GenerationConfig)')
+            if len(prompts) > self.max_batch_size:
+                raise NotImplementedError(f'{len(prompts)} prompts with multimodal input exceed max_batch_size {self.max_batch_size}: they '
+                                          f'would run through continuous batching, which does not take multimodal input')
+            if self.backend_config.tp > 1:
+                raise NotImplementedError('multimodal prompts with tp > 1 are not built')
+            if int(self.backend_config.quant_policy) == 42:
+                raise NotImplementedError('multimodal prompts with quant_policy=42 (TurboQuant KV) are not built')
+            self._resolve_words(g)
+            yield from self._generate_static(prompts, g)
+            return
         if isinstance(g, (list, tuple)):            # one GenerationConfig per prompt (lmdeploy/pipeline.py:97-143)
             yield from sorted(self.generate_continuous(prompts, g), key=lambda r: r.index)
             return
@@ -264,6 +327,9 @@ class Pipeline:
         """Continuous batching (engine scheduler: tm_engine_submit / step / poll): any number of prompts, each request
         leaves the batch when it stops and the next waiting one takes its slot.  Yields Responses in completion order
         (stream=False) or incremental Responses after every scheduler step (stream=True, see stream_infer)."""
+        if any(self._multimodal(p) is not None for p in prompts):
+            raise NotImplementedError('multimodal prompts through continuous batching / streaming: multimodal input runs as a static batch '
+                                      '(infer / __call__ with one GenerationConfig and at most max_batch_size prompts)')
         ids = [self._encode(p) for p in prompts]
         if isinstance(g, (list, tuple)):            # per-request generation configs: every request carries its own
             if len(g) != len(ids):
@@ -350,6 +416,7 @@ class Pipeline:
 
     def _generate_static(self, prompts: Sequence, g: GenerationConfig):
         ids = [self._encode(p) for p in prompts]
+        mm = [self._multimodal(p) for p in prompts]
         stop = self._stop_ids(g)
         # per-request admission on the host as the reference does it (lmdeploy/serve/async_engine.py:561-565): only a prompt
         # that leaves no room for a single new token (len >= session_len) is refused with INPUT_LENGTH_ERROR; otherwise the
@@ -370,14 +437,19 @@ class Pipeline:
         for idx, max_new in sorted(chunks, key=lambda c: c[0][0]):
             chunk = [ids[i] for i in idx]
             try:
-                self.engine.set_sampling([g.sampling_params(i) for i in idx] if g.sampling_params() else None)
                 lp = g.logits_params(sorted(stop)[:_ffi.MAX_STOP_IDS])
-                self.engine.set_logits_params([lp] * len(chunk) if lp else None)
-                self.engine.set_logprobs(g.logprobs or 0)
-                if g.output_logits and (lp or self.backend_config.tp > 1):
+                if g.output_logits and (lp or self.backend_config.tp > 1):      # (before anything is handed to the engine)
                     # the engine's processors rewrite the logits in place and a tensor-parallel rank holds a vocabulary shard: what could be read
                     # back would not be the reference's output (the raw lm_head row, src/turbomind/models/language_model.cc OutputLogits)
                     raise NotImplementedError('output_logits together with repetition_penalty / min_new_tokens / bad_token_ids, or with tp > 1')
+                self.engine.set_sampling([g.sampling_params(i) for i in idx] if g.sampling_params() else None)
+                self.engine.set_logits_params([lp] * len(chunk) if lp else None)
+                self.engine.set_logprobs(g.logprobs or 0)
+                if any(mm[i] is not None for i in idx):
+                    # armed right in front of the prefill that consumes it: the engine drops the input when that prefill fails, so a
+                    # chunk without multimodal input never meets an earlier chunk's rows (and engines that never see a dict prompt --
+                    # the tensor-parallel rank group -- need no such entry)
+                    self.engine.set_multimodal([mm[i] if mm[i] is not None else dict(prompt_len=len(ids[i])) for i in idx])
                 self.engine.prefill(chunk, max_new_tokens=max_new)
                 step_logits = [self.engine.fetch_logits().copy()] if g.output_logits else None   # [batch, vocab] fp16 behind every step
                 done = 1

@@ -92,6 +92,7 @@ class ModelConfig:
     layer_windows: list | None = None  # gpt-oss: one sliding window per layer (0 = full attention), from `layer_types`
     w4_dialect: str = 'awq'            # weight_format 'u4': how the checkpoint packs its 4-bit linears: 'awq' | 'gptq' | 'compressed-tensors'
     w4_zero_offset: int = 1            # GPTQ: what is added to a stored qzeros nibble (1: the v1 form; 0: gptq_v2)
+    mrope_section: tuple | None = None  # Qwen2-VL / Qwen2.5-VL: frequency pairs rotated by the t / h / w coordinate (sum = head_dim / 2)
 
     @property
     def group_size(self) -> int:
@@ -121,6 +122,58 @@ QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM', 'Qw
 QWEN2_ARCHS = ('Qwen2ForCausalLM', 'Qwen2MoeForCausalLM')
 QWEN3_MOE_KEYS = ('num_experts', 'num_experts_per_tok', 'moe_intermediate_size')
 QWEN2_MOE_KEYS = QWEN3_MOE_KEYS + ('shared_expert_intermediate_size',)
+
+# Everything the reader knows about how a Qwen2-VL / Qwen2.5-VL checkpoint is laid out, in one place.  The language model is a Qwen2
+# decoder (the Qwen2 reader, every weight format it serves); the vision tower stays with PyTorch (lmdeploy_amd/vl.py) and its tensors
+# are never read here.  The nested form -- language config under `text_config`, weights under `model.language_model.` -- is what the
+# installed transformers writes and is tested against it.  The published form (Qwen/Qwen2-VL-*: language config at the top level of
+# config.json, weights under `model.` with `visual.*` next to them) was written down from memory of those checkpoints and could not be
+# checked against one: a correction is one edit here.
+QWEN_VL = dict(
+    archs=('Qwen2VLForConditionalGeneration', 'Qwen2_5_VLForConditionalGeneration'),
+    refused_prefixes=('Qwen3VL',),                            # interleaved M-RoPE and deep-stack features: not built
+    text_config='text_config',                                # nested language config (absent: the top level holds it)
+    language_prefixes=('model.language_model.', 'model.'),    # tried in this order; `<prefix>embed_tokens.weight` decides
+    vision_prefixes=('model.visual.', 'visual.'),             # skipped
+    rope_keys=('rope_parameters', 'rope_scaling'),            # transformers 5 / 4
+    rope_types=('default', 'mrope', None),
+    section='mrope_section',
+)
+
+
+def _qwen_vl_language_config(arch: str, c: dict) -> dict:
+    """config.json of a Qwen2-VL / Qwen2.5-VL checkpoint -> the config of its language model in the Qwen2 reader's terms (plus
+    `mrope_section`), or NotImplementedError naming what is not served"""
+    V = QWEN_VL
+    text = dict(c.get(V['text_config']) or {})
+    lc = dict(c, **text)                      # nested keys win; the published form has everything at the top level
+    for k in (V['text_config'], 'vision_config'):
+        lc.pop(k, None)
+    rp = None
+    for key in V['rope_keys']:
+        rp = text.get(key) or c.get(key)
+        if rp:
+            break
+    if not isinstance(rp, dict) or V['section'] not in rp:
+        raise NotImplementedError(f'{arch}: config.json lacks {V["section"]} (under {" / ".join(V["rope_keys"])})')
+    t = rp.get('rope_type', rp.get('type'))
+    if t not in V['rope_types']:
+        raise NotImplementedError(f'{arch} with rope type {t}: M-RoPE is built for the default frequencies only (yarn / dynamic are not)')
+    D = lc.get('head_dim') or lc['hidden_size'] // lc['num_attention_heads']
+    if D != 128:
+        raise NotImplementedError(f'{arch} with head_dim {D}: M-RoPE is built for head_dim 128')
+    sec = rp[V['section']]
+    ok = isinstance(sec, (list, tuple)) and len(sec) == 3 and all(isinstance(v, int) and not isinstance(v, bool) and v >= 0 for v in sec)
+    if not ok or sum(sec) != D // 2:
+        raise NotImplementedError(f'{arch} with mrope_section {sec!r}: three non-negative integers that sum to head_dim / 2 = {D // 2} '
+                                  f'are required')
+    if 'rope_theta' in rp:
+        lc['rope_theta'] = rp['rope_theta']
+    lc.pop('rope_scaling', None)              # the frequencies are the default ones: nothing left for the RoPE-scaling branch
+    lc.pop('rope_parameters', None)
+    lc['architectures'] = ['Qwen2ForCausalLM']
+    lc['mrope_section'] = tuple(int(v) for v in sec)
+    return lc
 
 
 def _qwen3_moe_fields(arch: str, c: dict, quantized: bool, keys: tuple = QWEN3_MOE_KEYS) -> dict:
@@ -470,6 +523,16 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
     arch = (c.get('architectures') or ['LlamaForCausalLM'])[0]
     if arch == 'GptOssForCausalLM':
         return _read_gpt_oss(arch, c, model_path, tp)
+    if arch.startswith(QWEN_VL['refused_prefixes']):
+        raise NotImplementedError(f'architecture {arch}: Qwen3-VL (interleaved M-RoPE, deep-stack visual features) is not built; the '
+                                  f'vision-language models served are Qwen2-VL and Qwen2.5-VL')
+    mrope_section = None
+    if arch in QWEN_VL['archs']:
+        c = _qwen_vl_language_config(arch, c)
+        mrope_section = c['mrope_section']
+        if c.get('use_sliding_window'):
+            raise NotImplementedError(f'{arch} with use_sliding_window: sliding-window attention is not implemented')
+        arch = 'Qwen2ForCausalLM'
     kind = 'internlm2' if 'InternLM2' in arch else 'llama'
     qwen = arch in QWEN_ARCHS
     internlm3 = arch == 'InternLM3ForCausalLM'      # a plain Llama (the reference: supported_models.py) -- without projection biases
@@ -580,7 +643,8 @@ def read_config(model_path: str, tp: int = 1) -> ModelConfig:
                        quantized=q is not None, eos_token_id=c.get('eos_token_id'),
                        max_position_embeddings=int(c.get('max_position_embeddings', 8192)), weight_format=wfmt, fp8_scale_mode=fp8_mode,
                        **moe, group=group, w4_dialect=w4, w4_zero_offset=zero_offset,
-                       attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)))
+                       attn_bias=attn_bias, qk_norm=qk_norm, window=window, tie_word_embeddings=bool(c.get('tie_word_embeddings', False)),
+                       mrope_section=mrope_section)
 
 
 def gpt_oss_expert_slots(tensors: dict, layer: int) -> dict:
@@ -843,10 +907,16 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
     D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
     layers = []
     llama_names = cfg.arch != 'internlm2'        # Llama / Mixtral / Qwen2 / Qwen3
+    root = 'model.'
+    if getattr(cfg, 'mrope_section', None):      # Qwen2-VL: the language model's prefix (QWEN_VL); the vision tensors are never read
+        found = [pfx for pfx in QWEN_VL['language_prefixes'] if pfx + 'embed_tokens.weight' in t]
+        if not found:
+            raise ValueError(f'{model_path}: no embed_tokens.weight under any of {QWEN_VL["language_prefixes"]}')
+        root = found[0]
     for i in range(cfg.layers):
         extra = {}
         if llama_names:
-            p = f'model.layers.{i}'
+            p = f'{root}layers.{i}'
             q = _linear(t, p + '.self_attn.q_proj', cfg.quantized)
             k = _linear(t, p + '.self_attn.k_proj', cfg.quantized)
             v = _linear(t, p + '.self_attn.v_proj', cfg.quantized)
@@ -920,8 +990,8 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
         layers.append(dict(attn_norm=n1.astype(np.float16), ffn_norm=n2.astype(np.float16), w_qkv=_cat([q, k, v]), wo=wo, **ffn,
                            **extra))
     if llama_names:
-        emb = t.get('model.embed_tokens.weight')
-        norm = t.get('model.norm.weight')
+        emb = t.get(root + 'embed_tokens.weight')
+        norm = t.get(root + 'norm.weight')
         tied = getattr(cfg, 'tie_word_embeddings', False) or 'lm_head.weight' not in t
         head = emb if tied else t.get('lm_head.weight')
     else:

@@ -43,6 +43,19 @@ def make_model_config(cfg, weight_type: int = 0) -> _ffi.ModelConfig:
                             int(bool(getattr(cfg, 'attn_bias', 0))), int(bool(getattr(cfg, 'qk_norm', 0))))
 
 
+def pack_embedding_rows(embs, hidden: int, valid: int) -> np.ndarray:
+    """input_embeddings (arrays [n_i, valid]) -> one fp16 [sum n_i, hidden] array in the engine's row width.  A model served zero-padded
+    (hidden_valid: gpt-oss 2880 -> 2944) takes rows of its own width `valid`; the pad columns are +0, as the loader pads the token table."""
+    embs = [np.asarray(e, np.float16) for e in embs]
+    for e in embs:
+        if e.ndim != 2 or e.shape[1] != valid:
+            raise ValueError(f'input_embeddings: an array of shape {tuple(e.shape)}, rows of the model\'s hidden size {valid} are needed')
+    rows = np.zeros((sum(len(e) for e in embs), hidden), np.float16)
+    if embs:
+        rows[:, :valid] = np.concatenate(embs)
+    return rows
+
+
 class Engine:
 
     def __init__(self, model_cfg: _ffi.ModelConfig, *, tp: int = 1, rank: int = 0, device: int = 0,
@@ -64,7 +77,15 @@ class Engine:
         layer_windows = getattr(cfg, 'layer_windows', None)
         if layer_windows is not None:
             eng.set_layer_windows(layer_windows)
+        mrope_section = getattr(cfg, 'mrope_section', None)
+        if mrope_section:
+            eng.set_mrope_section(mrope_section)
         return eng
+
+    def set_mrope_section(self, sections: Sequence[int]):
+        """the three M-RoPE section sizes (t, h, w) of a Qwen2-VL language model; before start()"""
+        t, h, w = (int(v) for v in sections)
+        _ffi.check(self._lib.tm_engine_set_mrope_section(self._h, t, h, w))
 
     def set_layer_windows(self, windows: Sequence[int]):
         """one sliding window per layer (0 = full attention), replacing the model config's window; before start()"""
@@ -198,6 +219,27 @@ class Engine:
         sel = np.zeros((self.batch, self.max_new), np.float32)
         _ffi.check(self._lib.tm_engine_fetch_logprobs(self._h, vals.ctypes.data, idx.ctypes.data, num.ctypes.data, sel.ctypes.data))
         return vals, idx, num, sel
+
+    def set_multimodal(self, inputs):
+        """Static batch: the multimodal inputs of the NEXT prefill, one entry per sequence -- None (text) or a dict with `prompt_len`
+        and, all optional, `input_embeddings` (list of [n_i, hidden] float16 arrays), `input_embedding_ranges` (list of (begin, end)),
+        `mrope_position_ids` ([3, n]: t / h / w of the first n prompt tokens) and `mrope_position_delta`.  None / empty clears."""
+        if not inputs or all(i is None for i in inputs):
+            _ffi.check(self._lib.tm_engine_set_multimodal(self._h, None, 0))
+            return
+        hidden = int(self.cfg.model.hidden)
+        valid = int(self.cfg.model.hidden_valid) or hidden
+        arr, keep = (_ffi.MmInput * len(inputs))(), []
+        for k, it in enumerate(inputs):
+            it = it or {}
+            rows = pack_embedding_rows(it.get('input_embeddings') or [], hidden, valid)
+            ranges = np.ascontiguousarray(np.asarray(it.get('input_embedding_ranges') or [], np.int32).reshape(-1, 2))
+            pos = it.get('mrope_position_ids')
+            pos = np.zeros((0, 3), np.int32) if pos is None else np.ascontiguousarray(np.asarray(pos, np.int32).reshape(3, -1).T)
+            keep += [rows, ranges, pos]
+            arr[k] = _ffi.MmInput(int(it.get('prompt_len', 0)), rows.ctypes.data, len(rows), ranges.ctypes.data, len(ranges),
+                                  pos.ctypes.data, len(pos), int(it.get('mrope_position_delta') or 0))
+        _ffi.check(self._lib.tm_engine_set_multimodal(self._h, arr, len(inputs)))
 
     def prefill(self, prompts: Sequence[Sequence[int]], max_new_tokens: int):
         lens = np.asarray([len(p) for p in prompts], np.int32)
