@@ -211,6 +211,35 @@ int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, 
 int tm_decode_attention_window(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
                                float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
                                const void* sinks, tm_stream_t st);
+/* Verify attention (speculative decoding): paged split-K flash-decode for q_len[b] = cu_q_len[b + 1] - cu_q_len[b] query rows per
+ * sequence, 1 <= q_len[b] <= 8, over int8 / int4 KV at head_dim 128 on the matrix cores.  The rows' K / V are in the cache already
+ * (tm_kv_rope_store first, the prefill convention): k_len[b] counts EVERY row of this forward, hist = k_len[b] - q_len[b], and query
+ * row j of sequence b sees the tokens t < hist + j + 1.  q fp16 [rows][q_stride] rotated, out fp16 [rows][q_heads * 128] in forward
+ * row order; cu_q_len, k_len: device.  A score column of the kernel is a (row, query head) pair of one kv head -- q_len * group columns
+ * in chunks of 16, so q_len * group <= 16 costs the cache bytes and the MFMA count of one decode token.  splits >= 1; the workspace
+ * (tm_verify_attention_workspace bytes for rows = cu_q_len[batch]) is needed when splits > 1.  The call reads cu_q_len and k_len
+ * back to check them (it synchronises the stream); the engine's own verify forward does not.  TM_INVALID by name: a q_len outside
+ * 1 .. 8, k_len[b] < q_len[b], fp16 KV, kv bits 42, head_dim 64 (those run tm_flatten_kv + tm_prefill_attention).  No window, no
+ * sinks, no fused prologue. */
+size_t tm_verify_attention_workspace(int rows, int q_heads, int splits);
+int    tm_verify_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int q_heads,
+                           float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st);
+/* The device side of speculative decoding by prompt lookup, one sequence batch at a time (operator level; the engine runs the same
+ * kernels).  State, all device int arrays: hist [batch][hist_stride] token history (prompt + emitted tokens) and hist_len [batch];
+ * emitted [batch] tokens emitted so far; generated [batch][max_new]; k_len [batch]; next_id [batch]; totals int64 [4] = (sequence-steps
+ * that emitted, drafted, accepted, emitted), added to.
+ * tm_spec_propose: per sequence, for n = ngram_max .. ngram_min the suffix hist[L - n : L] is looked up among the starts i with
+ * hist[i : i + n] == suffix and i + n <= L - 1; the largest i of the first n that matches gives drafts[b] = hist[i + n : min(i + n + k, L)],
+ * n_draft[b] its length capped at max_new - emitted[b] - 1 (0: no match).  drafts [batch][k] (unused entries 0).
+ * tm_spec_accept: out_ids [batch][k + 1] = the greedy token behind every row of the verify forward (row 0 = next_id, rows 1 .. k the
+ * drafts); a = the longest prefix of the n_draft drafts with out_ids[j] == drafts[j]; out_ids[0 .. a] are emitted, cut at max_new -
+ * emitted[b], appended to generated and hist; k_len += emitted, next_id = the last one; step_emitted [batch] (may be NULL) receives the
+ * count.  A sequence with emitted == max_new is left alone.  1 <= k <= 7, 1 <= ngram_min <= ngram_max <= 8. */
+int tm_spec_propose(int* drafts, int* n_draft, const int* hist, int hist_stride, const int* hist_len, const int* emitted, int max_new,
+                    int batch, int k, int ngram_max, int ngram_min, tm_stream_t st);
+int tm_spec_accept(const int* out_ids, const int* drafts, const int* n_draft, int* hist, int hist_stride, int* hist_len, int* emitted,
+                   int* generated, int max_new, int* k_len, int* next_id, int64_t* totals, int* step_emitted, int batch, int k,
+                   tm_stream_t st);
 /* Causal prefill attention over flattened KV (dispatchAttention).  vt is the transposed V of tm_flatten_kv.  head_dim 128;
  * softmax_scale <= 0 -> 1/sqrt(128). */
 int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
@@ -732,6 +761,31 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
 /* run `steps` decode iterations for the admitted batch (every sequence generates one token per step,
  * ignore_eos semantics).  Asynchronous on the engine stream; tm_engine_sync() waits. */
 int tm_engine_decode(tm_engine* e, int steps);
+/* Speculative decoding by prompt lookup (n-gram drafting) for a static batch of greedy sequences: a step verifies k drafted tokens per
+ * sequence in ONE forward over batch * (k + 1) rows and emits 1 .. k + 1 tokens per sequence -- the tokens plain greedy decoding emits.
+ * tm_engine_set_speculative: before tm_engine_prefill (after tm_engine_start); k = 0 switches it off, 1 <= k <= 7, 1 <= ngram_min <=
+ *   ngram_max <= 8.  Armed, tm_engine_prefill reserves k tokens of KV slack per sequence (prompt + max_new_tokens + k <= session_len):
+ *   the rows behind the accepted ones are computed, stored and never read -- the next step overwrites them.
+ * tm_engine_decode_spec: `steps` steps of propose (from the device token history) -> verify forward -> accept; asynchronous.  The
+ *   forward is the prefill-shaped one (plain w_qkv, K/V store, then tm_verify_attention's kernel for int8 / int4 KV at head_dim 128,
+ *   flatten + prefill attention otherwise), the lm_head over every row, arg-max.  With use_graph the step is captured as one linear
+ *   chain after an eager first step (the flatten + prefill-attention path stays eager: it needs host-side maximum lengths).
+ * tm_engine_verify: one step with the caller's drafts (host_drafts [batch][k] ids in [0, vocab), host_n_draft [batch] in [0, k]) in
+ *   place of the proposer: where a draft model plugs in.  Synchronous.
+ * tm_engine_fetch_spec: host_tokens [batch][max_new_tokens], host_counts [batch] tokens emitted per sequence (the prefill's first
+ *   token included); tokens of a sequence stop at max_new_tokens (ignore_eos semantics: the host cuts at stop ids).
+ * tm_engine_fetch_spec_logits: logits of the last step's rows, fp16 [batch][k + 1][vocab] (row j: the distribution behind input row j).
+ * tm_engine_spec_stats: (sequence-steps that emitted, drafted, accepted, emitted) since tm_engine_set_speculative; emitted = accepted +
+ *   sequence-steps.
+ * Refused with TM_INVALID by name: tp > 1, quant_policy 42, a layer with a sliding window or sinks, M-RoPE sections, multimodal input,
+ * sampling / logits processors / logprobs armed for the batch, a continuous-batching session while k > 0 (tm_engine_submit*,
+ * tm_engine_step*, tm_engine_serve_start), tm_engine_decode on a batch admitted with k > 0 after a speculative step. */
+int tm_engine_set_speculative(tm_engine* e, int k, int ngram_max, int ngram_min);
+int tm_engine_decode_spec(tm_engine* e, int steps);
+int tm_engine_verify(tm_engine* e, const int* host_drafts, const int* host_n_draft);
+int tm_engine_fetch_spec(tm_engine* e, int* host_tokens, int* host_counts);
+int tm_engine_fetch_spec_logits(tm_engine* e, void* host_out);
+int tm_engine_spec_stats(tm_engine* e, int64_t* host_stats);
 /* Prompt scoring (Pipeline.get_ppl; the reference's return_ppl path, models/output_processor.cc:236-300).  Synchronous.
  * `batch` sequences (host ids concatenated, host lens) run through chunked prefill with the lm_head over EVERY prompt row and
  * per-row cross-entropy against the next token, from the raw logits (no penalties, bans or sampling).  host_nll receives

@@ -145,6 +145,18 @@ _SIGNATURES = {
     'tm_decode_attention_fused_qk': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_float, c_void_p, c_int, c_int, c_float, c_int, c_void_p, POINTER(KvCache),
                                              c_void_p]),
+    'tm_verify_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'tm_verify_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
+                                    POINTER(KvCache), c_void_p]),
+    'tm_spec_propose': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'tm_spec_accept': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'tm_engine_set_speculative': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'tm_engine_decode_spec': (c_int, [c_void_p, c_int]),
+    'tm_engine_verify': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'tm_engine_fetch_spec': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'tm_engine_fetch_spec_logits': (c_int, [c_void_p, c_void_p]),
+    'tm_engine_spec_stats': (c_int, [c_void_p, c_void_p]),
     'tm_prefill_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'tm_prefill_attention_hd': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

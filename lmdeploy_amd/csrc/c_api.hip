@@ -412,6 +412,83 @@ int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, 
     return launch_decode_attention(p, (hipStream_t)st);
 }
 
+size_t tm_verify_attention_workspace(int rows, int q_heads, int splits)
+{
+    return decode_attention_workspace_bytes(rows, q_heads, 128, splits);
+}
+
+int tm_verify_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int q_heads,
+                        float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st)
+{
+    TM_REQUIRE(out && q && cu_q_len && k_len && cache, "null pointer");
+    TM_REQUIRE(batch >= 0, "batch >= 0");
+    if (batch == 0) {
+        return 0;
+    }
+    // the operator-level call checks its row counts on the host (the engine's verify forward knows them: batch x (k + 1))
+    std::vector<int> cu((size_t)batch + 1), kl((size_t)batch);
+    TM_HIP_CHECK(hipMemcpyAsync(cu.data(), cu_q_len, cu.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)st));
+    TM_HIP_CHECK(hipMemcpyAsync(kl.data(), k_len, kl.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)st));
+    TM_HIP_CHECK(hipStreamSynchronize((hipStream_t)st));
+    int max_q = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int ql = cu[b + 1] - cu[b];
+        TM_REQUIRE(ql >= 1 && ql <= kVerifyMaxRows, "tm_verify_attention: 1 <= q_len[b] <= 8 rows per sequence");
+        TM_REQUIRE(kl[b] >= ql, "tm_verify_attention: k_len[b] counts every row of the forward (k_len[b] >= q_len[b])");
+        max_q = std::max(max_q, ql);
+    }
+    TM_REQUIRE(cu[0] == 0, "tm_verify_attention: cu_q_len[0] must be 0");
+    const int        rows = cu[batch];
+    VerifyAttnParams p{};
+    p.q          = (const half_t*)q;
+    p.q_stride   = q_stride;
+    p.out        = (half_t*)out;
+    p.cu_q_len   = cu_q_len;
+    p.k_len      = k_len;
+    p.batch      = batch;
+    p.q_heads    = q_heads;
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)cache->head_dim);
+    p.scale_log2 = s * 1.4426950408889634f;
+    p.splits     = splits < 1 ? 1 : splits;
+    p.partial_o  = (float*)workspace;
+    p.partial_ml = workspace ? (float*)workspace + (size_t)rows * q_heads * p.splits * 128 : nullptr;
+    p.cache      = to_view(cache);
+    p.max_q_len  = max_q;
+    return launch_verify_attention(p, (hipStream_t)st);
+}
+
+int tm_spec_propose(int* drafts, int* n_draft, const int* hist, int hist_stride, const int* hist_len, const int* emitted, int max_new,
+                    int batch, int k, int ngram_max, int ngram_min, tm_stream_t st)
+{
+    TM_REQUIRE(drafts && n_draft && hist && hist_len && emitted, "null pointer");
+    TM_REQUIRE(batch >= 1 && k >= 1 && k <= kSpecMaxDraft, "tm_spec_propose: batch >= 1, 1 <= k <= 7");
+    TM_REQUIRE(hist_stride >= 1 && max_new >= 1, "tm_spec_propose: hist_stride >= 1, max_new >= 1");
+    SpecState s{};  // the proposer reads hist, hist_len and emitted only
+    s.hist        = const_cast<int*>(hist);
+    s.hist_stride = hist_stride;
+    s.hist_len    = const_cast<int*>(hist_len);
+    s.emitted     = const_cast<int*>(emitted);
+    s.max_new     = max_new;
+    return launch_spec_propose(drafts, n_draft, s, batch, k, ngram_max, ngram_min, (hipStream_t)st);
+}
+
+int tm_spec_accept(const int* out_ids, const int* drafts, const int* n_draft, int* hist, int hist_stride, int* hist_len, int* emitted,
+                   int* generated, int max_new, int* k_len, int* next_id, int64_t* totals, int* step_emitted, int batch, int k,
+                   tm_stream_t st)
+{
+    SpecState s{};
+    s.hist        = hist;
+    s.hist_stride = hist_stride;
+    s.hist_len    = hist_len;
+    s.emitted     = emitted;
+    s.generated   = generated;
+    s.max_new     = max_new;
+    s.k_len       = k_len;
+    s.next_id     = next_id;
+    s.totals      = (long long*)totals;
+    return launch_spec_accept(out_ids, drafts, n_draft, s, batch, k, step_emitted, (hipStream_t)st);
+}
+
 int tm_prefill_attention(void* out, const void* q, int q_stride, const void* k, const void* vt, int k_stride,
                          const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                          int q_heads, int kv_heads, float softmax_scale, tm_stream_t st)

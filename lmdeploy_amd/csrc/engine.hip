@@ -1033,6 +1033,9 @@ int tm_engine_destroy(tm_engine* e)
     if (e->graph) {
         (void)hipGraphExecDestroy(e->graph);
     }
+    if (e->graph_spec) {
+        (void)hipGraphExecDestroy(e->graph_spec);
+    }
     if (e->graph_cb) {
         (void)hipGraphExecDestroy(e->graph_cb);
     }
@@ -1091,7 +1094,9 @@ int tm_engine_destroy(tm_engine* e)
                     e->d_tmp, e->d_logits, e->d_last, e->d_gemm_ws, e->scratch.xq, e->scratch.sx, e->d_attn_ws, e->d_kflat, e->d_vflat, e->d_rope,
                     e->d_ids, e->d_k_len, e->d_cu_q, e->d_cu_q_b, e->d_cu_koff, e->d_rows, e->d_generated, e->d_step,
                     e->d_prefill_ids, e->d_argmax_val, e->d_cand, e->d_cand_all, e->d_next_ids, e->d_ss, e->d_tickets,
-                    e->d_rope_row0, e->d_pos_delta, e->d_emb_rows, e->d_emb_index, e->d_mrope_pos};
+                    e->d_rope_row0, e->d_pos_delta, e->d_emb_rows, e->d_emb_index, e->d_mrope_pos, e->d_spec_hist, e->d_spec_len,
+                    e->d_spec_emitted, e->d_spec_drafts, e->d_spec_ndraft, e->d_spec_ids, e->d_spec_out, e->d_spec_cu_q, e->d_spec_k_len,
+                    e->d_spec_step, e->d_spec_totals, e->d_spec_logits, e->d_spec_attn_ws};
     for (void* p : bufs) {
         if (p) {
             (void)hipFree(p);

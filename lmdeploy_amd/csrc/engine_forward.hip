@@ -273,6 +273,28 @@ static int prefill_attention_block(tm_engine* e, const Layer& L, const KvCacheVi
     return 0;
 }
 
+// verify attention of R's sequences (speculative decoding: max_q_len = k + 1 rows each; their K/V stored before: kv_store) straight over
+// the paged cache -- int8 / int4 KV at head_dim 128, no window, no sinks (tm_engine_set_speculative refuses those models)
+static int verify_attention_block(tm_engine* e, const KvCacheView& cv, const Rows& R, int max_q_len, float scale_log2)
+{
+    VerifyAttnParams p{};
+    p.q          = e->d_qkv + (size_t)R.r0 * e->qkv_n;
+    p.q_stride   = e->qkv_n;
+    p.out        = e->d_attn + (size_t)R.r0 * e->q_heads * e->D;
+    p.cu_q_len   = R.cu_q;
+    p.k_len      = R.k_len;
+    p.batch      = R.nseq;
+    p.q_heads    = e->q_heads;
+    p.scale_log2 = scale_log2;
+    p.splits     = e->decode_splits;
+    p.partial_o  = e->d_spec_attn_ws;
+    p.partial_ml = e->d_spec_attn_ws + (size_t)R.rows * e->q_heads * e->decode_splits * e->D;
+    p.cache      = cv;
+    p.max_q_len  = max_q_len;
+    TM_PROF(P_ATTN, TM_TRY(launch_verify_attention(p, e->stream)));
+    return 0;
+}
+
 // decode attention of R's one-token sequences on stream `st`: a pure decode step, or the leading decode rows of a mixed forward.
 // prologue_slabs >= 1: the kernel's fused prologue (bias, q/k norm, RoPE, K/V quantise-store) reads the raw projection -- 1: the fp16 rows
 // of d_qkv, > 1: that many fp32 split-K slabs in d_gemm_ws; 0 (fp16 KV, head_dim 64, windows, per-sequence RoPE): kv_store first
@@ -654,7 +676,12 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
                     TM_HIP_CHECK(hipEventRecord(e->ev_aux_join, e->aux_stream));
                 }
             }
-            TM_TRY(prefill_attention_block(e, L, cv, own, max_q_len, max_k_len, kflat_stride, scale_log2));
+            if (e->fw_verify && e->spec_mfma) {
+                TM_TRY(verify_attention_block(e, cv, own, max_q_len, scale_log2));
+            }
+            else {
+                TM_TRY(prefill_attention_block(e, L, cv, own, max_q_len, max_k_len, kflat_stride, scale_log2));
+            }
             if (aux) {
                 TM_HIP_CHECK(hipStreamWaitEvent(st, e->ev_aux_join, 0));  // join: wo reads the decode rows' attention output too
             }
@@ -676,6 +703,12 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     if (e->scoring) {
         TM_REQUIRE(!decode && !md && !e->use_comm, "internal: scoring forward");
         return score_rows(e, M);
+    }
+    if (e->fw_verify) {  // speculative decoding: the greedy token behind EVERY row
+        TM_REQUIRE(!decode && !md && !e->use_comm, "internal: verify forward");
+        TM_PROF(P_LM_HEAD, TM_TRY(linear_plain(e, e->output, e->d_x, e->hidden, e->d_spec_logits, e->vocab_local, M, false)));
+        TM_PROF(P_SAMPLE, TM_TRY(launch_argmax(e->d_spec_out, nullptr, e->d_spec_logits, M, e->vocab_local, e->vocab_local, 0, st)));
+        return 0;
     }
     if (decode) {
         return head(e, e->d_x, nseq, slot0, d_ids, nullptr, M, e->d_k_len);
@@ -703,6 +736,77 @@ static int decode_step(tm_engine* e)
     TM_HIP_CHECK(hipGetLastError());
     TM_TRY(forward(e, e->d_ids, e->batch, e->batch, true, 1, 0, 0, 0));
     return commit_tokens(e);
+}
+
+// ---- speculative decoding by prompt lookup (speculative.hip) -----------------------------------------------------------
+// The batch state the device-side proposer / acceptance work on: the decode arrays (d_k_len = tokens in the cache, d_ids = the last
+// emitted token = row 0 of the next forward, d_generated [batch][max_new]) + the token history and per-sequence counters.
+static SpecState spec_state(const tm_engine* e)
+{
+    SpecState s{};
+    s.hist        = e->d_spec_hist;
+    s.hist_stride = e->cfg.session_len;
+    s.hist_len    = e->d_spec_len;
+    s.emitted     = e->d_spec_emitted;
+    s.generated   = e->d_generated;
+    s.max_new     = e->max_new;
+    s.k_len       = e->d_k_len;
+    s.next_id     = e->d_ids;
+    s.totals      = e->d_spec_totals;
+    return s;
+}
+
+// The flatten + prefill-attention path of the verify forward (fp16 KV, head_dim 64) needs what no kernel can tell the host: the longest
+// context and the sequences' offsets in the flat scratch.  Reads d_k_len back (a synchronisation per step: this path is never captured).
+static int spec_host_lengths(tm_engine* e, int* max_k_len)
+{
+    std::vector<int> kl(e->batch), koff(e->batch + 1, 0);
+    TM_HIP_CHECK(hipMemcpyAsync(kl.data(), e->d_k_len, (size_t)e->batch * 4, hipMemcpyDeviceToHost, e->stream));
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    *max_k_len = 0;
+    for (int b = 0; b < e->batch; ++b) {
+        const int n = kl[b] + e->spec_k + 1;
+        *max_k_len  = std::max(*max_k_len, n);
+        koff[b + 1] = koff[b] + (n + 63) / 64 * 64;
+    }
+    TM_REQUIRE(koff.back() <= e->kflat_stride,
+               "speculative decoding on the flatten + prefill-attention path (fp16 KV / head_dim 64): the batch's contexts do not fit the "
+               "flatten scratch -- lower the batch or the context, or use int8 / int4 KV at head_dim 128");
+    TM_HIP_CHECK(hipMemcpyAsync(e->d_cu_koff, koff.data(), koff.size() * 4, hipMemcpyHostToDevice, e->stream));
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));  // koff is pageable
+    return 0;
+}
+
+// rows (last token + drafts) -> verify forward over batch * (k + 1) rows -> acceptance.  The forward is the prefill-shaped one over the
+// step's own per-sequence arrays (cu_q = (k + 1) b, k_len = tokens in the cache + k + 1): plain w_qkv, K/V store, attention, lm_head
+// over every row, arg-max -- no fused prologue, no folded norm.
+static int spec_verify_accept(tm_engine* e)
+{
+    const SpecState s  = spec_state(e);
+    const int       k1 = e->spec_k + 1;
+    int             max_k_len = 0;
+    if (!e->spec_mfma) {
+        TM_TRY(spec_host_lengths(e, &max_k_len));
+    }
+    TM_TRY(launch_spec_rows(e->d_spec_ids, e->d_spec_k_len, e->d_spec_drafts, s, e->batch, e->spec_k, e->stream));
+    int* const cu_q  = e->d_cu_q;
+    int* const k_len = e->d_k_len;
+    e->d_cu_q        = e->d_spec_cu_q;
+    e->d_k_len       = e->d_spec_k_len;
+    e->fw_verify     = true;
+    const int rc     = forward(e, e->d_spec_ids, e->batch * k1, e->batch, false, k1, max_k_len, e->kflat_stride, 0);
+    e->fw_verify     = false;
+    e->d_cu_q        = cu_q;
+    e->d_k_len       = k_len;
+    TM_TRY(rc);
+    return launch_spec_accept(e->d_spec_out, e->d_spec_drafts, e->d_spec_ndraft, s, e->batch, e->spec_k, e->d_spec_step, e->stream);
+}
+
+static int spec_step(tm_engine* e)
+{
+    TM_TRY(launch_spec_propose(e->d_spec_drafts, e->d_spec_ndraft, spec_state(e), e->batch, e->spec_k, e->spec_ngram_max, e->spec_ngram_min,
+                               e->stream));
+    return spec_verify_accept(e);
 }
 
 }  // namespace tmk
@@ -1170,6 +1274,7 @@ int tm_engine_release(tm_engine* e)
     e->h_blocks.clear();
     e->h_len.clear();
     e->batch      = 0;
+    e->spec_batch = false;
     e->steps_done = 0;
     e->steps_fetched = 0;
     e->h_sampling.clear();
@@ -1205,6 +1310,15 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     TM_REQUIRE(e->batch == 0 && !e->sched, "a batch is already admitted (release it first)");
     TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
     TM_REQUIRE(max_new_tokens >= 1, "max_new_tokens >= 1");
+    // speculation armed (tm_engine_set_speculative, k > 0): a greedy text batch only, and k tokens of KV slack behind every sequence --
+    // the rows of a verify forward behind the accepted ones are stored, never read, and overwritten by the next step
+    const int spec_slack = e->spec_k;
+    if (spec_slack > 0) {
+        TM_REQUIRE(mm.empty(), "speculative decoding does not take multimodal input (tm_engine_set_speculative with k = 0 first)");
+        TM_REQUIRE(e->h_sampling.empty(), "speculative decoding is greedy: sampling parameters are armed (tm_engine_set_sampling)");
+        TM_REQUIRE(e->h_logits.empty(), "speculative decoding is greedy: logits processors are armed (tm_engine_set_logits_params)");
+        TM_REQUIRE(e->logprobs_next == 0, "speculative decoding does not record logprobs (tm_engine_set_logprobs)");
+    }
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));
     const tm_engine_config& c = e->cfg;
 
@@ -1212,11 +1326,12 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     int64_t need = 0;
     for (int b = 0; b < batch; ++b) {
         TM_REQUIRE(host_lens[b] >= 1, "empty prompt");
-        if (host_lens[b] + max_new_tokens > c.session_len) {
-            set_last_error("prompt + max_new_tokens exceeds session_len");
+        if (host_lens[b] + max_new_tokens + spec_slack > c.session_len) {
+            set_last_error(spec_slack ? "prompt + max_new_tokens + speculative tokens exceeds session_len" :
+                                        "prompt + max_new_tokens exceeds session_len");
             return TM_TOO_LONG;
         }
-        need += kv_blocks_owned((host_lens[b] + max_new_tokens + 63) / 64, e->ring_blocks);
+        need += kv_blocks_owned((host_lens[b] + max_new_tokens + spec_slack + 63) / 64, e->ring_blocks);
     }
     if (need > (int64_t)e->free_blocks.size()) {
         set_last_error("out of KV cache blocks");
@@ -1225,7 +1340,7 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     std::vector<uint64_t> ptrs((size_t)batch * e->max_blocks_per_seq, 0);
     e->h_blocks.assign(batch, {});
     for (int b = 0; b < batch; ++b) {
-        const int nb = (host_lens[b] + max_new_tokens + 63) / 64;
+        const int nb = (host_lens[b] + max_new_tokens + spec_slack + 63) / 64;
         for (int i = 0; i < kv_blocks_owned(nb, e->ring_blocks); ++i) {
             e->h_blocks[b].push_back(e->free_blocks.back());
             e->free_blocks.pop_back();
@@ -1312,6 +1427,20 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     TM_TRY(commit_tokens(e));
     TM_HIP_CHECK(hipStreamSynchronize(e->stream));
     e->steps_done = 1;
+    e->spec_batch = spec_slack > 0;
+    if (e->spec_batch) {  // the device token history: the prompts, then the first token
+        std::vector<int> hist((size_t)batch * c.session_len, 0);
+        for (int b = 0, off = 0; b < batch; off += host_lens[b], ++b) {
+            std::copy(host_ids + off, host_ids + off + host_lens[b], hist.begin() + (size_t)b * c.session_len);
+        }
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_spec_hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, e->stream));
+        TM_TRY(launch_spec_begin(spec_state(e), batch, e->stream));
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));  // hist is pageable
+        if (e->graph_spec && (e->graph_spec_batch != batch || e->graph_spec_max_new != max_new_tokens || e->graph_spec_k != e->spec_k)) {
+            (void)hipGraphExecDestroy(e->graph_spec);  // batch, max_new and k are captured kernel arguments
+            e->graph_spec = nullptr;
+        }
+    }
 
     setup_decode(e, batch);
     if (e->graph && (e->graph_batch != batch || e->graph_max_new != max_new_tokens || e->graph_sampling != e->sampling_on
@@ -1482,6 +1611,7 @@ int tm_engine_decode(tm_engine* e, int steps)
     }
     TM_REQUIRE(e && e->batch > 0, "no admitted batch");
     TM_REQUIRE(!e->sched, "continuous-batching session active: use tm_engine_step");
+    TM_REQUIRE(!e->spec_batch, "the batch was admitted with speculation armed: use tm_engine_decode_spec / tm_engine_verify");
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));
     if (e->steps_done + steps > e->max_new) {
         set_last_error("decode past max_new_tokens");
@@ -1512,6 +1642,163 @@ int tm_engine_decode(tm_engine* e, int steps)
         }
     }
     e->steps_done += steps;
+    return 0;
+}
+
+int tm_engine_set_speculative(tm_engine* e, int k, int ngram_max, int ngram_min)
+{
+    if (e && e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    TM_REQUIRE(e, "null pointer");
+    TM_REQUIRE(e->batch == 0, "set the speculative configuration before tm_engine_prefill (a batch is admitted)");
+    if (k == 0) {
+        e->spec_k = 0;
+        return 0;
+    }
+    TM_REQUIRE(!e->sched, "speculative decoding: a continuous-batching session is open (continuous batching does not speculate)");
+    TM_REQUIRE(e->started, "engine not started");
+    TM_REQUIRE(k >= 1 && k <= kSpecMaxDraft, "speculative decoding: 1 <= k <= 7 (k + 1 rows per sequence in the verify attention)");
+    TM_REQUIRE(1 <= ngram_min && ngram_min <= ngram_max && ngram_max <= kSpecMaxNgram,
+               "speculative decoding: 1 <= ngram_min <= ngram_max <= 8");
+    const tm_engine_config& c = e->cfg;
+    TM_REQUIRE(c.tp == 1 && !e->use_comm, "speculative decoding with tp > 1 is not built");
+    TM_REQUIRE(c.quant_policy != 42, "speculative decoding with quant_policy 42 (TurboQuant KV) is not built");
+    TM_REQUIRE(!e->windowed, "speculative decoding with a sliding window or attention sinks is not built");
+    TM_REQUIRE(e->mrope_section[0] + e->mrope_section[1] + e->mrope_section[2] == 0,
+               "speculative decoding with M-RoPE sections (multimodal models) is not built");
+    const int B = c.max_batch_size;
+    TM_REQUIRE((int64_t)B * (k + 1) <= e->max_tokens,
+               "speculative decoding: max_batch_size * (k + 1) rows exceed one forward (raise max_prefill_token_num)");
+    TM_HIP_CHECK(hipSetDevice(c.device));
+    if (!e->d_spec_hist) {
+        TM_TRY(dmalloc(&e->d_spec_hist, (size_t)B * c.session_len));
+        TM_TRY(dmalloc(&e->d_spec_len, (size_t)B));
+        TM_TRY(dmalloc(&e->d_spec_emitted, (size_t)B));
+        TM_TRY(dmalloc(&e->d_spec_ndraft, (size_t)B));
+        TM_TRY(dmalloc(&e->d_spec_k_len, (size_t)B));
+        TM_TRY(dmalloc(&e->d_spec_step, (size_t)B));
+        TM_TRY(dmalloc(&e->d_spec_cu_q, (size_t)B + 1));
+        TM_TRY(dmalloc(&e->d_spec_totals, (size_t)4));
+        TM_HIP_CHECK(hipMemset(e->d_spec_totals, 0, 4 * sizeof(long long)));
+    }
+    if (k > e->spec_cap_k) {  // the buffers that scale with k
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+        for (void* q : {(void*)e->d_spec_drafts, (void*)e->d_spec_ids, (void*)e->d_spec_out, (void*)e->d_spec_logits, (void*)e->d_spec_attn_ws}) {
+            if (q) {
+                (void)hipFree(q);
+            }
+        }
+        e->d_spec_drafts = e->d_spec_ids = e->d_spec_out = nullptr;
+        e->d_spec_logits = nullptr, e->d_spec_attn_ws = nullptr, e->spec_cap_k = 0;
+        const size_t rows = (size_t)B * (k + 1);
+        TM_TRY(dmalloc(&e->d_spec_drafts, (size_t)B * k));
+        TM_TRY(dmalloc(&e->d_spec_ids, rows));
+        TM_TRY(dmalloc(&e->d_spec_out, rows));
+        TM_TRY(dmalloc(&e->d_spec_logits, rows * e->vocab_local));
+        TM_HIP_CHECK(hipMalloc((void**)&e->d_spec_attn_ws, decode_attention_workspace_bytes((int)rows, e->q_heads, 128, 16)));
+        e->spec_cap_k = k;
+    }
+    std::vector<int> cu(B + 1);
+    for (int b = 0; b <= B; ++b) {
+        cu[b] = b * (k + 1);
+    }
+    TM_HIP_CHECK(hipMemcpy(e->d_spec_cu_q, cu.data(), cu.size() * 4, hipMemcpyHostToDevice));
+    e->spec_k         = k;
+    e->spec_ngram_max = ngram_max;
+    e->spec_ngram_min = ngram_min;
+    e->spec_mfma      = (c.quant_policy == 8 || c.quant_policy == 4) && e->D == 128;
+    return 0;
+}
+
+static int spec_entry(tm_engine* e)
+{
+    if (e && e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    TM_REQUIRE(e && e->batch > 0, "no admitted batch");
+    TM_REQUIRE(e->spec_batch && e->spec_k > 0, "the batch was admitted without speculation (tm_engine_set_speculative before tm_engine_prefill)");
+    TM_HIP_CHECK(hipSetDevice(e->cfg.device));
+    return 0;
+}
+
+int tm_engine_decode_spec(tm_engine* e, int steps)
+{
+    TM_TRY(spec_entry(e));
+    TM_REQUIRE(steps >= 0, "steps >= 0");
+    // the flatten + prefill-attention path needs host-side lengths per step: it stays eager
+    const bool graphs = graph_enabled(e) && e->spec_mfma;
+    if (graphs && !e->graph_spec) {
+        if (steps == 0) {
+            return 0;
+        }
+        TM_TRY(spec_step(e));  // one eager step first, as tm_engine_decode
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+        steps -= 1;
+        TM_TRY(capture_step(e, spec_step, &e->graph_spec));
+        e->graph_spec_batch   = e->batch;
+        e->graph_spec_max_new = e->max_new;
+        e->graph_spec_k       = e->spec_k;
+    }
+    for (int i = 0; i < steps; ++i) {
+        if (graphs && e->graph_spec) {
+            TM_HIP_CHECK(hipGraphLaunch(e->graph_spec, e->stream));
+        }
+        else {
+            TM_TRY(spec_step(e));
+        }
+    }
+    return 0;
+}
+
+int tm_engine_verify(tm_engine* e, const int* host_drafts, const int* host_n_draft)
+{
+    TM_TRY(spec_entry(e));
+    TM_REQUIRE(host_drafts && host_n_draft, "null pointer");
+    const int k = e->spec_k;
+    for (int b = 0; b < e->batch; ++b) {
+        TM_REQUIRE(host_n_draft[b] >= 0 && host_n_draft[b] <= k, "tm_engine_verify: 0 <= n_draft[b] <= k");
+        for (int j = 0; j < k; ++j) {
+            TM_REQUIRE(host_drafts[b * k + j] >= 0 && host_drafts[b * k + j] < e->cfg.model.vocab, "tm_engine_verify: a draft id outside [0, vocab)");
+        }
+    }
+    TM_HIP_CHECK(hipMemcpyAsync(e->d_spec_drafts, host_drafts, (size_t)e->batch * k * 4, hipMemcpyHostToDevice, e->stream));
+    TM_HIP_CHECK(hipMemcpyAsync(e->d_spec_ndraft, host_n_draft, (size_t)e->batch * 4, hipMemcpyHostToDevice, e->stream));
+    const int rc = spec_verify_accept(e);
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));  // the caller's arrays may be pageable
+    return rc;
+}
+
+int tm_engine_fetch_spec(tm_engine* e, int* host_tokens, int* host_counts)
+{
+    TM_REQUIRE(e && host_tokens && host_counts, "null pointer");
+    TM_REQUIRE(e->batch > 0 && e->spec_batch, "no batch admitted with speculation armed");
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    TM_HIP_CHECK(hipMemcpy(host_tokens, e->d_generated, (size_t)e->batch * e->max_new * 4, hipMemcpyDeviceToHost));
+    TM_HIP_CHECK(hipMemcpy(host_counts, e->d_spec_emitted, (size_t)e->batch * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tm_engine_fetch_spec_logits(tm_engine* e, void* host_out)
+{
+    TM_REQUIRE(e && host_out, "null pointer");
+    TM_REQUIRE(e->batch > 0 && e->spec_batch, "no batch admitted with speculation armed");
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    TM_HIP_CHECK(hipMemcpy(host_out, e->d_spec_logits, (size_t)e->batch * (e->spec_k + 1) * e->vocab_local * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tm_engine_spec_stats(tm_engine* e, int64_t* host_stats)
+{
+    TM_REQUIRE(e && host_stats, "null pointer");
+    if (!e->d_spec_totals) {  // never armed
+        host_stats[0] = host_stats[1] = host_stats[2] = host_stats[3] = 0;
+        return 0;
+    }
+    TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    TM_HIP_CHECK(hipMemcpy(host_stats, e->d_spec_totals, 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -323,6 +323,25 @@ struct tm_engine {
     float*  d_score_nll    = nullptr;  // [max_batch_size * session_len]
     int*    d_score_tgt    = nullptr;  // [max_batch_size * session_len] next token of every position, -1 at a sequence's last
 
+    // Speculative decoding by prompt lookup (tm_engine_set_speculative; static batch, greedy, tp 1; speculative.hip).
+    // spec_k > 0: armed -- the next tm_engine_prefill reserves spec_k tokens of KV slack per sequence and starts the device token
+    // history; such a batch (spec_batch) advances by tm_engine_decode_spec / tm_engine_verify only.  spec_k == 0: nothing below is
+    // allocated or read, and every path launches what it launched before the feature.
+    int        spec_k = 0, spec_ngram_max = 0, spec_ngram_min = 0;
+    int        spec_cap_k = 0;      // the k the buffers below are sized for (grown on demand)
+    bool       spec_batch = false;
+    bool       spec_mfma  = false;  // the verify forward's attention: attention_verify_mfma.hip (int8 / int4 KV, head_dim 128), else flatten + prefill attention
+    bool       fw_verify  = false;  // set around ONE forward: the verify forward (attention over 1 .. 8 rows per sequence, lm_head over every row)
+    int *      d_spec_hist = nullptr, *d_spec_len = nullptr, *d_spec_emitted = nullptr;  // [B][session_len], [B], [B]
+    int *      d_spec_drafts = nullptr, *d_spec_ndraft = nullptr;                          // [B][k], [B]
+    int *      d_spec_ids = nullptr, *d_spec_out = nullptr;                                // [B][k + 1] input rows / arg-max behind every row
+    int *      d_spec_cu_q = nullptr, *d_spec_k_len = nullptr, *d_spec_step = nullptr;     // [B + 1] = (k + 1) b, [B] = k_len + k + 1, [B] emitted by the last step
+    long long* d_spec_totals = nullptr;                                                    // [4]
+    half_t*    d_spec_logits = nullptr;                                                    // [B (k + 1)][vocab]
+    float*     d_spec_attn_ws = nullptr;                                                   // split-K partials of B (k + 1) rows
+    hipGraphExec_t graph_spec = nullptr;
+    int        graph_spec_batch = 0, graph_spec_max_new = 0, graph_spec_k = 0;
+
     // engine thread (tm_engine_serve_start): runs step_locked() while requests exist.  `mu` serialises the scheduler
     // and every device-side effect of submit / step / poll / cancel; API callers announce themselves in api_waiting so
     // that the loop (which re-locks immediately) lets them in between two steps.

@@ -28,6 +28,7 @@ static int cb_enter(tm_engine* e)
     }
     TM_REQUIRE(e->started, "engine not started");
     TM_REQUIRE(e->batch == 0, "a static batch is admitted (release it first)");
+    TM_REQUIRE(e->spec_k == 0, "speculative decoding is armed (tm_engine_set_speculative with k > 0): continuous batching does not speculate");
     TM_REQUIRE(e->h_mm.empty(), "continuous batching does not take multimodal input (tm_engine_set_multimodal arms a static tm_engine_prefill)");
     TM_REQUIRE(e->num_blocks >= 2, "continuous batching needs at least two KV blocks");
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));

@@ -147,6 +147,52 @@ int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st); 
 int launch_decode_attention_tq(const DecodeAttnParams& p, hipStream_t st);
 size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, int splits);
 
+// ---- attention_verify_mfma.hip ----------------------------------------------------------
+// Paged split-K attention for 1 .. 8 query rows per sequence over int8 / int4 KV at head_dim 128 (the verify forward of speculative
+// decoding).  The rows' K / V are in the cache already (launch_kv_rope_store first); k_len counts every row of the forward, row j of
+// sequence b sees the tokens t < k_len[b] - q_len[b] + j + 1.  No window, no sinks, no fused prologue.
+constexpr int kVerifyMaxRows = 8;
+struct VerifyAttnParams {
+    const half_t* q;         // [rows][q_stride] roped queries (head h at h*D)
+    int           q_stride;
+    half_t*       out;       // [rows][q_heads*D], forward row order
+    const int*    cu_q_len;  // [B+1] device
+    const int*    k_len;     // [B] device, context lengths including every row of this forward
+    int           batch;
+    int           q_heads;
+    float         scale_log2;
+    int           splits;
+    float*        partial_o;   // [rows][q_heads][splits][D]
+    float*        partial_ml;  // [rows][q_heads][splits][2]
+    KvCacheView   cache;
+    int           max_q_len;   // 1 .. kVerifyMaxRows: the host's bound on q_len[b]; sizes the grid, longer sequences are cut to it
+};
+int launch_verify_attention(const VerifyAttnParams& p, hipStream_t st);
+
+// ---- speculative.hip: prompt-lookup proposer and greedy acceptance of speculative decoding ----
+struct SpecState {
+    int* hist;       // [B][hist_stride] token history: prompt + emitted tokens
+    int  hist_stride;
+    int* hist_len;   // [B]
+    int* emitted;    // [B] tokens emitted so far (the prefill's first token included)
+    int* generated;  // [B][max_new]
+    int  max_new;
+    int* k_len;      // [B] tokens in the KV cache
+    int* next_id;    // [B] last emitted token = row 0 of the next step
+    long long* totals;  // [4] steps (live sequence-steps), drafted, accepted, emitted
+};
+constexpr int kSpecMaxDraft = 7;
+constexpr int kSpecMaxNgram = 8;
+// one workgroup per sequence: drafts [B][k] (unused entries 0), n_draft [B]
+int launch_spec_propose(int* drafts, int* n_draft, const SpecState& s, int batch, int k, int ngram_max, int ngram_min, hipStream_t st);
+// start of a batch: hist[b][0 .. k_len[b]) holds the prompt; the prefill's first token (next_id) joins it, hist_len = k_len + 1, emitted = 1
+int launch_spec_begin(const SpecState& s, int batch, hipStream_t st);
+// rows of the verify forward: ids [B][k+1] = (next_id, drafts), cu_q [B+1] = (k+1) b, k_len_fw [B] = k_len + k + 1
+int launch_spec_rows(int* ids, int* k_len_fw, const int* drafts, const SpecState& s, int batch, int k, hipStream_t st);
+// greedy acceptance: out_ids [B][k+1] is the arg-max behind every input row; step_emitted [B] (nullptr: not wanted) = tokens emitted by this step
+int launch_spec_accept(const int* out_ids, const int* drafts, const int* n_draft, const SpecState& s, int batch, int k, int* step_emitted,
+                       hipStream_t st);
+
 // ---- attention_prefill.hip --------------------------------------------------------------
 struct PrefillAttnParams {
     const half_t* q;         // [T][q_stride] roped

@@ -313,6 +313,37 @@ class TurbomindEngineConfig:
 
 
 @dataclass
+class SpeculativeConfig:
+    """Speculative decoding config: the reference's fields (lmdeploy/messages.py, SpeculativeConfig: method, model,
+    num_speculative_tokens; its PyTorch engine only) plus the n-gram sizes of prompt lookup.  Only method='ngram' is served: drafts
+    are copied from the sequence's own history behind the latest earlier occurrence of its last prompt_lookup_max .. prompt_lookup_min
+    tokens, so there is no draft model and no second checkpoint.  Greedy requests of a static batch speculate
+    (num_speculative_tokens drafted tokens verified per step, the output is the plain greedy output); sampling, logits processors,
+    logprobs, output_logits, streaming and continuous batching run the plain path."""
+    method: str
+    model: str = ''
+    num_speculative_tokens: int = 1
+    prompt_lookup_max: int = 3
+    prompt_lookup_min: int = 1
+
+    def __post_init__(self):
+        if self.method != 'ngram':
+            raise NotImplementedError(f'SpeculativeConfig.method={self.method!r} needs a draft model (eagle / eagle3 / deepseek_mtp ... '
+                                      f'run a second network): only "ngram" (prompt lookup) is served')
+        if self.model:
+            raise NotImplementedError(f'SpeculativeConfig.model={self.model!r}: method "ngram" has no draft model')
+        for k in ('num_speculative_tokens', 'prompt_lookup_max', 'prompt_lookup_min'):
+            if not isinstance(getattr(self, k), int) or isinstance(getattr(self, k), bool):
+                raise ValueError(f'SpeculativeConfig.{k} must be an integer')
+        if not 1 <= self.num_speculative_tokens <= 7:
+            raise ValueError(f'SpeculativeConfig.num_speculative_tokens={self.num_speculative_tokens}: 1 .. 7 (the verify attention '
+                             f'takes num_speculative_tokens + 1 <= 8 rows per sequence)')
+        if not 1 <= self.prompt_lookup_min <= self.prompt_lookup_max <= 8:
+            raise ValueError(f'SpeculativeConfig: 1 <= prompt_lookup_min ({self.prompt_lookup_min}) <= prompt_lookup_max '
+                             f'({self.prompt_lookup_max}) <= 8')
+
+
+@dataclass
 class Response:
     text: str
     generate_token_len: int

@@ -15,7 +15,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _ffi
-from .messages import STATUS_TO_RESPONSE, GenerationConfig, Response, ResponseType, TurbomindEngineConfig
+from .messages import STATUS_TO_RESPONSE, GenerationConfig, Response, ResponseType, SpeculativeConfig, TurbomindEngineConfig
 from .turbomind import checkpoint
 from .turbomind.engine import Engine
 from .turbomind.loader import export_weights
@@ -74,8 +74,13 @@ class Pipeline:
         returns rank 0's responses.  Expert path, unchanged: an externally launched process per GPU (torch.distributed.run, ...)
         passes its `rank` and the broadcast RCCL id (`comm_unique_id`); `_tp_link` is the worker side of the one-call form.
         `cache_blocks=N` (keyword, tp = 1): a KV pool of exactly N 64-token blocks instead of cache_max_entry_count x free memory."""
-        if kwargs.get('speculative_config') is not None or kwargs.get('chat_template_config') is not None:
-            raise NotImplementedError('speculative decoding / chat templates are outside the MI355X hot path')
+        if kwargs.get('chat_template_config') is not None:
+            raise NotImplementedError('chat templates are outside the MI355X hot path')
+        # speculative decoding by prompt lookup (SpeculativeConfig(method='ngram')): plain greedy calls of the static batch speculate
+        self.speculative_config = kwargs.get('speculative_config')
+        if self.speculative_config is not None and not isinstance(self.speculative_config, SpeculativeConfig):
+            raise TypeError('speculative_config must be a lmdeploy_amd.SpeculativeConfig')
+        self._spec_calls = dict(speculated=0, plain=0)     # static chunks / continuous calls that did / did not speculate
         cfg = backend_config or TurbomindEngineConfig()
         if not isinstance(cfg, TurbomindEngineConfig):
             raise NotImplementedError('only TurbomindEngineConfig is supported (the PyTorch engine is out of scope)')
@@ -105,6 +110,8 @@ class Pipeline:
                                  f'(lmdeploy/turbomind/converter.py:174-176)')
         # the TurboQuant KV cache (quant_policy=42): head_dim 128, full attention, tp = 1 -- refused here, by name, before any GPU work
         checkpoint.check_kv_quant_policy(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
+        if self.speculative_config is not None:     # window / sinks, quant_policy 42, tp > 1, M-RoPE: refused by name, before any GPU work
+            checkpoint.check_speculative(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
         session_len = cfg.session_len or self.model_cfg.max_position_embeddings
         self.session_len = int(session_len)
         devices = cfg.devices or list(range(cfg.tp))
@@ -212,6 +219,14 @@ class Pipeline:
             for i, r in zip(group, res):
                 nll[i] = r
         return [float(np.cumsum(r, dtype=np.float64)[-1] / len(r)) for r in nll]     # cumsum: sequential, in position order
+
+    def speculative_stats(self) -> dict:
+        """Totals of the speculative steps of this pipeline: steps = (step, sequence) pairs that emitted tokens, drafted / accepted =
+        drafted tokens offered / accepted, emitted = tokens emitted (= accepted + steps); speculated_calls / plain_calls = static
+        chunks that speculated / static chunks and continuous-batching calls that ran the plain path."""
+        if self.speculative_config is None:
+            raise ValueError('the pipeline was created without a speculative_config')
+        return dict(self.engine.spec_stats(), speculated_calls=self._spec_calls['speculated'], plain_calls=self._spec_calls['plain'])
 
     def close(self):
         self.engine.close()
@@ -331,6 +346,9 @@ class Pipeline:
             raise NotImplementedError('multimodal prompts through continuous batching / streaming: multimodal input runs as a static batch '
                                       '(infer / __call__ with one GenerationConfig and at most max_batch_size prompts)')
         ids = [self._encode(p) for p in prompts]
+        if self.speculative_config is not None:     # continuous batching does not speculate: the plain path, unchanged
+            self.engine.set_speculative(0)
+            self._spec_calls['plain'] += 1
         if isinstance(g, (list, tuple)):            # per-request generation configs: every request carries its own
             if len(g) != len(ids):
                 raise ValueError(f'{len(g)} generation configs for {len(ids)} prompts')
@@ -442,6 +460,13 @@ class Pipeline:
                     # the engine's processors rewrite the logits in place and a tensor-parallel rank holds a vocabulary shard: what could be read
                     # back would not be the reference's output (the raw lm_head row, src/turbomind/models/language_model.cc OutputLogits)
                     raise NotImplementedError('output_logits together with repetition_penalty / min_new_tokens / bad_token_ids, or with tp > 1')
+                # speculation (SpeculativeConfig 'ngram'): the plain greedy call only; every other call runs the plain path below unchanged
+                sc = self.speculative_config
+                spec = (sc is not None and not g.sampling_params() and lp is None and not g.logprobs and not g.output_logits
+                        and all(mm[i] is None for i in idx))
+                if sc is not None:
+                    self.engine.set_speculative(sc.num_speculative_tokens if spec else 0, sc.prompt_lookup_max, sc.prompt_lookup_min)
+                    self._spec_calls['speculated' if spec else 'plain'] += 1
                 self.engine.set_sampling([g.sampling_params(i) for i in idx] if g.sampling_params() else None)
                 self.engine.set_logits_params([lp] * len(chunk) if lp else None)
                 self.engine.set_logprobs(g.logprobs or 0)
@@ -450,9 +475,22 @@ class Pipeline:
                     # chunk without multimodal input never meets an earlier chunk's rows (and engines that never see a dict prompt --
                     # the tensor-parallel rank group -- need no such entry)
                     self.engine.set_multimodal([mm[i] if mm[i] is not None else dict(prompt_len=len(ids[i])) for i in idx])
+                if spec and any(len(p) + max_new + sc.num_speculative_tokens > limit for p in chunk):
+                    # no room for the verify forward's rows behind the last allowed token: this chunk decodes plainly
+                    spec = False
+                    self.engine.set_speculative(0)
+                    self._spec_calls['speculated'] -= 1
+                    self._spec_calls['plain'] += 1
                 self.engine.prefill(chunk, max_new_tokens=max_new)
                 step_logits = [self.engine.fetch_logits().copy()] if g.output_logits else None   # [batch, vocab] fp16 behind every step
                 done = 1
+                while spec:     # every step emits 1 .. k + 1 tokens per sequence; the device stops a sequence at max_new
+                    self.engine.decode_spec(min(8, max_new))
+                    toks, counts = self.engine.fetch_spec()
+                    if all(c >= max_new or (stop and any(int(t) in stop for t in row[:c])) for row, c in zip(toks, counts)):
+                        toks = [row[:c] for row, c in zip(toks, counts)]
+                        done = max_new
+                        break
                 while done < max_new:
                     n = 1 if step_logits is not None else min(32, max_new - done)
                     self.engine.decode(n)
@@ -463,7 +501,7 @@ class Pipeline:
                         toks = self.engine.fetch()
                         if all(any(int(t) in stop for t in row) for row in toks):
                             break
-                toks = self.engine.fetch()
+                toks = toks if spec else self.engine.fetch()
                 records = self.engine.fetch_logprobs() if g.logprobs else None
             except _ffi.TmError as e:
                 self.engine.release()

@@ -116,6 +116,21 @@ def check_kv_quant_policy(cfg, quant_policy: int, tp: int = 1, what: str = 'this
         raise NotImplementedError('quant_policy=42 (TurboQuant KV) with tp > 1: built for tp = 1')
 
 
+def check_speculative(cfg, quant_policy: int, tp: int = 1, what: str = 'this model'):
+    """Speculative decoding (prompt lookup) serves full-attention text models on one rank with quant_policy 0 / 4 / 8;
+    NotImplementedError with the reason for anything else -- before any GPU work, like check_kv_quant_policy."""
+    if tp > 1:
+        raise NotImplementedError('speculative decoding with tp > 1 is not built')
+    if int(quant_policy) == 42:
+        raise NotImplementedError('speculative decoding with quant_policy=42 (TurboQuant KV) is not built')
+    windows = [int(w) for w in (getattr(cfg, 'layer_windows', None) or [])]
+    if int(getattr(cfg, 'window', 0) or 0) > 0 or any(w > 0 for w in windows) or getattr(cfg, 'attn_sinks', 0):
+        raise NotImplementedError(f'speculative decoding with {what}, which has a sliding window or attention sinks, is not built: the '
+                                  f'verify attention serves full attention only')
+    if getattr(cfg, 'mrope_section', None):
+        raise NotImplementedError(f'speculative decoding with {what}, which has M-RoPE sections (a multimodal model), is not built')
+
+
 # Qwen decoders: the Llama layout plus the attention prologue.  Exact names: Qwen3-MoE (the Qwen3 prologue with a routed expert FFN
 # in every layer) and Qwen2-MoE (the Qwen2 prologue; routed experts plus a shared expert behind a sigmoid gate in every layer)
 QWEN_ARCHS = ('Qwen2ForCausalLM', 'Qwen3ForCausalLM', 'Qwen3MoeForCausalLM', 'Qwen2MoeForCausalLM')

@@ -251,6 +251,44 @@ class Engine:
     def decode(self, steps: int = 1):
         _ffi.check(self._lib.tm_engine_decode(self._h, steps))
 
+    # ---- speculative decoding by prompt lookup (static batch, greedy) -----------------------------
+    def set_speculative(self, k: int, ngram_max: int = 3, ngram_min: int = 1):
+        """Arm (k = 1 .. 7 drafted tokens per step) or switch off (k = 0) speculation for the NEXT prefill.  A batch admitted with
+        k > 0 advances by decode_spec / verify only; it emits the tokens plain greedy decoding emits."""
+        _ffi.check(self._lib.tm_engine_set_speculative(self._h, int(k), int(ngram_max), int(ngram_min)))
+        self._spec_k = int(k)
+
+    def decode_spec(self, steps: int = 1):
+        """`steps` speculative steps (propose from the token history -> verify forward -> accept); asynchronous"""
+        _ffi.check(self._lib.tm_engine_decode_spec(self._h, int(steps)))
+
+    def verify(self, drafts, n_draft):
+        """One speculative step with the caller's drafts: drafts [batch, k] token ids, n_draft [batch] in [0, k]"""
+        k = getattr(self, '_spec_k', 0)
+        d = np.ascontiguousarray(np.asarray(drafts, np.int32).reshape(self.batch, k))
+        n = np.ascontiguousarray(np.asarray(n_draft, np.int32).reshape(self.batch))
+        _ffi.check(self._lib.tm_engine_verify(self._h, d.ctypes.data, n.ctypes.data))
+
+    def fetch_spec(self):
+        """(tokens [batch, max_new] int32, counts [batch] int32): row b holds counts[b] emitted tokens, the prefill's first included"""
+        out = np.zeros((self.batch, self.max_new), np.int32)
+        cnt = np.zeros(self.batch, np.int32)
+        _ffi.check(self._lib.tm_engine_fetch_spec(self._h, out.ctypes.data, cnt.ctypes.data))
+        return out, cnt
+
+    def fetch_spec_logits(self) -> np.ndarray:
+        """logits of the last speculative step, fp16 [batch, k + 1, vocab]: row j is the distribution behind input row j"""
+        out = np.zeros((self.batch, getattr(self, '_spec_k', 0) + 1, self.cfg.model.vocab // self.cfg.tp), np.float16)
+        _ffi.check(self._lib.tm_engine_fetch_spec_logits(self._h, out.ctypes.data))
+        return out
+
+    def spec_stats(self) -> dict:
+        """totals since speculation was first armed: steps = (step, sequence) pairs that emitted, drafted, accepted, emitted
+        (= accepted + steps)"""
+        v = np.zeros(4, np.int64)
+        _ffi.check(self._lib.tm_engine_spec_stats(self._h, v.ctypes.data))
+        return dict(steps=int(v[0]), drafted=int(v[1]), accepted=int(v[2]), emitted=int(v[3]))
+
     def score(self, seqs: Sequence[Sequence[int]]) -> list:
         """Prompt scoring (tm_engine_score): per-token NLL in fp32 from the raw lm_head logits, one array of length len - 1 per
         sequence -- entry p is position p scored against token p + 1.  Synchronous; the engine is idle again on return."""
