@@ -222,8 +222,9 @@ def _fill(rng, L, klen, layer):
 
 def _decode(tm, dc, q_d, klen, Hq, splits, layer):
     B = len(klen)
-    out = torch.zeros((B, Hq * 128), dtype=torch.float16, device='cuda')
-    ws = torch.zeros(max(1, tm.tm_decode_attention_workspace(B, Hq, splits)), dtype=torch.uint8, device='cuda')
+    # poisoned, not zeroed: an output row or a split-K partial that is never written must not read as a plausible value
+    out = torch.full((B, Hq * 128), 0x7e00, dtype=torch.int16, device='cuda').view(torch.float16)
+    ws = torch.full((max(1, tm.tm_decode_attention_workspace(B, Hq, splits)),), 0xFF, dtype=torch.uint8, device='cuda')
     _ffi.check(tm.tm_decode_attention(out.data_ptr(), q_d.data_ptr(), Hq * 128, dev(np.asarray(klen, np.int32)).data_ptr(), B, Hq, 0.0,
                                       splits, ws.data_ptr(), dc.view(layer), st()))
     return host(out)
