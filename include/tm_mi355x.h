@@ -171,7 +171,8 @@ int tm_flatten_kv_window(void* k_out, void* v_out, int transpose_v, const int* c
 /* Paged flash-decode, one query token per sequence (dispatchDecoding).  q fp16 [batch][q_stride] already
  * rotated (head h at h*head_dim), out fp16 [batch][q_heads*head_dim], head_dim = cache->head_dim (64 or 128).  splits >= 1;
  * workspace of tm_decode_attention_workspace() bytes needed when splits > 1 (sized for head_dim 128, which is enough for 64).
- * softmax_scale <= 0 -> 1/sqrt(head_dim).  head_dim 64 runs the VALU kernel for every KV width.
+ * softmax_scale <= 0 -> 1/sqrt(head_dim).  head_dim 64 runs the window / sink MFMA kernel (tm_decode_attention_window_mfma, window 0)
+ * for int8 / int4 KV and the VALU kernel for fp16 KV; TM_ATTN_VALU=1 in the environment keeps every KV width on the VALU kernel.
  * Every k_len[b] >= 1 and the first block-table entry of every sequence is a mapped block (the engine parks free batch slots on a
  * dummy block with k_len = 1); a k_len = 0 entry reads that first block and produces no meaningful row. */
 size_t tm_decode_attention_workspace(int batch, int q_heads, int splits);
@@ -206,11 +207,20 @@ int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, 
  * attention_universal.h:411,474-480; the sink term L += expf(sink - M * scale) of attention_universal.h:529-535).
  * window > 0: the query at k_len - 1 sees the keys j with k_len - 1 - j < window, i.e. the last min(k_len, window) tokens; cache
  * tiles wholly before them are not read.  sinks (device fp16 [q_heads], may be NULL): one natural-log logit per head that joins
- * the softmax denominator and contributes no value.  Runs the VALU kernel for every KV width and head_dim (never the MFMA
- * kernel or its fused prologue).  window == 0 && sinks == NULL is tm_decode_attention, bit for bit; window < 0: TM_INVALID. */
+ * the softmax denominator and contributes no value.  int8 / int4 KV with a window or sinks runs the window / sink MFMA kernel
+ * (tm_decode_attention_window_mfma) at head_dim 64 and 128, fp16 KV the VALU kernel; never the fused prologue.  TM_ATTN_VALU=1 in
+ * the environment keeps int8 / int4 KV on the VALU kernel.  window == 0 && sinks == NULL is tm_decode_attention, bit for bit;
+ * window < 0: TM_INVALID. */
 int tm_decode_attention_window(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
                                float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
                                const void* sinks, tm_stream_t st);
+/* The same arguments, always on the window / sink MFMA kernel (split-K paged flash-decode on v_mfma_f32_16x16x32_f16 over the raw
+ * int8 / int4 codes, head_dim 64 and 128), whatever the environment says: the kernel tm_decode_attention_window runs for int8 / int4
+ * KV, and the A/B arm for measurements against TM_ATTN_VALU=1.  A window that covers every context gives the bits of window == 0; a
+ * sink of -inf gives the bits of no sink.  TM_INVALID by name: fp16 KV, kv bits 42, another head_dim, window < 0. */
+int tm_decode_attention_window_mfma(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
+                                    float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
+                                    const void* sinks, tm_stream_t st);
 /* Verify attention (speculative decoding): paged split-K flash-decode for q_len[b] = cu_q_len[b + 1] - cu_q_len[b] query rows per
  * sequence, 1 <= q_len[b] <= 8, over int8 / int4 KV at head_dim 128 on the matrix cores.  The rows' K / V are in the cache already
  * (tm_kv_rope_store first, the prefill convention): k_len[b] counts EVERY row of this forward, hist = k_len[b] - q_len[b], and query
@@ -615,8 +625,8 @@ int tm_debug_set_moe_router(int mode);
  * Engine level (static batcher around LanguageModel::Forward)
  * --------------------------------------------------------------------------------------------*/
 typedef struct tm_model_config {
-    /* head_dim: 64 or 128; q_heads / tp * head_dim must be a multiple of 128.  head_dim 64 decodes on the VALU attention kernel behind
-     * tm_kv_rope_store (no fused prologue) for every quant_policy; qk_norm needs head_dim 128. */
+    /* head_dim: 64 or 128; q_heads / tp * head_dim must be a multiple of 128.  head_dim 64 decodes behind tm_kv_rope_store (no fused
+     * prologue): int8 / int4 KV on the window / sink MFMA attention kernel, fp16 KV on the VALU one; qk_norm needs head_dim 128. */
     int   hidden, layers, q_heads, kv_heads, head_dim, inter, vocab;
     float rms_eps;
     float rope_base;
@@ -657,8 +667,8 @@ typedef struct tm_model_config {
     /* Sliding-window attention and attention sinks (AttentionParams::window_size / ::sinks, kernels/attention/attention_params.h:55-72).
      * attn_window: the window of every layer, 0 = none (tm_engine_set_layer_windows overrides it per layer); a window >= session_len is
      * full attention.  attn_sinks != 0 -> slot "layers.{i}.attention.sinks" fp16 [q_heads / tp], one natural-log logit per local head.
-     * An engine with a windowed layer or sinks decodes like head_dim 64: tm_kv_rope_store + the VALU attention kernel, no fused
-     * prologue, no folded norm.  KV blocks older than the window stay allocated. */
+     * An engine with a windowed layer or sinks decodes like head_dim 64: tm_kv_rope_store + the window / sink MFMA attention kernel (int8 /
+     * int4 KV; fp16 KV: the VALU kernel), no fused prologue, no folded norm.  KV blocks older than the window stay allocated. */
     int   attn_window, attn_sinks;
     /* gpt-oss (all three: tp == 1, no folded norm).
      * attn_out_bias != 0 -> slot "layers.{i}.attention.wo.bias" fp16 [hidden], added behind the o projection in the order of the

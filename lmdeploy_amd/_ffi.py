@@ -140,6 +140,8 @@ _SIGNATURES = {
                                     POINTER(KvCache), c_void_p]),
     'tm_decode_attention_window': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                            POINTER(KvCache), c_int, c_void_p, c_void_p]),
+    'tm_decode_attention_window_mfma': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
+                                                POINTER(KvCache), c_int, c_void_p, c_void_p]),
     'tm_decode_attention_fused': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_float, c_int, c_void_p, POINTER(KvCache), c_void_p]),
     'tm_decode_attention_fused_qk': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

@@ -449,7 +449,7 @@ static int launch_bits(const DecodeAttnParams& p, hipStream_t st)
     return 0;
 }
 
-// window / sinks: the VALU kernel's WS variant for every KV width, whatever TM_ATTN_VALU says
+// window / sinks on the VALU kernel's WS variant: fp16 KV always, int8 / int4 KV with TM_ATTN_VALU=1
 template<int D>
 static int launch_window(const DecodeAttnParams& p, hipStream_t st)
 {
@@ -462,6 +462,36 @@ static int launch_window(const DecodeAttnParams& p, hipStream_t st)
             return launch_bits<4, D, true>(p, st);
     }
     TM_REQUIRE(false, "kv bits in {16,8,4}");
+}
+
+// TM_ATTN_VALU=1 keeps int8 / int4 KV on the VALU kernel (A/B measurements); read once per process
+static bool attn_valu()
+{
+    static const bool valu = getenv("TM_ATTN_VALU") && atoi(getenv("TM_ATTN_VALU")) != 0;
+    return valu;
+}
+
+// attention_decode_ws_mfma.hip + the split merge (WS: the reduce adds the sink term; without sinks it is the plain merge)
+int launch_decode_attention_window_mfma(const DecodeAttnParams& p, hipStream_t st)
+{
+    TM_REQUIRE(p.splits >= 1 && p.splits <= 128, "1 <= splits <= 128 (kMaxKVSplits)");
+    TM_REQUIRE(p.splits == 1 || (p.partial_o && p.partial_ml), "split-K needs a workspace");
+    if (p.batch == 0) {
+        return 0;
+    }
+    if (const int rc = launch_decode_attention_ws_mfma(p, st)) {
+        return rc;
+    }
+    if (p.splits > 1) {
+        if (p.cache.layout.head_dim == 64) {
+            decode_reduce_kernel<64, true><<<dim3(p.q_heads, p.batch), 64, 0, st>>>(p);
+        }
+        else {
+            decode_reduce_kernel<128, true><<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
+        }
+        TM_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
 }
 
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
@@ -484,14 +514,21 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     TM_REQUIRE(fused || (!p.qkv_bias && !p.q_norm && !p.k_norm), "qkv bias / q-k norm need the fused decode prologue");
     TM_REQUIRE(fused || !p.pos_delta, "pos_delta needs the fused decode prologue (unfused: launch_kv_rope_store_mrope applies it)");
     TM_REQUIRE(p.window >= 0, "decode attention: window must be >= 0 (0 = full attention)");
+    const bool quant = L.bits == 8 || L.bits == 4;
     if (p.window > 0 || p.sinks) {
-        // the MFMA kernel and its fused prologue know neither: such a call runs kv_rope_store + the VALU kernel
+        // the head_dim-128 MFMA kernel and its fused prologue know neither: such a call runs kv_rope_store + the window / sink MFMA kernel
+        // (int8 / int4 KV) or the VALU kernel (fp16 KV)
         TM_REQUIRE(!fused, "fused decode prologue with a sliding window or attention sinks: run kv_rope_store + tm_decode_attention_window");
+        if (quant && !attn_valu()) {
+            return launch_decode_attention_window_mfma(p, st);
+        }
         return L.head_dim == 64 ? launch_window<64>(p, st) : launch_window<128>(p, st);
     }
     if (L.head_dim == 64) {
-        // before TM_ATTN_VALU is looked at: head_dim 64 has the VALU kernel only, for every KV width
         TM_REQUIRE(!fused, "fused decode prologue (MFMA kernel): head_dim must be 128, head_dim 64 runs kv_rope_store + tm_decode_attention");
+        if (quant && !attn_valu()) {
+            return launch_decode_attention_window_mfma(p, st);  // full attention is its window 0
+        }
         switch (L.bits) {
             case 16:
                 return launch_bits<16, 64>(p, st);
@@ -508,8 +545,7 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
         case 8: {
             // int8 KV (the headline configuration) runs on the matrix cores; TM_ATTN_VALU=1 keeps the VALU kernel
             // reachable for A/B measurements
-            static const bool valu = getenv("TM_ATTN_VALU") && atoi(getenv("TM_ATTN_VALU")) != 0;
-            if (valu && !fused) {
+            if (attn_valu() && !fused) {
                 return launch_bits<8>(p, st);
             }
             DecodeAttnParams pt = p;
@@ -525,8 +561,7 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
         }
         case 4: {
             // int4 KV: the same MFMA kernel, nibbles expanded to bytes on the way into LDS (TM_ATTN_VALU=1: VALU kernel)
-            static const bool valu4 = getenv("TM_ATTN_VALU") && atoi(getenv("TM_ATTN_VALU")) != 0;
-            if (valu4 && !fused) {
+            if (attn_valu() && !fused) {
                 return launch_bits<4>(p, st);
             }
             DecodeAttnParams pt = p;

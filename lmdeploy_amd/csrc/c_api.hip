@@ -357,6 +357,33 @@ int tm_decode_attention_window(void* out, const void* q, int q_stride, const int
     return launch_decode_attention(p, (hipStream_t)st);
 }
 
+int tm_decode_attention_window_mfma(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
+                                    float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, int window,
+                                    const void* sinks, tm_stream_t st)
+{
+    TM_REQUIRE(out && q && k_len && cache, "null pointer");
+    TM_REQUIRE(window >= 0, "tm_decode_attention_window_mfma: window must be >= 0 (0 = full attention)");
+    TM_REQUIRE(cache->bits == 8 || cache->bits == 4,
+               "tm_decode_attention_window_mfma: int8 / int4 KV only (fp16 and TurboQuant KV: tm_decode_attention_window)");
+    TM_REQUIRE(cache->head_dim == 64 || cache->head_dim == 128, "tm_decode_attention_window_mfma: head_dim 64 or 128");
+    DecodeAttnParams p{};
+    p.window     = window;
+    p.sinks      = (const half_t*)sinks;
+    p.q          = (const half_t*)q;
+    p.q_stride   = q_stride;
+    p.out        = (half_t*)out;
+    p.k_len      = k_len;
+    p.batch      = batch;
+    p.q_heads    = q_heads;
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)cache->head_dim);
+    p.scale_log2 = s * 1.4426950408889634f;
+    p.splits     = splits < 1 ? 1 : splits;
+    p.partial_o  = (float*)workspace;
+    p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * cache->head_dim : nullptr;
+    p.cache      = to_view(cache);
+    return launch_decode_attention_window_mfma(p, (hipStream_t)st);
+}
+
 int tm_decode_attention_fused(void* out, const void* qkv, int qkv_splits, int qkv_n, const void* cos_sin, int max_pos,
                               const int* k_len, int batch, int q_heads, float softmax_scale, int splits,
                               void* workspace, const tm_kv_cache* cache, tm_stream_t st)

@@ -927,7 +927,8 @@ void setup_decode(tm_engine* e, int batch)
         // count of TP = 8 (profiles/r04_gemm_experiments_session2.txt, call25): 64 x 4 workgroups 1.485 ms per step against
         // 1.547 .. 1.587 with 64 x 8 (Llama-3-8B shard), 5.06 against 5.26 (Llama-3-70B shard).  fp16 KV (VALU kernel, <= 4
         // heads per workgroup): two workgroups per CU as before.
-        // head_dim 64 decodes on the VALU kernel for every KV width: its head-per-workgroup rule
+        // head_dim 64, windows and sinks: kv_rope_store + attention_decode_ws_mfma.hip (int8 / int4 KV) or the VALU kernel (fp16 KV).  Their
+        // splits keep the VALU kernel's head-per-workgroup rule: the MFMA kernel then runs at least as many splits as its own rule would ask for
         // quant_policy 42 (TurboQuant KV): a VALU kernel of the same workgroup shape (attention_decode_tq.hip), never the fused prologue
         const bool mfma = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128 && !e->windowed;
         const int  group = e->q_heads / e->kv_heads;
@@ -963,8 +964,8 @@ void setup_decode(tm_engine* e, int batch)
     const char* fuse = getenv("TM_FUSE_QKV");
     // per-sequence RoPE tables (dynamic NTK active): the fused prologue reads the one shared table, so such an engine runs the unfused
     // decode path -- kv_rope_store with the row offsets, then plain decode attention
-    // head_dim 64: no MFMA kernel, so no fused prologue either -- the same unfused path
-    // a sliding window or attention sinks (e->windowed): the VALU kernel's variant serves them, the same unfused path for every layer
+    // head_dim 64: no fused prologue (the window / sink MFMA kernel and the VALU kernel are unfused) -- the same unfused path
+    // a sliding window or attention sinks (e->windowed): the same unfused path for every layer
     // u4 weights in groups of 32 (gemm_u4_g32.hip): the linear always finishes its own fp16 rows, no slab reaches the attention kernel -- such
     // a model runs kv_rope_store, then plain decode attention, the same unfused path
     const bool g32   = e->cfg.model.weight_type == TM_WEIGHT_U4 && e->cfg.model.group_size == 32;

@@ -132,7 +132,8 @@ struct DecodeAttnParams {
     const half_t*  q_norm   = nullptr;
     const half_t*  k_norm   = nullptr;
     float          qk_eps   = 0.f;
-    // Sliding window and attention sinks (VALU kernel only, never with the fused prologue; reference: attention_params.h:55-72).
+    // Sliding window and attention sinks (VALU kernel for fp16 KV, attention_decode_ws_mfma.hip for int8 / int4 KV; never with the fused
+    // prologue; reference: attention_params.h:55-72).
     // window > 0: the query at k_len - 1 sees keys j with k_len - 1 - j < window (0 = all).  sinks [q_heads]: natural-log logits that
     // join the softmax denominator and carry no value (nullptr = none).
     int            window = 0;
@@ -143,6 +144,10 @@ struct DecodeAttnParams {
 };
 int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip
+// attention_decode_ws_mfma.hip: int8 / int4 KV at head_dim 64 / 128 on the matrix cores, with window and sinks; unfused.  The kernel alone
+// (partials when splits > 1); launch_decode_attention_window_mfma adds the split merge and is what tm_decode_attention_window_mfma runs.
+int launch_decode_attention_ws_mfma(const DecodeAttnParams& p, hipStream_t st);
+int launch_decode_attention_window_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode.hip
 // attention_decode_tq.hip: KV bits 42 (TurboQuant), head_dim 128, in the rotated domain; no window, sinks or fused prologue
 int launch_decode_attention_tq(const DecodeAttnParams& p, hipStream_t st);
 size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, int splits);

@@ -215,7 +215,8 @@ class TurbomindEngineConfig:
     for a pack-quantized checkpoint; model_format='gptq' is not a value of this field (a GPTQ directory loads with model_format=None),
     and model_format='awq' on a GPTQ or compressed-tensors checkpoint is the reference's mismatch error.  Mistral / Mixtral
     checkpoints with an integer `sliding_window` (Mistral-7B-v0.1: 4096) are served with sliding-window attention: such an engine decodes
-    on the VALU attention kernel for every quant_policy.  When every layer has a window W < session_len a sequence keeps a ring of
+    on the window / sink MFMA attention kernel with quant_policy 8 / 4 (as do gpt-oss and head_dim 64 models) and on the VALU attention
+    kernel with fp16 or TurboQuant KV.  When every layer has a window W < session_len a sequence keeps a ring of
     R = ceil((W - 1 + C) / 64) + 1 KV blocks, C = max(max_batch_size, 64, max_prefill_token_num), instead of its whole context:
     it owns min(ceil((prompt + max_new_tokens) / 64), R) blocks (Mistral-7B-v0.1 at session_len 32768: 193 instead of 512), and
     prefill dequantises the window, not the history.  A model with one full-attention layer (gpt-oss alternates) keeps whole contexts;
