@@ -58,10 +58,23 @@ typedef struct tm_kv_cache {
     int             kv_heads;      /* local kv heads                                               */
     int             head_dim;      /* 64 | 128                                                     */
     int             block_len;     /* 64 tokens (lmdeploy/messages.py:323)                         */
-    int             bits;          /* quant_policy: 16 (none) | 8 | 4 | 42 (lmdeploy/messages.py:20-27) */
+    int             bits;          /* quant_policy: 16 (none) | 8 | 4 | 42 (lmdeploy/messages.py:20-27); TM_KV_BITS_FP8 for FP8 */
+    float           k_scale;       /* TM_KV_BITS_FP8 only: the layer's per-tensor scales (K code = e4m3(k / k_scale)); 0 = 1.0, */
+    float           v_scale;       /* so a caller that fills the seven fields above keeps what it had                           */
 } tm_kv_cache;
 
-/* bytes of one layer inside a block: kv_heads*2*block_len*(head_dim*bits/8) + kv_heads*2*block_len*4*[bits<16].
+/* tm_kv_cache::bits of the FP8 cache (QuantPolicy.FP8 = 16; 16 itself already means fp16 KV here): e4m3fn codes, one fp32 scale per
+ * tensor and layer, no per-token parameters.  Per kv head K data [block_len][head_dim] bytes, then V data: the layout of bits 8 without
+ * its parameter region.  Contract (lmdeploy/pytorch/kernels/cuda/fill_kv_cache.py:214-232, flatten_kv_cache.py:204-205,
+ * pagedattention.py:463-553): store code = e4m3fn_rne(clamp(f32(x) / scale, -448, 448)) (IEEE fp32 division; no NaN code is written),
+ * flatten f16(f32(code) * scale), decode S = (q . k_codes) * k_scale * softmax_scale, O = (sum_t P_t v_codes_t) * v_scale / L with fp32
+ * accumulators.  tm_kv_rope_store / _qk / _seq, tm_flatten_kv / _window and tm_decode_attention / _window serve it at head_dim 64 and
+ * 128 (window and sinks included); tm_kv_rope_store_mrope, tm_verify_attention, the fused decode prologue and
+ * tm_decode_attention_window_mfma return TM_INVALID with it. */
+#define TM_KV_BITS_FP8 108
+
+/* bytes of one layer inside a block: kv_heads*2*block_len*(head_dim*bits/8) + kv_heads*2*block_len*4*[bits<16];
+ * bits TM_KV_BITS_FP8: kv_heads*2*block_len*head_dim.
  * bits 42 (TurboQuant, head_dim 128 only): K rows of head_dim/2 bytes (3-bit Lloyd-Max code of the Hadamard-rotated row + the sign of
  * the residual per element), V rows of head_dim/4 bytes (2-bit code), one fp16 pair per row each (K: norm, residual norm; V: norm, 0):
  * kv_heads*block_len*(head_dim/2 + head_dim/4 + 8).  Per kv head K data [block_len][head_dim/2], then V data [block_len][head_dim/4];
@@ -698,7 +711,10 @@ typedef struct tm_engine_config {
     int   device;             /* HIP device ordinal                                          */
     int   max_batch_size;     /* TurbomindEngineConfig.max_batch_size                        */
     int   session_len;        /* max context per sequence                                    */
-    int   quant_policy;       /* 0 | 4 | 8 | 42 (lmdeploy/messages.py:20-27); 42 = TurboQuant KV: head_dim 128, no window / sinks, tp 1 */
+    int   quant_policy;       /* 0 | 4 | 8 | 16 | 42 (lmdeploy/messages.py:20-27); 42 = TurboQuant KV: head_dim 128, no window / sinks, tp 1;
+                               * 16 = FP8 (e4m3) KV, TM_KV_BITS_FP8 above: head_dim 64 / 128, windows and sinks included, decodes like head_dim 64
+                               * (tm_kv_rope_store + attention, no fused prologue, no folded norm); tp 1; speculative decoding, M-RoPE sections
+                               * and multimodal input return TM_INVALID; 17 (FP8_E5M2) is refused */
     int   cache_block_seq_len;/* 64                                                          */
     float cache_max_entry_count; /* fraction of free HBM for KV blocks if cache_blocks == 0 */
     int   cache_blocks;       /* explicit number of KV blocks (0 = derive)                   */
@@ -722,6 +738,10 @@ int tm_engine_destroy(tm_engine* e);
 /* Per-layer sliding windows (gpt-oss alternates sliding and full layers): window[i] replaces attn_window for layer i, 0 = full
  * attention.  Before tm_engine_start; layers must equal the model's; a negative window is TM_INVALID. */
 int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers);
+/* quant_policy 16 (FP8 KV): the per-tensor scales of every layer's K and V cache (host float [layers] each, finite and > 0; the
+ * `k_scale` / `v_scale` of FP8 checkpoints).  A setter like tm_engine_set_layer_windows, before tm_engine_start; an engine that never
+ * calls it runs with 1.0.  TM_INVALID on an engine of another quant_policy. */
+int tm_engine_set_kv_scales(tm_engine* e, const float* k_scale, const float* v_scale, int layers);
 /* Multimodal RoPE sections (Qwen2-VL / Qwen2.5-VL mrope_section): a setter like tm_engine_set_layer_windows rather than three more ints
  * in struct tm_model_config -- a choice, not a constraint (every caller that fills the struct positionally stays as it is).  Frequency pair j of a head rotates by the t coordinate for j < sec_t, by h for the next sec_h
  * pairs, by w for the rest (tm_kv_rope_store_mrope).  Before tm_engine_start.  0 / 0 / 0 = none (the engine as created); otherwise

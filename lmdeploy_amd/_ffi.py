@@ -44,9 +44,13 @@ class LogitsParam(C.Structure):
 
 
 class KvCache(C.Structure):
-    """struct tm_kv_cache"""
+    """struct tm_kv_cache; k_scale / v_scale: the FP8 cache's per-tensor scales (bits == KV_BITS_FP8), 0 = 1.0"""
     _fields_ = [('block_ptrs', c_void_p), ('cu_block_nums', c_void_p), ('layer_offset', c_int64),
-                ('kv_heads', c_int), ('head_dim', c_int), ('block_len', c_int), ('bits', c_int)]
+                ('kv_heads', c_int), ('head_dim', c_int), ('block_len', c_int), ('bits', c_int),
+                ('k_scale', c_float), ('v_scale', c_float)]
+
+
+KV_BITS_FP8 = 108   # TM_KV_BITS_FP8: tm_kv_cache.bits of QuantPolicy.FP8 (16 itself is fp16 KV there)
 
 
 class RopeParam(C.Structure):
@@ -119,6 +123,7 @@ _SIGNATURES = {
                                      c_void_p, c_float, POINTER(KvCache), c_void_p]),
     'tm_engine_rope_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     'tm_engine_set_layer_windows': (c_int, [c_void_p, c_void_p, c_int]),
+    'tm_engine_set_kv_scales': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'tm_engine_kv_info': (c_int, [c_void_p, POINTER(c_int), POINTER(c_int64)]),
     'tm_kv_rope_store': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                  POINTER(KvCache), c_void_p]),

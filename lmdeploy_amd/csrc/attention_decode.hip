@@ -494,7 +494,7 @@ int launch_decode_attention_window_mfma(const DecodeAttnParams& p, hipStream_t s
     return 0;
 }
 
-int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
+int launch_decode_attention(const DecodeAttnParams& p, KvScales scales, hipStream_t st)
 {
     const KvLayout& L = p.cache.layout;
     TM_REQUIRE((L.head_dim == 64 || L.head_dim == 128) && L.block_len == 64, "decode attention: head_dim 64 or 128, block_len 64");
@@ -502,6 +502,23 @@ int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st)
     TM_REQUIRE(p.splits >= 1 && p.splits <= 128, "1 <= splits <= 128 (kMaxKVSplits)");
     TM_REQUIRE(p.splits == 1 || (p.partial_o && p.partial_ml), "split-K needs a workspace");
     if (p.batch == 0) {
+        return 0;
+    }
+    if (L.bits == kKvBitsFp8) {
+        // FP8 KV: a kernel of its own for every call (window 0 and no sinks included), which names what it refuses; the plain merge
+        // serves its partials (attention_decode_fp8_mfma.hip)
+        if (const int rc = launch_decode_attention_fp8_mfma(p, scales, st)) {
+            return rc;
+        }
+        if (p.splits > 1) {
+            if (L.head_dim == 64) {
+                decode_reduce_kernel<64, true><<<dim3(p.q_heads, p.batch), 64, 0, st>>>(p);
+            }
+            else {
+                decode_reduce_kernel<128, true><<<dim3(p.q_heads, p.batch), 128, 0, st>>>(p);
+            }
+            TM_HIP_CHECK(hipGetLastError());
+        }
         return 0;
     }
     if (L.bits == 42) {

@@ -40,6 +40,12 @@ static KvCacheView to_view(const tm_kv_cache* c)
     return v;
 }
 
+// tm_kv_cache::k_scale / ::v_scale (FP8 KV; 0 = 1.0: what a caller that fills the first seven fields leaves there)
+static KvScales to_scales(const tm_kv_cache* c)
+{
+    return KvScales{c->k_scale == 0.f ? 1.f : c->k_scale, c->v_scale == 0.f ? 1.f : c->v_scale};
+}
+
 // Per-pair inverse frequencies of one RoPE recipe (init_rope_kernel_param, attention_weight.cc:37-93 + the init_* functions of
 // rotary_embedding.h:11-52).  Deterministic recipe shared with the oracle: freq is an fp32 product run through exp2 in double and
 // rounded to fp32; everything behind it is stated in fp32 operation by operation.
@@ -288,7 +294,7 @@ int tm_kv_rope_store_seq(void* qkv, int q_heads, const int* cu_q_len, const int*
 {
     TM_REQUIRE(qkv && cu_q_len && k_len && cache, "null pointer");
     return launch_kv_rope_store((half_t*)qkv, q_heads, cu_q_len, k_len, batch, total_tokens, (const half2_t*)cos_sin,
-                                max_pos, to_view(cache), (hipStream_t)st, (const half_t*)qkv_bias, (const half_t*)q_norm,
+                                max_pos, to_view(cache), to_scales(cache), (hipStream_t)st, (const half_t*)qkv_bias, (const half_t*)q_norm,
                                 (const half_t*)k_norm, qk_eps, rope_row0);
 }
 
@@ -308,7 +314,7 @@ int tm_flatten_kv(void* k_out, void* v_out, int transpose_v, const int* cu_k_off
 {
     TM_REQUIRE(k_out && v_out && cu_k_off && k_len && cache, "null pointer");
     return launch_flatten_kv((half_t*)k_out, (half_t*)v_out, transpose_v, cu_k_off, k_len, batch, max_k_len, k_stride,
-                             to_view(cache), (hipStream_t)st);
+                             to_view(cache), to_scales(cache), (hipStream_t)st);
 }
 
 int tm_flatten_kv_window(void* k_out, void* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
@@ -318,7 +324,7 @@ int tm_flatten_kv_window(void* k_out, void* v_out, int transpose_v, const int* c
     TM_REQUIRE(window >= 0, "flatten: window must be >= 0 (0 = the whole context)");
     TM_REQUIRE(window == 0 || cu_q_len, "flatten: a window needs cu_q_len");
     return launch_flatten_kv_window((half_t*)k_out, (half_t*)v_out, transpose_v, cu_k_off, k_len, cu_q_len, window, batch,
-                                    max_k_len, k_stride, to_view(cache), (hipStream_t)st);
+                                    max_k_len, k_stride, to_view(cache), to_scales(cache), (hipStream_t)st);
 }
 
 size_t tm_decode_attention_workspace(int batch, int q_heads, int splits)
@@ -354,7 +360,7 @@ int tm_decode_attention_window(void* out, const void* q, int q_stride, const int
     p.partial_o  = (float*)workspace;
     p.partial_ml = workspace ? (float*)workspace + (size_t)batch * q_heads * p.splits * cache->head_dim : nullptr;
     p.cache      = to_view(cache);
-    return launch_decode_attention(p, (hipStream_t)st);
+    return launch_decode_attention(p, to_scales(cache), (hipStream_t)st);
 }
 
 int tm_decode_attention_window_mfma(void* out, const void* q, int q_stride, const int* k_len, int batch, int q_heads,
@@ -364,7 +370,7 @@ int tm_decode_attention_window_mfma(void* out, const void* q, int q_stride, cons
     TM_REQUIRE(out && q && k_len && cache, "null pointer");
     TM_REQUIRE(window >= 0, "tm_decode_attention_window_mfma: window must be >= 0 (0 = full attention)");
     TM_REQUIRE(cache->bits == 8 || cache->bits == 4,
-               "tm_decode_attention_window_mfma: int8 / int4 KV only (fp16 and TurboQuant KV: tm_decode_attention_window)");
+               "tm_decode_attention_window_mfma: int8 / int4 KV only (fp16, FP8 and TurboQuant KV: tm_decode_attention_window)");
     TM_REQUIRE(cache->head_dim == 64 || cache->head_dim == 128, "tm_decode_attention_window_mfma: head_dim 64 or 128");
     DecodeAttnParams p{};
     p.window     = window;
@@ -410,6 +416,8 @@ int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, 
     TM_REQUIRE(pos_delta == nullptr || cos_sin != nullptr, "fused decode prologue: pos_delta needs a RoPE table");
     TM_REQUIRE(cache->head_dim == 128,
                "fused decode prologue: head_dim must be 128 (head_dim 64: tm_kv_rope_store + tm_decode_attention)");
+    TM_REQUIRE(cache->bits != kKvBitsFp8,
+               "fused decode prologue with FP8 KV (TM_KV_BITS_FP8) is not built: run tm_kv_rope_store + tm_decode_attention");
     TM_REQUIRE(cache->bits != 42,
                "fused decode prologue with kv bits 42 (TurboQuant) is not built: run tm_kv_rope_store + tm_decode_attention");
     TM_REQUIRE(cache->bits == 8 || cache->bits == 4, "fused decode prologue: int8 / int4 KV only");
@@ -436,7 +444,7 @@ int tm_decode_attention_fused_delta(void* out, const void* qkv, int qkv_splits, 
     p.k_norm     = (const half_t*)k_norm;
     p.qk_eps     = qk_eps;
     p.pos_delta  = pos_delta;
-    return launch_decode_attention(p, (hipStream_t)st);
+    return launch_decode_attention(p, KvScales{}, (hipStream_t)st);  // the fused prologue serves int8 / int4 KV only (checked above)
 }
 
 size_t tm_verify_attention_workspace(int rows, int q_heads, int splits)
@@ -448,6 +456,7 @@ int tm_verify_attention(void* out, const void* q, int q_stride, const int* cu_q_
                         float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st)
 {
     TM_REQUIRE(out && q && cu_q_len && k_len && cache, "null pointer");
+    TM_REQUIRE(cache->bits != kKvBitsFp8, "tm_verify_attention with FP8 KV (TM_KV_BITS_FP8) is not built");
     TM_REQUIRE(batch >= 0, "batch >= 0");
     if (batch == 0) {
         return 0;

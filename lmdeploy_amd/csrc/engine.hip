@@ -279,8 +279,11 @@ int tm_engine_create(tm_engine** out, const tm_engine_config* c)
     TM_REQUIRE(m.q_heads % c->tp == 0 && m.inter % c->tp == 0 && m.vocab % c->tp == 0, "heads/inter/vocab % tp");
     TM_REQUIRE(m.kv_heads % c->tp == 0 || c->tp % m.kv_heads == 0, "kv_heads vs tp");
     TM_REQUIRE(m.rope_type >= 0 && m.rope_type <= 4, "rope_type in {0 default, 1 linear, 2 llama3, 3 yarn, 4 dynamic}");
-    TM_REQUIRE(c->quant_policy == 0 || c->quant_policy == 4 || c->quant_policy == 8 || c->quant_policy == 42,
-               "quant_policy in {0,4,8,42} (lmdeploy/messages.py:351-358)");
+    TM_REQUIRE(c->quant_policy != 17, "quant_policy 17 (FP8_E5M2 KV) is not built: FP8 KV is quant_policy 16 (e4m3)");
+    TM_REQUIRE(c->quant_policy == 0 || c->quant_policy == 4 || c->quant_policy == 8 || c->quant_policy == 16 || c->quant_policy == 42,
+               "quant_policy in {0,4,8,16,42} (lmdeploy/messages.py:351-358)");
+    // FP8 KV (include/tm_mi355x.h, TM_KV_BITS_FP8): head_dim 64 / 128, windows and sinks included; one rank
+    TM_REQUIRE(c->quant_policy != 16 || c->tp == 1, "quant_policy 16 (FP8 KV) with tp > 1 is not built (run with tp = 1)");
     // TurboQuant KV (turboquant.h): the 128-wide rotation, full attention, one rank
     TM_REQUIRE(c->quant_policy != 42 || m.head_dim == 128, "quant_policy 42 (TurboQuant KV) needs head_dim 128: head_dim 64 is not built");
     TM_REQUIRE(c->quant_policy != 42 || (m.attn_window == 0 && m.attn_sinks == 0),
@@ -433,6 +436,22 @@ int tm_engine_set_layer_windows(tm_engine* e, const int* window, int layers)
     return 0;
 }
 
+int tm_engine_set_kv_scales(tm_engine* e, const float* k_scale, const float* v_scale, int layers)
+{
+    TM_REQUIRE(e && k_scale && v_scale, "null pointer");
+    TM_REQUIRE(!e->started, "tm_engine_set_kv_scales: call before tm_engine_start");
+    TM_REQUIRE(e->cfg.quant_policy == 16, "tm_engine_set_kv_scales: the engine's quant_policy must be 16 (FP8 KV)");
+    TM_REQUIRE(layers == e->cfg.model.layers, "tm_engine_set_kv_scales: one k_scale and one v_scale per layer of the model");
+    for (int i = 0; i < layers; ++i) {
+        TM_REQUIRE(k_scale[i] > 0.f && v_scale[i] > 0.f && std::isfinite(k_scale[i]) && std::isfinite(v_scale[i]),
+                   "tm_engine_set_kv_scales: scales must be finite and > 0");
+    }
+    for (int i = 0; i < layers; ++i) {
+        e->layers[i].kv_scales = KvScales{k_scale[i], v_scale[i]};
+    }
+    return 0;
+}
+
 int tm_engine_set_mrope_section(tm_engine* e, int sec_t, int sec_h, int sec_w)
 {
     TM_REQUIRE(e, "null pointer");
@@ -443,6 +462,7 @@ int tm_engine_set_mrope_section(tm_engine* e, int sec_t, int sec_h, int sec_w)
         TM_REQUIRE(m.head_dim == 128, "mrope_section needs head_dim 128: M-RoPE is not built for head_dim 64");
         TM_REQUIRE(sec_t + sec_h + sec_w == m.head_dim / 2, "mrope_section must sum to head_dim / 2");
         TM_REQUIRE(m.rope_type != 4, "mrope_section with rope_type 4 (dynamic NTK, per-sequence tables) is not built");
+        TM_REQUIRE(e->cfg.quant_policy != 16, "mrope_section with quant_policy 16 (FP8 KV) is not built");
     }
     e->mrope_section[0] = sec_t;
     e->mrope_section[1] = sec_h;
@@ -711,7 +731,7 @@ int tm_engine_start(tm_engine* e)
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));
     const tm_engine_config& c = e->cfg;
     const tm_model_config&  m = c.model;
-    const int bits = c.quant_policy == 0 ? 16 : c.quant_policy;
+    const int bits = c.quant_policy == 0 ? 16 : c.quant_policy == 16 ? kKvBitsFp8 : c.quant_policy;
     e->layout      = KvLayout{e->kv_heads, e->D, c.cache_block_seq_len, bits};
     e->block_bytes = (int64_t)m.layers * e->layout.layer_size();
     e->max_blocks_per_seq = (c.session_len + 63) / 64;
@@ -774,7 +794,7 @@ int tm_engine_start(tm_engine* e)
         TM_REQUIRE(c.quant_policy != 42 || !e->windowed,
                    "quant_policy 42 (TurboQuant KV) with a sliding window or attention sinks is not built");
         // the folded norm divides by hidden and has no bias term: a zero-padded model or an o_proj bias runs the norm launches
-        if (e->windowed || e->hidden_valid != e->hidden || m.attn_out_bias) {
+        if (e->windowed || e->hidden_valid != e->hidden || m.attn_out_bias || c.quant_policy == 16) {
             e->fold_norm = 0;
         }
         // block ring: only when EVERY layer is windowed (one KV block holds all layers, so one full-attention layer keeps every

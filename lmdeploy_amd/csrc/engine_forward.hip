@@ -241,7 +241,7 @@ static int kv_store(tm_engine* e, const Layer& L, const KvCacheView& cv, const R
                                           L.q_norm, L.k_norm, e->cfg.model.rms_eps);
     }
     return launch_kv_rope_store(e->d_qkv + (size_t)R.r0 * e->qkv_n, e->q_heads, R.cu_q, R.k_len, R.nseq, R.rows, e->d_rope, e->rope_max_pos, cv,
-                                st, L.qkv_bias, L.q_norm, L.k_norm, e->cfg.model.rms_eps, rope_row0 ? rope_row0 + R.s0 : nullptr);
+                                L.kv_scales, st, L.qkv_bias, L.q_norm, L.k_norm, e->cfg.model.rms_eps, rope_row0 ? rope_row0 + R.s0 : nullptr);
 }
 
 // prefill attention of R's sequences: their K/V (stored before: kv_store) flattened into the scratch, attention over it
@@ -250,7 +250,7 @@ static int prefill_attention_block(tm_engine* e, const Layer& L, const KvCacheVi
 {
     // (a windowed layer flattens from the first 64-key stage of its window on: launch_flatten_kv_window; window 0 = the whole context)
     TM_PROF(P_KV_STORE, TM_TRY(launch_flatten_kv_window(e->d_kflat, e->d_vflat, 1, e->d_cu_koff + R.s0, R.k_len, R.cu_q, L.window, R.nseq,
-                                                       max_k_len, kflat_stride, cv, e->stream)));
+                                                       max_k_len, kflat_stride, cv, L.kv_scales, e->stream)));
     PrefillAttnParams p{};
     p.q          = e->d_qkv + (size_t)R.r0 * e->qkv_n;
     p.q_stride   = e->qkv_n;
@@ -331,7 +331,7 @@ static int decode_attention_block(tm_engine* e, const Layer& L, const KvCacheVie
     p.cache      = cv;
     p.window     = L.window;
     p.sinks      = L.sinks;
-    TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, st)));
+    TM_PROF(P_ATTN, TM_TRY(launch_decode_attention(p, L.kv_scales, st)));
     return 0;
 }
 
@@ -930,6 +930,7 @@ void setup_decode(tm_engine* e, int batch)
         // head_dim 64, windows and sinks: kv_rope_store + attention_decode_ws_mfma.hip (int8 / int4 KV) or the VALU kernel (fp16 KV).  Their
         // splits keep the VALU kernel's head-per-workgroup rule: the MFMA kernel then runs at least as many splits as its own rule would ask for
         // quant_policy 42 (TurboQuant KV): a VALU kernel of the same workgroup shape (attention_decode_tq.hip), never the fused prologue
+        // quant_policy 16 (FP8 KV): kv_rope_store + attention_decode_fp8_mfma.hip; its splits follow the head-per-workgroup rule too
         const bool mfma = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && e->D == 128 && !e->windowed;
         const int  group = e->q_heads / e->kv_heads;
         int        hpw   = 1;
@@ -1215,6 +1216,7 @@ int tm_engine_set_multimodal(tm_engine* e, const tm_mm_input* host, int batch)
     }
     TM_REQUIRE(e->cfg.tp == 1 && !e->use_comm, "multimodal input with tp > 1 is not built");
     TM_REQUIRE(e->cfg.quant_policy != 42, "multimodal input with quant_policy 42 (TurboQuant KV) is not built");
+    TM_REQUIRE(e->cfg.quant_policy != 16, "multimodal input with quant_policy 16 (FP8 KV) is not built");
     TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
     const bool sections = e->mrope_section[0] + e->mrope_section[1] + e->mrope_section[2] > 0;
     std::vector<tmk::MmSeqT> mm(batch);
@@ -1666,6 +1668,7 @@ int tm_engine_set_speculative(tm_engine* e, int k, int ngram_max, int ngram_min)
     const tm_engine_config& c = e->cfg;
     TM_REQUIRE(c.tp == 1 && !e->use_comm, "speculative decoding with tp > 1 is not built");
     TM_REQUIRE(c.quant_policy != 42, "speculative decoding with quant_policy 42 (TurboQuant KV) is not built");
+    TM_REQUIRE(c.quant_policy != 16, "speculative decoding with quant_policy 16 (FP8 KV) is not built");
     TM_REQUIRE(!e->windowed, "speculative decoding with a sliding window or attention sinks is not built");
     TM_REQUIRE(e->mrope_section[0] + e->mrope_section[1] + e->mrope_section[2] == 0,
                "speculative decoding with M-RoPE sections (multimodal models) is not built");

@@ -71,6 +71,7 @@ struct Layer {
     // sliding window of this layer after clamping (0: full attention) and its sink logits [q_heads] (nullptr: none); tm_engine_start
     int         window    = 0;
     half_t*     sinks     = nullptr;
+    KvScales    kv_scales;  // quant_policy 16 (FP8 KV): this layer's k_scale / v_scale (tm_engine_set_kv_scales; 1.0 otherwise)
     // mixture of experts: gate slot + per-expert slots feed `moe`; the dense w13 / w2 are unused unless the layer has a shared
     // expert (tm_model_config.moe_shared_inter: Qwen2-MoE), which IS the dense FFN at the shared width, gated inside moe's combine
     bool                     is_moe = false;

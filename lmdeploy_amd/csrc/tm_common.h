@@ -155,6 +155,16 @@ __device__ __forceinline__ float upper_max(float v)
     return v;
 }
 
+// two e4m3 bytes (bytes 1, 0 of w, or 3, 2 with `high`) -> two fp16 lanes holding code * 2^-8, exactly: a byte in the high half of its
+// lane is s eeee mmm 0...; an arithmetic shift by one and clearing bit 14 leaves s 0eeee mmm0..., the fp16 of the same value at
+// exponent bias 15 instead of 7.  Subnormals map to subnormals, and every byte (the NaN codes 0x7f / 0xff too) to a finite number.
+typedef short short2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f8_widen2(uint32_t w, bool high)
+{
+    const uint32_t t = __builtin_amdgcn_perm(0u, w, high ? 0x030c020cu : 0x010c000cu);
+    return bit_cast<uint32_t>(bit_cast<short2_t>(t) >> 1) & 0xbfffbfffu;
+}
+
 __device__ __forceinline__ float fast_exp2(float x)
 {
     return __builtin_amdgcn_exp2f(x);  // v_exp_f32 (no denormal range handling needed here)

@@ -7,6 +7,13 @@
 namespace tmk {
 
 // ---- paged KV cache geometry (reference: kernels/attention/block.h:126-219) ----------------
+constexpr int kKvBitsFp8 = 108;  // = TM_KV_BITS_FP8: the FP8 cache's tag in KvLayout::bits (16 is fp16 KV)
+// The FP8 cache's per-tensor scales of one layer.  They travel next to the view, not inside it: KvCacheView and DecodeAttnParams are
+// kernel arguments of every cache kernel, and only the FP8 instantiations read scales.  A mandatory launcher argument (no default): a caller
+// that forgot it would run an FP8 cache at 1.0 without a word.
+struct KvScales {
+    float k = 1.f, v = 1.f;
+};
 struct KvLayout {
     int kv_heads;
     int head_dim;   // 64 | 128
@@ -17,9 +24,14 @@ struct KvLayout {
     __host__ __device__ int v_token_size() const { return bits == 42 ? head_dim / 4 : token_data_size(); }
     __host__ __device__ int layer_size() const
     {
-        return bits == 42 ? kv_heads * tq_head_data_size() + kv_heads * 2 * tq_head_param_size() :
-                            kv_heads * 2 * head_data_size() + kv_heads * 2 * head_param_size();
+        return bits == kKvBitsFp8 ? kv_heads * 2 * block_len * head_dim :
+               bits == 42         ? kv_heads * tq_head_data_size() + kv_heads * 2 * tq_head_param_size() :
+                                    kv_heads * 2 * head_data_size() + kv_heads * 2 * head_param_size();
     }
+    // ---- bits kKvBitsFp8 (e4m3 codes, one byte each, no per-token parameters): per kv head K rows [block_len][head_dim], then V rows.
+    // Only the code paths of that tag call these. ----
+    __host__ __device__ int f8_k_data(int head, int ti) const { return (head * 2 * block_len + ti) * head_dim; }
+    __host__ __device__ int f8_v_data(int head, int ti) const { return f8_k_data(head, ti) + block_len * head_dim; }
     // ---- bits 16 / 8 / 4: the offsets the kernels of those widths compile (unchanged by the TurboQuant rows below) ----
     __host__ __device__ int token_data_size() const { return bits * head_dim / 8; }
     __host__ __device__ int token_param_size() const { return bits < 16 ? 4 : 0; }
@@ -72,7 +84,7 @@ int launch_residual_rmsnorm(half_t* y, half_t* resid, const half_t* hidden, cons
 // Qwen prologue (all nullptr: today's kernel): qkv_bias [q_heads + 2 kv_heads][D] is added to q, k and v (fp16); q_norm /
 // k_norm [D] run a per-head RMSNorm (eps qk_eps) on q / k first.  Order: norm -> bias -> RoPE.
 int launch_kv_rope_store(half_t* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
-                         const half2_t* cos_sin, int max_pos, KvCacheView cache, hipStream_t st,
+                         const half2_t* cos_sin, int max_pos, KvCacheView cache, KvScales scales, hipStream_t st,
                          const half_t* qkv_bias = nullptr, const half_t* q_norm = nullptr, const half_t* k_norm = nullptr,
                          float qk_eps = 0.f, const int* rope_row0 = nullptr);
 // The same with M-RoPE in sections (Qwen2-VL): frequency pair j reads table row clamp(c, 0, max_pos - 1) of its section's coordinate
@@ -82,6 +94,13 @@ int launch_kv_rope_store_mrope(half_t* qkv, int q_heads, const int* cu_q_len, co
                                const half2_t* cos_sin, int max_pos, const int* mrope_pos, const int* pos_delta, int sec_t, int sec_h,
                                int sec_w, KvCacheView cache, hipStream_t st, const half_t* qkv_bias = nullptr,
                                const half_t* q_norm = nullptr, const half_t* k_norm = nullptr, float qk_eps = 0.f);
+
+// kv_cache_fp8.hip: the FP8 cache's instantiations, reached through the launchers of kv_cache.hip (which check the arguments) only
+int launch_kv_rope_store_fp8(half_t* qkv, int q_heads, const int* cu_q_len, const int* k_len, int batch, int total_tokens,
+                             const half2_t* cos_sin, int max_pos, KvCacheView cache, KvScales scales, hipStream_t st, const half_t* qkv_bias,
+                             const half_t* q_norm, const half_t* k_norm, float qk_eps, const int* rope_row0);
+int launch_flatten_kv_fp8(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int k_stride,
+                          KvCacheView cache, KvScales scales, const int* cu_q_len, int window, dim3 grid, hipStream_t st);
 
 // per-pair inverse frequencies of one RoPE recipe (rope_inv_freq, c_api.hip) + the factor on cos / sin (YaRN; 1 otherwise): what the
 // host table builder and rope_table_kernel share, so both build the same table
@@ -94,13 +113,13 @@ int launch_rope_table(half2_t* out, int max_pos, int dim, const RopeInvFreq& f, 
 // Gather + dequantise (two-rounding "flatten" form) the whole context of every sequence into linear
 // scratch: K [kv_heads][k_stride][D]; V either [kv_heads][k_stride][D] or transposed [kv_heads][D][k_stride].
 int launch_flatten_kv(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len, int batch,
-                      int max_k_len, int k_stride, KvCacheView cache, hipStream_t st);
+                      int max_k_len, int k_stride, KvCacheView cache, KvScales scales, hipStream_t st);
 // The same for a layer with a sliding window (cu_q_len [batch + 1]: the forward's query rows): 64-token tiles that end at or below
 // max(k_len - q_len - window + 1, 0) are skipped -- not read, their scratch left unwritten: the windowed prefill kernel never stages them.
 // window == 0 is launch_flatten_kv.
 int launch_flatten_kv_window(half_t* k_out, half_t* v_out, int transpose_v, const int* cu_k_off, const int* k_len,
                              const int* cu_q_len, int window, int batch, int max_k_len, int k_stride, KvCacheView cache,
-                             hipStream_t st);
+                             KvScales scales, hipStream_t st);
 
 // ---- attention_decode.hip ---------------------------------------------------------------
 struct DecodeAttnParams {
@@ -142,12 +161,15 @@ struct DecodeAttnParams {
     // clamp(k_len - 1 + pos_delta[b], 0, max_pos - 1).  nullptr: the prologue as it was (its own kernel instantiations).
     const int*     pos_delta = nullptr;
 };
-int launch_decode_attention(const DecodeAttnParams& p, hipStream_t st);
+int launch_decode_attention(const DecodeAttnParams& p, KvScales scales, hipStream_t st);  // scales: the FP8 cache's, else unread
 int launch_decode_attention_i8_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode_mfma.hip
 // attention_decode_ws_mfma.hip: int8 / int4 KV at head_dim 64 / 128 on the matrix cores, with window and sinks; unfused.  The kernel alone
 // (partials when splits > 1); launch_decode_attention_window_mfma adds the split merge and is what tm_decode_attention_window_mfma runs.
 int launch_decode_attention_ws_mfma(const DecodeAttnParams& p, hipStream_t st);
 int launch_decode_attention_window_mfma(const DecodeAttnParams& p, hipStream_t st);  // attention_decode.hip
+// attention_decode_fp8_mfma.hip: the FP8 cache (kKvBitsFp8) at head_dim 64 / 128 on the matrix cores, with window and sinks; unfused.
+// The kernel alone: partials in decode_reduce_kernel's layout when splits > 1 (launch_decode_attention merges them).
+int launch_decode_attention_fp8_mfma(const DecodeAttnParams& p, KvScales scales, hipStream_t st);
 // attention_decode_tq.hip: KV bits 42 (TurboQuant), head_dim 128, in the rotated domain; no window, sinks or fused prologue
 int launch_decode_attention_tq(const DecodeAttnParams& p, hipStream_t st);
 size_t decode_attention_workspace_bytes(int batch, int q_heads, int head_dim, int splits);

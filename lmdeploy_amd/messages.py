@@ -185,7 +185,8 @@ class TurbomindEngineConfig:
     channel (`quant_method: "compressed-tensors"`, `format: "float-quantized"`: llm-compressor `*-FP8-dynamic`) load as they are, dense
     and Mixtral alike, head_dim 64 included: every decoder linear and expert runs on the fp8 matrix cores with its activations quantised
     per token (never coarser than a per-tensor static scale: `input_scale` / `activation_scheme: "static"` and `k_scale` / `v_scale` /
-    `kv_cache_scheme` in such a checkpoint are read past; the KV cache follows quant_policy, and quant_policy=16 stays refused);
+    `kv_cache_scheme` in such a checkpoint are read past; the KV cache follows quant_policy, and quant_policy=16 stays refused HERE: the
+    FP8 KV cache is served one level down, by turbomind.engine.Engine(quant_policy=16) with checkpoint.read_kv_scales, DESIGN.md 7.14);
     lm_head and router gates stay fp16; TM_FP8_MFMA=0 is refused for them.  model_format='fp8_channel' asks for that form (a
     `synthetic:` model is built in it).  MXFP4 W4A4 checkpoints in AMD Quark's layout (`quant_method: "quark"`: fp4 per-group weights,
     group 32, e8m0 scales, dynamic fp4 input activations; `<proj>.weight` uint8 [out][in/2] and `<proj>.weight_scale` uint8 [out][in/32])

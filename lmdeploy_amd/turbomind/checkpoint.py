@@ -4,7 +4,8 @@ Host-side mirror of the reference loader for Llama / InternLM2 / Mixtral / Qwen2
 g128; GPTQ g128, symmetric, no act-order; compressed-tensors `pack-quantized` g128 or -- dense models -- g32: the W4 table below),
 FP8 (e4m3: 128x128 block scales, `.weight_scale_inv`; or one scale per tensor / per output channel, `.weight_scale` -- AutoFP8
 `quant_method: "fp8"` without weight_block_size and compressed-tensors `float-quantized`; their static `input_scale` / `k_scale` /
-`v_scale` tensors are read past: activations are quantised per token, the KV cache follows quant_policy), INT8 W8A8 (int8 codes with
+`v_scale` tensors are read past by the weight readers: activations are quantised per token, the KV cache follows quant_policy;
+read_kv_scales returns `k_scale` / `v_scale` for an engine with the FP8 KV cache, quant_policy 16), INT8 W8A8 (int8 codes with
 one scale per tensor / output channel: `quant_method: "smooth_quant"` with `.scale`, compressed-tensors `int-quantized` with
 `.weight_scale`; dense models; the INT8 table below) or fp16 / bf16 weights
 (dense linears and MoE experts alike), and for gpt-oss
@@ -867,7 +868,7 @@ def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
         if s.shape not in ((), (1,), (N,), (N, 1)):
             raise ValueError(f'{sname}: shape {tuple(s.shape)} is neither a per-tensor ([] / [1]) nor a per-channel '
                              f'([{N}] / [{N}, 1]) scale')
-        # (.input_scale / .k_scale / .v_scale of static checkpoints are not read)
+        # (.input_scale of static checkpoints is not read; .k_scale / .v_scale: read_kv_scales)
         return {'i8' if w.dtype == np.int8 else 'f8': np.ascontiguousarray(w.T),
                 'cs': np.ascontiguousarray(np.broadcast_to(s.reshape(-1), (N,)))}
     if quantized and (prefix + '.weight_scale_inv') in t:       # FP8Format.normalize: transpose weight and scales
@@ -883,6 +884,29 @@ def _linear(t: _Tensors, prefix: str, quantized: bool) -> dict:
                     s=t.get(prefix + '.scales').astype(np.float16),
                     z=unpack_awq_gemm(t.get(prefix + '.qzeros')).astype(np.float16))
     return dict(w=np.ascontiguousarray(t.get(prefix + '.weight').astype(np.float16).T))
+
+
+# The FP8 KV cache's per-tensor scales (Engine(quant_policy=16).set_kv_scales): one scalar per layer next to the attention projections, under the Llama-family
+# names.  These are the names vLLM-style FP8 checkpoints (AutoFP8 with a kv-cache scheme, llm-compressor `kv_cache_scheme`) are documented
+# to carry; no published checkpoint with them was at hand to check the names against.
+KV_SCALES = dict(k='model.layers.{i}.self_attn.k_scale', v='model.layers.{i}.self_attn.v_scale')
+
+
+def read_kv_scales(model_path: str, layers: int) -> tuple:
+    """-> (k_scale [layers], v_scale [layers]) fp32 for tm_engine_set_kv_scales; a layer without the tensor gets 1.0"""
+    t = _Tensors(model_path)
+    out = []
+    for name in (KV_SCALES['k'], KV_SCALES['v']):
+        vals = np.ones(layers, np.float32)
+        for i in range(layers):
+            key = name.format(i=i)
+            if key in t:
+                s = t.get(key).astype(np.float32).reshape(-1)
+                if s.size != 1 or not np.isfinite(s[0]) or s[0] <= 0:
+                    raise ValueError(f'{key}: expected one finite scale > 0, got shape {tuple(s.shape)} value {s[:1]}')
+                vals[i] = s[0]
+        out.append(vals)
+    return out[0], out[1]
 
 
 def _cat(parts: list) -> dict:

@@ -87,6 +87,12 @@ class Engine:
         t, h, w = (int(v) for v in sections)
         _ffi.check(self._lib.tm_engine_set_mrope_section(self._h, t, h, w))
 
+    def set_kv_scales(self, k_scale: Sequence[float], v_scale: Sequence[float]):
+        """quant_policy=16 (FP8 KV): one k_scale and one v_scale per layer; before start()"""
+        k = (C.c_float * len(k_scale))(*[float(s) for s in k_scale])
+        v = (C.c_float * len(v_scale))(*[float(s) for s in v_scale])
+        _ffi.check(self._lib.tm_engine_set_kv_scales(self._h, k, v, len(k_scale)))
+
     def set_layer_windows(self, windows: Sequence[int]):
         """one sliding window per layer (0 = full attention), replacing the model config's window; before start()"""
         arr = (C.c_int * len(windows))(*[int(w) for w in windows])
