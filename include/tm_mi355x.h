@@ -816,6 +816,48 @@ int tm_engine_verify(tm_engine* e, const int* host_drafts, const int* host_n_dra
 int tm_engine_fetch_spec(tm_engine* e, int* host_tokens, int* host_counts);
 int tm_engine_fetch_spec_logits(tm_engine* e, void* host_out);
 int tm_engine_spec_stats(tm_engine* e, int64_t* host_stats);
+/* Multi-LoRA (lora.hip): the delta of up to TM_LORA_MAX_SLOTS resident adapters added IN PLACE to the finished fp16 result
+ * of a base linear, one launch per linear.  Arithmetic contract, per row m whose id a = adapter_of_row[m] names a filled slot:
+ *   t[r]    = fp16( sum_k x[m][k] * A_a[r][k] )                        fp32 accumulation, rounded once to fp16
+ *   y[m][n] = fp16( float(y[m][n]) + sum_r float(t[r]) * B_a[n][r] )   fp32 sum over the rank slice of n's column segment
+ * A row whose id is -1 (or names an empty slot), a column outside every segment and every byte of y outside [0, N) of a row are not
+ * written at all.  lora_alpha / r (use_rslora: lora_alpha / sqrt(r)) is folded into B by the caller; ranks are zero-padded by the caller
+ * to multiples of 16.
+ * tm_lora_table_create: the table of ONE linear [K -> N] with n_segments (1 .. 3) column segments [seg_begin[g], seg_end[g]) (host
+ *   arrays; ascending, disjoint, multiples of 16 -- the fused w_qkv has three, q | k | v) and `slots` (1 .. 8) adapter slots.
+ * tm_lora_table_set: fill (or replace) a slot from fp16 host or device memory: seg_rank [n_segments] (host; multiples of 16, <= 64, 0 =
+ *   this adapter leaves the segment alone), A [sum seg_rank][K] (the segments' rank slices stacked in segment order), B [N][ldb] (row n of
+ *   segment g holds its seg_rank[g] entries first; ldb >= max seg_rank, ldb % 8 == 0).  Synchronous.
+ * tm_lora_plan: row ids -> tiles of 16 rows of one slot, in `plan_ws` (device, tm_lora_plan_workspace(M) bytes); once per forward,
+ *   whatever the number of linears.  adapter_of_row: device int32 [M]; host_ids (may be NULL): its host copy, checked against
+ *   [-1, slots) -- the kernels never check ids, they treat an id outside [0, slots) as -1.
+ * tm_lora_apply: the delta launch.  x [M][ldx] fp16 (ldx % 8 == 0, 16-byte aligned), y [M][ldy] fp16 (ldy % 4 == 0, 8-byte aligned).
+ * Refused with TM_INVALID by name: rank over 64 per segment, more than 8 slots, more than 3 segments, K or N not a multiple of 16,
+ * null pointers, ids outside [-1, slots). */
+#define TM_LORA_MAX_SLOTS 8
+#define TM_LORA_MAX_SEGMENTS 3
+#define TM_LORA_MAX_RANK 64
+typedef struct tm_lora_table tm_lora_table;
+int    tm_lora_table_create(tm_lora_table** out, int K, int N, int n_segments, const int* seg_begin, const int* seg_end, int slots);
+int    tm_lora_table_set(tm_lora_table* t, int slot, const void* A, const void* B, const int* seg_rank, int ldb);
+int    tm_lora_table_destroy(tm_lora_table* t);
+size_t tm_lora_plan_workspace(int M);
+int    tm_lora_plan(void* plan_ws, const int* adapter_of_row, const int* host_ids, int M, int slots, tm_stream_t st);
+int    tm_lora_apply(const tm_lora_table* t, const void* x, int ldx, void* y, int ldy, int M, const void* plan_ws, tm_stream_t st);
+/* Multi-LoRA in the engine (static batches, tp 1, dense models).  linear_kind: */
+enum { TM_LORA_QKV = 0, TM_LORA_WO = 1, TM_LORA_W2 = 2, TM_LORA_W13 = 3 };
+/* tm_engine_load_adapter: after tm_engine_start, while no batch is admitted: adapter `slot` (0 .. 7) of `layer`'s linear, operands as for
+ *   tm_lora_table_set (w_qkv: segments q | k | v, any subset by seg_rank 0; wo, w2: one segment).  From the first loaded adapter on the
+ *   engine runs the unfused schedule (every linear finishes its own fp16 rows: no fused decode prologue, no folded norm, no deferred
+ *   split-K slabs), the plan kernel at the head of every forward and the delta launch directly behind each of the three linears.  With no
+ *   adapter loaded nothing changes.  A failed call leaves the table and the schedule as they were.
+ * tm_engine_set_adapters: slot per sequence (host, -1 = none) of the NEXT tm_engine_prefill's `n` sequences; consumed by it (a prefill
+ *   without it runs every sequence on the base weights).  It writes a device array the captured decode step reads.
+ * Refused by name: TM_LORA_W13 (gate_proj / up_proj: the delta would have to land ahead of the fused SiLU epilogue), mixture-of-experts
+ * models, tp > 1, quant_policy 42, models served zero-padded (hidden_valid), speculative decoding while an adapter is loaded, multimodal prompts with an adapter selected, ids
+ * outside [-1, 8).  Continuous batching serves base requests only. */
+int tm_engine_load_adapter(tm_engine* e, int slot, int layer, int linear_kind, const void* A, const void* B, const int* seg_rank, int ldb);
+int tm_engine_set_adapters(tm_engine* e, const int* slot_per_sequence, int n);
 /* Prompt scoring (Pipeline.get_ppl; the reference's return_ppl path, models/output_processor.cc:236-300).  Synchronous.
  * `batch` sequences (host ids concatenated, host lens) run through chunked prefill with the lm_head over EVERY prompt row and
  * per-row cross-entropy against the next token, from the raw logits (no penalties, bans or sampling).  host_nll receives

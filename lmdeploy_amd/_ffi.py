@@ -50,6 +50,9 @@ class KvCache(C.Structure):
                 ('k_scale', c_float), ('v_scale', c_float)]
 
 
+LORA_MAX_SLOTS, LORA_MAX_SEGMENTS, LORA_MAX_RANK = 8, 3, 64    # TM_LORA_MAX_*
+LORA_QKV, LORA_WO, LORA_W2, LORA_W13 = 0, 1, 2, 3             # TM_LORA_*: linear_kind of tm_engine_load_adapter
+
 KV_BITS_FP8 = 108   # TM_KV_BITS_FP8: tm_kv_cache.bits of QuantPolicy.FP8 (16 itself is fp16 KV there)
 
 
@@ -265,6 +268,14 @@ _SIGNATURES = {
     'tm_p2p_allreduce_norm_2shot': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                             c_int, c_int, c_void_p]),
     'tm_p2p_allgather': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'tm_lora_table_create': (c_int, [POINTER(c_void_p), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int]),
+    'tm_lora_table_set': (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_int]),
+    'tm_lora_table_destroy': (c_int, [c_void_p]),
+    'tm_lora_plan_workspace': (c_size_t, [c_int]),
+    'tm_lora_plan': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'tm_lora_apply': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'tm_engine_load_adapter': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int), c_int]),
+    'tm_engine_set_adapters': (c_int, [c_void_p, POINTER(c_int), c_int]),
     'tm_engine_create': (c_int, [POINTER(c_void_p), POINTER(EngineConfig)]),
     'tm_engine_destroy': (c_int, [c_void_p]),
     'tm_comm_unique_id': (c_int, [c_void_p]),

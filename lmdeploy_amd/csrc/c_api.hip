@@ -1240,6 +1240,61 @@ int tm_moe_destroy(tm_moe* m)
     return 0;
 }
 
+// ---- multi-LoRA delta (lora.hip) ------------------------------------------------------------------------------------
+struct tm_lora_table {
+    tmk::LoraTable t;
+};
+
+int tm_lora_table_create(tm_lora_table** out, int K, int N, int n_segments, const int* seg_begin, const int* seg_end, int slots)
+{
+    TM_REQUIRE(out, "null pointer");
+    auto*     o  = new tm_lora_table();
+    const int rc = lora_table_init(o->t, K, N, n_segments, seg_begin, seg_end, slots);
+    if (rc) {
+        delete o;
+        return rc;
+    }
+    *out = o;
+    return 0;
+}
+
+int tm_lora_table_set(tm_lora_table* t, int slot, const void* A, const void* B, const int* seg_rank, int ldb)
+{
+    TM_REQUIRE(t, "lora: null table");
+    return lora_table_set(t->t, slot, A, B, seg_rank, ldb);
+}
+
+int tm_lora_table_destroy(tm_lora_table* t)
+{
+    if (t) {
+        lora_table_free(t->t);
+        delete t;
+    }
+    return 0;
+}
+
+size_t tm_lora_plan_workspace(int M)
+{
+    return M >= 1 ? lora_plan_workspace_bytes(M) : 0;
+}
+
+int tm_lora_plan(void* plan_ws, const int* adapter_of_row, const int* host_ids, int M, int slots, tm_stream_t st)
+{
+    TM_REQUIRE(plan_ws && adapter_of_row, "lora plan: null pointer");
+    TM_REQUIRE(M >= 1, "lora plan: M >= 1");
+    TM_REQUIRE(slots >= 1 && slots <= TM_LORA_MAX_SLOTS, "lora: at most 8 adapter slots");
+    for (int m = 0; host_ids && m < M; ++m) {
+        TM_REQUIRE(host_ids[m] >= -1 && host_ids[m] < slots, "lora: adapter id outside [-1, slots)");
+    }
+    return launch_lora_plan(plan_ws, adapter_of_row, nullptr, 0, M, slots, (hipStream_t)st);
+}
+
+int tm_lora_apply(const tm_lora_table* t, const void* x, int ldx, void* y, int ldy, int M, const void* plan_ws, tm_stream_t st)
+{
+    TM_REQUIRE(t, "lora: null table");
+    return launch_lora_delta(t->t, (const half_t*)x, ldx, (half_t*)y, ldy, M, plan_ws, (hipStream_t)st);
+}
+
 // ---- host-only scheduler hooks (scheduler.h) ----------------------------------------------------------------------
 struct tm_sched {
     tmk::BatchScheduler impl;

@@ -1098,8 +1098,13 @@ int tm_engine_destroy(tm_engine* e)
         if (L.is_moe) {
             moe_free(L.moe);
         }
+        for (LoraTable* t : {&L.lora_qkv, &L.lora_wo, &L.lora_w2}) {
+            if (t->dev) {
+                lora_table_free(*t);
+            }
+        }
     }
-    for (void* q : {e->d_moe_ws, (void*)e->d_shared}) {
+    for (void* q : {e->d_moe_ws, (void*)e->d_shared, (void*)e->d_lora_seq, e->d_lora_plan}) {
         if (q) {
             (void)hipFree(q);
         }

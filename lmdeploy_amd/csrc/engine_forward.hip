@@ -139,11 +139,24 @@ static int linear_deferrable(tm_engine* e, LinearSlots& l, const half_t* x, int 
 
 // row-parallel linear followed by (all-reduce +) residual + RMSNorm; without a communicator the norm launch sums the slabs
 // (bias: the o_proj bias, r = h(h(r + out) + bias) -- the HAS_BIAS arm of the norm kernel; nullptr for every other linear)
+// the LoRA delta of a static batch's forward, directly behind the linear that finished y (no-op: no adapter loaded for this linear)
+static int lora_delta(tm_engine* e, const LoraTable& t, const half_t* x, int ldx, half_t* y, int ldy, int M, int cat)
+{
+    if (e->fw_lora && t.dev) {
+        TM_PROF(cat, TM_TRY(launch_lora_delta(t, x, ldx, y, ldy, M, e->d_lora_plan, e->stream)));
+    }
+    return 0;
+}
+
+// (lora: the linear's adapter table; while an adapter is loaded nothing is deferred -- the delta is added to the finished fp16 rows)
 static int linear_residual_norm(tm_engine* e, LinearSlots& l, const half_t* x, int ldx, int M, const half_t* norm_w,
-                                int gemm_cat, const half_t* bias = nullptr)
+                                int gemm_cat, const half_t* bias = nullptr, const LoraTable* lora = nullptr)
 {
     int slabs = 1;
-    TM_PROF(gemm_cat, TM_TRY(linear_deferrable(e, l, x, ldx, e->d_tmp, e->hidden, M, false, !e->use_comm, &slabs)));
+    TM_PROF(gemm_cat, TM_TRY(linear_deferrable(e, l, x, ldx, e->d_tmp, e->hidden, M, false, !e->use_comm && !e->lora_on, &slabs)));
+    if (lora) {
+        TM_TRY(lora_delta(e, *lora, x, ldx, e->d_tmp, e->hidden, M, gemm_cat));
+    }
     if (slabs > 1) {
         TM_PROF(P_RES_NORM, TM_TRY(launch_residual_rmsnorm(e->d_x, e->d_resid, nullptr, e->d_gemm_ws, slabs, bias, norm_w,
                                                            e->cfg.model.rms_eps, M, e->hidden, e->stream, e->hidden_valid)));
@@ -162,7 +175,7 @@ static void fold_tiling(tm_engine* e, const LinearWeight& w, int M, int* shape, 
 
 static bool fold_ok(const tm_engine* e, const Layer& L, int M)
 {
-    return e->fold_norm != 0 && !L.is_moe && M <= e->fold_max_rows && dec32_supported(L.qkv.w, M) && dec32_supported(L.wo.w, M) && dec32_supported(L.w13.w, M)
+    return e->fold_norm != 0 && !e->lora_on && !L.is_moe && M <= e->fold_max_rows && dec32_supported(L.qkv.w, M) && dec32_supported(L.wo.w, M) && dec32_supported(L.w13.w, M)
            && dec32_supported(L.w2.w, M);
 }
 
@@ -224,7 +237,7 @@ static int qkv_project(tm_engine* e, Layer& L, const Rows& R, bool fold, bool fu
     TM_PROF(P_GEMM_QKV, TM_TRY(fold  ? linear_fold_consume(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false, ss_tiles, fused, slabs) :
                                fused ? linear_deferrable(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false, true, slabs) :
                                        linear_plain(e, L.qkv, x, e->hidden, y, e->qkv_n, R.rows, false)));
-    return 0;
+    return R.r0 == 0 ? lora_delta(e, L.lora_qkv, x, e->hidden, y, e->qkv_n, R.rows, P_GEMM_QKV) : 0;  // (row halves: tp > 1, no adapters)
 }
 
 // RoPE + K/V quantise-store of R's rows of d_qkv (rope_row0: the forward's per-sequence table rows, nullptr: one table)
@@ -367,9 +380,9 @@ static int pipe_ffn(tm_engine* e, Layer& L, const Rows& R, hipEvent_t* done)
 // -- the unsplit tail of a layer over all M rows: from the attention output to the next layer's normalised input
 static int tail_dense(tm_engine* e, Layer& L, int M, const half_t* next_norm)
 {
-    TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias));
+    TM_TRY(linear_residual_norm(e, L.wo, e->d_attn, e->q_heads * e->D, M, L.ffn_norm, P_GEMM_O, L.wo_bias, &L.lora_wo));
     TM_PROF(P_GEMM_GATE_UP, TM_TRY(linear_plain(e, L.w13, e->d_x, e->hidden, e->d_act, e->inter, M, true)));
-    return linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN);
+    return linear_residual_norm(e, L.w2, e->d_act, e->inter, M, next_norm, P_GEMM_DOWN, nullptr, &L.lora_w2);
 }
 
 // wo's epilogue updates the residual stream and hands r . g + sums of squares to w1w3, whose accumulators take the row factor before
@@ -627,6 +640,12 @@ int forward(tm_engine* e, const int* d_ids, int M, int nseq, bool decode, int ma
     }
     TM_PROF(P_RES_NORM, TM_TRY(launch_rmsnorm(e->d_x, e->d_resid, e->layers[0].attn_norm, m.rms_eps, M, e->hidden, st, e->hidden_valid)));
     // tp > 1 prefill through RCCL: whole dense layers as two micro-batches, or their row-wise part as two row halves (side-stream all-reduces)
+    // multi-LoRA: a static batch's forward (prefill, decode; not scoring, not a scheduler's) sorts its rows by adapter slot once
+    // (profiled with the w_qkv category, whose delta launch is its first reader: there is no category of its own)
+    e->fw_lora = e->lora_on && !e->sched && !md && !e->scoring && !e->fw_verify;
+    if (e->fw_lora) {
+        TM_PROF(P_GEMM_QKV, TM_TRY(launch_lora_plan(e->d_lora_plan, e->d_lora_seq + slot0, decode ? nullptr : e->d_cu_q, nseq, M, kLoraMaxSlots, st)));
+    }
     e->pipe_events_used = 0;
     const bool  pipe     = !decode && !md && prefill_pipe_ok(e, M);
     const int   Ma       = pipe ? (M / 2 + 63) / 64 * 64 : 0;
@@ -971,7 +990,7 @@ void setup_decode(tm_engine* e, int batch)
     // a model runs kv_rope_store, then plain decode attention, the same unfused path
     const bool g32   = e->cfg.model.weight_type == TM_WEIGHT_U4 && e->cfg.model.group_size == 32;
     e->fuse_qkv      = (e->cfg.quant_policy == 8 || e->cfg.quant_policy == 4) && !(valu && atoi(valu)) && !(fuse && !atoi(fuse))
-                  && !e->d_rope_row0 && e->D == 128 && !e->windowed && !g32;
+                  && !e->d_rope_row0 && e->D == 128 && !e->windowed && !g32 && !e->lora_on;  // (an adapter loaded: the unfused path too)
 }
 
 // Chunked prefill of `batch` sequences into the batch slots [slot0, slot0 + batch): whole sequences,
@@ -1256,6 +1275,76 @@ int tm_engine_set_multimodal(tm_engine* e, const tm_mm_input* host, int batch)
     return 0;
 }
 
+// ---- multi-LoRA (lora.hip) ----------------------------------------------------------------------------
+int tm_engine_load_adapter(tm_engine* e, int slot, int layer, int linear_kind, const void* A, const void* B, const int* seg_rank, int ldb)
+{
+    if (e && e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    TM_REQUIRE(e && A && B && seg_rank, "null pointer");
+    TM_REQUIRE(e->started, "engine not started");
+    TM_REQUIRE(e->batch == 0 && !e->sched, "load adapters while no batch is admitted (release it first)");
+    const tm_engine_config& c = e->cfg;
+    TM_REQUIRE(linear_kind != TM_LORA_W13,
+               "LoRA on gate_proj / up_proj is not built: the delta would have to land ahead of the fused SiLU epilogue of w1w3");
+    TM_REQUIRE(linear_kind == TM_LORA_QKV || linear_kind == TM_LORA_WO || linear_kind == TM_LORA_W2, "LoRA: linear_kind is w_qkv, wo or w2");
+    TM_REQUIRE(c.model.moe_experts == 0, "LoRA on mixture-of-experts models is not built");
+    TM_REQUIRE(c.tp == 1 && !e->use_comm, "LoRA with tp > 1 is not built");
+    TM_REQUIRE(c.quant_policy != 42, "LoRA with quant_policy 42 (TurboQuant KV) is not built");
+    TM_REQUIRE(e->hidden_valid == e->hidden, "LoRA on a model served zero-padded (hidden_valid != hidden) is not built");
+    TM_REQUIRE(e->spec_k == 0, "LoRA: speculative decoding is armed (speculative decoding while an adapter is loaded is not built)");
+    TM_REQUIRE(layer >= 0 && layer < c.model.layers, "LoRA: layer outside the model");
+    TM_REQUIRE(slot >= 0 && slot < kLoraMaxSlots, "LoRA: slot outside [0, 8) (at most 8 adapter slots)");
+    TM_HIP_CHECK(hipSetDevice(c.device));
+    Layer&     L   = e->layers[layer];
+    LoraTable& t   = linear_kind == TM_LORA_QKV ? L.lora_qkv : linear_kind == TM_LORA_WO ? L.lora_wo : L.lora_w2;
+    const int  kq  = e->q_heads * e->D, kkv = e->kv_heads * e->D;
+    if (!t.dev) {
+        const int qkv_b[3] = {0, kq, kq + kkv}, qkv_e[3] = {kq, kq + kkv, kq + 2 * kkv}, zero[1] = {0};
+        const int wo_e[1] = {e->hidden};
+        if (linear_kind == TM_LORA_QKV) {
+            TM_TRY(lora_table_init(t, e->hidden, e->qkv_n, 3, qkv_b, qkv_e, kLoraMaxSlots));
+        }
+        else {
+            TM_TRY(lora_table_init(t, linear_kind == TM_LORA_WO ? kq : e->inter, e->hidden, 1, zero, wo_e, kLoraMaxSlots));
+        }
+    }
+    TM_TRY(lora_table_set(t, slot, A, B, seg_rank, ldb));
+    if (!e->d_lora_seq) {
+        const size_t B8 = (size_t)c.max_batch_size;
+        TM_TRY(dmalloc(&e->d_lora_seq, B8));
+        TM_HIP_CHECK(hipMemset(e->d_lora_seq, 0xff, B8 * 4));
+        TM_HIP_CHECK(hipMalloc(&e->d_lora_plan, lora_plan_workspace_bytes(e->max_tokens)));
+    }
+    e->lora_on = true;
+    // the schedule changes with the first adapter, and a launch's LDS with the widest rank: captured steps are captured again
+    for (hipGraphExec_t* g : {&e->graph, &e->graph_cb}) {
+        if (*g) {
+            (void)hipGraphExecDestroy(*g);
+            *g = nullptr;
+        }
+    }
+    return 0;
+}
+
+int tm_engine_set_adapters(tm_engine* e, const int* slot_per_sequence, int n)
+{
+    if (e && e->loop_on.load()) {
+        set_last_error("the engine thread is running (tm_engine_serve_stop first)");
+        return TM_CONFLICT;
+    }
+    TM_REQUIRE(e && slot_per_sequence, "null pointer");
+    TM_REQUIRE(e->batch == 0 && !e->sched, "set the adapters before tm_engine_prefill");
+    TM_REQUIRE(e->lora_on, "tm_engine_set_adapters: no adapter is loaded (tm_engine_load_adapter)");
+    TM_REQUIRE(n >= 1 && n <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
+    for (int i = 0; i < n; ++i) {
+        TM_REQUIRE(slot_per_sequence[i] >= -1 && slot_per_sequence[i] < kLoraMaxSlots, "LoRA: adapter id outside [-1, 8)");
+    }
+    e->h_lora_seq.assign(slot_per_sequence, slot_per_sequence + n);
+    return 0;
+}
+
 int tm_engine_release(tm_engine* e)
 {
     if (e && e->loop_on.load()) {
@@ -1309,6 +1398,8 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     TM_REQUIRE(e && host_ids && host_lens, "null pointer");
     std::vector<tmk::MmSeqT> mm;
     mm.swap(e->h_mm);  // tm_engine_set_multimodal's input belongs to THIS call: consumed, whatever happens below
+    std::vector<int> lora_seq;
+    lora_seq.swap(e->h_lora_seq);  // tm_engine_set_adapters' likewise
     TM_REQUIRE(e->started, "engine not started");
     TM_REQUIRE(e->batch == 0 && !e->sched, "a batch is already admitted (release it first)");
     TM_REQUIRE(batch >= 1 && batch <= e->cfg.max_batch_size, "1 <= batch <= max_batch_size");
@@ -1324,6 +1415,15 @@ int tm_engine_prefill(tm_engine* e, const int* host_ids, const int* host_lens, i
     }
     TM_HIP_CHECK(hipSetDevice(e->cfg.device));
     const tm_engine_config& c = e->cfg;
+    if (e->lora_on) {  // the slots of this batch's sequences (none armed: base weights), before any forward reads them
+        TM_REQUIRE(spec_slack == 0, "speculative decoding while an adapter is loaded is not built");
+        TM_REQUIRE(lora_seq.empty() || (int)lora_seq.size() == batch, "tm_engine_set_adapters: batch size differs from the prefill's");
+        const bool selected = std::any_of(lora_seq.begin(), lora_seq.end(), [](int s) { return s >= 0; });
+        TM_REQUIRE(mm.empty() || !selected, "LoRA: multimodal prompts with an adapter selected are not built");
+        lora_seq.resize((size_t)c.max_batch_size, -1);
+        TM_HIP_CHECK(hipMemcpyAsync(e->d_lora_seq, lora_seq.data(), lora_seq.size() * 4, hipMemcpyHostToDevice, e->stream));
+        TM_HIP_CHECK(hipStreamSynchronize(e->stream));
+    }
 
     // ---- admit: reserve blocks for prompt + generation ------------------------------------------
     int64_t need = 0;
@@ -1667,6 +1767,7 @@ int tm_engine_set_speculative(tm_engine* e, int k, int ngram_max, int ngram_min)
                "speculative decoding: 1 <= ngram_min <= ngram_max <= 8");
     const tm_engine_config& c = e->cfg;
     TM_REQUIRE(c.tp == 1 && !e->use_comm, "speculative decoding with tp > 1 is not built");
+    TM_REQUIRE(!e->lora_on, "speculative decoding while an adapter is loaded is not built");
     TM_REQUIRE(c.quant_policy != 42, "speculative decoding with quant_policy 42 (TurboQuant KV) is not built");
     TM_REQUIRE(c.quant_policy != 16, "speculative decoding with quant_policy 16 (FP8 KV) is not built");
     TM_REQUIRE(!e->windowed, "speculative decoding with a sliding window or attention sinks is not built");

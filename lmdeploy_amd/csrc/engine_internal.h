@@ -78,6 +78,8 @@ struct Layer {
     bool                     has_shared = false;
     std::vector<LinearSlots> ex13, ex2;
     MoeBlock                 moe;
+    // multi-LoRA (tm_engine_load_adapter): the adapter tables of w_qkv (segments q | k | v), wo and w2; dev == nullptr: none loaded
+    LoraTable                lora_qkv, lora_wo, lora_w2;
 };
 
 // host copy of one sequence's tm_mm_input (tm_engine_set_multimodal)
@@ -342,6 +344,15 @@ struct tm_engine {
     float*     d_spec_attn_ws = nullptr;                                                   // split-K partials of B (k + 1) rows
     hipGraphExec_t graph_spec = nullptr;
     int        graph_spec_batch = 0, graph_spec_max_new = 0, graph_spec_k = 0;
+
+    // Multi-LoRA (tm_engine_load_adapter / tm_engine_set_adapters; lora.hip).  lora_on: some adapter is loaded -- every
+    // forward runs the unfused schedule (no fused decode prologue, no folded norm, no deferred split-K slabs) and a static batch's
+    // forward the plan kernel at its head + the delta launch behind w_qkv, wo and w2.  false: nothing below is allocated or read.
+    bool             lora_on     = false;
+    int*             d_lora_seq  = nullptr;  // [max_batch_size] slot of every batch slot's sequence, -1 = none; read by the captured step
+    void*            d_lora_plan = nullptr;  // the row tiles of the current forward (lora_plan_workspace_bytes(max_tokens))
+    std::vector<int> h_lora_seq;             // armed by tm_engine_set_adapters for the next tm_engine_prefill, which consumes it
+    bool             fw_lora     = false;    // set by forward(): this forward carries the delta launches
 
     // engine thread (tm_engine_serve_start): runs step_locked() while requests exist.  `mu` serialises the scheduler
     // and every device-side effect of submit / step / poll / cancel; API callers announce themselves in api_waiting so

@@ -619,6 +619,39 @@ int launch_gather_rows(half_t* out, const half_t* in, const int* rows, int n, in
 // targets[r] < 0: 0 (row not read); targets[r] >= V: NaN.  rows == 0: no-op.
 int launch_cross_entropy(float* nll, const half_t* logits, const int* targets, int rows, int V, int ld, hipStream_t st);
 int launch_silu_mul(half_t* out, const half_t* gate_up, int M, int inter, hipStream_t st);
+
+// ---- lora.hip (multi-LoRA delta; the contract, lane maps and LDS map are in its header) ----
+constexpr int kLoraMaxSlots = 8, kLoraMaxSegments = 3, kLoraMaxRank = 64;
+// one resident adapter of one linear, as the kernel reads it from device memory: A [rt][K] (the segments' rank slices stacked), B [N][ldb]
+// (a column of segment g holds its rank[g] entries first); rt == 0: empty slot
+struct LoraSlotDev {
+    const half_t* A;
+    const half_t* B;
+    int           rank[kLoraMaxSegments], toff[kLoraMaxSegments];
+    int           rt, ldb;
+};
+struct LoraTableDev {
+    LoraSlotDev slot[kLoraMaxSlots];
+};
+// the adapter table of one linear: geometry + host image of the device table (the kernel takes `dev`, so a captured launch sees a slot
+// that is filled later -- as long as its stacked rank stays within rt_max, which sizes the launch's LDS)
+struct LoraTable {
+    LoraTableDev* dev = nullptr;
+    LoraTableDev  host{};
+    int           K = 0, N = 0, slots = 0, nseg = 0, rt_max = 0;
+    int           seg_begin[kLoraMaxSegments] = {0, 0, 0}, seg_end[kLoraMaxSegments] = {0, 0, 0};
+};
+inline int lora_plan_tiles(int M) { return M / 16 + kLoraMaxSlots; }  // sum over slots of ceil(rows / 16) <= this
+size_t lora_plan_workspace_bytes(int M);
+int lora_table_init(LoraTable& t, int K, int N, int nseg, const int* seg_begin, const int* seg_end, int slots);
+int lora_table_set(LoraTable& t, int slot, const void* A, const void* B, const int* seg_rank, int ldb);  // fp16 host or device operands
+void lora_table_free(LoraTable& t);
+int lora_table_check(const LoraTable& t);
+int lora_slot_check(const LoraTable& t, const int* seg_rank, int ldb, LoraSlotDev* out);  // ranks -> offsets, with the refusals
+// ids [M] per row (cu_q == nullptr) or [nseq] per sequence with cu_q [nseq + 1] row offsets; -1 (anything outside [0, nslots)) = none
+int launch_lora_plan(void* plan_ws, const int* ids, const int* cu_q, int nseq, int M, int nslots, hipStream_t stream);
+int launch_lora_delta(const LoraTable& t, const half_t* x, int ldx, half_t* y, int ldy, int M, const void* plan_ws, hipStream_t stream);
+
 int launch_quantize_groupwise_u4(int32_t* qweight, half_t* scales, half_t* zeros, half_t* dequant, const half_t* w,
                                  int K, int N, int group, hipStream_t st);
 

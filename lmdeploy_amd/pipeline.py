@@ -81,6 +81,11 @@ class Pipeline:
         if self.speculative_config is not None and not isinstance(self.speculative_config, SpeculativeConfig):
             raise TypeError('speculative_config must be a lmdeploy_amd.SpeculativeConfig')
         self._spec_calls = dict(speculated=0, plain=0)     # static chunks / continuous calls that did / did not speculate
+        # LoRA adapters ({name: PEFT directory}): resident in the engine, selected per prompt by `adapter_name` (static batch)
+        adapters = dict(kwargs.get('adapters') or {})
+        self.adapters = {}                                 # name -> engine slot
+        if adapters and self.speculative_config is not None:
+            raise NotImplementedError('speculative decoding while an adapter is loaded is not built')
         cfg = backend_config or TurbomindEngineConfig()
         if not isinstance(cfg, TurbomindEngineConfig):
             raise NotImplementedError('only TurbomindEngineConfig is supported (the PyTorch engine is out of scope)')
@@ -110,6 +115,10 @@ class Pipeline:
                                  f'(lmdeploy/turbomind/converter.py:174-176)')
         # the TurboQuant KV cache (quant_policy=42): head_dim 128, full attention, tp = 1 -- refused here, by name, before any GPU work
         checkpoint.check_kv_quant_policy(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
+        if adapters:     # MoE, tp > 1, quant_policy 42: refused by name, before any GPU work
+            checkpoint.check_lora(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
+            if len(adapters) > checkpoint.LORA_MAX_SLOTS:
+                raise ValueError(f'{len(adapters)} adapters: at most {checkpoint.LORA_MAX_SLOTS} are resident in one engine')
         if self.speculative_config is not None:     # window / sinks, quant_policy 42, tp > 1, M-RoPE: refused by name, before any GPU work
             checkpoint.check_speculative(self.model_cfg, int(cfg.quant_policy), cfg.tp, what=model_path)
         session_len = cfg.session_len or self.model_cfg.max_position_embeddings
@@ -160,6 +169,8 @@ class Pipeline:
                     self.tokenizer = AutoTokenizer.from_pretrained(model_path)
             self.engine.start()
             self.max_batch_size = cfg.max_batch_size or 64
+            for name, path in adapters.items():
+                self._load_adapter(name, checkpoint.read_lora(path, self.model_cfg))
             if self._group is not None:
                 from .turbomind import tp_group
                 self._group.wait_ready()
@@ -169,24 +180,81 @@ class Pipeline:
                 self._group.close()
             raise
 
+    # ---- LoRA adapters ---------------------------------------------------------------------------------
+    _LORA_KIND = dict(qkv=_ffi.LORA_QKV, wo=_ffi.LORA_WO, w2=_ffi.LORA_W2)
+
+    def _load_adapter(self, name: str, layers: list):
+        """layers: per layer {'qkv' | 'wo' | 'w2': (A, B, ranks)} as checkpoint.lora_operands lays them out -> the next free engine slot"""
+        if name in self.adapters:
+            raise ValueError(f'adapter {name!r} is already loaded')
+        if len(self.adapters) >= checkpoint.LORA_MAX_SLOTS:
+            raise ValueError(f'at most {checkpoint.LORA_MAX_SLOTS} adapters are resident in one engine')
+        if self.speculative_config is not None:
+            raise NotImplementedError('speculative decoding while an adapter is loaded is not built')
+        checkpoint.check_lora(self.model_cfg, int(self.backend_config.quant_policy), self.backend_config.tp)
+        slot = len(self.adapters)
+        for li, lins in enumerate(layers):
+            for lin, (A, B, ranks) in lins.items():
+                self.engine.load_adapter(slot, li, self._LORA_KIND[lin], A, B, ranks)
+        self.adapters[name] = slot
+
+    def load_synthetic_adapter(self, name: str, rank: int = 16, seed: int = 0, scale: float = 1.0) -> list:
+        """A random adapter on q / k / v / o / down of every layer (tests, timing): A ~ N(0, 1 / K), B ~ N(0, scale^2 / r) in the
+        engine's own channel order.  Returns the raw per-layer {'q' | 'k' | 'v' | 'o' | 'down': (A [r, K], B [N, r])} float32 arrays."""
+        m, rng = self.model_cfg, np.random.default_rng(seed)
+        kq, kkv = m.q_heads * m.head_dim, m.kv_heads * m.head_dim
+        shapes = dict(q=(m.hidden, kq), k=(m.hidden, kkv), v=(m.hidden, kkv), o=(kq, m.hidden), down=(m.inter, m.hidden))
+        raw = [{n: (rng.standard_normal((rank, K)).astype(np.float32) / np.sqrt(K),
+                    rng.standard_normal((N, rank)).astype(np.float32) * scale / np.sqrt(rank)) for n, (K, N) in shapes.items()}
+               for _ in range(m.layers)]
+        self._load_adapter(name, [dict(qkv=checkpoint.lora_operands([L['q'], L['k'], L['v']], [kq, kkv, kkv], 1.0),
+                                       wo=checkpoint.lora_operands([L['o']], [m.hidden], 1.0),
+                                       w2=checkpoint.lora_operands([L['down']], [m.hidden], 1.0)) for L in raw])
+        return raw
+
+    def _adapter_slots(self, adapter_name, n: int):
+        """adapter_name (None | str | list of str / None, one per prompt) -> engine slot per prompt, None when no prompt selects one"""
+        names = adapter_name if isinstance(adapter_name, (list, tuple)) else [adapter_name] * n
+        if len(names) != n:
+            raise ValueError(f'{len(names)} adapter names for {n} prompts')
+        for a in names:
+            if a is not None and a not in self.adapters:
+                raise ValueError(f'unknown adapter {a!r} (loaded: {sorted(self.adapters)})')
+        slots = [-1 if a is None else self.adapters[a] for a in names]
+        return slots if any(s >= 0 for s in slots) else None
+
     # ---- reference-compatible entry points -----------------------------------------------------------
     def __call__(self, prompts, gen_config: GenerationConfig | None = None, **kwargs):
         return self.infer(prompts, gen_config, **kwargs)
 
-    def infer(self, prompts, gen_config: GenerationConfig | None = None, **kwargs) -> list[Response] | Response:
+    def infer(self, prompts, gen_config: GenerationConfig | None = None, adapter_name=None, **kwargs) -> list[Response] | Response:
         single = isinstance(prompts, (str, dict)) or (len(prompts) > 0 and isinstance(prompts[0], (int, np.integer)))
         batch = [prompts] if single else list(prompts)
         out = []
+        slots = self._adapter_slots(adapter_name, len(batch))
+        if slots is not None:     # an adapter is selected: one static batch, or a refusal by name
+            g = gen_config or GenerationConfig()
+            if isinstance(g, (list, tuple)) or len(batch) > self.max_batch_size:
+                raise NotImplementedError('adapter_name with one GenerationConfig per prompt or more prompts than max_batch_size: those requests '
+                                          'run through continuous batching, which serves the base model only')
+            if any(self._multimodal(p) is not None for p in batch):
+                raise NotImplementedError('multimodal prompts with an adapter selected are not built')
+            self._resolve_words(g)
+            out = list(self._generate_static(batch, g, slots))
+            return out[0] if single else out
         for res in self._generate(batch, gen_config or GenerationConfig()):
             out.append(res)
         return out[0] if single else out
 
-    def stream_infer(self, prompts, gen_config: GenerationConfig | None = None, stream_response: bool = True, **kwargs):
+    def stream_infer(self, prompts, gen_config: GenerationConfig | None = None, stream_response: bool = True, adapter_name=None, **kwargs):
         """Streaming generation through the engine scheduler (lmdeploy/pipeline.py:145-178).  stream_response=True
         (the reference's default): after every scheduler step one Response per request that produced tokens, carrying the
         NEW token ids (`token_ids`), the total generated so far (`generate_token_len`) and `finish_reason` None until the
         request ends ('stop' | 'length'); the stop token itself is never part of the output.  stream_response=False: one
         final Response per request, in completion order."""
+        if adapter_name is not None and self._adapter_slots(adapter_name, 1 if isinstance(prompts, (str, dict)) else len(prompts)) is not None:
+            raise NotImplementedError('streaming with an adapter selected is not built: streaming runs through continuous batching, which '
+                                      'serves the base model only (infer / __call__ take adapter_name)')
         yield from self.generate_continuous(list(prompts), gen_config or GenerationConfig(), stream=stream_response)
 
     def get_ppl(self, input_ids: list[int] | list[list[int]]) -> list[float]:
@@ -432,7 +500,7 @@ class Pipeline:
         finally:
             self.engine.release()
 
-    def _generate_static(self, prompts: Sequence, g: GenerationConfig):
+    def _generate_static(self, prompts: Sequence, g: GenerationConfig, adapter_slots=None):
         ids = [self._encode(p) for p in prompts]
         mm = [self._multimodal(p) for p in prompts]
         stop = self._stop_ids(g)
@@ -481,6 +549,8 @@ class Pipeline:
                     self.engine.set_speculative(0)
                     self._spec_calls['speculated'] -= 1
                     self._spec_calls['plain'] += 1
+                if adapter_slots is not None:     # armed right in front of the prefill that consumes it, like the multimodal input
+                    self.engine.set_adapters([adapter_slots[i] for i in idx])
                 self.engine.prefill(chunk, max_new_tokens=max_new)
                 step_logits = [self.engine.fetch_logits().copy()] if g.output_logits else None   # [batch, vocab] fp16 behind every step
                 done = 1

@@ -1039,3 +1039,112 @@ def load_hf_weights(model_path: str, cfg: ModelConfig) -> dict:
         head = t.get('output.weight')
     return dict(tok_embeddings=emb.astype(np.float16), layers=layers, norm=norm.astype(np.float16),
                 output=np.ascontiguousarray(head.astype(np.float16).T))
+
+
+# ---- LoRA adapters (PEFT layout; Pipeline(adapters=...)) ------------------------------------------------------------------------
+# (no `peft` was at hand when this was written: the file names, config keys and tensor names below were written down from memory of PEFT's
+# save_pretrained output, tests/test_host_lora.py reads a hand-written safetensors file)
+LORA = dict(
+    config='adapter_config.json', weights='adapter_model.safetensors',
+    keys=('r', 'lora_alpha', 'target_modules', 'use_rslora'),
+    prefix='base_model.model.model.layers.{i}.', A='.lora_A.weight', B='.lora_B.weight',
+    # target module -> (module path under the layer, the engine's linear, its column segment)
+    targets={'q_proj': ('self_attn.q_proj', 'qkv', 0), 'k_proj': ('self_attn.k_proj', 'qkv', 1), 'v_proj': ('self_attn.v_proj', 'qkv', 2),
+             'o_proj': ('self_attn.o_proj', 'wo', 0), 'down_proj': ('mlp.down_proj', 'w2', 0),
+             # InternLM2: the fused wqkv ([q_0 .. q_{g-1}, k, v] per kv group) shares one A between its three segments
+             'wqkv': ('attention.wqkv', 'qkv', None), 'wo': ('attention.wo', 'wo', 0), 'w2': ('feed_forward.w2', 'w2', 0)},
+    gated=('gate_proj', 'up_proj', 'w1', 'w3'))
+LORA_MAX_RANK, LORA_MAX_SLOTS = 64, 8
+
+
+def check_lora(cfg, quant_policy: int, tp: int = 1, what: str = 'this model'):
+    """LoRA adapters are served for dense models on one rank; NotImplementedError with the reason for anything else, before any GPU work"""
+    if cfg.moe_experts:
+        raise NotImplementedError(f'LoRA adapters with {what}, a mixture-of-experts model, are not built')
+    if tp > 1:
+        raise NotImplementedError('LoRA adapters with tp > 1 are not built')
+    if int(quant_policy) == 42:
+        raise NotImplementedError('LoRA adapters with quant_policy=42 (TurboQuant KV) are not built')
+    if cfg.hidden % 128 or cfg.inter % 128:
+        raise NotImplementedError(f'LoRA adapters with {what}, which is served zero-padded, are not built')
+
+
+def lora_scale(r: int, lora_alpha: float, use_rslora: bool = False) -> float:
+    """what is folded into B: lora_alpha / r, or lora_alpha / sqrt(r) with use_rslora"""
+    return float(lora_alpha) / (float(r) ** 0.5 if use_rslora else float(r))
+
+
+def lora_operands(parts: list, seg_cols: list, scale: float) -> tuple:
+    """One linear of one adapter in the kernel's layout.  parts: per column segment (A [r, K], B [n_g, r]) or None; seg_cols: the segments'
+    widths.  -> (A fp16 [sum R_g, K]: the segments' rank slices stacked, R_g = r padded with zero rows to a multiple of 16; B fp16 [N, ldb]:
+    scale * B_g in the first r columns of its segment's rows, zero elsewhere; [R_g]: 0 for an absent segment)."""
+    ranks = [0 if p is None else -(-p[0].shape[0] // 16) * 16 for p in parts]
+    K = next(p[0].shape[1] for p in parts if p is not None)
+    A = np.zeros((sum(ranks), K), np.float16)
+    B = np.zeros((sum(seg_cols), max(ranks)), np.float16)
+    toff = n0 = 0
+    for p, R, n in zip(parts, ranks, seg_cols):
+        if p is not None:
+            a, b = np.asarray(p[0], np.float32), np.asarray(p[1], np.float32)
+            if a.shape[0] > LORA_MAX_RANK:
+                raise NotImplementedError(f'LoRA rank {a.shape[0]}: rank over {LORA_MAX_RANK} per segment is not built')
+            if b.shape != (n, a.shape[0]) or a.shape[1] != K:
+                raise ValueError(f'LoRA operands: lora_A {a.shape} / lora_B {b.shape} do not fit a [{K} -> {n}] linear')
+            A[toff:toff + a.shape[0]] = a
+            B[n0:n0 + n, :a.shape[0]] = b * np.float32(scale)
+        toff += R
+        n0 += n
+    return A, B, ranks
+
+
+def read_lora(path: str, cfg: ModelConfig) -> list:
+    """A PEFT LoRA adapter directory -> per layer {'qkv' | 'wo' | 'w2': (A, B, ranks)} (lora_operands; q / k rows of B channel-permuted
+    like the base w_qkv).  Everything the engine does not serve is refused by name."""
+    with open(os.path.join(path, LORA['config'])) as f:
+        c = json.load(f)
+    if c.get('use_dora'):
+        raise NotImplementedError(f'{path}: use_dora adapters are not built')
+    if c.get('bias', 'none') != 'none':
+        raise NotImplementedError(f'{path}: bias={c["bias"]!r}: LoRA adapters that train biases (bias != \'none\') are not built')
+    if c.get('modules_to_save'):
+        raise NotImplementedError(f'{path}: modules_to_save {c["modules_to_save"]} is not built (the adapter replaces whole modules)')
+    for k in ('rank_pattern', 'alpha_pattern'):
+        if c.get(k):
+            raise NotImplementedError(f'{path}: {k} (per-module ranks / alphas) is not built')
+    r, lora_alpha, targets, use_rslora = (c.get(k) for k in LORA['keys'])
+    targets = [targets] if isinstance(targets, str) else sorted(targets)
+    for tname in targets:
+        if tname in LORA['gated']:
+            raise NotImplementedError(f'{path}: target module {tname}: gate_proj / up_proj adapters are not built (their delta would have '
+                                      f'to land ahead of the fused SiLU epilogue of w1w3)')
+        if tname not in LORA['targets']:
+            raise NotImplementedError(f'{path}: target module {tname} is outside q_proj / k_proj / v_proj / o_proj / down_proj')
+    scale = lora_scale(int(r), lora_alpha, bool(use_rslora))
+    if not os.path.exists(os.path.join(path, LORA['weights'])):
+        raise FileNotFoundError(f'{path}: no {LORA["weights"]}')
+    t = _Tensors(path)
+    D, Hq, Hkv = cfg.head_dim, cfg.q_heads, cfg.kv_heads
+    widths = dict(qkv=[Hq * D, Hkv * D, Hkv * D], wo=[cfg.hidden], w2=[cfg.hidden])
+    layers = []
+    for i in range(cfg.layers):
+        parts = dict(qkv=[None] * 3, wo=[None], w2=[None])
+        for tname in targets:
+            mod, lin, seg = LORA['targets'][tname]
+            key = LORA['prefix'].format(i=i) + mod
+            if key + LORA['A'] not in t:
+                continue
+            a, b = t.get(key + LORA['A']).astype(np.float32), t.get(key + LORA['B']).astype(np.float32)
+            if seg is None:      # InternLM2's fused wqkv: B's rows split like the base weight's columns
+                bg = b.reshape(Hkv, Hq // Hkv + 2, D, -1)
+                bs = (bg[:, :-2].reshape(Hq * D, -1), bg[:, -2].reshape(Hkv * D, -1), bg[:, -1].reshape(Hkv * D, -1))
+                parts[lin] = [(a, x) for x in bs]
+            else:
+                parts[lin][seg] = (a, b)
+        for seg, heads in ((0, Hq), (1, Hkv)):      # q / k output channels: rotate-half pairs -> adjacent pairs, like the base weight
+            if parts['qkv'][seg] is not None:
+                a, b = parts['qkv'][seg]
+                parts['qkv'][seg] = (a, np.ascontiguousarray(permute_qk_for_interleaved_rope(b.T, heads, D).T))
+        layers.append({lin: lora_operands(p, widths[lin], scale) for lin, p in parts.items() if any(x is not None for x in p)})
+    if not any(layers):
+        raise ValueError(f'{path}: no lora_A / lora_B tensors found under {LORA["prefix"]}')
+    return layers

@@ -247,6 +247,21 @@ class Engine:
                                   pos.ctypes.data, len(pos), int(it.get('mrope_position_delta') or 0))
         _ffi.check(self._lib.tm_engine_set_multimodal(self._h, arr, len(inputs)))
 
+    # ---- multi-LoRA (static batch) ---------------------------------------------------------------
+    def load_adapter(self, slot: int, layer: int, kind: int, A: np.ndarray, B: np.ndarray, seg_rank: Sequence[int]):
+        """One linear of adapter `slot` (0 .. 7): kind _ffi.LORA_QKV / LORA_WO / LORA_W2, A fp16 [sum seg_rank, K] and B fp16 [N, ldb] as
+        checkpoint.lora_operands lays them out (ranks padded to multiples of 16, the scale folded into B).  After start(), while no
+        batch is admitted.  From the first adapter on every forward runs the unfused schedule."""
+        A, B = np.ascontiguousarray(A, np.float16), np.ascontiguousarray(B, np.float16)
+        ranks = (C.c_int * len(seg_rank))(*[int(r) for r in seg_rank])
+        _ffi.check(self._lib.tm_engine_load_adapter(self._h, int(slot), int(layer), int(kind), A.ctypes.data, B.ctypes.data, ranks,
+                                                    int(B.shape[1])))
+
+    def set_adapters(self, slots: Sequence[int]):
+        """Static batch: the adapter slot of every sequence of the NEXT prefill (-1 = the base weights)"""
+        arr = (C.c_int * len(slots))(*[int(s) for s in slots])
+        _ffi.check(self._lib.tm_engine_set_adapters(self._h, arr, len(slots)))
+
     def prefill(self, prompts: Sequence[Sequence[int]], max_new_tokens: int):
         lens = np.asarray([len(p) for p in prompts], np.int32)
         ids = np.concatenate([np.asarray(p, np.int32) for p in prompts]).astype(np.int32)
