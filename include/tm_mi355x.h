@@ -282,6 +282,24 @@ int tm_prefill_attention_window(void* out, const void* q, int q_stride, const vo
                                 const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len,
                                 int q_heads, int kv_heads, int head_dim, float softmax_scale, int window, const void* sinks,
                                 tm_stream_t st);
+/* Attention of the Qwen2-VL / Qwen2.5-VL vision tower (attention_vision.hip): bidirectional flash attention over
+ * packed variable-length segments with the tower's rotate-half 2-D RoPE applied inside.  Replaces: the ViT attention of the
+ * reference's qwenvit model, Attn / CreateVitAttentionParams (src/turbomind/models/qwenvit/qwenvit.cc) -> dispatchAttention with a
+ * non-causal mask.  Token i attends token j iff both lie in the same segment [cu_seqlens[s], cu_seqlens[s + 1]).
+ *   qkv   fp16 [tokens][qkv_stride], a row = q | k | v of `heads` heads of head_dim (the fused qkv linear's output, unrotated);
+ *   cos, sin   fp16 (cs_f32 == 0) or fp32 [tokens][cs_stride]; the first head_dim / 2 values of a row are read;
+ *   q' = fp16(f32(q) * cos + rotate_half(f32(q)) * sin), k' alike; out fp16 [tokens][heads * head_dim] = softmax(scale q' k'^T) v,
+ *   fp32 accumulation; softmax_scale <= 0: 1 / sqrt(head_dim).  Rows outside every segment are not written.
+ *   cu_seqlens: device int32 [nseg + 1]; host_cu_seqlens (may be NULL): its host copy, checked here.
+ *   work: device int32 [n_work][2] = (segment, 64-row query block), what tm_vision_attention_plan writes (host side, longest
+ *   segments first; call it with host_work NULL for the count) -- upload it once per forward, every block of the tower reuses it.
+ * Asynchronous on st.  TM_INVALID by name: head_dim other than 64 / 80 / 128, 3 * heads * head_dim over qkv_stride, a host
+ * cu_seqlens that does not start at 0, decreases or runs past `tokens`, rows that are not 16-byte aligned.  No causal mask, GQA,
+ * window, sink, bias or dropout. */
+int tm_vision_attention_plan(const int* host_cu_seqlens, int nseg, int* host_work, int capacity, int* n_work);
+int tm_vision_attention(void* out, const void* qkv, int qkv_stride, const int* cu_seqlens, const int* host_cu_seqlens, int nseg,
+                        const int* work, int n_work, int tokens, int heads, int head_dim, const void* cos, const void* sin,
+                        int cs_stride, int cs_f32, float softmax_scale, tm_stream_t st);
 
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st);
 /* tm_embedding for multimodal prompts (the reference's input_embeddings / input_embedding_ranges, lmdeploy/turbomind/turbomind.py:632-674):

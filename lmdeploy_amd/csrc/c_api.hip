@@ -571,6 +571,52 @@ int tm_prefill_attention_window(void* out, const void* q, int q_stride, const vo
     return launch_prefill_attention(p, (hipStream_t)st);
 }
 
+// ---- vision-tower attention (attention_vision.hip) ------------------------------------------------------------------
+int tm_vision_attention_plan(const int* host_cu_seqlens, int nseg, int* host_work, int capacity, int* n_work)
+{
+    TM_REQUIRE(host_cu_seqlens && n_work, "tm_vision_attention_plan: null pointer");
+    TM_REQUIRE(nseg >= 0 && capacity >= 0, "tm_vision_attention_plan: negative size");
+    const int n = vision_plan(host_cu_seqlens, nseg, host_work, capacity);
+    TM_REQUIRE(n >= 0, "tm_vision_attention_plan: cu_seqlens must start at 0 and never decrease");
+    *n_work = n;
+    return 0;
+}
+
+int tm_vision_attention(void* out, const void* qkv, int qkv_stride, const int* cu_seqlens, const int* host_cu_seqlens, int nseg,
+                        const int* work, int n_work, int tokens, int heads, int head_dim, const void* cos, const void* sin,
+                        int cs_stride, int cs_f32, float softmax_scale, tm_stream_t st)
+{
+    TM_REQUIRE(head_dim == 64 || head_dim == 80 || head_dim == 128, "tm_vision_attention: head_dim must be 64, 80 or 128");
+    TM_REQUIRE(out && qkv && cu_seqlens && cos && sin && (work || n_work == 0), "tm_vision_attention: null pointer");
+    TM_REQUIRE(heads >= 1 && tokens >= 0 && nseg >= 0 && n_work >= 0, "tm_vision_attention: negative size");
+    TM_REQUIRE((long long)3 * heads * head_dim <= qkv_stride, "tm_vision_attention: 3 * heads * head_dim exceeds the qkv row stride");
+    TM_REQUIRE(qkv_stride % 8 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)out % 8 == 0,
+               "tm_vision_attention: qkv rows must be 16-byte aligned (stride % 8), out 8-byte aligned");
+    TM_REQUIRE(cs_stride >= head_dim / 2 && cs_stride % (cs_f32 ? 4 : 8) == 0 && (uintptr_t)cos % 16 == 0 && (uintptr_t)sin % 16 == 0,
+               "tm_vision_attention: cos / sin rows must hold head_dim / 2 values and be 16-byte aligned");
+    if (host_cu_seqlens) {
+        TM_REQUIRE(vision_plan(host_cu_seqlens, nseg, nullptr, 0) >= 0,
+                   "tm_vision_attention: cu_seqlens must start at 0 and never decrease");
+        TM_REQUIRE(host_cu_seqlens[nseg] <= tokens, "tm_vision_attention: cu_seqlens runs past the tokens");
+    }
+    VisionAttnParams p{};
+    p.qkv        = (const half_t*)qkv;
+    p.qkv_stride = qkv_stride;
+    p.out        = (half_t*)out;
+    p.cu_seqlens = cu_seqlens;
+    p.work       = (const int2*)work;
+    p.cos        = cos;
+    p.sin        = sin;
+    p.cs_stride  = cs_stride;
+    p.tokens     = tokens;
+    p.nseg       = nseg;
+    p.n_work     = n_work;
+    p.heads      = heads;
+    const float s = softmax_scale > 0.f ? softmax_scale : 1.0f / std::sqrt((float)head_dim);
+    p.scale_log2 = s * 1.4426950408889634f;
+    return launch_vision_attention(p, head_dim, cs_f32 != 0, (hipStream_t)st);
+}
+
 int tm_embedding(void* out, const void* table, const int* ids, int tokens, int hidden, int vocab, tm_stream_t st)
 {
     TM_REQUIRE(out && table && ids, "null pointer");

@@ -242,6 +242,25 @@ struct PrefillAttnParams {
 };
 int launch_prefill_attention(const PrefillAttnParams& p, hipStream_t st);
 
+// ---- attention_vision.hip ---------------------------------------------------------------
+struct VisionAttnParams {
+    const half_t* qkv;         // [tokens][qkv_stride]: q | k | v of every head, unrotated
+    int           qkv_stride;  // elements, >= 3 * heads * D
+    half_t*       out;         // [tokens][heads * D]
+    const int*    cu_seqlens;  // [nseg + 1], device
+    const int2*   work;        // [n_work] (segment, 64-row query block), device
+    const void*   cos;         // [tokens][cs_stride] fp16 or fp32; the first D / 2 of a row are read
+    const void*   sin;
+    int           cs_stride;
+    int           tokens;
+    int           nseg;
+    int           n_work;
+    int           heads;
+    float         scale_log2;
+};
+int vision_plan(const int* cu_seqlens, int nseg, int* work, int capacity);
+int launch_vision_attention(const VisionAttnParams& p, int head_dim, bool cs_f32, hipStream_t st);
+
 // ---- gemm_w4a16.hip ---------------------------------------------------------------------
 // What a linear IS, resolved once where it is declared from (weight_type, fp8_scale_mode, expert?) by linear_format(): the key of the
 // format table in linear.hip, which owns everything that depends on it (staging parts, repack, activation quantisation, run, bytes).
