@@ -247,6 +247,38 @@ int tm_decode_attention_window_mfma(void* out, const void* q, int q_stride, cons
 size_t tm_verify_attention_workspace(int rows, int q_heads, int splits);
 int    tm_verify_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int q_heads,
                            float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st);
+/* Multi-head Latent Attention (DeepSeek-V2 / V3 / R1, Kimi-K2, MiniCPM3) in the absorbed form on a paged latent cache
+ * (attention_mla.hip).  Replaces: the reference's MLA arm, invokeMLACopyQKV (src/turbomind/kernels/attention/
+ * mla_utils.cu) and the head_dim-576 decode kernel (src/turbomind/kernels/attention/decoding_sm80_576.cu).
+ * Latent cache layout: a tm_kv_cache view with kv_heads = 1, head_dim = 576, bits = 16, block_len = 64.  Inside a block one layer is
+ * [64 tokens][576] fp16 = the normalised latent c (kv_lora_rank 512), then the rotated k_pe (qk_rope_head_dim 64): one 1152-byte row
+ * per token that every query head reads, as K over all 576 elements and as V over the first 512.  No V region, no per-token
+ * parameters; tm_mla_layer_size gives the bytes of a layer (block_len * 576 * 2; -1 for another geometry), layer_offset = layer *
+ * that.  block_ptrs / cu_block_nums work as everywhere else.  Only the three calls below understand this layout: every other call
+ * returns TM_INVALID for head_dim 576.
+ * tm_mla_kv_store: the rows of one forward in tm_kv_rope_store's convention (k_len[b] counts every row of the forward, row j of
+ *   sequence b sits at position k_len[b] - q_len[b] + j).  kv_a fp16 [total_tokens][kv_stride] = the output of kv_a_proj_with_mqa,
+ *   512 latent then 64 rope; norm_w fp16 [512]; q fp16 [total_tokens][q_stride] = `heads` heads of q_lat (512) | q_pe (64), q_lat =
+ *   q_nope W_UK absorbed by the caller.  The token's cache row receives h(h(f32(x) * inv_rms) * w) | rope(k_pe) and each head's q_pe is
+ *   rotated in place: pairs (2i, 2i + 1) by row min(pos, max_pos - 1) of cos_sin ([max_pos][32][2] fp16, tm_rope_table with rope_dim
+ *   64; NULL = no rotation), DeepSeek-V2's complex convention.
+ * tm_mla_attention: split-K paged flash attention; out fp16 [rows][heads * 512] is the LATENT output (the caller applies W_UV and
+ *   o_proj), q as the store left it.  Query row j of sequence b sees the tokens t < k_len[b] - q_len[b] + j + 1; q_len[b] >= 0 has no
+ *   upper bound: one kernel serves decode, verify-sized rows and chunked prefill (a score column is a (row, head) pair, 16 columns per
+ *   workgroup; H = 16 makes one decode token one full chunk).  softmax_scale must be given (> 0): 1 / sqrt(qk_nope + qk_rope), times
+ *   mscale^2 under YaRN.  1 <= splits <= 128; the workspace (tm_mla_attention_workspace bytes for rows = cu_q_len[batch]) is needed
+ *   when splits > 1.
+ * Both calls read cu_q_len and k_len back to check them (they synchronise the stream).  TM_INVALID by name: a cache view other than
+ * kv_heads 1 / head_dim 576 / bits 16 / block_len 64, k_len[b] < q_len[b], heads outside 1 .. 128, splits outside 1 .. 128, splits > 1
+ * without a workspace, softmax_scale <= 0, rows that are not 16-byte aligned.  No window, sinks, quantised latent, tp > 1 or fused
+ * prologue. */
+int64_t tm_mla_layer_size(int block_len, int kv_lora_rank, int rope_dim);
+int     tm_mla_kv_store(const void* kv_a, int kv_stride, const void* norm_w, float eps, void* q, int q_stride, int heads,
+                        const int* cu_q_len, const int* k_len, int batch, int total_tokens, const void* cos_sin, int max_pos,
+                        const tm_kv_cache* cache, tm_stream_t st);
+size_t  tm_mla_attention_workspace(int rows, int heads, int splits);
+int     tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int heads,
+                         float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st);
 /* The device side of speculative decoding by prompt lookup, one sequence batch at a time (operator level; the engine runs the same
  * kernels).  State, all device int arrays: hist [batch][hist_stride] token history (prompt + emitted tokens) and hist_len [batch];
  * emitted [batch] tokens emitted so far; generated [batch][max_new]; k_len [batch]; next_id [batch]; totals int64 [4] = (sequence-steps

@@ -158,6 +158,12 @@ _SIGNATURES = {
     'tm_verify_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
     'tm_verify_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                     POINTER(KvCache), c_void_p]),
+    'tm_mla_layer_size': (c_int64, [c_int, c_int, c_int]),
+    'tm_mla_kv_store': (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_int, POINTER(KvCache), c_void_p]),
+    'tm_mla_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'tm_mla_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
+                                 POINTER(KvCache), c_void_p]),
     'tm_vision_attention_plan': (c_int, [POINTER(c_int), c_int, POINTER(c_int), c_int, POINTER(c_int)]),
     'tm_vision_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -493,6 +493,84 @@ int tm_verify_attention(void* out, const void* q, int q_stride, const int* cu_q_
     return launch_verify_attention(p, (hipStream_t)st);
 }
 
+// ---- Multi-head Latent Attention (attention_mla.hip) ------------------------------------------------------------------
+int64_t tm_mla_layer_size(int block_len, int kv_lora_rank, int rope_dim)
+{
+    if (block_len != 64 || kv_lora_rank != 512 || rope_dim != 64) {
+        set_last_error("invalid argument: MLA: block_len 64, kv_lora_rank 512 and qk_rope_head_dim 64 only");
+        return -1;
+    }
+    return (int64_t)block_len * (kv_lora_rank + rope_dim) * 2;
+}
+
+// the operator-level MLA calls check their row counts on the host, as tm_verify_attention does (they synchronise the stream)
+static int mla_rows(const int* cu_q_len, const int* k_len, int batch, hipStream_t st, int* rows, int* max_q)
+{
+    TM_REQUIRE(batch >= 1, "MLA: batch >= 1");
+    std::vector<int> cu((size_t)batch + 1), kl((size_t)batch);
+    TM_HIP_CHECK(hipMemcpyAsync(cu.data(), cu_q_len, cu.size() * 4, hipMemcpyDeviceToHost, st));
+    TM_HIP_CHECK(hipMemcpyAsync(kl.data(), k_len, kl.size() * 4, hipMemcpyDeviceToHost, st));
+    TM_HIP_CHECK(hipStreamSynchronize(st));
+    TM_REQUIRE(cu[0] == 0, "MLA: cu_q_len[0] must be 0");
+    *max_q = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int ql = cu[b + 1] - cu[b];
+        TM_REQUIRE(ql >= 0, "MLA: cu_q_len must not decrease");
+        TM_REQUIRE(kl[b] >= ql, "MLA: k_len[b] counts every row of the forward (k_len[b] >= q_len[b])");
+        *max_q = std::max(*max_q, ql);
+    }
+    *rows = cu[batch];
+    return 0;
+}
+
+int tm_mla_kv_store(const void* kv_a, int kv_stride, const void* norm_w, float eps, void* q, int q_stride, int heads,
+                    const int* cu_q_len, const int* k_len, int batch, int total_tokens, const void* cos_sin, int max_pos,
+                    const tm_kv_cache* cache, tm_stream_t st)
+{
+    TM_REQUIRE(kv_a && norm_w && q && cu_q_len && k_len && cache, "null pointer");
+    TM_REQUIRE(cache->head_dim == 576 && cache->kv_heads == 1 && cache->bits == 16 && cache->block_len == 64,
+               "tm_mla_kv_store: the latent cache is kv_heads 1, head_dim 576 (kv_lora_rank 512 + qk_rope_head_dim 64), bits 16, block_len 64");
+    int rows = 0, max_q = 0;
+    TM_TRY_RC(mla_rows(cu_q_len, k_len, batch, (hipStream_t)st, &rows, &max_q));
+    TM_REQUIRE(rows == total_tokens, "tm_mla_kv_store: cu_q_len[batch] != total_tokens");
+    return launch_mla_kv_store((const half_t*)kv_a, kv_stride, (const half_t*)norm_w, eps, (half_t*)q, q_stride, heads, cu_q_len, k_len,
+                               batch, total_tokens, (const half2_t*)cos_sin, max_pos, to_view(cache), (hipStream_t)st);
+}
+
+size_t tm_mla_attention_workspace(int rows, int heads, int splits)
+{
+    return splits > 1 ? (size_t)rows * heads * splits * (512 + 2) * sizeof(float) : 0;
+}
+
+int tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int heads,
+                     float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st)
+{
+    TM_REQUIRE(out && q && cu_q_len && k_len && cache, "null pointer");
+    TM_REQUIRE(cache->head_dim == 576 && cache->kv_heads == 1 && cache->bits == 16 && cache->block_len == 64,
+               "tm_mla_attention: the latent cache is kv_heads 1, head_dim 576 (kv_lora_rank 512 + qk_rope_head_dim 64), bits 16, block_len 64");
+    TM_REQUIRE(heads >= 1 && heads <= 128, "tm_mla_attention: 1 <= H <= 128 query heads");
+    TM_REQUIRE(splits >= 1 && splits <= 128, "tm_mla_attention: 1 <= splits <= 128");
+    TM_REQUIRE(splits == 1 || workspace, "tm_mla_attention: split-K needs a workspace");
+    int rows = 0, max_q = 0;
+    TM_TRY_RC(mla_rows(cu_q_len, k_len, batch, (hipStream_t)st, &rows, &max_q));
+    MlaAttnParams p{};
+    p.q          = (const half_t*)q;
+    p.q_stride   = q_stride;
+    p.out        = (half_t*)out;
+    p.cu_q_len   = cu_q_len;
+    p.k_len      = k_len;
+    p.batch      = batch;
+    p.heads      = heads;
+    p.scale_log2 = softmax_scale * 1.4426950408889634f;
+    p.splits     = splits;
+    p.partial_o  = (float*)workspace;
+    p.partial_ml = workspace ? (float*)workspace + (size_t)rows * heads * splits * 512 : nullptr;
+    p.cache      = to_view(cache);
+    p.max_q_len  = max_q;
+    p.rows       = rows;
+    return launch_mla_attention(p, (hipStream_t)st);
+}
+
 int tm_spec_propose(int* drafts, int* n_draft, const int* hist, int hist_stride, const int* hist_len, const int* emitted, int max_new,
                     int batch, int k, int ngram_max, int ngram_min, tm_stream_t st)
 {

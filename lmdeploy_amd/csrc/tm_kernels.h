@@ -196,6 +196,31 @@ struct VerifyAttnParams {
 };
 int launch_verify_attention(const VerifyAttnParams& p, hipStream_t st);
 
+// ---- attention_mla.hip ------------------------------------------------------------------
+// Multi-head Latent Attention, absorbed form, on a latent cache of one [c (512) | k_pe (64)] fp16 row per token: KvLayout{1, 576, 64, 16}.
+// Store: rows of one forward in launch_kv_rope_store's convention; kv_a [T][kv_stride] = latent | rope part, q [T][q_stride] = H heads of
+// q_lat (512) | q_pe (64); the cache row receives rmsnorm(latent) * norm_w | rope(k_pe), every q_pe is rotated in place.
+int launch_mla_kv_store(const half_t* kv_a, int kv_stride, const half_t* norm_w, float eps, half_t* q, int q_stride, int heads,
+                        const int* cu_q_len, const int* k_len, int batch, int total_tokens, const half2_t* cos_sin, int max_pos,
+                        KvCacheView cache, hipStream_t st);
+struct MlaAttnParams {
+    const half_t* q;         // [rows][q_stride]: head h at h * 576, as the store left it
+    int           q_stride;
+    half_t*       out;       // [rows][heads * 512]: the latent output
+    const int*    cu_q_len;  // [B+1] device
+    const int*    k_len;     // [B] device, context lengths including every row of this forward
+    int           batch;
+    int           heads;
+    float         scale_log2;
+    int           splits;
+    float*        partial_o;   // [rows][heads][splits][512]
+    float*        partial_ml;  // [rows][heads][splits][2]
+    KvCacheView   cache;
+    int           max_q_len;   // the host's bound on q_len[b]: sizes the grid
+    int           rows;        // cu_q_len[batch]
+};
+int launch_mla_attention(const MlaAttnParams& p, hipStream_t st);
+
 // ---- speculative.hip: prompt-lookup proposer and greedy acceptance of speculative decoding ----
 struct SpecState {
     int* hist;       // [B][hist_stride] token history: prompt + emitted tokens
