@@ -279,6 +279,33 @@ int     tm_mla_kv_store(const void* kv_a, int kv_stride, const void* norm_w, flo
 size_t  tm_mla_attention_workspace(int rows, int heads, int splits);
 int     tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len, const int* k_len, int batch, int heads,
                          float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st);
+/* MLA prefill in the EXPANDED form (attention_mla_prefill.hip): per head k_nope = W_UK c and v = c W_UV are expanded
+ * from the latent once per forward, and attention runs at qk width 192 / v width 128 -- 640 flop per (row, head, key) where the absorbed
+ * tm_mla_attention spends 2176.  Replaces: the reference's 192-wide prefill arm next to its 576 decode arm.  Geometry fixed:
+ * kv_lora_rank 512, qk_rope_head_dim 64, qk_nope_head_dim 128, v_head_dim 128.
+ * tm_mla_flatten: gathers the latent rows of `batch` sequences from the latent cache view above into linear fp16 lat_out [rows][576]:
+ *   sequence b's tokens 0 .. k_len[b] - 1 land at rows cu_k_off[b] .. (device int32 [batch], >= 0, the caller's to keep apart), the 1152
+ *   bytes of a row unchanged; every other row of lat_out is left unwritten.  max_k_len >= every k_len[b] sizes the grid.
+ * tm_mla_prefill_attention: causal varlen flash attention on v_mfma_f32_16x16x32_f16.
+ *   q     fp16 [rows][q_stride], head h at h * 192 = q_nope (128) | q_pe (64), q_pe ALREADY rotated (tm_mla_kv_store rotates the q_pe
+ *         columns of the absorbed layout; the caller copies them over);
+ *   kv    fp16 [tokens][kv_stride], head h at h * 256 = k_nope (128) | v (128): kv_b_proj's output as it stands, V not transposed;
+ *   k_pe  fp16 [tokens][pe_stride], 64 wide, rotated, ONE row per token shared by all heads -- normally lat_out + 512 with stride 576;
+ *   out   fp16 [rows][heads * 128].
+ *   Query row j of sequence b (row cu_q_len[b] + j) sees the tokens t < k_len[b] - q_len[b] + j + 1 of that sequence, at kv / k_pe row
+ *   cu_k_off[b] + t; rows behind them are never read.  cu_q_len [batch + 1], cu_k_off [batch], k_len [batch]: device int32.
+ *   max_q_len >= every q_len[b] sizes the grid (128 query rows per workgroup, longest blocks first).  softmax_scale must be given (> 0):
+ *   1 / sqrt(qk_nope + qk_rope) = 1 / sqrt(192), times mscale^2 under YaRN.
+ * Both calls are asynchronous on st and read NOTHING back: the lengths are not checked on the host, and a sequence with
+ * k_len[b] < q_len[b] is skipped by the kernel (its rows of out stay unwritten), not refused.  TM_INVALID by name: a cache view other
+ * than kv_heads 1 / head_dim 576 / bits 16 / block_len 64 (flatten); heads outside 1 .. 128, softmax_scale <= 0, q_stride < heads * 192,
+ * kv_stride < heads * 256, pe_stride < 64, rows that are not 16-byte aligned (pointers % 16, strides % 8).  No window, sinks, quantised
+ * latent, tp > 1, other widths; chunked prefill re-expands the history once per chunk. */
+int tm_mla_flatten(void* lat_out, const int* cu_k_off, const int* k_len, int batch, int max_k_len, const tm_kv_cache* cache,
+                   tm_stream_t st);
+int tm_mla_prefill_attention(void* out, const void* q, int q_stride, const void* kv, int kv_stride, const void* k_pe, int pe_stride,
+                             const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len, int heads,
+                             float softmax_scale, tm_stream_t st);
 /* The device side of speculative decoding by prompt lookup, one sequence batch at a time (operator level; the engine runs the same
  * kernels).  State, all device int arrays: hist [batch][hist_stride] token history (prompt + emitted tokens) and hist_len [batch];
  * emitted [batch] tokens emitted so far; generated [batch][max_new]; k_len [batch]; next_id [batch]; totals int64 [4] = (sequence-steps

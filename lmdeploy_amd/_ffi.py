@@ -164,6 +164,9 @@ _SIGNATURES = {
     'tm_mla_attention_workspace': (c_size_t, [c_int, c_int, c_int]),
     'tm_mla_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                  POINTER(KvCache), c_void_p]),
+    'tm_mla_flatten': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(KvCache), c_void_p]),
+    'tm_mla_prefill_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_float, c_void_p]),
     'tm_vision_attention_plan': (c_int, [POINTER(c_int), c_int, POINTER(c_int), c_int, POINTER(c_int)]),
     'tm_vision_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -571,6 +571,36 @@ int tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len
     return launch_mla_attention(p, (hipStream_t)st);
 }
 
+// ---- MLA prefill in the expanded form (attention_mla_prefill.hip): both calls are asynchronous, nothing is read back ----
+int tm_mla_flatten(void* lat_out, const int* cu_k_off, const int* k_len, int batch, int max_k_len, const tm_kv_cache* cache,
+                   tm_stream_t st)
+{
+    TM_REQUIRE(lat_out && cu_k_off && k_len && cache, "null pointer");
+    return launch_mla_flatten((half_t*)lat_out, cu_k_off, k_len, batch, max_k_len, to_view(cache), (hipStream_t)st);
+}
+
+int tm_mla_prefill_attention(void* out, const void* q, int q_stride, const void* kv, int kv_stride, const void* k_pe, int pe_stride,
+                             const int* cu_q_len, const int* cu_k_off, const int* k_len, int batch, int max_q_len, int heads,
+                             float softmax_scale, tm_stream_t st)
+{
+    MlaPrefillParams p{};
+    p.q          = (const half_t*)q;
+    p.q_stride   = q_stride;
+    p.kv         = (const half_t*)kv;
+    p.kv_stride  = kv_stride;
+    p.k_pe       = (const half_t*)k_pe;
+    p.pe_stride  = pe_stride;
+    p.out        = (half_t*)out;
+    p.cu_q_len   = cu_q_len;
+    p.cu_k_off   = cu_k_off;
+    p.k_len      = k_len;
+    p.batch      = batch;
+    p.heads      = heads;
+    p.max_q_len  = max_q_len;
+    p.scale_log2 = softmax_scale * 1.4426950408889634f;
+    return launch_mla_prefill_attention(p, (hipStream_t)st);
+}
+
 int tm_spec_propose(int* drafts, int* n_draft, const int* hist, int hist_stride, const int* hist_len, const int* emitted, int max_new,
                     int batch, int k, int ngram_max, int ngram_min, tm_stream_t st)
 {

@@ -221,6 +221,29 @@ struct MlaAttnParams {
 };
 int launch_mla_attention(const MlaAttnParams& p, hipStream_t st);
 
+// ---- attention_mla_prefill.hip ----------------------------------------------------------
+// MLA prefill in the expanded form.  Flatten: the latent rows 0 .. k_len[b] - 1 of every sequence, bytes unchanged, to lat_out row
+// cu_k_off[b] ([rows][576] fp16); max_k_len sizes the grid.  Attention: causal varlen flash attention at qk 192 / v 128 over the linear
+// rows the caller expanded with kv_b_proj; asynchronous, nothing is read back (a sequence with k_len < q_len is skipped).
+int launch_mla_flatten(half_t* lat_out, const int* cu_k_off, const int* k_len, int batch, int max_k_len, KvCacheView cache, hipStream_t st);
+struct MlaPrefillParams {
+    const half_t* q;          // [rows][q_stride]: head h at h * 192 = q_nope (128) | rotated q_pe (64)
+    int           q_stride;
+    const half_t* kv;         // [tokens][kv_stride]: head h at h * 256 = k_nope (128) | v (128)
+    int           kv_stride;
+    const half_t* k_pe;       // [tokens][pe_stride]: 64 wide, rotated, one row per token for all heads
+    int           pe_stride;
+    half_t*       out;        // [rows][heads * 128]
+    const int*    cu_q_len;   // [B+1] device
+    const int*    cu_k_off;   // [B] device: sequence b's token 0 in kv / k_pe
+    const int*    k_len;      // [B] device, context lengths including every row of this forward
+    int           batch;
+    int           heads;
+    int           max_q_len;  // the host's bound on q_len[b]: sizes the grid (rows of a longer sequence's first blocks stay unwritten)
+    float         scale_log2;
+};
+int launch_mla_prefill_attention(const MlaPrefillParams& p, hipStream_t st);
+
 // ---- speculative.hip: prompt-lookup proposer and greedy acceptance of speculative decoding ----
 struct SpecState {
     int* hist;       // [B][hist_stride] token history: prompt + emitted tokens
