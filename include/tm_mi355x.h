@@ -256,6 +256,12 @@ int    tm_verify_attention(void* out, const void* q, int q_stride, const int* cu
  * parameters; tm_mla_layer_size gives the bytes of a layer (block_len * 576 * 2; -1 for another geometry), layer_offset = layer *
  * that.  block_ptrs / cu_block_nums work as everywhere else.  Only the three calls below understand this layout: every other call
  * returns TM_INVALID for head_dim 576.
+ * FP8 latent cache (attention_mla_fp8.hip): the same view with bits = TM_KV_BITS_FP8 holds one 640-byte row per token,
+ * 512 e4m3fn codes of c / k_scale then the rotated k_pe as 64 fp16; a layer is [64][640] bytes (tm_mla_layer_size_fp8; -1 for another
+ * geometry).  k_scale is the layer's latent scale (0 = 1.0, finite and >= 0), v_scale is ignored.  The store quantises the fp16 latent with
+ * the FP8 KV cache's arithmetic, e4m3fn(clamp(f32(c16) / k_scale, -448, 448)); attention widens the codes exactly to fp16, runs both
+ * products on v_mfma_f32_16x16x32_f16 and applies k_scale on the fp32 accumulators: S = softmax_scale * (k_scale * sum q_lat code +
+ * sum q_pe k_pe), O = k_scale * sum P code / l; tm_mla_flatten writes f16(f32(code) * k_scale) | k_pe.
  * tm_mla_kv_store: the rows of one forward in tm_kv_rope_store's convention (k_len[b] counts every row of the forward, row j of
  *   sequence b sits at position k_len[b] - q_len[b] + j).  kv_a fp16 [total_tokens][kv_stride] = the output of kv_a_proj_with_mqa,
  *   512 latent then 64 rope; norm_w fp16 [512]; q fp16 [total_tokens][q_stride] = `heads` heads of q_lat (512) | q_pe (64), q_lat =
@@ -269,10 +275,12 @@ int    tm_verify_attention(void* out, const void* q, int q_stride, const int* cu
  *   mscale^2 under YaRN.  1 <= splits <= 128; the workspace (tm_mla_attention_workspace bytes for rows = cu_q_len[batch]) is needed
  *   when splits > 1.
  * Both calls read cu_q_len and k_len back to check them (they synchronise the stream).  TM_INVALID by name: a cache view other than
- * kv_heads 1 / head_dim 576 / bits 16 / block_len 64, k_len[b] < q_len[b], heads outside 1 .. 128, splits outside 1 .. 128, splits > 1
- * without a workspace, softmax_scale <= 0, rows that are not 16-byte aligned.  No window, sinks, quantised latent, tp > 1 or fused
- * prologue. */
+ * kv_heads 1 / head_dim 576 / bits 16 or TM_KV_BITS_FP8 / block_len 64, a negative or non-finite k_scale on the FP8 view, k_len[b] <
+ * q_len[b], heads outside 1 .. 128, splits outside 1 .. 128, splits > 1
+ * without a workspace, softmax_scale <= 0, rows that are not 16-byte aligned.  No window, sinks, per-token or per-block scales, quantised
+ * k_pe, tp > 1 or fused prologue. */
 int64_t tm_mla_layer_size(int block_len, int kv_lora_rank, int rope_dim);
+int64_t tm_mla_layer_size_fp8(int block_len, int kv_lora_rank, int rope_dim);
 int     tm_mla_kv_store(const void* kv_a, int kv_stride, const void* norm_w, float eps, void* q, int q_stride, int heads,
                         const int* cu_q_len, const int* k_len, int batch, int total_tokens, const void* cos_sin, int max_pos,
                         const tm_kv_cache* cache, tm_stream_t st);
@@ -285,7 +293,7 @@ int     tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q
  * kv_lora_rank 512, qk_rope_head_dim 64, qk_nope_head_dim 128, v_head_dim 128.
  * tm_mla_flatten: gathers the latent rows of `batch` sequences from the latent cache view above into linear fp16 lat_out [rows][576]:
  *   sequence b's tokens 0 .. k_len[b] - 1 land at rows cu_k_off[b] .. (device int32 [batch], >= 0, the caller's to keep apart), the 1152
- *   bytes of a row unchanged; every other row of lat_out is left unwritten.  max_k_len >= every k_len[b] sizes the grid.
+ *   bytes of a row unchanged (from the FP8 view: the codes dequantised to fp16, k_pe copied); every other row of lat_out is left unwritten.  max_k_len >= every k_len[b] sizes the grid.
  * tm_mla_prefill_attention: causal varlen flash attention on v_mfma_f32_16x16x32_f16.
  *   q     fp16 [rows][q_stride], head h at h * 192 = q_nope (128) | q_pe (64), q_pe ALREADY rotated (tm_mla_kv_store rotates the q_pe
  *         columns of the absorbed layout; the caller copies them over);
@@ -298,9 +306,9 @@ int     tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q
  *   1 / sqrt(qk_nope + qk_rope) = 1 / sqrt(192), times mscale^2 under YaRN.
  * Both calls are asynchronous on st and read NOTHING back: the lengths are not checked on the host, and a sequence with
  * k_len[b] < q_len[b] is skipped by the kernel (its rows of out stay unwritten), not refused.  TM_INVALID by name: a cache view other
- * than kv_heads 1 / head_dim 576 / bits 16 / block_len 64 (flatten); heads outside 1 .. 128, softmax_scale <= 0, q_stride < heads * 192,
- * kv_stride < heads * 256, pe_stride < 64, rows that are not 16-byte aligned (pointers % 16, strides % 8).  No window, sinks, quantised
- * latent, tp > 1, other widths; chunked prefill re-expands the history once per chunk. */
+ * than kv_heads 1 / head_dim 576 / bits 16 or TM_KV_BITS_FP8 / block_len 64 (flatten); heads outside 1 .. 128, softmax_scale <= 0, q_stride < heads * 192,
+ * kv_stride < heads * 256, pe_stride < 64, rows that are not 16-byte aligned (pointers % 16, strides % 8).  No window, sinks,
+ * tp > 1, other widths; chunked prefill re-expands the history once per chunk. */
 int tm_mla_flatten(void* lat_out, const int* cu_k_off, const int* k_len, int batch, int max_k_len, const tm_kv_cache* cache,
                    tm_stream_t st);
 int tm_mla_prefill_attention(void* out, const void* q, int q_stride, const void* kv, int kv_stride, const void* k_pe, int pe_stride,

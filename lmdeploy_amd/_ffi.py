@@ -159,6 +159,7 @@ _SIGNATURES = {
     'tm_verify_attention': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p,
                                     POINTER(KvCache), c_void_p]),
     'tm_mla_layer_size': (c_int64, [c_int, c_int, c_int]),
+    'tm_mla_layer_size_fp8': (c_int64, [c_int, c_int, c_int]),
     'tm_mla_kv_store': (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                 c_int, POINTER(KvCache), c_void_p]),
     'tm_mla_attention_workspace': (c_size_t, [c_int, c_int, c_int]),

@@ -12,7 +12,8 @@
 //
 // mla_kv_store_kernel: one wave per token row.  c = rmsnorm(kv_a[:512]) * w through norm_row (norm_row.h: the project's row arithmetic
 // and its fp32 reduction), k_pe = rope(kv_a[512:]) and every head's q_pe rotated in place: pairs (2i, 2i + 1) by the (cos, sin) of
-// table row min(pos, max_pos - 1), fp16 operation by operation as kv_rope_store_kernel states it.
+// table row min(pos, max_pos - 1), fp16 operation by operation as kv_rope_store_kernel states it.  F8 (the FP8 latent view of
+// attention_mla_fp8.hip, 640-byte rows): the same fp16 c goes through a 1 KB LDS row and f8_quant8 (kv_cache_kernels.h), lane by lane.
 //
 // mla_attention_kernel.  Contract of launch_verify_attention: k_len[b] counts every row of the forward, hist = k_len[b] - q_len[b],
 // row j sees the tokens t < hist + j + 1; q_len is unbounded.
@@ -89,11 +90,14 @@ __device__ __forceinline__ int mla_swz(int r)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // store: one wave per token row
 // ---------------------------------------------------------------------------------------------------------------------------------
+template<bool F8>
 __global__ __launch_bounds__(64) void mla_kv_store_kernel(const half_t* __restrict__ kv_a, int kv_stride, const half_t* __restrict__ norm_w,
                                                           float eps, half_t* __restrict__ q, int q_stride, int heads,
                                                           const int* __restrict__ cu_q_len, const int* __restrict__ k_len, int batch,
-                                                          const half2_t* __restrict__ cos_sin, int max_pos, KvCacheView cache)
+                                                          const half2_t* __restrict__ cos_sin, int max_pos, KvCacheView cache, float k_scale)
 {
+    constexpr int kRowBytes = F8 ? kMlaF8RowBytes : kMlaRowBytes;
+    constexpr int kPeOff    = F8 ? kMlaRank : kMlaRank * 2;  // byte offset of k_pe in the cache row
     __shared__ float red[8];
     const int token = blockIdx.x;
     const int lane  = threadIdx.x;
@@ -104,11 +108,18 @@ __global__ __launch_bounds__(64) void mla_kv_store_kernel(const half_t* __restri
         return;  // workgroup-uniform; the entry point refuses k_len[b] < q_len[b] before it launches
     }
     const int blk = pos >> 6;
-    char*     row = (char*)cache.block_ptrs[cache.cu_block_nums[b] + blk] + cache.layer_offset + (pos & 63) * kMlaRowBytes;
+    char*     row = (char*)cache.block_ptrs[cache.cu_block_nums[b] + blk] + cache.layer_offset + (pos & 63) * kRowBytes;
     const half_t* src = kv_a + (size_t)token * kv_stride;
 
     // c = h(h(f32(x) * inv) * w) over the 512 latent elements: 64 vectors of 8, one per lane
-    norm_row<0, false, 1>((half_t*)row, nullptr, src, nullptr, 0, nullptr, norm_w, eps, 1, kMlaRank, 0, lane, 64, red);
+    if constexpr (F8) {  // the lane quantises the 8 halves it wrote itself: no barrier
+        __shared__ __attribute__((aligned(16))) half_t c16[kMlaRank];
+        norm_row<0, false, 1>(c16, nullptr, src, nullptr, 0, nullptr, norm_w, eps, 1, kMlaRank, 0, lane, 64, red);
+        *(u32x2*)(row + lane * 8) = f8_quant8(*(const half8_t*)(c16 + lane * 8), k_scale);
+    }
+    else {
+        norm_row<0, false, 1>((half_t*)row, nullptr, src, nullptr, 0, nullptr, norm_w, eps, 1, kMlaRank, 0, lane, 64, red);
+    }
 
     // k_pe (item `heads`) into the cache row, q_pe of every head in place: 8 lanes x 4 pairs per 64-wide rope part
     const int p = pos < max_pos ? pos : max_pos - 1;
@@ -135,7 +146,7 @@ __global__ __launch_bounds__(64) void mla_kv_store_kernel(const half_t* __restri
                 x[2 * i + 1]    = b0 + b1;
             }
         }
-        *(half8_t*)(isq ? qp : (half_t*)(row + kMlaRank * 2) + c * 8) = x;
+        *(half8_t*)(isq ? qp : (half_t*)(row + kPeOff) + c * 8) = x;
     }
 }
 
@@ -401,12 +412,12 @@ __global__ __launch_bounds__(128) void mla_reduce_kernel(MlaAttnParams p)
     *(half4_t*)(p.out + rh * kMlaRank + d) = half4_t{(half_t)(o[0] * inv), (half_t)(o[1] * inv), (half_t)(o[2] * inv), (half_t)(o[3] * inv)};
 }
 
-int mla_check_cache(const KvCacheView& c)
+int mla_check_cache(const KvCacheView& c, bool f8_ok = false)
 {
     const KvLayout& L = c.layout;
     TM_REQUIRE(L.head_dim == kMlaRow, "MLA: the latent cache row is kv_lora_rank 512 + qk_rope_head_dim 64 = head_dim 576");
     TM_REQUIRE(L.kv_heads == 1, "MLA: the latent cache has kv_heads 1 (every query head reads the same row)");
-    TM_REQUIRE(L.bits == 16, "MLA: fp16 latent cache only (bits 16); a quantised latent cache is not built");
+    TM_REQUIRE(L.bits == 16 || (f8_ok && L.bits == kKvBitsFp8), "MLA: latent cache of bits 16 (or TM_KV_BITS_FP8: attention_mla_fp8.hip)");
     TM_REQUIRE(L.block_len == 64, "MLA: block_len 64");
     TM_REQUIRE(c.block_ptrs && c.cu_block_nums, "null pointer");
     return 0;
@@ -416,9 +427,9 @@ int mla_check_cache(const KvCacheView& c)
 
 int launch_mla_kv_store(const half_t* kv_a, int kv_stride, const half_t* norm_w, float eps, half_t* q, int q_stride, int heads,
                         const int* cu_q_len, const int* k_len, int batch, int total_tokens, const half2_t* cos_sin, int max_pos,
-                        KvCacheView cache, hipStream_t st)
+                        KvCacheView cache, float k_scale, hipStream_t st)
 {
-    if (const int rc = mla_check_cache(cache)) {
+    if (const int rc = mla_check_cache(cache, true)) {
         return rc;
     }
     TM_REQUIRE(kv_a && norm_w && q && cu_q_len && k_len, "null pointer");
@@ -428,11 +439,14 @@ int launch_mla_kv_store(const half_t* kv_a, int kv_stride, const half_t* norm_w,
     TM_REQUIRE(((uintptr_t)kv_a | (uintptr_t)q | (uintptr_t)norm_w | (uintptr_t)cos_sin) % 16 == 0, "MLA store: 16-byte aligned pointers");
     TM_REQUIRE(cos_sin == nullptr || max_pos >= 1, "MLA store: a RoPE table needs max_pos >= 1");
     TM_REQUIRE(batch >= 1 && total_tokens >= 0, "batch >= 1, total_tokens >= 0");
+    const bool f8 = cache.layout.bits == kKvBitsFp8;
+    TM_REQUIRE(!f8 || (k_scale > 0.f && k_scale <= 3.0e38f), "MLA store: k_scale of the FP8 latent cache must be finite and > 0");
     if (total_tokens == 0) {
         return 0;
     }
-    mla_kv_store_kernel<<<total_tokens, 64, 0, st>>>(kv_a, kv_stride, norm_w, eps, q, q_stride, heads, cu_q_len, k_len, batch, cos_sin,
-                                                     cos_sin ? max_pos : 1 << 30, cache);
+    const auto K = f8 ? mla_kv_store_kernel<true> : mla_kv_store_kernel<false>;
+    K<<<total_tokens, 64, 0, st>>>(kv_a, kv_stride, norm_w, eps, q, q_stride, heads, cu_q_len, k_len, batch, cos_sin,
+                                   cos_sin ? max_pos : 1 << 30, cache, k_scale);
     TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -465,6 +479,13 @@ int launch_mla_attention(const MlaAttnParams& p, hipStream_t st)
         mla_reduce_kernel<<<dim3(p.rows, p.heads), 128, 0, st>>>(p);
         TM_HIP_CHECK(hipGetLastError());
     }
+    return 0;
+}
+
+int launch_mla_reduce(const MlaAttnParams& p, hipStream_t st)
+{
+    mla_reduce_kernel<<<dim3(p.rows, p.heads), 128, 0, st>>>(p);
+    TM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 

@@ -503,6 +503,31 @@ int64_t tm_mla_layer_size(int block_len, int kv_lora_rank, int rope_dim)
     return (int64_t)block_len * (kv_lora_rank + rope_dim) * 2;
 }
 
+int64_t tm_mla_layer_size_fp8(int block_len, int kv_lora_rank, int rope_dim)
+{
+    if (block_len != 64 || kv_lora_rank != 512 || rope_dim != 64) {
+        set_last_error("invalid argument: MLA: block_len 64, kv_lora_rank 512 and qk_rope_head_dim 64 only");
+        return -1;
+    }
+    return (int64_t)block_len * kMlaF8RowBytes;  // 512 code bytes + 64 fp16 per token
+}
+
+// the latent view of the three MLA calls: fp16 rows (bits 16) or FP8 rows (TM_KV_BITS_FP8, whose k_scale must be usable)
+static int mla_view(const tm_kv_cache* cache, const char* who)
+{
+    if (!(cache->head_dim == 576 && cache->kv_heads == 1 && (cache->bits == 16 || cache->bits == kKvBitsFp8) && cache->block_len == 64)) {
+        set_last_error(std::string("invalid argument: ") + who
+                       + ": the latent cache is kv_heads 1, head_dim 576 (kv_lora_rank 512 + qk_rope_head_dim 64), bits 16 or TM_KV_BITS_FP8, "
+                         "block_len 64");
+        return TM_INVALID;
+    }
+    if (cache->bits == kKvBitsFp8 && !(cache->k_scale >= 0.f && std::isfinite(cache->k_scale))) {
+        set_last_error(std::string("invalid argument: ") + who + ": k_scale of the FP8 latent cache must be finite and >= 0 (0 = 1.0)");
+        return TM_INVALID;
+    }
+    return 0;
+}
+
 // the operator-level MLA calls check their row counts on the host, as tm_verify_attention does (they synchronise the stream)
 static int mla_rows(const int* cu_q_len, const int* k_len, int batch, hipStream_t st, int* rows, int* max_q)
 {
@@ -528,13 +553,12 @@ int tm_mla_kv_store(const void* kv_a, int kv_stride, const void* norm_w, float e
                     const tm_kv_cache* cache, tm_stream_t st)
 {
     TM_REQUIRE(kv_a && norm_w && q && cu_q_len && k_len && cache, "null pointer");
-    TM_REQUIRE(cache->head_dim == 576 && cache->kv_heads == 1 && cache->bits == 16 && cache->block_len == 64,
-               "tm_mla_kv_store: the latent cache is kv_heads 1, head_dim 576 (kv_lora_rank 512 + qk_rope_head_dim 64), bits 16, block_len 64");
+    TM_TRY_RC(mla_view(cache, "tm_mla_kv_store"));
     int rows = 0, max_q = 0;
     TM_TRY_RC(mla_rows(cu_q_len, k_len, batch, (hipStream_t)st, &rows, &max_q));
     TM_REQUIRE(rows == total_tokens, "tm_mla_kv_store: cu_q_len[batch] != total_tokens");
     return launch_mla_kv_store((const half_t*)kv_a, kv_stride, (const half_t*)norm_w, eps, (half_t*)q, q_stride, heads, cu_q_len, k_len,
-                               batch, total_tokens, (const half2_t*)cos_sin, max_pos, to_view(cache), (hipStream_t)st);
+                               batch, total_tokens, (const half2_t*)cos_sin, max_pos, to_view(cache), to_scales(cache).k, (hipStream_t)st);
 }
 
 size_t tm_mla_attention_workspace(int rows, int heads, int splits)
@@ -546,8 +570,7 @@ int tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len
                      float softmax_scale, int splits, void* workspace, const tm_kv_cache* cache, tm_stream_t st)
 {
     TM_REQUIRE(out && q && cu_q_len && k_len && cache, "null pointer");
-    TM_REQUIRE(cache->head_dim == 576 && cache->kv_heads == 1 && cache->bits == 16 && cache->block_len == 64,
-               "tm_mla_attention: the latent cache is kv_heads 1, head_dim 576 (kv_lora_rank 512 + qk_rope_head_dim 64), bits 16, block_len 64");
+    TM_TRY_RC(mla_view(cache, "tm_mla_attention"));
     TM_REQUIRE(heads >= 1 && heads <= 128, "tm_mla_attention: 1 <= H <= 128 query heads");
     TM_REQUIRE(splits >= 1 && splits <= 128, "tm_mla_attention: 1 <= splits <= 128");
     TM_REQUIRE(splits == 1 || workspace, "tm_mla_attention: split-K needs a workspace");
@@ -568,6 +591,9 @@ int tm_mla_attention(void* out, const void* q, int q_stride, const int* cu_q_len
     p.cache      = to_view(cache);
     p.max_q_len  = max_q;
     p.rows       = rows;
+    if (cache->bits == kKvBitsFp8) {
+        return launch_mla_attention_fp8(p, to_scales(cache).k, (hipStream_t)st);
+    }
     return launch_mla_attention(p, (hipStream_t)st);
 }
 
@@ -576,6 +602,10 @@ int tm_mla_flatten(void* lat_out, const int* cu_k_off, const int* k_len, int bat
                    tm_stream_t st)
 {
     TM_REQUIRE(lat_out && cu_k_off && k_len && cache, "null pointer");
+    TM_TRY_RC(mla_view(cache, "tm_mla_flatten"));
+    if (cache->bits == kKvBitsFp8) {
+        return launch_mla_flatten_fp8((half_t*)lat_out, cu_k_off, k_len, batch, max_k_len, to_view(cache), to_scales(cache).k, (hipStream_t)st);
+    }
     return launch_mla_flatten((half_t*)lat_out, cu_k_off, k_len, batch, max_k_len, to_view(cache), (hipStream_t)st);
 }
 

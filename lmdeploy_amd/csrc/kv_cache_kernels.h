@@ -39,6 +39,23 @@ __device__ __forceinline__ float row_max(float v)
     return v;
 }
 
+// 8 halves -> 8 e4m3fn code bytes of the FP8 cache: cvt_pk_fp8_f32(clamp(f32(x) / scale, -448, 448)), the IEEE fp32 division, RNE.
+// The one quantiser of every FP8 store (kv_rope_store_kernel below, the MLA latent store of attention_mla_fp8.hip).
+__device__ __forceinline__ u32x2 f8_quant8(half8_t x, float scale)
+{
+    float y[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        y[e] = fminf(fmaxf((float)x[e] / scale, -448.0f), 448.0f);
+    }
+    u32x2 w;
+    w[0] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+    w[0] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], (int)w[0], true);
+    w[1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
+    w[1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], (int)w[1], true);
+    return w;
+}
+
 // QKX: the Qwen prologue (per-head RMSNorm of q / k, then the q / k / v bias; either may be nullptr) in front of RoPE.
 // One 16-lane row holds one 128-wide head of one token, so the head's sum of squares is a row DPP reduction like row_max.  The norm
 // exists at D = 128 only (head_norm8 fixes 1/128 and the 16-partial tree); the launcher refuses it at D = 64, the bias works there.
@@ -196,17 +213,7 @@ __global__ __launch_bounds__(256) void kv_rope_store_kernel(half_t* __restrict__
     else if constexpr (BITS == kKvBitsFp8) {
         const auto  sc    = std::tuple<float, float>(mr...);
         const float scale = is_k ? std::get<0>(sc) : std::get<1>(sc);
-        float       y[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            y[e] = fminf(fmaxf((float)x[e] / scale, -448.0f), 448.0f);
-        }
-        u32x2 w;
-        w[0] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-        w[0] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], (int)w[0], true);
-        w[1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
-        w[1] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], (int)w[1], true);
-        *(u32x2*)(block + doff + lane16 * 8) = w;  // the row's LPR lanes: D consecutive bytes
+        *(u32x2*)(block + doff + lane16 * 8) = f8_quant8(x, scale);  // the row's LPR lanes: D consecutive bytes
     }
     else if constexpr (BITS == kTqBits) {
         // TurboQuant (turboquant.h): the row's 16 lanes rotate, code and pack it; whole rows got here together

@@ -199,10 +199,11 @@ int launch_verify_attention(const VerifyAttnParams& p, hipStream_t st);
 // ---- attention_mla.hip ------------------------------------------------------------------
 // Multi-head Latent Attention, absorbed form, on a latent cache of one [c (512) | k_pe (64)] fp16 row per token: KvLayout{1, 576, 64, 16}.
 // Store: rows of one forward in launch_kv_rope_store's convention; kv_a [T][kv_stride] = latent | rope part, q [T][q_stride] = H heads of
-// q_lat (512) | q_pe (64); the cache row receives rmsnorm(latent) * norm_w | rope(k_pe), every q_pe is rotated in place.
+// q_lat (512) | q_pe (64); the cache row receives rmsnorm(latent) * norm_w | rope(k_pe), every q_pe is rotated in place.  On the FP8 latent
+// view (bits kKvBitsFp8, below) the normalised latent is then quantised by k_scale into 512 code bytes; at bits 16 k_scale is not read.
 int launch_mla_kv_store(const half_t* kv_a, int kv_stride, const half_t* norm_w, float eps, half_t* q, int q_stride, int heads,
                         const int* cu_q_len, const int* k_len, int batch, int total_tokens, const half2_t* cos_sin, int max_pos,
-                        KvCacheView cache, hipStream_t st);
+                        KvCacheView cache, float k_scale, hipStream_t st);
 struct MlaAttnParams {
     const half_t* q;         // [rows][q_stride]: head h at h * 576, as the store left it
     int           q_stride;
@@ -220,6 +221,15 @@ struct MlaAttnParams {
     int           rows;        // cu_q_len[batch]
 };
 int launch_mla_attention(const MlaAttnParams& p, hipStream_t st);
+int launch_mla_reduce(const MlaAttnParams& p, hipStream_t st);  // the split-K merge alone (attention_mla_fp8.hip writes the same partials)
+
+// ---- attention_mla_fp8.hip --------------------------------------------------------------
+// Attention and flatten on the FP8 latent cache, KvLayout{1, 576, 64, kKvBitsFp8}: one 640-byte row per token, 512 e4m3fn codes of
+// c / k_scale, then k_pe as 64 fp16.  k_scale is the layer's latent scale (> 0, finite); the other arguments are the fp16 launchers'.
+constexpr int kMlaF8RowBytes = 640;
+int launch_mla_attention_fp8(const MlaAttnParams& p, float k_scale, hipStream_t st);
+int launch_mla_flatten_fp8(half_t* lat_out, const int* cu_k_off, const int* k_len, int batch, int max_k_len, KvCacheView cache,
+                           float k_scale, hipStream_t st);
 
 // ---- attention_mla_prefill.hip ----------------------------------------------------------
 // MLA prefill in the expanded form.  Flatten: the latent rows 0 .. k_len[b] - 1 of every sequence, bytes unchanged, to lat_out row

@@ -9,6 +9,10 @@ so attention runs on the cached latent c (512) | k_pe (64) alone: one 1152-byte 
 Expanded form (prefill): the context's latent rows are gathered from the cache, k_nope = W_UK c and v = c W_UV are expanded per head
 once per forward, and attention runs at qk width 192 / v width 128: 640 flop per (row, head, key) where the absorbed form spends 2176.
 The cache rows are written by the same tm_mla_kv_store call in both forms.  Chunked prefill re-expands the history once per chunk.
+
+FP8 latent cache: a view with bits = _ffi.KV_BITS_FP8 and k_scale = the layer's latent scale holds 640-byte rows, 512 e4m3fn codes of
+c / k_scale then k_pe as fp16 (row_bytes(); the layer size is tm_mla_layer_size_fp8).  The same calls serve it -- the store quantises,
+csrc/attention_mla_fp8.hip attends on the codes and flattens them to fp16 for the expanded form -- so mla_forward takes no new argument.
 """
 from __future__ import annotations
 
@@ -23,6 +27,14 @@ FORMS = ('absorbed', 'expanded', 'auto')
 # (below the constant it stays absorbed, also where expanded would already win).  It is H = 16's 70 us of torch expansion einsums that
 # sets it: an engine that expands with its own GEMM should measure again.
 AUTO_EXPANDED_MIN_Q_LEN = 1536
+
+
+def row_bytes(bits: int) -> int:
+    """Bytes of one cached token for a latent view's `bits`: 16 -> 1152 (576 fp16), _ffi.KV_BITS_FP8 -> 640 (512 codes + 64 fp16)."""
+    from . import _ffi
+    if bits not in (16, _ffi.KV_BITS_FP8):
+        raise ValueError(f'the MLA latent cache is bits 16 or KV_BITS_FP8 ({_ffi.KV_BITS_FP8}), got {bits}')
+    return ROW * 2 if bits == 16 else RANK + ROPE * 2
 
 
 def absorb(kv_b_proj_weight, H: int, nope: int, v_dim: int):
@@ -91,7 +103,7 @@ def mla_forward(q_nope, q_pe, kv_a, norm_w, W_UK, W_UV, cache, cu_q_len, k_len, 
     are the same bytes in every form.
 
     q_nope fp16 [T, H, nope], q_pe fp16 [T, H, 64] (unrotated), kv_a fp16 [T, 576] (kv_a_proj_with_mqa's output), norm_w fp16 [512]
-    (kv_a_layernorm), W_UK / W_UV from absorb(), cache: _ffi.KvCache view of the latent cache (kv_heads 1, head_dim 576, bits 16),
+    (kv_a_layernorm), W_UK / W_UV from absorb(), cache: _ffi.KvCache view of the latent cache (kv_heads 1, head_dim 576, bits 16 or KV_BITS_FP8 with k_scale),
     cu_q_len int32 [B + 1] and k_len int32 [B] device tensors (k_len counts every row of this forward), cos_sin fp16 [max_pos, 32, 2]
     device table or None.  Returns fp16 [T, H, v_dim].  The rows' latent is written to the cache."""
     pick_form(form, 0)  # an unknown form is refused before anything else happens
